@@ -6,12 +6,21 @@ A step (chassis.py:151-171) = `model.run(wav, mel, voice, jitter)` ->
 `FusedAdam.step()` (gradient / EMA-statistic collectives inside for N > 1) on the drop-in module surface
 (autoencoder_model.AutoEncoder), over one batch of 8 windows x 5000 output samples per GPU (BASELINE.json configs[1];
 weak scaling), synthetic data, random-init weights.  The headline `value` is that step with the batches (a pool of 8
-distinct ones, jitter indices included) already resident in HBM, as the contract asks.  `host_fed` is the same step fed
-from pinned host memory through the device prefetcher (H2D on a copy stream, jitter generated on the device): the
-PCIe-inclusive rate, reported beside `value`.  `engine_only` repeats the measurement below the module surface
-(TrainEngine forward / backward / adam on one resident batch: round 1's number).
+distinct ones, jitter indices included) already resident in HBM, as the contract asks.  A plain run sets up, warms up,
+times --steps such steps and prints the line (`value`, `ms_per_step` = milliseconds per timed step, the configuration).
+
+--full adds the side measurements after the timed steps.  `host_fed` is the same step fed from pinned host memory
+through the device prefetcher (H2D on a copy stream, jitter generated on the device): the PCIe-inclusive rate, reported
+beside `value`.  `engine_only` repeats the measurement below the module surface (TrainEngine forward / backward / adam
+on one resident batch: round 1's number).  `box` (measured before the timed steps), `data_parallel` (N > 1),
+`roofline`, `kernel_ms_by_tag`, `cpu_baseline` and `parity` as described below.
+
+--dump-outputs DIR writes what the timed path computed in its last step (loss, logits, target, parameters, gradients,
+codebook; large ones as a fixed seeded sample) as DIR/<name>.npy: the inputs depend on the arguments only, so two builds
+run with the same arguments compare output for output.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full      # + host_fed, engine_only, roofline, CPU baseline, parity
     python bench.py --gpus N ...          # spawns N ranks itself (torch.distributed.run) when WORLD_SIZE is unset
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -64,12 +73,20 @@ def parse():
     ap.add_argument("--nf-deep", dest="nf_deep", type=int, default=-1, help="fp32 NT: launches of <= this many blocks use the deep ring (0 never)")
     ap.add_argument("--nt-window", dest="nt_window", type=int, default=-1, help="largest dilation on the one-window NT kernel (0 off)")
     ap.add_argument("--check-replicas", dest="check_replicas", action="store_true",
-                    help="N > 1: report the largest parameter difference between the ranks after the run")
+                    help="N > 1: report the largest parameter difference between the ranks after the run (needs --full)")
     ap.add_argument("--nt-chain", dest="nt_chain", default="", help="f or f,b: stages per chained NT launch of the decoder forward / backward (default: the engine's 64,0; 0 = one launch per GEMM)")
     ap.add_argument("--merge-packs", dest="merge_packs", type=int, default=-1, help="1: all weight-layout packs of a step as one launch")
-    ap.add_argument("--per-op", default=None, help="write per-op HIP-event times (ms) to this file")
+    ap.add_argument("--per-op", default=None, help="write per-op HIP-event times (ms) to this file (needs --full)")
     ap.add_argument("--engine-only", action="store_true", help="headline = the engine-level step (no module surface / loader)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: box record, the other step (engine / boundary), host-fed step, "
+                         "data-parallel exposure, roofline, CPU baseline and parity (default: the headline step only)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
+    args = ap.parse_args()
+    if not args.full and (args.per_op or args.check_replicas):
+        ap.error("--per-op and --check-replicas belong to the side measurements: add --full")
+    return args
 
 
 def spawn(args):
@@ -351,6 +368,46 @@ def pmc_traffic(kernel_prefix, tag="r06"):
     return None, f"kernel {kernel_prefix} not in profiles/{tag}_pmc_hbm_traffic.csv"
 
 
+DUMP_SAMPLE = 1 << 22          # elements kept of each large output (fixed seeded indices): 4 x 16 MB at most
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(dirpath, model, eng, last):
+    """What the timed path handed its caller in the last timed step, as float32 / float64 .npy files in `dirpath`:
+    loss; pred (B, Q, w-1) logits and target (B, w-1) as model.run returns them (the engine-level step: the same view of
+    the engine's logits); every parameter after the optimizer step and its gradient of that step, concatenated in
+    named_parameters() order; the VQ codebook.  Outputs of more than DUMP_SAMPLE elements are sampled at sorted indices
+    drawn from a generator with a fixed seed, so that two builds run with the same arguments compare element for element."""
+    import numpy as np
+    import torch
+    model._dp_finish()
+    torch.cuda.synchronize()
+
+    def sample(t, seed):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:DUMP_SAMPLE].sort().values
+            flat = flat[idx.to(flat.device)]
+        return flat.float().cpu().numpy()
+    w = eng.n_win
+    pred = last["pred"] if "pred" in last else eng.logits()[:, :w - 1, :].permute(0, 2, 1)
+    loss = last["loss"] if "loss" in last else eng.loss_buf[0]
+    names = [n for n, _ in model.named_parameters()]
+    out = {"loss": np.array([float(loss)], dtype=np.float64),
+           "pred": sample(pred, 1),
+           "params": sample(torch.cat([eng.ps.view(n).detach().reshape(-1) for n in names]), 2),
+           "grads": sample(torch.cat([eng.ps.view(n, True).detach().reshape(-1) for n in names]), 3)}
+    if "target" in last:
+        out["target"] = last["target"].detach().float().cpu().numpy()
+    if getattr(eng, "emb", None) is not None:
+        out["codebook"] = eng.emb.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, f"outputs of {total} bytes exceed the {DUMP_LIMIT}-byte dump limit"
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -445,7 +502,7 @@ def main():
         dp.attach(model, sharded=sharded, bf16_grads=bf16_grads)  # collectives inside run() / backward() / step()
         dp.broadcast_params(eng)
     loader = DevicePrefetcher(host_batches(model, args.batch, rank), device, depth=2,
-                              jitter=DeviceJitter(args.jitter_prob, seed=2507 + rank))
+                              jitter=DeviceJitter(args.jitter_prob, seed=2507 + rank)) if args.full else None
 
     def fence():
         torch.cuda.synchronize()
@@ -464,6 +521,7 @@ def main():
         wav, mel, voice, _none = next(src)
         resident.append((wav.to(device), mel.to(device), voice.to(device), jit(args.batch, mel.shape[2], device)))
     cursor = [0]
+    last = {}                                                    # what the step's caller received (--dump-outputs)
 
     def step():
         wav, mel, voice, jitter = resident[cursor[0] % len(resident)]
@@ -472,6 +530,7 @@ def main():
         pred, target, loss = model.run(wav, mel, voice, jitter)
         loss.backward()
         opt.step()
+        last["pred"], last["target"], last["loss"] = pred, target, loss
 
     def host_step():
         wav, mel, voice, jitter = next(loader)
@@ -509,7 +568,7 @@ def main():
         return dt
 
     box = None
-    if rank == 0 and not args.no_box:
+    if args.full and rank == 0 and not args.no_box:
         try:
             box = box_record(lib, eng, device)
         except Exception as e:                                   # never lose the bench line
@@ -517,10 +576,13 @@ def main():
     head_fn, other_fn = (engine_step, step) if args.engine_only else (step, engine_step)
     dt = timed(head_fn)
     loss_val = float(eng.loss_buf[0])
-    dt_other = timed(other_fn)
-    dt_host = timed(host_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, eng, last)           # (--engine-only: `last` is empty)
+    if args.full:
+        dt_other = timed(other_fn)
+        dt_host = timed(host_step)
     dp_info = None
-    if dp is not None:
+    if args.full and dp is not None:
         # how much of the exchange the compute stream actually waits for: events around every collective wait, over a
         # few extra steps outside the timed region (every rank; rank 0's numbers are printed)
         dp.finish()
@@ -718,7 +780,7 @@ def main():
         return roof, kern
 
     roof, kern = None, {}
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             roof, kern = roofline_block()
         except Exception as e:                                   # never lose the bench line
@@ -726,10 +788,10 @@ def main():
             roof = {"error": f"{type(e).__name__}: {e}", "trace": traceback.format_exc()[-600:]}
 
     cpu, parity = None, None
-    if world > 1:
+    if args.full and world > 1:
         cpu = {"value": None, "unit": "samples/s", "cores": 0, "kind": "port",
                "sample": "measured at --gpus 1 only (rank 0 would hold the other ranks for ~30 s)"}
-    elif rank == 0 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and not args.no_cpu_baseline:
         try:
             cpu, parity = cpu_baseline(hps, eng)
         except Exception as e:                                   # never lose the GPU line
@@ -756,14 +818,17 @@ def main():
                                                         + (" (bf16 gradient transport)" if bf16_grads else "")),
                        "loss": float(loss_val),
                        "decoder": "bf16 MFMA, fp32 accumulate", "encoder_vq": "fp32 MFMA exact chain (forward), bf16 MFMA (backward)"},
-            names[1] + "_only" if names[1] == "engine" else "through_boundary":
-                {"ms_per_step": 1e3 * dt_other / args.steps, "value": samples / dt_other, "unit": "samples/s"},
-            "host_fed": {"ms_per_step": 1e3 * dt_host / args.steps, "value": samples / dt_host, "unit": "samples/s",
-                         "path": "pinned host batch -> DevicePrefetcher (H2D on a copy stream, jitter generated on the device) -> the "
-                                 "same step: PCIe-inclusive, reported beside `value`, never as it"},
-            "roofline": roof, "cpu_baseline": cpu, "parity": parity, "box": box, "data_parallel": dp_info,
-            "kernel_ms_by_tag": {str(k): round(v, 4) for k, v in sorted(kern.items())},
         }
+        if args.full:
+            out.update({
+                names[1] + "_only" if names[1] == "engine" else "through_boundary":
+                    {"ms_per_step": 1e3 * dt_other / args.steps, "value": samples / dt_other, "unit": "samples/s"},
+                "host_fed": {"ms_per_step": 1e3 * dt_host / args.steps, "value": samples / dt_host, "unit": "samples/s",
+                             "path": "pinned host batch -> DevicePrefetcher (H2D on a copy stream, jitter generated on the device) -> the "
+                                     "same step: PCIe-inclusive, reported beside `value`, never as it"},
+                "roofline": roof, "cpu_baseline": cpu, "parity": parity, "box": box, "data_parallel": dp_info,
+                "kernel_ms_by_tag": {str(k): round(v, 4) for k, v in sorted(kern.items())},
+            })
         print(json.dumps(out))
     if world > 1:
         sys.stdout.flush()

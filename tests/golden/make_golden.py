@@ -702,10 +702,13 @@ def gen_par():
     """The key / value sets of the reference's par/arch.*.json and par/train.*.json (north_star: "par/*.json config
     schema"), as data, so that config.from_par is tested against every file the reference ships."""
     import glob
+    import shutil
     out = {}
+    os.makedirs(os.path.join(HERE, "par"), exist_ok=True)
     for path in sorted(glob.glob(os.path.join(REF, "par", "*.json"))):
         with open(path) as fh:
             out[os.path.basename(path)] = json.load(fh)
+        shutil.copyfile(path, os.path.join(HERE, "par", os.path.basename(path)))     # the files themselves: config.load_par
     with open(os.path.join(HERE, "par_values.json"), "w") as fh:
         json.dump(out, fh, indent=1, sort_keys=True)
     print("par_values.json:", sorted(out))

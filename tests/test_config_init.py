@@ -55,11 +55,13 @@ def test_unknown_key_is_rejected():
         config.from_par(dict(PAR["arch.mi.json"], dec_n_bogus=3))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/par"), reason="reference checkout not present")
 def test_load_par_on_the_reference_files():
+    # tests/golden/par/: the reference's par/*.json files byte for byte (make_golden.py gen_par)
+    par_dir = os.path.join(HERE, "golden", "par")
+    assert sorted(os.listdir(par_dir)) == ARCH + TRAIN
     for a in ARCH:
         for t in [None] + TRAIN:
-            hps = config.load_par(f"/root/reference/par/{a}", f"/root/reference/par/{t}" if t else None)
+            hps = config.load_par(os.path.join(par_dir, a), os.path.join(par_dir, t) if t else None)
             assert hps == config.from_par(PAR[a], PAR[t] if t else None)
 
 

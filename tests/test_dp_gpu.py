@@ -27,7 +27,7 @@ def _bench(backend, share, sharded, timeout=420, gpus=2, n_win=1000, extra_env=N
     env.pop("WORLD_SIZE", None)
     env.update(extra_env or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--check-replicas", "--n-win", str(n_win)]
+           "--full", "--no-cpu-baseline", "--check-replicas", "--n-win", str(n_win)]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not lines:

@@ -22,7 +22,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 run() {   # name, env..., -- bench args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" python bench.py --gpus $N --steps 30 --warmup 5 --no-cpu-baseline --check-replicas "$@" > $O/$name.json 2> $O/$name.err
+  env "${envs[@]}" python bench.py --gpus $N --steps 30 --warmup 5 --full --no-cpu-baseline --check-replicas "$@" > $O/$name.json 2> $O/$name.err
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 try:

@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_cursor; rm -rf $O; mkdir -p $O
 for tag in off on; do
   extra=""; [ $tag = on ] && extra="--wgrad-cursor 4,2"
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/$tag -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline $extra > $O/$tag.log 2>&1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/$tag -- python $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline $extra > $O/$tag.log 2>&1
 done
 python - <<PY
 import csv, glob, collections

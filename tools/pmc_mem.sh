@@ -9,7 +9,7 @@ for C in "TA_BUSY_avr TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYC
          "TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum TCC_LATENCY_FIFO_FULL_sum TCC_IB_STALL_sum SQ_VMEM_TA_ADDR_FIFO_FULL TCC_CYCLE_sum" \
          "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/p$i -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --engine-only --lanes 0 > $O/p$i.log 2>&1
+  timeout 200 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/p$i -- python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --engine-only --lanes 0 > $O/p$i.log 2>&1
 done
 python - <<PY
 import csv, glob, collections

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/${1:-gpurun_out/pmc_sq_waves}; rm -rf $O; mkdir -p $O
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_BUSY_CU_CYCLES \
-  --kernel-trace --output-format csv -d $O/raw -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-box --lanes 0 > $O/run.log 2>&1
+  --kernel-trace --output-format csv -d $O/raw -- python $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-box --lanes 0 > $O/run.log 2>&1
 python - <<PY
 import csv, glob, collections
 O = "$O"
