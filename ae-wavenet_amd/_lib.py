@@ -23,7 +23,7 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN) = range(1, 26)
+ OP_NT_CHAIN, OP_GRAD_NORM) = range(1, 27)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -174,7 +174,18 @@ class Reduce(C.Structure):
 class Adam(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("lr", f32),
                 ("beta1", f32), ("beta2", f32), ("eps", f32), ("bc1", f32), ("bc2", f32),
-                ("grad_scale", f32), ("pad_", i32), ("guard", vp)]
+                ("grad_scale", f32), ("pad_", i32), ("guard", vp), ("clip", vp)]
+
+
+GRAD_NORM_CHUNK, GRAD_NORM_MAX_RANGES = 16384, 8
+
+
+class GradNorm(C.Structure):
+    """aew_grad_norm_t: deterministic sum of squares over ranges of the flat gradient buffer + the clip coefficient
+    Adam.clip reads (out[1..2])."""
+    _fields_ = [("x", vp * GRAD_NORM_MAX_RANGES), ("n", i64 * GRAD_NORM_MAX_RANGES), ("n_ranges", i32), ("finalize", i32),
+                ("add_in", vp), ("sumsq", vp), ("max_norm", f32), ("grad_scale", f32), ("eps", f32), ("pad_", i32),
+                ("out", vp), ("scratch", vp), ("ticket", vp), ("guard", vp)]
 
 
 class Zero(C.Structure):
@@ -221,7 +232,7 @@ class _OpU(C.Union):
                 ("lcs", LcScatter), ("spk", SpkBias), ("spkb", SpkBwd), ("base", BaseGather),
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
-                ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain)]
+                ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm)]
 
 
 class Op(C.Structure):
@@ -233,7 +244,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_LC_SCATTER: "lcs", OP_SPK_BIAS: "spk", OP_SPK_BWD: "spkb",
             OP_BASE_GATHER: "base", OP_SOFTMAX_NLL: "sm", OP_COLSUM: "cs", OP_REDUCE: "red",
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
-            OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain"}
+            OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
+            OP_GRAD_NORM: "gnorm"}
 
 # ---- autoregressive sampler (aew_actor_t / aew_sampler_t) ----
 ACT_NONE, ACT_EARLY, ACT_LATE, ACT_RES, ACT_SKIP, ACT_POST1, ACT_POST2, ACT_SAMPLE = -1, 0, 1, 2, 3, 4, 5, 6
@@ -312,13 +324,14 @@ def load():
     lib.aew_nt_chain_dep_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.aew_gemm_nt_small_split.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     lib.aew_colsum_det_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.aew_grad_norm_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
-                       (9, NtStage), (10, NtChain)):
+                       (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 20:
+    if lib.aew_abi_version() != 21:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib
@@ -365,4 +378,5 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_set_lanes", "aew_set_tn_cursor", "aew_set_nt_wave_rows", "aew_set_nt_pipe",
            "aew_set_tn_target_blocks", "aew_set_tn_small", "aew_set_nt_small_tiles", "aew_set_nt_small_deep", "aew_set_nt_small_waves", "aew_set_nf_deep", "aew_set_nf_loaders", "aew_set_nt_rows192",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
-           "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned")
+           "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
+           "aew_grad_norm_size")

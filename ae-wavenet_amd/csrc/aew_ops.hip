@@ -1192,10 +1192,16 @@ __global__ __launch_bounds__(1024) void k_moments(const aew_moments_t p) {
 // =============================================================================================
 // Adam (torch.optim.Adam defaults; checkpoint.py:49-50), flat buffer, float4 vectorised
 // =============================================================================================
+template <bool CLIP>
 __global__ void k_adam(const aew_adam_t a) {
     const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i4 >= a.n) return;
     if (a.guard && *a.guard) return;                   // a chained launch of this step gave up a wait: parameters stay
+    float gs = a.grad_scale;
+    if (CLIP) {
+        if (a.clip[1] != 0.f) return;                  // the gradient norm of this step was inf / nan: parameters and moments stay
+        gs = a.clip[0];                                // (1.0f exactly when the norm is within the bound)
+    }
     const float inv_sqrt_bc2 = rsqrtf(a.bc2);
     const float step = a.lr / a.bc1;
     if (i4 + 4 <= a.n) {
@@ -1206,7 +1212,7 @@ __global__ void k_adam(const aew_adam_t a) {
         float* pp = &p.x; float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float gr = gp[r] * a.grad_scale;
+            const float gr = CLIP ? gp[r] * a.grad_scale * gs : gp[r] * a.grad_scale;
             mp[r] = a.beta1 * mp[r] + (1.f - a.beta1) * gr;
             vp[r] = a.beta2 * vp[r] + (1.f - a.beta2) * gr * gr;
             pp[r] -= step * mp[r] / (sqrtf(vp[r]) * inv_sqrt_bc2 + a.eps);
@@ -1216,13 +1222,111 @@ __global__ void k_adam(const aew_adam_t a) {
         *reinterpret_cast<float4*>(a.v + i4) = v;
     } else {
         for (int64_t i = i4; i < a.n; ++i) {
-            const float gr = a.g[i] * a.grad_scale;
+            const float gr = CLIP ? a.g[i] * a.grad_scale * gs : a.g[i] * a.grad_scale;
             const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * gr;
             const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * gr * gr;
             a.m[i] = m; a.v[i] = v;
             a.p[i] -= step * m / (sqrtf(v) * inv_sqrt_bc2 + a.eps);
         }
     }
+}
+
+// =============================================================================================
+// global gradient norm + clip coefficient (aew_grad_norm_t; torch.nn.utils.clip_grad_norm_): one streaming read of the
+// flat gradient buffer, fp64 sums in ONE order, the coefficient stays on the device for k_adam<true>
+// =============================================================================================
+// Sum of the 256 threads' values in a fixed order: xor butterfly inside each wave, then waves 0..3 ascending.  Every
+// thread returns the total.  (sh: 4 doubles; safe to call again right away - two barriers per call.)
+__device__ __forceinline__ double gn_block_sum(double v, double* sh) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    __syncthreads();                                   // (a previous call's readers are done with sh)
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+__global__ __launch_bounds__(256) void k_grad_norm(const aew_grad_norm_t p) {
+    constexpr int64_t CH = AEW_GRAD_NORM_CHUNK;
+    __shared__ double sh[4];
+    __shared__ unsigned ticket;
+    const int tid = threadIdx.x;
+    // block -> (range, chunk): ranges ascending, chunks ascending (uniform scalar arithmetic, <= 8 steps)
+    int64_t first = 0, len = 0;
+    const float* x = nullptr;
+    {
+        int64_t blk = blockIdx.x;
+        for (int i = 0; i < p.n_ranges; ++i) {
+            const int64_t nc = (p.n[i] + CH - 1) / CH;
+            if (blk < nc) { x = p.x[i]; first = blk * CH; len = min(CH, p.n[i] - first); break; }
+            blk -= nc;
+        }
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (x) {
+        const float4* x4 = reinterpret_cast<const float4*>(x + first);      // 16-byte aligned: x is, CH is a multiple of 4
+        const int n4 = (int)(len >> 2);
+        int j = tid;
+        for (; j + 7 * 256 < n4; j += 8 * 256) {                              // eight 16-byte loads in flight per thread
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = x4[j + u * 256];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                a0 += (double)v[u].x * (double)v[u].x; a1 += (double)v[u].y * (double)v[u].y;
+                a2 += (double)v[u].z * (double)v[u].z; a3 += (double)v[u].w * (double)v[u].w;
+            }
+        }
+        for (; j < n4; j += 256) {                                            // the last chunk of a range
+            const float4 v = x4[j];
+            a0 += (double)v.x * (double)v.x; a1 += (double)v.y * (double)v.y;
+            a2 += (double)v.z * (double)v.z; a3 += (double)v.w * (double)v.w;
+        }
+        const int tail = (int)(len & 3);                                      // n % 4 elements: threads 0..2, one each
+        if (tid < tail) { const double t = (double)x[first + 4 * (int64_t)n4 + tid]; a0 += t * t; }
+    }
+    const double part = gn_block_sum((a0 + a1) + (a2 + a3), sh);
+    // The ticket pattern of k_colsum's deterministic form: the partial leaves write-through at device scope and has been
+    // acknowledged (vmcnt) before this block draws its ticket; the last arriver reads every partial with device-scope
+    // loads.  (No release / acquire fence: a fence would write back / invalidate the whole L2 once per block.)
+    if (tid == 0) {
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(p.scratch) + blockIdx.x,
+                           (unsigned long long)__double_as_longlong(part), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ticket = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (ticket != gridDim.x - 1u) return;
+    if (tid == 0) __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
+    const int nparts = (int)gridDim.x, per = (nparts + 255) / 256;
+    double s = 0.0;
+    {
+        const int q0 = tid * per, q1 = min(nparts, q0 + per);
+        const unsigned long long* sc = reinterpret_cast<const unsigned long long*>(p.scratch);
+        for (int q = q0; q < q1; q += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                v[u] = q + u < q1 ? __longlong_as_double((long long)__hip_atomic_load(sc + q + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0.0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += v[u];
+        }
+    }
+    double total = gn_block_sum(s, sh);
+    if (tid != 0) return;
+    if (p.add_in) total += p.add_in[0];
+    p.sumsq[0] = total;
+    if (!p.finalize || (p.guard && *p.guard)) return;
+    const double norm = sqrt(total) * fabs((double)p.grad_scale);
+    const float nf = (float)norm;
+    const bool bad = !(fabs(total) <= 1.7976931348623157e308);                // inf or nan
+    float coef = 1.0f;
+    if (bad) coef = 0.f;
+    else if (!(nf <= p.max_norm)) coef = fminf(1.0f, (float)((double)p.max_norm / (norm + (double)p.eps)));
+    p.out[0] = nf;
+    p.out[1] = coef;
+    p.out[2] = bad ? 1.f : 0.f;
+    if (bad) p.out[3] += 1.f;
 }
 
 // =============================================================================================
@@ -1934,7 +2038,36 @@ static int launch_moments(const aew_moments_t& p, hipStream_t st) {
 }
 static int launch_adam(const aew_adam_t& p, hipStream_t st) {
     if (((uintptr_t)p.p | (uintptr_t)p.g | (uintptr_t)p.m | (uintptr_t)p.v) & 15) return AEW_E_ALIGN;
-    hipLaunchKernelGGL(k_adam, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
+    if (p.clip) hipLaunchKernelGGL(k_adam<true>, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_adam<false>, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
+    return (int)hipGetLastError();
+}
+static int grad_norm_blocks(const aew_grad_norm_t& p, int64_t* blocks) {
+    if (p.n_ranges < 1 || p.n_ranges > AEW_GRAD_NORM_MAX_RANGES) return AEW_E_ARG;
+    int64_t nb = 0;
+    for (int i = 0; i < p.n_ranges; ++i) {
+        if (p.n[i] < 0 || (p.n[i] > 0 && !p.x[i])) return AEW_E_ARG;
+        if ((uintptr_t)p.x[i] & 15) return AEW_E_ALIGN;
+        nb += (p.n[i] + AEW_GRAD_NORM_CHUNK - 1) / AEW_GRAD_NORM_CHUNK;
+    }
+    if (nb > 0x7fffffff) return AEW_E_ARG;
+    *blocks = nb > 0 ? nb : 1;                       // all ranges empty: one block that has nothing to add still finalizes
+    return 0;
+}
+extern "C" int aew_grad_norm_size(const aew_grad_norm_t* g, int64_t* scratch_doubles, int32_t* tickets) {
+    if (!g || !scratch_doubles || !tickets) return AEW_E_ARG;
+    int64_t nb;
+    if (int rc = grad_norm_blocks(*g, &nb)) return rc;
+    *scratch_doubles = nb;
+    *tickets = 1;
+    return 0;
+}
+static int launch_grad_norm(const aew_grad_norm_t& p, hipStream_t st) {
+    int64_t nb;
+    if (int rc = grad_norm_blocks(p, &nb)) return rc;
+    if (!p.sumsq || !p.scratch || !p.ticket || (p.finalize && !p.out)) return AEW_E_ARG;
+    if (((uintptr_t)p.sumsq | (uintptr_t)p.scratch | (uintptr_t)p.add_in) & 7) return AEW_E_ALIGN;
+    hipLaunchKernelGGL(k_grad_norm, dim3((unsigned)nb), dim3(256), 0, st, p);
     return (int)hipGetLastError();
 }
 static int launch_zero(const aew_zero_t& z, hipStream_t st) {

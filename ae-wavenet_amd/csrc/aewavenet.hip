@@ -52,6 +52,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_MFCC: return launch_mfcc(op.u.mfcc, st);
         case AEW_OP_MOMENTS: return launch_moments(op.u.mom, st);
         case AEW_OP_GEMM_TN_GROUP: return launch_gemm_tn_group(op.u.tng, st);
+        case AEW_OP_GRAD_NORM: return launch_grad_norm(op.u.gnorm, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -72,6 +73,8 @@ extern "C" int aew_sizeof(int which) {
         case 8: return (int)sizeof(aew_tuning_t);
         case 9: return (int)sizeof(aew_nt_stage_t);
         case 10: return (int)sizeof(aew_nt_chain_t);
+        case 11: return (int)sizeof(aew_adam_t);
+        case 12: return (int)sizeof(aew_grad_norm_t);
         default: return -1;
     }
 }

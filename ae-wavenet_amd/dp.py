@@ -19,6 +19,14 @@ Two schedules for the gradient exchange (same result up to fp32 summation order)
                       decoder's only between the two (TrainEngine.pack_dec_late).  Optional
                       bf16 gradient transport (half the xGMI bytes of the reduce-scatter; fp32 master parameters and
                       moments unchanged).
+
+Gradient clipping (max_grad_norm in the Adam keywords; aew_grad_norm_t): the coefficient needs the norm of the WHOLE reduced
+gradient, so in such a step no Adam range runs before every region is reduced - the overlap of the decoder's Adam with
+the encoder's reduction is given up.  All-reduce schedule: every rank holds the full reduced gradient and computes the
+same norm, no collective.  Sharded schedule: a rank holds reduced values only for its shards and the replicated
+remainders; it sums its shards, the ranks all-reduce that ONE fp64 word, and a second launch adds the remainders (equal
+on every rank, so counted once).  torch.nn.utils.clip_grad_norm_ on the .grad views must NOT be used with the sharded
+schedule: after loss.backward() the reduce-scatters are still in flight and .grad holds this rank's unreduced values.
 """
 from __future__ import annotations
 
@@ -183,7 +191,9 @@ class DataParallel:
           * EMA statistics: async all-reduce issued after the encoder / VQ part of the forward, consumed by the
             (deferred) EMA accumulation after the backward;
           * decoder gradients: async all-reduce between the two backward plans (under the encoder backward);
-          * encoder gradients: all-reduce after the backward, under the Adam update of the decoder range."""
+          * encoder gradients: all-reduce after the backward, under the Adam update of the decoder range.
+        With max_grad_norm (an Adam keyword) both reductions are waited for first: the norm launch reads the whole
+        reduced buffer (identical on every rank, so no collective), then the two Adam ranges run."""
         if self._solo():
             eng.forward()
             eng.backward()
@@ -205,9 +215,12 @@ class DataParallel:
             work["enc"] = dist.all_reduce(flat[:lo], op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         self._guard_wait()
         self._wait(work["dec"], "grads.decoder")
+        if lo > 0 and adam_kw.get("max_grad_norm") is not None:
+            self._wait(work.pop("enc"), "grads.encoder")         # the norm (first range, count=True) reads every gradient
         eng.adam_step(lr, grad_scale, lo=lo, hi=n, **adam_kw)
         if lo > 0:
-            self._wait(work["enc"], "grads.encoder")
+            if "enc" in work:
+                self._wait(work["enc"], "grads.encoder")
             eng.adam_step(lr, grad_scale, lo=0, hi=lo, count=False, **adam_kw)
         self.moments_step = eng.step_count  # all-reduce schedule: every rank updates everything
 
@@ -323,8 +336,25 @@ class DataParallel:
         st["head"] = self._reduce_region(flat, 0, lo, bf16_grads) if lo > 0 else ([], [])
         self._st = st
 
+    def _clip_norm_sharded(self, eng, regions, max_grad_norm: float, grad_scale: float):
+        """The clip coefficient of a sharded step, once every region is reduced: the sum of squares of this rank's shards
+        (one launch), all-reduced over the ranks as ONE fp64 word, then a finalizing launch that adds the replicated
+        remainders (the same values on every rank: counted once; empty ranges where a region has none).  Every rank sums
+        the same words in the same order, so all hold the same coefficient bit for bit."""
+        shards, rems = [], []
+        for a, b in regions:                             # the regions this step's backward_exchange reduced
+            s, rem = self._split(a, b)
+            shards.append((a + self.rank * s, a + (self.rank + 1) * s))
+            rems.append((rem, b))
+        eng.grad_norm_step(shards, max_grad_norm, grad_scale, finalize=False)
+        dist.all_reduce(eng.clip_sumsq[1:2], op=dist.ReduceOp.SUM, group=self.group)
+        eng.grad_norm_step(rems, max_grad_norm, grad_scale, finalize=True, add_partial=True)
+
     def optimizer_step(self, eng, lr: float, grad_scale: float = 1.0, **adam_kw):
-        """Sharded Adam + all-gather of the updated parameters (left in flight: finish() before the next forward)."""
+        """Sharded Adam + all-gather of the updated parameters (left in flight: finish() before the next forward).
+        With max_grad_norm (an Adam keyword) the step first waits for ALL regions' reductions, computes the global norm
+        (_clip_norm_sharded) and only then runs the shard / remainder Adam calls: the decoder's Adam no longer overlaps
+        the head's reduction in such a step."""
         n, lo = eng.ps.numel, eng.dec_grad_offset
         st, self._st = self._st, None
         pend, counted, dec_end = [], True, n
@@ -334,6 +364,18 @@ class DataParallel:
         late = self._late(eng)
         dec_gathers = [] if late else None
         self._guard_wait()
+        clip = adam_kw.get("max_grad_norm")
+        if clip is not None:
+            for key, what in (("dec_hi", "grads.decoder_hi"), ("dec", "grads.decoder"), ("head", "grads.encoder")):
+                if key in st:
+                    for w in st[key][0]:
+                        self._wait(w, what)
+                    for f in st[key][1]:
+                        f()
+                    st[key] = ([], [])
+            regions = ([(st["hi"], n), (lo, st["hi"])] if "dec_hi" in st else [(lo, n)]) + [(0, lo)]
+            self._clip_norm_sharded(eng, regions, clip, grad_scale)
+            adam_kw = dict(adam_kw, norm_done=True)
         if "dec_hi" in st:                               # the upper layers' region: reduced under the rest of the chain
             for w in st["dec_hi"][0]:
                 self._wait(w, "grads.decoder_hi")

@@ -567,6 +567,20 @@ class TrainEngine:
         ad.lr, ad.beta1, ad.beta2, ad.eps, ad.bc1, ad.bc2, ad.grad_scale = 1e-4, 0.9, 0.999, 1e-8, 1.0, 1.0, 1.0
         ad.guard = self.chain_guard.data_ptr()
         self.opt.add(L.OP_ADAM, ad, "adam", TAG_ADAM)
+        # ===== global-norm gradient clipping (a plan of its own; runs only when adam_step() is given max_grad_norm)
+        self.clip = Plan("clip")
+        gn = L.GradNorm()
+        gn.x[0], gn.n[0], gn.n_ranges, gn.finalize = ps.grads.data_ptr(), ps.numel, 1, 1
+        gn.max_norm, gn.grad_scale, gn.eps = 1.0, 1.0, 1e-6
+        # any cut of [0, numel) into <= 8 ranges has at most this many chunks (aew_grad_norm_size)
+        self.clip_scratch = ws.alloc("clip.scratch", ps.numel // L.GRAD_NORM_CHUNK + 1 + L.GRAD_NORM_MAX_RANGES, torch.float64)
+        self.clip_ticket = ws.alloc("clip.ticket", 4, torch.int32)
+        self.clip_sumsq = ws.alloc("clip.sumsq", 2, torch.float64)     # [0] the total; [1] a sharded caller's partial sum
+        self.clip_out = ws.alloc("clip.out", 4, torch.float32)         # norm, coefficient, non-finite flag, steps skipped
+        gn.sumsq, gn.out = self.clip_sumsq.data_ptr(), self.clip_out.data_ptr()
+        gn.scratch, gn.ticket = self.clip_scratch.data_ptr(), self.clip_ticket.data_ptr()
+        gn.guard = self.chain_guard.data_ptr()
+        self.clip.add(L.OP_GRAD_NORM, gn, "grad norm", TAG_ADAM)
 
     def _vae_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.Vae:
         va = L.Vae()
@@ -823,16 +837,51 @@ class TrainEngine:
         self.finish_ema()
         self.cb.run(self._stream())
 
+    def grad_norm_step(self, ranges, max_grad_norm: float, grad_scale: float = 1.0, finalize: bool = True,
+                       add_partial: bool = False):
+        """One launch of the gradient-norm op over element ranges [(lo, hi), ...] of the flat gradient buffer (lo a
+        multiple of 4, hi >= lo; empty ranges allowed, at most 8).  finalize=True: the total goes to clip_sumsq[0] and
+        norm / coefficient / flag / skip count to clip_out (what adam_step(max_grad_norm=...) reads).  finalize=False:
+        the sum goes to clip_sumsq[1] only - a sharded caller all-reduces that word and passes add_partial=True to the
+        finalizing launch, which adds it in.  No host synchronisation."""
+        if not (max_grad_norm > 0):
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
+        g = self.clip.array()[0].u.gnorm
+        if not 1 <= len(ranges) <= L.GRAD_NORM_MAX_RANGES:
+            raise ValueError("1..8 ranges")
+        for i in range(L.GRAD_NORM_MAX_RANGES):
+            lo, hi = ranges[i] if i < len(ranges) else (0, 0)
+            assert lo % 4 == 0 and 0 <= lo <= hi <= self.ps.numel
+            g.x[i], g.n[i] = self.ps.grads.data_ptr() + 4 * lo, hi - lo
+        g.n_ranges, g.finalize = len(ranges), int(finalize)
+        g.add_in = self.clip_sumsq.data_ptr() + 8 if add_partial else None
+        g.sumsq = self.clip_sumsq.data_ptr() + (0 if finalize else 8)
+        g.max_norm, g.grad_scale, g.eps = float(max_grad_norm), float(grad_scale), 1e-6
+        self.clip.run(self._stream())
+
+    def grad_norm(self) -> torch.Tensor:
+        """Device view [4] of the last clipped step: total gradient norm (of grad_scale * g), clip coefficient, non-finite
+        flag, steps skipped so far.  Reading it is the caller's synchronisation."""
+        return self.clip_out[:4]
+
     def adam_step(self, lr: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                  lo: int = 0, hi: Optional[int] = None, count: bool = True):
+                  lo: int = 0, hi: Optional[int] = None, count: bool = True, max_grad_norm: Optional[float] = None,
+                  norm_done: bool = False):
         """One Adam step over the flat buffer, or over its element range [lo, hi) (multiples of 4): a
         data-parallel caller updates the decoder tail while the encoder gradients are still being
-        reduced (`count=False` on all but the first range of a step)."""
+        reduced (`count=False` on all but the first range of a step).
+        max_grad_norm: clip the gradient to this global norm (torch.nn.utils.clip_grad_norm_): the first range of a step
+        (count=True) runs the norm plan over the WHOLE buffer first - every gradient must be final by then - and every
+        range multiplies the coefficient in; a step whose norm is inf / nan changes nothing on the device (step_count
+        still advances, like a step the chain guard stopped).  norm_done=True: the caller has run grad_norm_step()
+        itself (sharded data parallel).  None: the op reads no clip word - the step of an engine without clipping."""
         if count:
             self.step_count += 1
         self.weights_version += 1
         hi = self.ps.numel if hi is None else hi
         assert lo % 4 == 0 and (hi % 4 == 0 or hi == self.ps.numel) and 0 <= lo < hi <= self.ps.numel
+        if max_grad_norm is not None and count and not norm_done:
+            self.grad_norm_step([(0, self.ps.numel)], max_grad_norm, grad_scale)
         a = self.opt.array()[0].u.adam
         a.p, a.g = self.ps.params.data_ptr() + 4 * lo, self.ps.grads.data_ptr() + 4 * lo
         a.m, a.v = self.adam_m.data_ptr() + 4 * lo, self.adam_v.data_ptr() + 4 * lo
@@ -841,6 +890,7 @@ class TrainEngine:
         a.bc1 = 1.0 - betas[0] ** self.step_count
         a.bc2 = 1.0 - betas[1] ** self.step_count
         a.grad_scale = grad_scale
+        a.clip = self.clip_out.data_ptr() + 4 if max_grad_norm is not None else None
         self.opt.run(self._stream())
 
     # --------------------------------------------------------------------------------------

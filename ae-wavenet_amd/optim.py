@@ -14,12 +14,21 @@ class FusedAdam(torch.optim.Optimizer):
     change of batch size) the model carries them (`HipModelBase._opt_carry`), so they survive every
     engine rebuild.  state_dict() / load_state_dict() speak torch.optim.Adam's format (per-parameter
     `step`, `exp_avg`, `exp_avg_sq`, parameters numbered in model.parameters() order) so that
-    checkpoints interchange with the reference (checkpoint.py:61-63,87-98)."""
+    checkpoints interchange with the reference (checkpoint.py:61-63,87-98).
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
+    max_grad_norm: clip the gradient to this global L2 norm inside the step - what
+    `torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)` in front of `step()` does, as one launch over
+    the flat gradient buffer whose result stays on the device (aew_grad_norm_t): the norm is that of
+    grad_scale * gradient, after the data-parallel reduction; a step whose norm is inf / nan is skipped on the device
+    (parameters and moments keep their bits, `skipped_steps` counts it; the step number still advances).  None = off.
+    The value lives in `param_groups[0]["max_grad_norm"]`, where a schedule may change it."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None):
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0):
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (a positive number, or None for no clipping)")
         self.model = model
         params = list(model.parameters())
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm))
         self.grad_scale = grad_scale
 
     @torch.no_grad()
@@ -28,12 +37,37 @@ class FusedAdam(torch.optim.Optimizer):
         if eng is None:
             raise RuntimeError("FusedAdam.step() before the first model.run()")
         g = self.param_groups[0]
+        c = g.get("max_grad_norm")
+        if c is not None and not (float(c) > 0):
+            raise ValueError(f"Invalid max_grad_norm: {c}")
         dp = getattr(self.model, "_dp", None)
         if dp is not None and dp.sharded and not dp._solo():
             # data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather
-            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"])
+            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c)
         else:
-            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"])
+            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"], max_grad_norm=c)
+
+    # ---- what the last clipped step saw (0-d device tensors: reading one is the caller's synchronisation) ----------
+    def _clip_word(self, i):
+        eng = self.model._engine
+        if eng is None:
+            raise RuntimeError("FusedAdam: no step has run yet")
+        return eng.grad_norm()[i]
+
+    @property
+    def grad_norm(self):
+        """Global norm of grad_scale * gradient at the last step taken with max_grad_norm (before clipping)."""
+        return self._clip_word(0)
+
+    @property
+    def clip_coef(self):
+        """min(1, max_grad_norm / (norm + 1e-6)) of that step; 0 when its norm was inf / nan."""
+        return self._clip_word(1)
+
+    @property
+    def skipped_steps(self):
+        """Steps skipped so far because their gradient norm was inf / nan (counted on the device)."""
+        return self._clip_word(3)
 
     # ---- torch.optim.Adam-compatible state -------------------------------------------------
     def _layout(self):
@@ -52,6 +86,8 @@ class FusedAdam(torch.optim.Optimizer):
         group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(lay)))}
+        if g.get("max_grad_norm") is not None:                  # (an extra key: torch.optim.Adam.load_state_dict carries it along)
+            group["max_grad_norm"] = g["max_grad_norm"]
         state = {}
         st = self.model._opt_state_flat()
         if st is not None and int(st[0]) > 0:
@@ -72,6 +108,8 @@ class FusedAdam(torch.optim.Optimizer):
         for k in ("lr", "betas", "eps"):
             if k in g0:
                 self.param_groups[0][k] = tuple(g0[k]) if k == "betas" else g0[k]
+        if g0.get("max_grad_norm") is not None:                 # absent (a torch.optim.Adam checkpoint): keep the constructor's
+            self.param_groups[0]["max_grad_norm"] = g0["max_grad_norm"]
         st = state_dict.get("state", {})
         m, v = torch.zeros(total), torch.zeros(total)
         step, found = 0, False

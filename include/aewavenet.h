@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 20
+#define AEW_ABI_VERSION 21
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -473,7 +473,52 @@ typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.op
     const uint32_t* guard;       /* ABI 20, optional: device word read at launch time; non-zero = the update is a no-op.
                                     The engine points it at the STICKY word of its chained launches (aew_nt_chain_t.sticky):
                                     a step in which a hand-off wait gave up does not reach the parameters.              */
+    const float* clip;           /* ABI 21, optional: device [2] = out[1..2] of an aew_grad_norm_t op of this step, read at launch
+                                    time.  clip[1] != 0 (the gradient norm was inf / nan): the update is a no-op, like `guard`;
+                                    else the gradient is g * grad_scale * clip[0], so the moments see the CLIPPED gradient
+                                    (torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam).  clip[0] = 1.0f leaves every
+                                    bit as without it.  A skipped step still counts on the HOST (bc1 / bc2 advance: the
+                                    convention of `guard`).  NULL = no clipping: the kernel of ABI 20, bit for bit.          */
 } aew_adam_t;
+
+/* ---------------------------------------------------------------------------------------
+ * Global gradient norm (ABI 21): what torch.nn.utils.clip_grad_norm_ computes over the parameters' .grad - here ONE
+ * deterministic sum of squares over ranges of the flat fp32 gradient buffer, and a device-side clip coefficient that
+ * aew_adam_t.clip multiplies in.  The host never reads the norm.
+ *   launch   : one kernel; block j owns one chunk of AEW_GRAD_NORM_CHUNK floats of one range (ranges ascending, chunks
+ *              ascending) - the grid depends on the range lengths only, never on the device
+ *   sum      : fp64 from the first add; per thread four chains (the float4 components, float4 t, t + 256, ... of the
+ *              chunk), a fixed butterfly inside the wave, waves ascending; one fp64 partial per block to `scratch`
+ *   combine  : the block that draws the last ticket adds the partials - thread t the contiguous run
+ *              [t * per, (t + 1) * per), per = ceil(blocks / 256), ascending, then the same wave / block tree - plus
+ *              add_in[0], and is the only writer of sumsq / out.  No atomics on data: the bits do not depend on the
+ *              order of arrival.
+ *   finalize : norm = |grad_scale| * sqrt(total).  total inf / nan: out = {norm, 0, 1, skipped + 1}; else
+ *              out = {norm, norm <= max_norm ? 1.0f (exactly) : max_norm / (norm + eps), 0, skipped}.
+ * Data parallel with sharded gradients: launch 1 (finalize = 0) over this rank's shards, all-reduce of the one fp64
+ * word `sumsq`, launch 2 (finalize = 1, add_in = that word) over what every rank holds.
+ * AEW_E_ARG: n_ranges outside 1..8, n[i] < 0, a NULL pointer where one is needed, finalize without out;
+ * AEW_E_ALIGN: x[i] not 16-byte aligned.
+ * ------------------------------------------------------------------------------------- */
+#define AEW_GRAD_NORM_CHUNK 16384
+#define AEW_GRAD_NORM_MAX_RANGES 8
+typedef struct {
+    const float* x[AEW_GRAD_NORM_MAX_RANGES];   /* 16-byte aligned (may be NULL where n[i] = 0)                           */
+    int64_t n[AEW_GRAD_NORM_MAX_RANGES];        /* >= 0, any length                                                       */
+    int32_t n_ranges;            /* 1..8                                                                                  */
+    int32_t finalize;            /* 1: also write out[] from the total                                                    */
+    const double* add_in;        /* optional device [1]: added to the sum (the other ranks' shards, after their all-reduce) */
+    double* sumsq;               /* device [1]: sum over the ranges of x^2 (+ add_in[0])                                   */
+    float max_norm, grad_scale, eps;   /* the norm is that of grad_scale * x; eps = 1e-6 is clip_grad_norm_'s               */
+    int32_t pad_;
+    float* out;                  /* [4]: total norm, clip coefficient, non-finite flag (0 / 1), steps skipped so far (a
+                                    running count: zeroed by the caller once)                                             */
+    double* scratch;             /* aew_grad_norm_size doubles                                                            */
+    uint32_t* ticket;            /* aew_grad_norm_size words, zeroed once by the caller, left zero by every launch         */
+    const uint32_t* guard;       /* optional, like aew_adam_t.guard: non-zero = the op leaves out[] untouched              */
+} aew_grad_norm_t;
+/* What scratch / ticket must hold.  Host logic only; the launcher uses the same arithmetic. */
+int aew_grad_norm_size(const aew_grad_norm_t* g, int64_t* scratch_doubles, int32_t* tickets);
 
 typedef struct { void* ptr; int64_t bytes; } aew_zero_t;
 
@@ -605,7 +650,7 @@ enum {
     AEW_OP_VQ_EMA, AEW_OP_VQ_BWD, AEW_OP_LC_GATHER, AEW_OP_LC_SCATTER, AEW_OP_SPK_BIAS,
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
-    AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN
+    AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -630,14 +675,14 @@ typedef struct {
         aew_lc_scatter_t lcs; aew_spk_bias_t spk; aew_spk_bwd_t spkb; aew_base_gather_t base;
         aew_softmax_nll_t sm; aew_colsum_t cs; aew_reduce_t red; aew_adam_t adam; aew_zero_t zero;
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
-        aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain;
+        aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */

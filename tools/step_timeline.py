@@ -25,7 +25,7 @@ def main():
                 ws *= max(int(r.get(k, 1) or 1), 1)
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0][:48], wg // max(ws, 1)))
     rows.sort()
-    adam = [i for i, r in enumerate(rows) if r[2].startswith("k_adam")]
+    adam = [i for i, r in enumerate(rows) if "k_adam" in r[2]]
     if len(adam) < 4:
         print("not enough steps in the trace")
         return

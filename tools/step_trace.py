@@ -21,7 +21,7 @@ def main():
                 wg *= max(int(r.get(k, 1) or 1), 1) // max(int(r.get(w, 1) or 1), 1) or 1
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0][:60], wg))
     rows.sort()
-    adam = [i for i, r in enumerate(rows) if r[2].startswith("k_adam")]
+    adam = [i for i, r in enumerate(rows) if "k_adam" in r[2]]
     if len(adam) < 4:
         print("not enough steps in the trace")
         return
