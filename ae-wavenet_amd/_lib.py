@@ -23,7 +23,7 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN, OP_GRAD_NORM) = range(1, 27)
+ OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO) = range(1, 28)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -174,7 +174,27 @@ class Reduce(C.Structure):
 class Adam(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("lr", f32),
                 ("beta1", f32), ("beta2", f32), ("eps", f32), ("bc1", f32), ("bc2", f32),
-                ("grad_scale", f32), ("pad_", i32), ("guard", vp), ("clip", vp)]
+                ("grad_scale", f32), ("pad_", i32), ("guard", vp), ("clip", vp), ("track", vp)]
+
+
+UW_CHUNK = 4096
+
+
+class UwChunk(C.Structure):
+    """aew_uw_chunk_t: one chunk of the flat parameter buffer (never crosses a tensor boundary, no pad elements)."""
+    _fields_ = [("off", i64), ("len", i32), ("tensor", i32)]
+
+
+class UwTrack(C.Structure):
+    """aew_uw_track_t: the HOST record Adam.track points at (keep it alive while a plan holds its address)."""
+    _fields_ = [("chunks", vp), ("chunks_host", vp), ("n_chunks", i64), ("part", vp), ("base", i64), ("zero", i32),
+                ("pad_", i32)]
+
+
+class UpdateRatio(C.Structure):
+    """aew_update_ratio_t: the chunk sums of a tracked Adam step -> per-tensor update norm, weight norm and their ratio."""
+    _fields_ = [("part", vp), ("first", vp), ("n_tensors", i32), ("finalize", i32), ("add_in", vp), ("sums", vp),
+                ("out", vp)]
 
 
 GRAD_NORM_CHUNK, GRAD_NORM_MAX_RANGES = 16384, 8
@@ -232,7 +252,8 @@ class _OpU(C.Union):
                 ("lcs", LcScatter), ("spk", SpkBias), ("spkb", SpkBwd), ("base", BaseGather),
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
-                ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm)]
+                ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
+                ("ratio", UpdateRatio)]
 
 
 class Op(C.Structure):
@@ -245,7 +266,22 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_BASE_GATHER: "base", OP_SOFTMAX_NLL: "sm", OP_COLSUM: "cs", OP_REDUCE: "red",
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
-            OP_GRAD_NORM: "gnorm"}
+            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio"}
+
+
+
+def uw_chunks(offs, lens):
+    """(chunk table as a ctypes array of UwChunk, [first chunk of each tensor] + [number of chunks]) for tensors at flat
+    offsets `offs` with `lens` elements: aew_uw_chunks, the arithmetic the tracked Adam launch relies on."""
+    lib = load()
+    P = len(offs)
+    o, ln = (C.c_int64 * P)(*offs), (C.c_int64 * P)(*lens)
+    nc, first = C.c_int64(), (C.c_int32 * (P + 1))()
+    check(lib.aew_uw_chunks(o, ln, P, None, 0, C.byref(nc), None), "aew_uw_chunks")
+    chunks = (UwChunk * max(nc.value, 1))()
+    check(lib.aew_uw_chunks(o, ln, P, C.cast(chunks, C.c_void_p), nc.value, C.byref(nc), first), "aew_uw_chunks")
+    return chunks, list(first)
+
 
 # ---- autoregressive sampler (aew_actor_t / aew_sampler_t) ----
 ACT_NONE, ACT_EARLY, ACT_LATE, ACT_RES, ACT_SKIP, ACT_POST1, ACT_POST2, ACT_SAMPLE = -1, 0, 1, 2, 3, 4, 5, 6
@@ -325,13 +361,16 @@ def load():
     lib.aew_gemm_nt_small_split.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     lib.aew_colsum_det_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.aew_grad_norm_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.aew_uw_chunks.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64,
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
-                       (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm)):
+                       (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
+                       (15, UpdateRatio)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 21:
+    if lib.aew_abi_version() != 22:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib
@@ -379,4 +418,4 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_set_tn_target_blocks", "aew_set_tn_small", "aew_set_nt_small_tiles", "aew_set_nt_small_deep", "aew_set_nt_small_waves", "aew_set_nf_deep", "aew_set_nf_loaders", "aew_set_nt_rows192",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
-           "aew_grad_norm_size")
+           "aew_grad_norm_size", "aew_uw_chunks")

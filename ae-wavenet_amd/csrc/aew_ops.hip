@@ -1192,6 +1192,17 @@ __global__ __launch_bounds__(1024) void k_moments(const aew_moments_t p) {
 // =============================================================================================
 // Adam (torch.optim.Adam defaults; checkpoint.py:49-50), flat buffer, float4 vectorised
 // =============================================================================================
+// One element's update.  The untracked and the tracked launch both go through this function, vector and scalar paths
+// alike, so their roundings cannot differ.  gs: the clip coefficient (CLIP only).
+template <bool CLIP>
+__device__ __forceinline__ void adam_elem(const aew_adam_t& a, const float gs, const float step, const float inv_sqrt_bc2,
+                                          float& p, const float g, float& m, float& v) {
+    const float gr = CLIP ? g * a.grad_scale * gs : g * a.grad_scale;
+    m = a.beta1 * m + (1.f - a.beta1) * gr;
+    v = a.beta2 * v + (1.f - a.beta2) * gr * gr;
+    p -= step * m / (sqrtf(v) * inv_sqrt_bc2 + a.eps);
+}
+
 template <bool CLIP>
 __global__ void k_adam(const aew_adam_t a) {
     const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -1211,22 +1222,16 @@ __global__ void k_adam(const aew_adam_t a) {
         float4 v = *reinterpret_cast<float4*>(a.v + i4);
         float* pp = &p.x; float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float gr = CLIP ? gp[r] * a.grad_scale * gs : gp[r] * a.grad_scale;
-            mp[r] = a.beta1 * mp[r] + (1.f - a.beta1) * gr;
-            vp[r] = a.beta2 * vp[r] + (1.f - a.beta2) * gr * gr;
-            pp[r] -= step * mp[r] / (sqrtf(vp[r]) * inv_sqrt_bc2 + a.eps);
-        }
+        for (int r = 0; r < 4; ++r) adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pp[r], gp[r], mp[r], vp[r]);
         *reinterpret_cast<float4*>(a.p + i4) = p;
         *reinterpret_cast<float4*>(a.m + i4) = m;
         *reinterpret_cast<float4*>(a.v + i4) = v;
     } else {
         for (int64_t i = i4; i < a.n; ++i) {
-            const float gr = CLIP ? a.g[i] * a.grad_scale * gs : a.g[i] * a.grad_scale;
-            const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * gr;
-            const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * gr * gr;
+            float p = a.p[i], m = a.m[i], v = a.v[i];
+            adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, p, a.g[i], m, v);
             a.m[i] = m; a.v[i] = v;
-            a.p[i] -= step * m / (sqrtf(v) * inv_sqrt_bc2 + a.eps);
+            a.p[i] = p;
         }
     }
 }
@@ -1327,6 +1332,115 @@ __global__ __launch_bounds__(256) void k_grad_norm(const aew_grad_norm_t p) {
     p.out[1] = coef;
     p.out[2] = bad ? 1.f : 0.f;
     if (bad) p.out[3] += 1.f;
+}
+
+// =============================================================================================
+// update / weight ratios (aew_uw_track_t, aew_update_ratio_t; chassis.py:162-185): the Adam launch with one block per
+// chunk of the host's chunk table, fp64 sums of (p_old - p_new)^2 and p_old^2 per chunk, then one block per tensor
+// =============================================================================================
+template <bool CLIP>
+__global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_uw_chunk_t* __restrict__ chunks, double* part,
+                                                 const int64_t base, const int chunk0) {
+    constexpr int IT = AEW_UW_CHUNK / 1024;            // float4 rounds of the block over a whole chunk
+    __shared__ double sh[4];
+    const int tid = threadIdx.x;
+    const int ci = chunk0 + (int)blockIdx.x;
+    const aew_uw_chunk_t c = chunks[ci];
+    // this launch's part of the chunk, as indices into a.p: [s, e_sum) enters the sums, [s, e_adam) is updated (the pad
+    // elements behind a tensor's last chunk too, as the untracked launch updates them).  s is a multiple of 4.
+    const int64_t cs = c.off - base;
+    const int64_t s = cs > 0 ? cs : 0;
+    const int64_t e_sum = min(cs + (int64_t)c.len, a.n);
+    const int64_t e_adam = min(cs + (int64_t)((c.len + 3) & ~3), a.n);
+    bool skip = a.guard && *a.guard;                   // a skipped step still reads p: zero difference, true weight norm
+    float gs = a.grad_scale;
+    if (CLIP) {
+        skip = skip || a.clip[1] != 0.f;
+        gs = a.clip[0];
+    }
+    const float inv_sqrt_bc2 = rsqrtf(a.bc2);
+    const float step = a.lr / a.bc1;
+    double sd = 0.0, sw = 0.0;                         // one chain per sum and thread, elements ascending
+    float4 p[IT], g[IT], m[IT], v[IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {                  // every load of the block's part in flight first
+        const int64_t i4 = s + (int64_t)(it * 256 + tid) * 4;
+        if (i4 + 4 <= e_adam) {
+            p[it] = *reinterpret_cast<const float4*>(a.p + i4);
+            if (!skip) {
+                g[it] = *reinterpret_cast<const float4*>(a.g + i4);
+                m[it] = *reinterpret_cast<const float4*>(a.m + i4);
+                v[it] = *reinterpret_cast<const float4*>(a.v + i4);
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int64_t i4 = s + (int64_t)(it * 256 + tid) * 4;
+        if (i4 + 4 <= e_adam) {
+            const float4 old = p[it];
+            const float* op = &old.x;
+            float* pp = &p[it].x; float* gp = &g[it].x; float* mp = &m[it].x; float* vp = &v[it].x;
+            if (!skip) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pp[r], gp[r], mp[r], vp[r]);
+                *reinterpret_cast<float4*>(a.p + i4) = p[it];
+                *reinterpret_cast<float4*>(a.m + i4) = m[it];
+                *reinterpret_cast<float4*>(a.v + i4) = v[it];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (i4 + r < e_sum) {
+                    const float d = op[r] - pp[r];     // fp32, as the reference's `c - p`
+                    sd += (double)d * (double)d;
+                    sw += (double)op[r] * (double)op[r];
+                }
+        }
+    }
+    if (tid == 0 && (e_adam & 3)) {                    // a.n % 4 elements at the very end of the buffer, behind thread 0's chain
+        for (int64_t i = e_adam & ~(int64_t)3; i < e_adam; ++i) {
+            const float old = a.p[i];
+            float pn = old;
+            if (!skip) {
+                float mm = a.m[i], vv = a.v[i];
+                adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pn, a.g[i], mm, vv);
+                a.m[i] = mm; a.v[i] = vv;
+                a.p[i] = pn;
+            }
+            if (i < e_sum) {
+                const float d = old - pn;
+                sd += (double)d * (double)d;
+                sw += (double)old * (double)old;
+            }
+        }
+    }
+    sd = gn_block_sum(sd, sh);
+    sw = gn_block_sum(sw, sh);
+    if (tid == 0) {                                    // the chunk's only writer in this launch; earlier launches of the step are
+        part[2 * (int64_t)ci] += sd;                   // complete (stream order)
+        part[2 * (int64_t)ci + 1] += sw;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_update_ratio(const aew_update_ratio_t p) {
+    __shared__ double sh[4];
+    const int t = blockIdx.x, tid = threadIdx.x, P = p.n_tensors;
+    double s0 = 0.0, s1 = 0.0;
+    if (p.part) {
+        const int c0 = p.first[t], nc = p.first[t + 1] - c0, per = (nc + 255) / 256;
+        const int q0 = min(nc, tid * per), q1 = min(nc, q0 + per);
+        for (int q = c0 + q0; q < c0 + q1; ++q) { s0 += p.part[2 * (int64_t)q]; s1 += p.part[2 * (int64_t)q + 1]; }
+    }
+    s0 = gn_block_sum(s0, sh);
+    s1 = gn_block_sum(s1, sh);
+    if (tid != 0) return;
+    if (!p.finalize) { p.sums[t] = s0; p.sums[P + t] = s1; return; }
+    if (p.add_in) { s0 += p.add_in[t]; s1 += p.add_in[P + t]; }
+    if (p.sums) { p.sums[t] = s0; p.sums[P + t] = s1; }
+    const float un = (float)sqrt(s0), wn = (float)sqrt(s1);
+    p.out[t] = un;
+    p.out[P + t] = wn;
+    p.out[2 * P + t] = un / wn;
 }
 
 // =============================================================================================
@@ -2036,8 +2150,67 @@ static int launch_moments(const aew_moments_t& p, hipStream_t st) {
     hipLaunchKernelGGL(k_moments, dim3(1), dim3(1024), 0, st, p);
     return (int)hipGetLastError();
 }
+extern "C" int aew_uw_chunks(const int64_t* off, const int64_t* len, int32_t n_tensors, aew_uw_chunk_t* chunks, int64_t cap,
+                             int64_t* n_chunks, int32_t* first) {
+    if (!off || !len || !n_chunks || n_tensors < 1) return AEW_E_ARG;
+    int64_t nc = 0, end = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        if (len[t] < 0 || off[t] < end) return AEW_E_ARG;
+        if (off[t] & 3) return AEW_E_ALIGN;
+        if (first) first[t] = (int32_t)nc;
+        for (int64_t o = 0; o < len[t]; o += AEW_UW_CHUNK, ++nc) {
+            if (!chunks) continue;
+            if (nc >= cap) return AEW_E_ARG;
+            chunks[nc].off = off[t] + o;
+            chunks[nc].len = (int32_t)(len[t] - o < AEW_UW_CHUNK ? len[t] - o : AEW_UW_CHUNK);
+            chunks[nc].tensor = t;
+        }
+        if (nc > 0x7fffffff) return AEW_E_ARG;
+        end = off[t] + len[t];
+    }
+    if (first) first[n_tensors] = (int32_t)nc;
+    *n_chunks = nc;
+    return 0;
+}
+static int launch_adam_tracked(const aew_adam_t& p, hipStream_t st) {
+    const aew_uw_track_t& t = *p.track;
+    if (!t.chunks || !t.chunks_host || !t.part || t.n_chunks < 1 || t.n_chunks > 0x7fffffff || t.base < 0 || p.n < 1) return AEW_E_ARG;
+    if ((t.base & 3) || ((uintptr_t)t.part & 15)) return AEW_E_ALIGN;
+    const aew_uw_chunk_t* ch = t.chunks_host;
+    auto pad_end = [&](int64_t c) { return ch[c].off + ((ch[c].len + 3) & ~3); };
+    // c0: the first chunk that ends (pad elements included) behind base; c1: the last one that starts in front of base + n
+    int64_t lo = 0, hi = t.n_chunks;
+    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (pad_end(mid) > t.base) hi = mid; else lo = mid + 1; }
+    const int64_t c0 = lo;
+    lo = c0, hi = t.n_chunks;
+    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (ch[mid].off < t.base + p.n) lo = mid + 1; else hi = mid; }
+    const int64_t c1 = lo - 1;
+    // the chunks (+ pads) must cover the range without a gap: an element outside every chunk would miss its update
+    if (c0 >= t.n_chunks || c1 < c0 || ch[c0].off > t.base || pad_end(c1) < t.base + p.n) return AEW_E_ARG;
+    for (int64_t c = c0; c < c1; ++c)
+        if (ch[c].len < 1 || ch[c].len > AEW_UW_CHUNK || pad_end(c) != ch[c + 1].off) return AEW_E_ARG;
+    if (ch[c1].len < 1 || ch[c1].len > AEW_UW_CHUNK) return AEW_E_ARG;
+    if (t.zero) {
+        aew_zero_t z;
+        z.ptr = t.part; z.bytes = t.n_chunks * 16;
+        if (int rc = launch_zero(z, st)) return rc;
+    }
+    const dim3 grid((unsigned)(c1 - c0 + 1));
+    if (p.clip) hipLaunchKernelGGL(k_adam_uw<true>, grid, dim3(256), 0, st, p, t.chunks, t.part, t.base, (int)c0);
+    else hipLaunchKernelGGL(k_adam_uw<false>, grid, dim3(256), 0, st, p, t.chunks, t.part, t.base, (int)c0);
+    return (int)hipGetLastError();
+}
+static int launch_update_ratio(const aew_update_ratio_t& p, hipStream_t st) {
+    if (p.n_tensors < 1 || !p.first || (!p.part && !p.add_in)) return AEW_E_ARG;
+    if (p.finalize ? !p.out : (!p.part || !p.sums)) return AEW_E_ARG;
+    if (((uintptr_t)p.part | (uintptr_t)p.add_in | (uintptr_t)p.sums) & 7) return AEW_E_ALIGN;
+    if (((uintptr_t)p.first | (uintptr_t)p.out) & 3) return AEW_E_ALIGN;
+    hipLaunchKernelGGL(k_update_ratio, dim3((unsigned)p.n_tensors), dim3(256), 0, st, p);
+    return (int)hipGetLastError();
+}
 static int launch_adam(const aew_adam_t& p, hipStream_t st) {
     if (((uintptr_t)p.p | (uintptr_t)p.g | (uintptr_t)p.m | (uintptr_t)p.v) & 15) return AEW_E_ALIGN;
+    if (p.track) return launch_adam_tracked(p, st);
     if (p.clip) hipLaunchKernelGGL(k_adam<true>, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(k_adam<false>, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
     return (int)hipGetLastError();

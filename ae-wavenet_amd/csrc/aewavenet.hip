@@ -53,6 +53,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_MOMENTS: return launch_moments(op.u.mom, st);
         case AEW_OP_GEMM_TN_GROUP: return launch_gemm_tn_group(op.u.tng, st);
         case AEW_OP_GRAD_NORM: return launch_grad_norm(op.u.gnorm, st);
+        case AEW_OP_UPDATE_RATIO: return launch_update_ratio(op.u.ratio, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -75,6 +76,9 @@ extern "C" int aew_sizeof(int which) {
         case 10: return (int)sizeof(aew_nt_chain_t);
         case 11: return (int)sizeof(aew_adam_t);
         case 12: return (int)sizeof(aew_grad_norm_t);
+        case 13: return (int)sizeof(aew_uw_chunk_t);
+        case 14: return (int)sizeof(aew_uw_track_t);
+        case 15: return (int)sizeof(aew_update_ratio_t);
         default: return -1;
     }
 }

@@ -27,6 +27,14 @@ same norm, no collective.  Sharded schedule: a rank holds reduced values only fo
 remainders; it sums its shards, the ranks all-reduce that ONE fp64 word, and a second launch adds the remainders (equal
 on every rank, so counted once).  torch.nn.utils.clip_grad_norm_ on the .grad views must NOT be used with the sharded
 schedule: after loss.backward() the reduce-scatters are still in flight and .grad holds this rank's unreduced values.
+
+Update / weight ratios (track in the Adam keywords; aew_uw_track_t): the Adam launches sum per chunk of the parameter
+tensors they cover.  All-reduce schedule: every rank updates everything - the two range calls of train_step leave the
+sums of a whole-buffer step, no collective.  Sharded schedule: every rank sums over its shards, rank 0 alone over the
+replicated remainders (equal on every rank: counted once); the per-tensor fp64 pairs are all-reduced (2 P words) and a
+finalizing launch takes norms and ratios from them, so every rank holds the same ratios while the parameter all-gathers
+are still in flight.  The reference's clone-and-norm loop around optim.step() must NOT be used with the sharded schedule:
+after the step p.data is complete only once those all-gathers are.
 """
 from __future__ import annotations
 
@@ -277,7 +285,9 @@ class DataParallel:
             else:
                 defer.append(gather)
         if rem < b:
-            eng.adam_step(lr, grad_scale, lo=rem, hi=b, count=count, **adam_kw)
+            # the replicated remainder: every rank updates it, rank 0 alone adds it to the update / weight sums
+            eng.adam_step(lr, grad_scale, lo=rem, hi=b, count=count,
+                          **dict(adam_kw, track=bool(adam_kw.get("track")) and self.rank == 0))
         return work
 
     def finish(self, region=None):
@@ -354,7 +364,7 @@ class DataParallel:
         """Sharded Adam + all-gather of the updated parameters (left in flight: finish() before the next forward).
         With max_grad_norm (an Adam keyword) the step first waits for ALL regions' reductions, computes the global norm
         (_clip_norm_sharded) and only then runs the shard / remainder Adam calls: the decoder's Adam no longer overlaps
-        the head's reduction in such a step."""
+        the head's reduction in such a step.  With track (an Adam keyword) the step ends with _ratios_sharded."""
         n, lo = eng.ps.numel, eng.dec_grad_offset
         st, self._st = self._st, None
         pend, counted, dec_end = [], True, n
@@ -397,6 +407,16 @@ class DataParallel:
         for g in dec_gathers or []:
             pend.append(("dec", g()))
         self._pending = pend
+        if adam_kw.get("track"):
+            self._ratios_sharded(eng)
+
+    def _ratios_sharded(self, eng):
+        """The update / weight ratios of a sharded step: this rank's chunk sums per tensor (one launch), all-reduced over
+        the ranks as 2 P fp64 words, then the finalizing launch that reads those words alone.  Every rank receives the
+        same words, so all hold the same ratios bit for bit - without waiting for the parameter all-gathers."""
+        eng.ratio_step(finalize=False)
+        dist.all_reduce(eng.uw_sums[:2 * eng.uw_n], op=dist.ReduceOp.SUM, group=self.group)
+        eng.ratio_step(finalize=True, add_partial=True)
 
     def train_step_sharded(self, eng, lr: float, grad_scale: float = 1.0, bf16_grads: bool = False, **adam_kw):
         """forward + backward + sharded optimizer step (see the module docstring).  Every rank ends with the same

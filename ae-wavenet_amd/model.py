@@ -7,6 +7,7 @@ and `mfcc_inverter.MfccInverter` wrap it in the reference's nn.Module surface
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import math
@@ -581,6 +582,27 @@ class TrainEngine:
         gn.scratch, gn.ticket = self.clip_scratch.data_ptr(), self.clip_ticket.data_ptr()
         gn.guard = self.chain_guard.data_ptr()
         self.clip.add(L.OP_GRAD_NORM, gn, "grad norm", TAG_ADAM)
+        # ===== per-parameter update / weight ratios (aew_uw_track_t: runs only when adam_step() is given track=True)
+        names = ps.names()
+        chunks, first = L.uw_chunks([ps.off[n] for n in names], [ps.numel_of(n) for n in names])
+        P, nch = len(names), first[-1]
+        self.uw_n, self.uw_first_host, self._uw_chunks_host = P, first, chunks
+        self.uw_chunks = ws.alloc("uw.chunks", 2 * nch, torch.int64)          # aew_uw_chunk_t records (16 bytes each)
+        self.uw_chunks[:2 * nch].copy_(torch.frombuffer(bytearray(bytes(chunks))[:16 * nch], dtype=torch.int64))
+        self.uw_first = ws.alloc("uw.first", P + 1, torch.int32)
+        self.uw_first[:P + 1].copy_(torch.tensor(first, dtype=torch.int32))
+        self.uw_part = ws.alloc("uw.part", 2 * nch, torch.float64)            # per chunk: sum (p_old - p_new)^2, sum p_old^2
+        self.uw_sums = ws.alloc("uw.sums", 2 * P, torch.float64)              # per tensor, [2][P]
+        self.uw_out = ws.alloc("uw.out", 3 * P, torch.float32)                # [3][P]: update norm, weight norm, ratio
+        tr = self.uw_track = L.UwTrack()                                      # host record; the Adam op holds its address
+        tr.chunks, tr.chunks_host, tr.n_chunks = self.uw_chunks.data_ptr(), C.addressof(chunks), nch
+        tr.part = self.uw_part.data_ptr()
+        self._uw_zero, self._uw_stale = True, False
+        self.ratio = Plan("ratio")
+        ur = L.UpdateRatio()
+        ur.part, ur.first, ur.n_tensors, ur.finalize = self.uw_part.data_ptr(), self.uw_first.data_ptr(), P, 1
+        ur.sums, ur.out = self.uw_sums.data_ptr(), self.uw_out.data_ptr()
+        self.ratio.add(L.OP_UPDATE_RATIO, ur, "update ratio", TAG_ADAM)
 
     def _vae_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.Vae:
         va = L.Vae()
@@ -864,9 +886,32 @@ class TrainEngine:
         flag, steps skipped so far.  Reading it is the caller's synchronisation."""
         return self.clip_out[:4]
 
+    def ratio_step(self, finalize: bool = True, add_partial: bool = False):
+        """One launch of the update-ratio op over the chunk sums the tracked Adam calls of this step left.  finalize=True:
+        per-tensor update norm, weight norm and ratio go to uw_out (what update_ratios() returns).  finalize=False: the
+        per-tensor fp64 pairs go to uw_sums only - a sharded caller all-reduces those 2 P words and then passes
+        finalize=True, add_partial=True, which takes the totals from uw_sums alone.  No host synchronisation."""
+        if self._uw_zero:                                # no tracked Adam call since the step began: nothing was summed
+            self.uw_part.zero_()
+            self._uw_zero = False
+        r = self.ratio.array()[0].u.ratio
+        r.finalize = int(finalize)
+        r.part = None if add_partial else self.uw_part.data_ptr()
+        r.add_in = self.uw_sums.data_ptr() if add_partial else None
+        self.ratio.run(self._stream())
+        self._uw_stale = not finalize
+
+    def update_ratios(self) -> torch.Tensor:
+        """Device view [3][P] of the last tracked step, P tensors in ps.names() order: update norm ||p_old - p_new||,
+        weight norm ||p_old||, their ratio (chassis.py:180-183).  A step made of range calls is reduced here, once, when
+        its results are first asked for.  Reading the view is the caller's synchronisation."""
+        if self._uw_stale:
+            self.ratio_step()
+        return self.uw_out[:3 * self.uw_n].view(3, self.uw_n)
+
     def adam_step(self, lr: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                   lo: int = 0, hi: Optional[int] = None, count: bool = True, max_grad_norm: Optional[float] = None,
-                  norm_done: bool = False):
+                  norm_done: bool = False, track: bool = False):
         """One Adam step over the flat buffer, or over its element range [lo, hi) (multiples of 4): a
         data-parallel caller updates the decoder tail while the encoder gradients are still being
         reduced (`count=False` on all but the first range of a step).
@@ -874,9 +919,13 @@ class TrainEngine:
         (count=True) runs the norm plan over the WHOLE buffer first - every gradient must be final by then - and every
         range multiplies the coefficient in; a step whose norm is inf / nan changes nothing on the device (step_count
         still advances, like a step the chain guard stopped).  norm_done=True: the caller has run grad_norm_step()
-        itself (sharded data parallel).  None: the op reads no clip word - the step of an engine without clipping."""
+        itself (sharded data parallel).  None: the op reads no clip word - the step of an engine without clipping.
+        track: the launch also sums (p_old - p_new)^2 and p_old^2 per chunk of the parameter tensors it covers
+        (aew_uw_track_t); the first tracked call of a step clears the sums, a whole-buffer step reduces them to
+        update_ratios() right away, range calls leave that to the accessor.  False: the op carries no record."""
         if count:
             self.step_count += 1
+            self._uw_zero = True
         self.weights_version += 1
         hi = self.ps.numel if hi is None else hi
         assert lo % 4 == 0 and (hi % 4 == 0 or hi == self.ps.numel) and 0 <= lo < hi <= self.ps.numel
@@ -891,7 +940,17 @@ class TrainEngine:
         a.bc2 = 1.0 - betas[1] ** self.step_count
         a.grad_scale = grad_scale
         a.clip = self.clip_out.data_ptr() + 4 if max_grad_norm is not None else None
+        a.track = None
+        if track:
+            self.uw_track.base, self.uw_track.zero = lo, int(self._uw_zero)
+            a.track = C.addressof(self.uw_track)
+            self._uw_zero = False
         self.opt.run(self._stream())
+        if track:
+            if lo == 0 and hi == self.ps.numel:
+                self.ratio_step()
+            else:
+                self._uw_stale = True
 
     # --------------------------------------------------------------------------------------
     # views for the module surface / tests

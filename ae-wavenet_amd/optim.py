@@ -21,14 +21,25 @@ class FusedAdam(torch.optim.Optimizer):
     the flat gradient buffer whose result stays on the device (aew_grad_norm_t): the norm is that of
     grad_scale * gradient, after the data-parallel reduction; a step whose norm is inf / nan is skipped on the device
     (parameters and moments keep their bits, `skipped_steps` counts it; the step number still advances).  None = off.
-    The value lives in `param_groups[0]["max_grad_norm"]`, where a schedule may change it."""
+    The value lives in `param_groups[0]["max_grad_norm"]`, where a schedule may change it.
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None):
+    track_update_ratio: every step also leaves, per parameter tensor, the norm of its update, the norm of the weights
+    before the step and their ratio on the device (`update_norm`, `weight_norm`, `update_ratio`) - what the reference's
+    progress step computes with a clone of every parameter in front of `step()` and a loop of norms behind it
+    (chassis.py:162-163,180-183), here summed inside the Adam launch (aew_uw_track_t): no clone, no host
+    synchronisation, one summation order, and right under the sharded data-parallel schedule.  Parameters and moments
+    are bit for bit those of an untracked step.  The value lives in `param_groups[0]["track_update_ratio"]`."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None,
+                 track_update_ratio=False):
         if max_grad_norm is not None and not (float(max_grad_norm) > 0):
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (a positive number, or None for no clipping)")
+        if not isinstance(track_update_ratio, (bool, int)) or track_update_ratio not in (0, 1):
+            raise ValueError(f"Invalid track_update_ratio: {track_update_ratio!r} (True or False)")
         self.model = model
         params = list(model.parameters())
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
+                                      track_update_ratio=bool(track_update_ratio)))
         self.grad_scale = grad_scale
 
     @torch.no_grad()
@@ -40,12 +51,13 @@ class FusedAdam(torch.optim.Optimizer):
         c = g.get("max_grad_norm")
         if c is not None and not (float(c) > 0):
             raise ValueError(f"Invalid max_grad_norm: {c}")
+        track = bool(g.get("track_update_ratio"))
         dp = getattr(self.model, "_dp", None)
         if dp is not None and dp.sharded and not dp._solo():
             # data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather
-            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c)
+            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track)
         else:
-            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"], max_grad_norm=c)
+            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"], max_grad_norm=c, track=track)
 
     # ---- what the last clipped step saw (0-d device tensors: reading one is the caller's synchronisation) ----------
     def _clip_word(self, i):
@@ -69,6 +81,31 @@ class FusedAdam(torch.optim.Optimizer):
         """Steps skipped so far because their gradient norm was inf / nan (counted on the device)."""
         return self._clip_word(3)
 
+    # ---- what the last tracked step did per tensor ({parameter name: 0-d device tensor}, named_parameters() order) ---
+    def _ratio_row(self, i):
+        eng = self.model._engine
+        if eng is None:
+            raise RuntimeError("FusedAdam: no step has run yet")
+        out = eng.update_ratios()                                # [3][P] views; P in the flat buffer's = named_parameters() order
+        return {name: out[i, k] for k, (name, _) in enumerate(self.model.named_parameters())}
+
+    @property
+    def update_norm(self):
+        """||p_before - p_after|| per parameter tensor at the last step taken with track_update_ratio (0 for a step the
+        device skipped)."""
+        return self._ratio_row(0)
+
+    @property
+    def weight_norm(self):
+        """||p_before|| per parameter tensor of that step."""
+        return self._ratio_row(1)
+
+    @property
+    def update_ratio(self):
+        """update_norm / weight_norm, a plain fp32 division: inf / nan for a zero-initialised tensor, as the reference's
+        `t.norm(c - p.data) / c.norm()`."""
+        return self._ratio_row(2)
+
     # ---- torch.optim.Adam-compatible state -------------------------------------------------
     def _layout(self):
         """[(name, flat offset, numel, shape)] and the flat length: the ParamStore rule (engine.py), computed from
@@ -88,6 +125,8 @@ class FusedAdam(torch.optim.Optimizer):
                  "params": list(range(len(lay)))}
         if g.get("max_grad_norm") is not None:                  # (an extra key: torch.optim.Adam.load_state_dict carries it along)
             group["max_grad_norm"] = g["max_grad_norm"]
+        if g.get("track_update_ratio"):
+            group["track_update_ratio"] = True
         state = {}
         st = self.model._opt_state_flat()
         if st is not None and int(st[0]) > 0:
@@ -110,6 +149,8 @@ class FusedAdam(torch.optim.Optimizer):
                 self.param_groups[0][k] = tuple(g0[k]) if k == "betas" else g0[k]
         if g0.get("max_grad_norm") is not None:                 # absent (a torch.optim.Adam checkpoint): keep the constructor's
             self.param_groups[0]["max_grad_norm"] = g0["max_grad_norm"]
+        if g0.get("track_update_ratio") is not None:            # absent: keep the constructor's
+            self.param_groups[0]["track_update_ratio"] = bool(g0["track_update_ratio"])
         st = state_dict.get("state", {})
         m, v = torch.zeros(total), torch.zeros(total)
         step, found = 0, False

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 21
+#define AEW_ABI_VERSION 22
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -462,6 +462,53 @@ typedef struct {                 /* v_i = scale_i * sum(x_i[0:n_i]);  out[1+i] =
                                          be frozen into a captured graph)                                    */
 } aew_reduce_t;
 
+/* ---------------------------------------------------------------------------------------
+ * Per-parameter update / weight ratios (ABI 22): what the reference's training loop computes around optim.step()
+ * (chassis.py:162-185: clone every parameter, step, norm(clone - p) / norm(clone) per tensor) - here from inside the
+ * Adam launch, which holds the old and the new value of every element in registers: no clone, no extra pass over
+ * memory, no host synchronisation, ONE summation order.
+ *   chunk table : the host cuts the flat buffer into chunks (aew_uw_chunks): no chunk crosses a tensor boundary, a chunk
+ *                 holds at most AEW_UW_CHUNK elements, tensors ascending, chunks ascending within a tensor, the pad
+ *                 elements behind a tensor (each starts at a multiple of 4) belong to no chunk.
+ *   Adam launch : aew_adam_t.track set - one block per chunk that overlaps the launch's element range
+ *                 [base, base + n) of the flat buffer.  The per-element arithmetic is that of the untracked launch (the
+ *                 same device function), so p / m / v come out bit for bit; the pad elements behind a chunk are updated
+ *                 by its block, like the untracked launch updates them, and enter no sum.  Each block accumulates, in
+ *                 fp64, sum (p_old - p_new)^2 - the difference taken in fp32, as the reference's `c - p` - and
+ *                 sum p_old^2 over its part of the chunk: per thread one chain per sum (elements ascending), a fixed
+ *                 butterfly inside the wave, waves ascending.  Thread 0 ADDS the pair to part[chunk] with plain loads
+ *                 and stores: the launches of one step are ordered by the stream and no two blocks of a launch share
+ *                 a chunk, so no atomics and the bits do not depend on the order of arrival.  `zero` != 0 (the first
+ *                 launch of a step) clears part[] in front of the launch.
+ *                 A step skipped on the device (guard word non-zero, clip[1] != 0) still reads p: it adds p_old^2 and
+ *                 a zero difference - the step then reports an update norm of 0 and the true weight norm.
+ *   reduce      : AEW_OP_UPDATE_RATIO (aew_update_ratio_t), one block per tensor.
+ * ------------------------------------------------------------------------------------- */
+#ifndef AEW_UW_CHUNK
+#define AEW_UW_CHUNK 4096        /* elements per chunk = per block of the tracked Adam launch; a multiple of 1024          */
+#endif
+typedef struct {
+    int64_t off;                 /* first element in the flat buffer (a multiple of 4)                                     */
+    int32_t len;                 /* 1 .. AEW_UW_CHUNK                                                                      */
+    int32_t tensor;              /* index of the tensor it belongs to                                                      */
+} aew_uw_chunk_t;
+/* The chunk table of tensors at flat offsets off[t] (multiples of 4, ascending, off[t + 1] >= off[t] + len[t]) with
+ * len[t] >= 0 elements.  Writes the number of chunks to *n_chunks, the records to chunks[0 .. cap) when chunks != NULL
+ * (AEW_E_ARG if cap is too small) and the first chunk of each tensor to first[0 .. n_tensors] when first != NULL
+ * (first[n_tensors] = the number of chunks; a tensor of length 0 has none).  Host logic only: the engine, the tests and
+ * the launcher's range arithmetic all read this one table. */
+int aew_uw_chunks(const int64_t* off, const int64_t* len, int32_t n_tensors, aew_uw_chunk_t* chunks, int64_t cap,
+                  int64_t* n_chunks, int32_t* first);
+typedef struct {                 /* HOST record aew_adam_t.track points at (read at launch time only)                      */
+    const aew_uw_chunk_t* chunks;        /* device copy of the table                                                      */
+    const aew_uw_chunk_t* chunks_host;   /* host copy: the launcher finds the chunks that overlap [base, base + n) in it    */
+    int64_t n_chunks;
+    double* part;                /* device [n_chunks][2]: {sum (p_old - p_new)^2, sum p_old^2} per chunk, 16-byte aligned   */
+    int64_t base;                /* flat offset of aew_adam_t.p[0] (a multiple of 4): the table speaks flat offsets          */
+    int32_t zero;                /* != 0: clear part[] first (the first launch of a step)                                   */
+    int32_t pad_;
+} aew_uw_track_t;
+
 typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.optim.Adam defaults,
                                     checkpoint.py:49-50)                                      */
     float* p; const float* g; float* m; float* v;
@@ -479,7 +526,33 @@ typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.op
                                     (torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam).  clip[0] = 1.0f leaves every
                                     bit as without it.  A skipped step still counts on the HOST (bc1 / bc2 advance: the
                                     convention of `guard`).  NULL = no clipping: the kernel of ABI 20, bit for bit.          */
+    const aew_uw_track_t* track; /* ABI 22, optional HOST pointer: also accumulate the update / weight sums of this launch's
+                                    range per chunk (see above).  The chunks must cover [base, base + n): AEW_E_ARG otherwise,
+                                    and for a NULL table / part or base < 0; AEW_E_ALIGN for base % 4 or part % 16.
+                                    NULL = the launch of ABI 21, grid and bits.                                            */
 } aew_adam_t;
+
+/* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
+ * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
+ * wave / block tree of the gradient norm - separately for the two sums.
+ *   finalize = 0 : sums[0][t] = sum (p_old - p_new)^2, sums[1][t] = sum p_old^2 - nothing else is written.
+ *   finalize = 1 : the totals are the chunk sums (part may be NULL: none) + add_in[.][t] (optional); they go to sums
+ *                  when that is given and out[0][t] = (float) sqrt(total 0) - the update norm, out[1][t] =
+ *                  (float) sqrt(total 1) - the weight norm BEFORE the step, out[2][t] = out[0][t] / out[1][t], a plain fp32
+ *                  division: a zero-initialised bias gives inf (or nan when it did not move), as the reference's loop.
+ * Data parallel with sharded updates: launch 1 (finalize = 0) over what this rank updated, all-reduce of the 2 P fp64
+ * words, launch 2 (finalize = 1, part = NULL, add_in = those words).
+ * AEW_E_ARG: n_tensors < 1, first NULL, neither part nor add_in, finalize = 0 without part or sums, finalize = 1 without
+ * out; AEW_E_ALIGN: part / add_in / sums not 8-byte, first / out not 4-byte aligned. */
+typedef struct {
+    const double* part;          /* device [n_chunks][2] (aew_uw_track_t.part)                                             */
+    const int32_t* first;        /* device [n_tensors + 1]: first chunk of each tensor (aew_uw_chunks)                      */
+    int32_t n_tensors;           /* P                                                                                     */
+    int32_t finalize;
+    const double* add_in;        /* optional device [2][P]                                                                 */
+    double* sums;                /* device [2][P]                                                                          */
+    float* out;                  /* device [3][P]: update norm, weight norm, ratio                                         */
+} aew_update_ratio_t;
 
 /* ---------------------------------------------------------------------------------------
  * Global gradient norm (ABI 21): what torch.nn.utils.clip_grad_norm_ computes over the parameters' .grad - here ONE
@@ -650,7 +723,7 @@ enum {
     AEW_OP_VQ_EMA, AEW_OP_VQ_BWD, AEW_OP_LC_GATHER, AEW_OP_LC_SCATTER, AEW_OP_SPK_BIAS,
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
-    AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM
+    AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -675,14 +748,14 @@ typedef struct {
         aew_lc_scatter_t lcs; aew_spk_bias_t spk; aew_spk_bwd_t spkb; aew_base_gather_t base;
         aew_softmax_nll_t sm; aew_colsum_t cs; aew_reduce_t red; aew_adam_t adam; aew_zero_t zero;
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
-        aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm;
+        aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
