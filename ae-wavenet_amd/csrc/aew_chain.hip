@@ -135,7 +135,8 @@ __global__ __launch_bounds__(CHAIN_THREADS, 4) void k_nt_chain(const aew_nt_stag
 // ---- host side ----------------------------------------------------------------------------------------------
 #include <vector>
 
-static int win_dwp(const aew_gemm_nt_t& g);
+static int win_dwp(const aew_gemm_nt_t& g, const aew_tuning_t& T);
+static void nt_pick(const aew_gemm_nt_t& g, const aew_tuning_t& T, NtPick* out);
 static int check_seg(const aew_seg_t& s, int esize, int ktile);
 static int launch_zero(const aew_zero_t& z, hipStream_t st);
 
@@ -201,10 +202,12 @@ static int chain_desc_ok(const aew_gemm_nt_t& g, int force) {
         const int64_t extent = ((int64_t)(g.batch - 1) * v->batch_stride + rows * v->row_pitch) * (v->dtype == AEW_BF16 ? 2 : 4);
         if (extent < 0 || extent > 0x7fffffffLL) return AEW_E_UNSUP;
     }
+    // the stand-alone launch would run the default body or the one-window body (force: or a small-launch shape), and no
+    // A/B record is in force: nt_mem128 / nt_deep veto the chain also for the stages whose own pick they leave alone
     const aew_tuning_t& T = AEW_T();
-    if (T.nt_wave_rows != 64 || T.nt_mem128 || T.nt_deep) return AEW_E_UNSUP;          // an A/B shape is selected
-    const int tiles256 = ((g.M + NT_BM - 1) / NT_BM) * g.batch * (g.N_pad / NT_BN);
-    if (!force && T.nt_small_tiles > 0 && tiles256 <= T.nt_small_tiles) return AEW_E_UNSUP;   // small launches: 64-row tiles
+    NtPick p;
+    nt_pick(g, T, &p);
+    if (!(p.kernel == 0 || p.kernel == 6 || (force && p.kernel == 1)) || T.nt_mem128 || T.nt_deep) return AEW_E_UNSUP;
     return 0;
 }
 
@@ -229,7 +232,7 @@ extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stag
         aew_nt_stage_t& S = out[s];
         S = aew_nt_stage_t{};
         S.g = g;
-        const int dwp = win_dwp(g);
+        const int dwp = win_dwp(g, AEW_T());
         S.kind = dwp == 0 ? 0 : (dwp == 1 ? 1 : 2);
         has_gated = has_gated || g.epi == AEW_EPI_GATED;
         has_dfg = has_dfg || g.epi == AEW_EPI_DFG;

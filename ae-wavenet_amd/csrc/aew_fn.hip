@@ -640,7 +640,6 @@ __global__ __launch_bounds__(FN_THREADS, 3) void k_fn(const aew_gemm_nt_t g) {
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int aew_set_fn(int on) { g_tune.fn_enable = on ? 1 : 0; return 0; }
 extern "C" int aew_set_fn_ring3(int min_k_tiles) { g_tune.fn_ring3 = min_k_tiles < 0 ? 0 : min_k_tiles; return 0; }
-int g_fn_enable_flag() { return AEW_T().fn_enable; }
 
 template <int NTW, int EPI, int NTW2, int NST = 2, int MTCAP = 0>
 static int fn_launch(const aew_gemm_nt_t& g, hipStream_t st) {
@@ -679,6 +678,11 @@ static bool fn_supported(const aew_gemm_nt_t& g) {
     return true;
 }
 
+static void fn_shape(const aew_gemm_nt_t& g, int* grid, int* threads) {      // (for nt_pick)
+    *grid = fn_sched(g.M, g.batch).n_chunks;
+    *threads = FN_THREADS;
+}
+
 static int launch_fn(const aew_gemm_nt_t& g, hipStream_t st) {
     const int a = g.N_pad / 128;
     if (g.W2) {
@@ -706,25 +710,6 @@ static int launch_fn(const aew_gemm_nt_t& g, hipStream_t st) {
             if (a == 3) return fn_launch<3, AEW_EPI_STORE, 0>(g, st);
             return fn_launch<4, AEW_EPI_STORE, 0>(g, st);
     }
-}
-
-// Which kernel launch_gemm_nt runs for this descriptor under the current settings (bench.py / tools: per-kernel
-// rooflines are grouped by the kernel that ran, like a rocprofv3 kernel trace groups them by name).
-//   0 k_gemm_nt_bf16 (256- or 192-row tiles)   1 k_gemm_nt_bf16_p64 (64-row tiles: launches of few tiles)
-//   2 k_fn (full-N loader / consumer)          3 k_gemm_nt_f32        4 k_gemm_nt_check      5 an A/B shape
-//   6 k_gemm_nt_bf16_win (one LDS window for both taps of a dilated pair)
-extern "C" int aew_nt_kernel(const aew_gemm_nt_t* gp) {
-    if (!gp) return AEW_E_ARG;
-    const aew_gemm_nt_t& g = *gp;
-    if (g.impl == 1) return 4;
-    if (g.dtype != AEW_BF16) return 3;
-    if (g.impl == 2 && g_fn_enable_flag() && fn_supported(g)) return 2;
-    if (AEW_T().nt_wave_rows != 64) return 5;
-    bool zspan = true;
-    for (int s = 0; s < g.n_segs; ++s) zspan = zspan && g.seg[s].k_len * 2 <= AEW_ZERO_SPAN;
-    const int tiles256 = ((g.M + NT_BM - 1) / NT_BM) * g.batch * (g.N_pad / NT_BN);
-    if (AEW_T().nt_small_tiles > 0 && tiles256 <= AEW_T().nt_small_tiles && zspan) return 1;
-    return win_dwp(g) ? 6 : 0;
 }
 
 extern "C" int aew_set_nt_window(int max_dist) { g_tune.nt_window = max_dist < 0 ? 0 : (max_dist > 64 ? 64 : max_dist); return 0; }

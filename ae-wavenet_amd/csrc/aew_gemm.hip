@@ -2648,6 +2648,9 @@ __global__ void k_gemm_tn_check(const aew_gemm_tn_t g, int splits, int rows_per_
     g.out[(int64_t)slab * g.out_batch_stride + (int64_t)n * g.K_total + k] = acc;
 }
 
+// what nt_pick (host section below) answers: the aew_nt_kernel code, the row of the variant table (-1: a full-N kernel), that
+// row's tile and block, the launch's grid.x (all K ranges), the split-K ranges it runs and the window pieces (0: not the window body)
+struct NtPick { int kernel, variant, bm, bn, threads, lds_bytes, grid, k_split, dwp; };
 #include "aew_win.hip"                                // k_gemm_nt_bf16_win: one LDS window for both dilation taps
 #include "aew_chain.hip"                              // k_nt_chain: a run of dependent NT GEMMs as one launch
 
@@ -2655,6 +2658,65 @@ __global__ void k_gemm_tn_check(const aew_gemm_tn_t g, int splits, int rows_per_
 // =============================================================================================
 // host-side launchers
 // =============================================================================================
+
+// ---- the NT variant table: ONE row per kernel instantiation the NT launcher can run ---------------------------------
+// X(id, sub, aew_nt_kernel code, kernel, dynamic LDS bytes, the kernel's Cfg): tile and block come from the Cfg the kernel
+// itself is built on, and a launch's grid from its row's tile.  ensure_big_lds, the launch and aew_nt_pick read the rows.
+// sub: epilogue (fp32: loader waves).  Codes: 0 the default 256- / 192-row body, 1 the 64-row shapes of small launches,
+// 3 fp32, 4 check, 5 an A/B shape, 6 the one-window body (2, the full-N kernels, keep their own launcher: launch_fn).
+template <int RT, int S, int LD> struct NfRow : NfCfg<RT, S> { static constexpr int BN = NF_BN, THREADS = 256 + 256 * LD; };
+struct CheckRow { static constexpr int BM = 1, BN = 256, THREADS = 64; };   // one thread per (m, channel quad), grid (quads / 64, M, batch)
+#define AEW_NT_BF16_ROWS(X, E)                                                                                          \
+    X(DEEP2, E, 5, (k_gemm_nt_bf16<E, false, 8, 2, 256, 5>), (5 * NtCfg<8, 2, 256>::STAGE_BYTES), NtCfg<8, 2, 256>)      \
+    X(DEEP1, E, 5, (k_gemm_nt_bf16<E, false, 4, 1, 256, 6>), (6 * NtCfg<4, 1, 256>::STAGE_BYTES), NtCfg<4, 1, 256>)      \
+    X(T192, E, 0, (k_gemm_nt_bf16<E, false, 3, 1, 192>), (NtCfg<3, 1, 192>::LDS_BYTES), NtCfg<3, 1, 192>)                \
+    X(T128, E, 5, (k_gemm_nt_bf16<E, false, 4, 1, 128>), (NtCfg<4, 1, 128>::LDS_BYTES), NtCfg<4, 1, 128>)                \
+    X(S64N, E, 1, (k_gemm_nt_bf16_p64<E, 1, 4, 1, 5>), (5 * P64Cfg<1, 4, 1>::STAGE_BYTES), P64Cfg<1, 4, 1>)              \
+    X(S64W8, E, 1, (k_gemm_nt_bf16_p64<E, 1, 4, 2, 5>), (5 * P64Cfg<1, 4, 2>::STAGE_BYTES), P64Cfg<1, 4, 2>)             \
+    X(S64DEEP, E, 1, (k_gemm_nt_bf16_p64<E, 4, 1, 2, 5>), (5 * P64Cfg<4, 1, 2>::STAGE_BYTES), P64Cfg<4, 1, 2>)           \
+    X(S64, E, 1, (k_gemm_nt_bf16_p64<E, 4, 1, 2>), (P64Cfg<4, 1, 2>::LDS_BYTES), P64Cfg<4, 1, 2>)                        \
+    X(K64_256, E, 5, (k_gemm_nt_bf16_p64<E, 4, 4, 2>), (P64Cfg<4, 4, 2>::LDS_BYTES), P64Cfg<4, 4, 2>)                    \
+    X(K64_128, E, 5, (k_gemm_nt_bf16_p64<E, 4, 2, 2>), (P64Cfg<4, 2, 2>::LDS_BYTES), P64Cfg<4, 2, 2>)                    \
+    X(K64_WIDE, E, 5, (k_gemm_nt_bf16_p64<E, 8, 2, 4>), (P64Cfg<8, 2, 4>::LDS_BYTES), P64Cfg<8, 2, 4>)                   \
+    X(WIDE16, E, 5, (k_gemm_nt_bf16<E, false, 4, 2>), (NtCfg<4, 2>::LDS_BYTES), NtCfg<4, 2>)                             \
+    X(PIPE_WIDE, E, 5, (k_gemm_nt_bf16_pipe<E, 2>), (NtCfg<8, 2>::LDS_BYTES), NtCfg<8, 2>)                               \
+    X(PIPE, E, 5, (k_gemm_nt_bf16_pipe<E, 1>), (NtCfg<8, 1>::LDS_BYTES), NtCfg<8, 1>)                                    \
+    X(WIDE, E, 5, (k_gemm_nt_bf16<E, false, 8, 2>), (NtCfg<8, 2>::LDS_BYTES), NtCfg<8, 2>)                               \
+    X(FAT, E, 5, (k_gemm_nt_bf16<E, false, 8>), (NtCfg<4, 1>::LDS_BYTES), NtCfg<8>)                                      \
+    X(DEF, E, 0, (k_gemm_nt_bf16<E, false, 4>), (NtCfg<4, 1>::LDS_BYTES), NtCfg<4>)
+// the one-window body (STORE and GATED only): 256-row tiles with one or four extra window pieces, 192-row tiles with four
+#define AEW_NT_WIN_ROWS(X, E)                                                                       \
+    X(WIN1, E, 6, (k_gemm_nt_bf16_win<E, 4, 1>), (WinCfg<4, 1>::LDS_BYTES), WinCfg<4, 1>)           \
+    X(WIN4, E, 6, (k_gemm_nt_bf16_win<E, 4, 4>), (WinCfg<4, 4>::LDS_BYTES), WinCfg<4, 4>)           \
+    X(WIN192, E, 6, (k_gemm_nt_bf16_win<E, 3, 4>), (WinCfg<3, 4>::LDS_BYTES), WinCfg<3, 4>)
+// fp32: row tiles of 16 * RT rows of the flattened (batch, m) axis, ring of S stages; LD = 1: four loader waves more
+#define AEW_NT_F32_ROWS(X, LD)                                                                      \
+    X(F1_7, LD, 3, (k_gemm_nt_f32<1, 7, LD>), (NfCfg<1, 7>::LDS_BYTES), NfRow<1, 7, LD>)            \
+    X(F1_14, LD, 3, (k_gemm_nt_f32<1, 14, LD>), (NfCfg<1, 14>::LDS_BYTES), NfRow<1, 14, LD>)        \
+    X(F2_12, LD, 3, (k_gemm_nt_f32<2, 12, LD>), (NfCfg<2, 12>::LDS_BYTES), NfRow<2, 12, LD>)        \
+    X(F4_4, LD, 3, (k_gemm_nt_f32<4, 4, LD>), (NfCfg<4, 4>::LDS_BYTES), NfRow<4, 4, LD>)
+#if AEW_FN_ABLATE       /* tools library only: the ablation variants (ABL = true) do not exist in the product build */
+#define AEW_NT_ABL_ROWS(X, G, S, D)                                                                 \
+    X(ABL_WIDE, G, 5, (k_gemm_nt_bf16<G, true, 8, 2>), (NtCfg<8, 2>::LDS_BYTES), NtCfg<8, 2>)       \
+    X(ABL_FAT, G, 5, (k_gemm_nt_bf16<G, true, 8>), (NtCfg<4, 1>::LDS_BYTES), NtCfg<8>)              \
+    X(ABL_DEF, G, 0, (k_gemm_nt_bf16<G, true, 4>), (NtCfg<4, 1>::LDS_BYTES), NtCfg<4>)              \
+    X(ABL_DEF, S, 0, (k_gemm_nt_bf16<S, true, 4>), (NtCfg<4, 1>::LDS_BYTES), NtCfg<4>)              \
+    X(ABL_DEF, D, 0, (k_gemm_nt_bf16<D, true, 4>), (NtCfg<4, 1>::LDS_BYTES), NtCfg<4>)
+#else
+#define AEW_NT_ABL_ROWS(X, G, S, D)
+#endif
+#define AEW_NT_ROWS(X)                                                                                                        \
+    AEW_NT_BF16_ROWS(X, AEW_EPI_STORE) AEW_NT_BF16_ROWS(X, AEW_EPI_GATED) AEW_NT_BF16_ROWS(X, AEW_EPI_RES_SKIP)                \
+    AEW_NT_BF16_ROWS(X, AEW_EPI_DFG) AEW_NT_WIN_ROWS(X, AEW_EPI_STORE) AEW_NT_WIN_ROWS(X, AEW_EPI_GATED) AEW_NT_F32_ROWS(X, 0) \
+    AEW_NT_F32_ROWS(X, 1) X(CHECK, 0, 4, (k_gemm_nt_check<uint16_t>), 0, CheckRow) X(CHECK, 1, 4, (k_gemm_nt_check<float>), 0, CheckRow) \
+    AEW_NT_ABL_ROWS(X, AEW_EPI_GATED, AEW_EPI_STORE, AEW_EPI_DFG)
+
+struct NtRow { const void* fn; const char* name; int kernel, bm, bn, threads, lds; };
+#define AEW_ROW(ID, SUB, CODE, K, LDS, ...) {reinterpret_cast<const void*>(K), #K, CODE, __VA_ARGS__::BM, __VA_ARGS__::BN, __VA_ARGS__::THREADS, LDS},
+#define AEW_ID(ID, SUB, ...) NTV_##ID##_##SUB,
+static const NtRow g_nt_rows[] = {AEW_NT_ROWS(AEW_ROW)};
+enum { AEW_NT_ROWS(AEW_ID) NTV_COUNT };                         // row of (id, sub): NTV_id_sub; NTV_SUB(id, sub) for a run-time sub
+#define NTV_SUB(ID, SUB) (NTV_##ID##_0 + (SUB) * (NTV_##ID##_1 - NTV_##ID##_0))
 
 // kernels using more than 64 KiB of dynamic LDS must opt in once per process
 static int ensure_big_lds() {
@@ -2667,45 +2729,8 @@ static int ensure_big_lds() {
 #define AEW_SET_LDS(fn, bytes)                                                                       \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
     if (e != hipSuccess) return (int)e;
-#define NT_LDS_BYTES (NtCfg<4, 1>::LDS_BYTES)
-#define AEW_SET_NT(EPI)                                                   \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 8, 2, 4>), (P64Cfg<8, 2, 4>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 4, 2, 2>), (P64Cfg<4, 2, 2>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 4, 4, 2>), (P64Cfg<4, 4, 2>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 4, 1, 2>), (P64Cfg<4, 1, 2>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 4, 1, 2, 5>), (5 * P64Cfg<4, 1, 2>::STAGE_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 1, 4, 2, 5>), (5 * P64Cfg<1, 4, 2>::STAGE_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_p64<EPI, 1, 4, 1, 5>), (5 * P64Cfg<1, 4, 1>::STAGE_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16_pipe<EPI, 1>), (NtCfg<8, 1>::LDS_BYTES))      \
-    AEW_SET_LDS((k_gemm_nt_bf16_pipe<EPI, 2>), (NtCfg<8, 2>::LDS_BYTES))      \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 8>), NT_LDS_BYTES)           \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 8, 2>), (NtCfg<8, 2>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 4, 2>), (NtCfg<4, 2>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 4>), NT_LDS_BYTES)          \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 3, 1, 192>), (NtCfg<3, 1, 192>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 4, 1, 128>), (NtCfg<4, 1, 128>::LDS_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 4, 1, 256, 6>), (6 * NtCfg<4, 1, 256>::STAGE_BYTES)) \
-    AEW_SET_LDS((k_gemm_nt_bf16<EPI, false, 8, 2, 256, 5>), (5 * NtCfg<8, 2, 256>::STAGE_BYTES))
-    AEW_SET_NT(AEW_EPI_STORE)
-    AEW_SET_NT(AEW_EPI_GATED)
-    AEW_SET_NT(AEW_EPI_RES_SKIP)
-    AEW_SET_NT(AEW_EPI_DFG)
-#if AEW_FN_ABLATE       /* tools library only: the ablation variants (ABL = true) do not exist in the product build */
-    AEW_SET_LDS((k_gemm_nt_bf16<AEW_EPI_GATED, true, 8>), NT_LDS_BYTES)
-    AEW_SET_LDS((k_gemm_nt_bf16<AEW_EPI_GATED, true, 8, 2>), (NtCfg<8, 2>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_bf16<AEW_EPI_GATED, true, 4>), NT_LDS_BYTES)
-    AEW_SET_LDS((k_gemm_nt_bf16<AEW_EPI_STORE, true, 4>), NT_LDS_BYTES)
-    AEW_SET_LDS((k_gemm_nt_bf16<AEW_EPI_DFG, true, 4>), NT_LDS_BYTES)
-#endif
-#undef AEW_SET_NT
-    AEW_SET_LDS((k_gemm_nt_f32<1, 7, 0>), (NfCfg<1, 7>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<1, 14, 0>), (NfCfg<1, 14>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<2, 12, 0>), (NfCfg<2, 12>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<1, 7, 1>), (NfCfg<1, 7>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<1, 14, 1>), (NfCfg<1, 14>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<2, 12, 1>), (NfCfg<2, 12>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<4, 4, 0>), (NfCfg<4, 4>::LDS_BYTES))
-    AEW_SET_LDS((k_gemm_nt_f32<4, 4, 1>), (NfCfg<4, 4>::LDS_BYTES))
+    for (const NtRow& r : g_nt_rows)
+        if (r.lds) { AEW_SET_LDS(r.fn, r.lds) }
     AEW_SET_LDS(k_gemm_tn_bf16_big, TNB_LDS_BYTES)
     AEW_SET_LDS(k_gemm_tn_bf16<0>, TN_LDS_BYTES)
     AEW_SET_LDS(k_gemm_tn_bf16<1>, TN_LDS_BYTES)
@@ -2731,252 +2756,223 @@ static int check_seg(const aew_seg_t& s, int esize, int ktile) {
 
 // full-N kernels (aew_fn.hip, same translation unit)
 static bool fn_supported(const aew_gemm_nt_t& g);
+static void fn_shape(const aew_gemm_nt_t& g, int* grid, int* threads);
 static int launch_fn(const aew_gemm_nt_t& g, hipStream_t st);
-extern int g_fn_enable_flag();
-
-// the 64 x 64 shape of launches of very few blocks (see the p64 kernel's table): does the launcher take it for g, under
-// the calling thread's tuning record?  *blocks = its grid (one K range)
-static bool nt_small64(const aew_gemm_nt_t& g, int* blocks) {
-    if (g.dtype != AEW_BF16 || g.impl != 0 || g.N_pad % 128) return false;
-    for (int s = 0; s < g.n_segs; ++s)
-        if (g.seg[s].k_len * 2 > AEW_ZERO_SPAN) return false;
-    const int tiles256 = ((g.M + NT_BM - 1) / NT_BM) * g.batch * (g.N_pad / NT_BN);
-    const bool p64r = AEW_T().nt_wave_rows == 64 && AEW_T().nt_small_tiles > 0 && tiles256 <= AEW_T().nt_small_tiles;
-    if (!(p64r && AEW_T().nt_small_w8 && AEW_T().nt_small_n64 > 0 &&
-          ((g.M + 63) / 64) * g.batch * (g.N_pad / 128) <= AEW_T().nt_small_n64))
-        return false;
-    const int row_tiles = ((g.M + 63) / 64) * g.batch;
-    *blocks = ((row_tiles + 7) / 8) * 8 * (g.N_pad / 64);
-    return true;
+static bool nt_takes_fn(const aew_gemm_nt_t& g, const aew_tuning_t& T) {
+    return g.dtype == AEW_BF16 && g.impl == 2 && T.fn_enable && fn_supported(g);
 }
 
-extern "C" int aew_gemm_nt_small_split(const aew_gemm_nt_t* g, int target_blocks, int* k_split, int64_t* ws_bytes, int* n_tickets) {
-    if (!g || !k_split || !ws_bytes || !n_tickets) return AEW_E_ARG;
-    *k_split = 1;
-    *ws_bytes = 0;
-    *n_tickets = 0;
-    int blocks = 0;
-    if (!nt_small64(*g, &blocks)) return 0;
-    const int kt = g->K_total / 64;
-    int best = 1;
-    for (int S = 2; S <= 8; ++S)                             // at least four K tiles per range: the ring is five deep
-        if (kt % S == 0 && kt / S >= 4 && blocks * S <= target_blocks) best = S;
-    if (best == 1) return 0;
-    *k_split = best;
-    *ws_bytes = (int64_t)best * blocks * (P64Cfg<1, 4, 1>::NW * 4 * 64 * 16);
-    *n_tickets = blocks * P64Cfg<1, 4, 1>::NW;
-    return 0;
+// Which kernel runs g under T, on which grid: THE selection - the launcher, aew_nt_kernel / aew_nt_pick, the small-launch
+// split rule and the chain builder all read it.  Pure (no HIP calls, no state beyond T) and total: it checks nothing
+// (nt_check does, around it).  Of a fused gated layer (W2) outside the full-N kernels it describes the GATED launch.
+static void nt_pick(const aew_gemm_nt_t& g, const aew_tuning_t& T, NtPick* out) {
+    if (g.W2 && !nt_takes_fn(g, T)) {                        // runs unfused: the GATED launch, which may itself be a full-N one
+        aew_gemm_nt_t a = g; a.W2 = nullptr;
+        return nt_pick(a, T, out);
+    }
+    NtPick p = {};
+    p.k_split = 1;
+    int v, tiles;
+    if (g.impl == 1) {
+        v = NTV_SUB(CHECK, g.dtype != AEW_BF16);
+        tiles = (((g.epi == AEW_EPI_GATED) ? g.N_pad / 8 : g.N_pad / 4) + 63) / 64;      // grid.x; grid.y / .z = M, batch
+    } else if (g.dtype != AEW_BF16) {
+        // shape by block count (see the kernel's header): one block per CU with the whole LDS as ring where the launch
+        // is that small - 16-row tiles first (more, shorter chains), else 32-row tiles - and the 3-blocks-per-CU shape
+        // for anything larger (workgroups: tiles x k ranges; the shape thresholds see the whole grid).  Split-K launches:
+        // 64-row tiles (four chains per wave share one W fragment: four times the MFMAs per weight byte staged; the k
+        // ranges restore the workgroup count), two workgroups per CU on a 4-stage ring
+        const int rows = g.M * g.batch, n_nt = g.N_pad / NF_BN, ld = T.nf_loaders ? 1 : 0;
+        p.k_split = g.k_split > 1 ? g.k_split : 1;
+        const int tiles1 = ((rows + 15) / 16) * n_nt * p.k_split, tiles2 = ((rows + 31) / 32) * n_nt * p.k_split;
+        v = (p.k_split > 1 && rows >= 64) ? NTV_SUB(F4_4, ld) : (T.nf_deep && tiles1 <= T.nf_deep) ? NTV_SUB(F1_14, ld)
+            : (T.nf_deep && tiles2 <= T.nf_deep) ? NTV_SUB(F2_12, ld) : NTV_SUB(F1_7, ld);
+        tiles = ((rows + g_nt_rows[v].bm - 1) / g_nt_rows[v].bm) * n_nt * p.k_split;
+    } else if (nt_takes_fn(g, T)) {
+        p.kernel = 2; p.variant = -1;
+        fn_shape(g, &p.grid, &p.threads);
+        *out = p;
+        return;
+    } else {
+        bool zspan = true;                                   // masked rows stream from aew_zero_region
+        for (int s = 0; s < g.n_segs && s < AEW_MAX_SEGS; ++s) zspan = zspan && g.seg[s].k_len * 2 <= AEW_ZERO_SPAN;
+        const bool wide = T.nt_wave_rows == 256 && g.N_pad % 256 == 0 && !(g.epi == AEW_EPI_RES_SKIP && g.n_split % 256);
+        const bool p64 = wide && T.nt_pipe == 2 && zspan;    // 256 x 256 tiles, K tiles of 64
+        // 256 x 256 tiles as SIXTEEN waves of 64 x 64 (A/B, round 6: the A operand staged once per two N tiles, with the wave
+        // count of two 8-wave blocks - what the 8-fat-wave form of this tile lacks); one block per CU, 3 x 32 KiB ring
+        const bool wide16 = T.nt_wave_rows == 512 && g.N_pad % 256 == 0 && g.epi != AEW_EPI_RES_SKIP;
+        // launches that would be a small fraction of one tile wave use 64-row tiles (default shape only)
+        const int tiles256 = ((g.M + NT_BM - 1) / NT_BM) * g.batch * (g.N_pad / NT_BN);
+        const bool p64r = T.nt_wave_rows == 64 && T.nt_small_tiles > 0 && tiles256 <= T.nt_small_tiles && zspan;
+        const int dwp = win_dwp(g, T);
+        // memory-bound launches (the K loop of G2 is 8 steps, dz carries 100 MB of epilogue operands): 128-row tiles, so
+        // that the launch is several tile waves and one block's stores run under another's K loop
+        const bool memb = T.nt_mem128 && T.nt_wave_rows == 64 && !p64r && !dwp && zspan &&
+                          (g.epi == AEW_EPI_DFG || (g.epi == AEW_EPI_STORE && g.K_total <= 256));
+        const bool t128 = memb && T.nt_mem128 == 1;
+        const bool p128 = !p64r && (T.nt_wave_rows == 0 || (memb && T.nt_mem128 == 2)) && zspan;      // 128 x 128 tiles, K tiles of 64
+        const bool p256 = T.nt_wave_rows == 1 && zspan;      // 256 x 128 tiles, K tiles of 64, one block per CU
+        // 192-row tiles (8 waves of 48 x 64) where they shorten the launch.  Blocks spread over the 256 CUs before
+        // they double up, and a CU is MFMA-bound with one block already, so a launch costs about
+        // ceil(tiles / 256) * rows-per-tile; the 192-row shape is ~5 % less efficient per row (12 MFMAs per wave
+        // and K step instead of 16), hence the margin.
+        bool t192 = false;
+        if (T.nt_wave_rows == 64 && !p64r && T.nt_rows192 && !memb) {
+            const int tiles192 = ((g.M + 191) / 192) * g.batch * (g.N_pad / NT_BN);
+            const int c256 = ((tiles256 + 255) / 256) * 256, c192 = ((tiles192 + 255) / 256) * 192;
+            t192 = T.nt_rows192 == 2 || c192 * 10 < c256 * 9;
+        }
+        const bool deep2 = (T.nt_deep == 2 || T.nt_deep == 3) && T.nt_wave_rows == 64 && !p64r && !memb && g.N_pad % 256 == 0 &&
+                           !(g.epi == AEW_EPI_RES_SKIP && g.n_split % 256);
+        const bool deep1 = (T.nt_deep == 1 || T.nt_deep == 2) && !deep2 && T.nt_wave_rows == 64 && !p64r && !memb;
+        if (deep1 || deep2) t192 = false;
+        // 64 x 64 tiles for launches of very few 64 x 128 blocks (see the p64 kernel's table); of the other small launches,
+        // those of few blocks run a 5-stage ring, as 8 waves or 2
+        const int blocks64 = ((((g.M + 63) / 64) * g.batch + 7) / 8) * 8 * (g.N_pad / 128);
+        const bool p64n = p64r && T.nt_small_w8 && T.nt_small_n64 > 0 && ((g.M + 63) / 64) * g.batch * (g.N_pad / 128) <= T.nt_small_n64;
+        const int epi = (g.epi >= AEW_EPI_STORE && g.epi <= AEW_EPI_DFG) ? g.epi : AEW_EPI_STORE;   // (others: refused by nt_check)
+        if (dwp && !p64r && T.nt_wave_rows == 64 && !deep1 && !deep2) {   // both taps of a dilated pair from one LDS window
+            p.dwp = dwp;                                     // (192-row tiles always take the 256-row window: four pieces)
+            v = t192 ? NTV_SUB(WIN192, epi) : dwp == 1 ? NTV_SUB(WIN1, epi) : NTV_SUB(WIN4, epi);
+        } else {
+            v = deep2 ? NTV_DEEP2_0 : deep1 ? NTV_DEEP1_0 : t192 ? NTV_T192_0 : t128 ? NTV_T128_0 : p64n ? NTV_S64N_0
+                : (p64r && blocks64 <= T.nt_small_deep) ? (T.nt_small_w8 ? NTV_S64W8_0 : NTV_S64DEEP_0) : p64r ? NTV_S64_0
+                : p256 ? NTV_K64_256_0 : p128 ? NTV_K64_128_0 : p64 ? NTV_K64_WIDE_0 : wide16 ? NTV_WIDE16_0
+                : (T.nt_pipe && wide) ? NTV_PIPE_WIDE_0 : (T.nt_pipe && T.nt_wave_rows == 128) ? NTV_PIPE_0
+                : wide ? NTV_WIDE_0 : T.nt_wave_rows == 128 ? NTV_FAT_0 : NTV_DEF_0;
+            // split-K of a small launch: honoured by the 64 x 64 shape (every other shape contracts the whole K axis; the
+            // plan's slabs then stay unused).  bf16 has no canonical order to keep: the partial sums are added in ascending order
+            if (g.k_split > 1 && v == NTV_S64N_0) p.k_split = g.k_split;
+#if AEW_FN_ABLATE   /* an op with ablation switches takes its ablation variant where the shape picked has one */
+            const int abl = !g.reserved ? -1 : (epi == AEW_EPI_GATED && v == NTV_WIDE_0) ? NTV_ABL_WIDE_1
+                            : (epi == AEW_EPI_GATED && v == NTV_FAT_0) ? NTV_ABL_FAT_1 : v != NTV_DEF_0 ? -1
+                            : epi == AEW_EPI_GATED ? NTV_ABL_DEF_1 : epi == AEW_EPI_STORE ? NTV_ABL_DEF_0 : epi == AEW_EPI_DFG ? NTV_ABL_DEF_3 : -1;
+            v = abl >= 0 ? abl : v + epi * (NTV_DEF_1 - NTV_DEF_0);
+#else
+            v += epi * (NTV_DEF_1 - NTV_DEF_0);
+#endif
+        }
+        const int row_tiles = ((g.M + g_nt_rows[v].bm - 1) / g_nt_rows[v].bm) * g.batch;
+        tiles = ((row_tiles + 7) / 8) * 8 * (g.N_pad / g_nt_rows[v].bn);
+        if (p.k_split <= 8) tiles *= p.k_split;              // (more ranges: refused by nt_check)
+        if (T.nt_wave_rows != 64) p.kernel = 5;              // every shape of an A/B record counts as one
+    }
+    const NtRow& r = g_nt_rows[v];
+    if (!p.kernel) p.kernel = r.kernel;
+    p.variant = v; p.bm = r.bm; p.bn = r.bn; p.threads = r.threads; p.lds_bytes = r.lds; p.grid = tiles;
+    *out = p;
 }
 
-static int launch_gemm_nt(const aew_gemm_nt_t& g, hipStream_t st) {
+// the launcher's descriptor checks, in its order, around the pick (*p: valid on 0)
+static int nt_check(const aew_gemm_nt_t& g, const aew_tuning_t& T, NtPick* p) {
     if (g.n_segs < 1 || g.n_segs > AEW_MAX_SEGS || g.M <= 0 || g.batch <= 0 || !g.W) return AEW_E_ARG;
     if (g.W2) {
         // fused gated layer: z tile -> residual 1x1 (see aewavenet.h)
         if (g.epi != AEW_EPI_GATED || g.dtype != AEW_BF16 || g.N2 <= 0 || g.N2 > g.N2_pad || (g.N2 & 7) || g.N2_pad % 128 ||
             !g.out3.ptr || !g.out0.ptr || g.out0.dtype != AEW_BF16 || ((uintptr_t)g.W2 & 15))
             return AEW_E_ARG;
-        {   // the residual GEMM consumes z for every row m in [0, M): out0 must hold them all
-            const int64_t r0 = g.out0.row_off, r1 = (int64_t)(g.M - 1) * g.out0.row_step + g.out0.row_off;
-            if (r0 < g.out0.row_lo || r0 >= g.out0.row_hi || r1 < g.out0.row_lo || r1 >= g.out0.row_hi) return AEW_E_ARG;
-        }
-        if (!(g.impl == 2 && g_fn_enable_flag() && fn_supported(g))) {
-            // unfused execution with the same result: GATED, then a STORE | ADD_AUX0 GEMM over the z it wrote
-            aew_gemm_nt_t a = g;
-            a.W2 = nullptr;
-            int rc = launch_gemm_nt(a, st);
-            if (rc) return rc;
-            aew_gemm_nt_t b2 = {};
-            b2.dtype = AEW_BF16; b2.impl = g.impl == 2 ? 0 : g.impl;
-            b2.M = g.M; b2.N = g.N2; b2.N_pad = g.N2_pad; b2.batch = g.batch;
-            b2.n_segs = 1; b2.K_total = g.N_pad / 2;
-            b2.seg[0].ptr = g.out0.ptr; b2.seg[0].batch_stride = g.out0.batch_stride; b2.seg[0].row_pitch = g.out0.row_pitch;
-            b2.seg[0].row_step = g.out0.row_step; b2.seg[0].row_off = g.out0.row_off;
-            b2.seg[0].row_lo = g.out0.row_lo; b2.seg[0].row_hi = g.out0.row_hi; b2.seg[0].k_len = g.N_pad / 2;
-            b2.W = g.W2; b2.epi = AEW_EPI_STORE; b2.flags = g.aux0.ptr ? AEW_EF_ADD_AUX0 : 0;
-            b2.out0 = g.out3; b2.aux0 = g.aux0;
-            return launch_gemm_nt(b2, st);
-        }
+        // the residual GEMM consumes z for every row m in [0, M): out0 must hold them all
+        const int64_t r0 = g.out0.row_off, r1 = (int64_t)(g.M - 1) * g.out0.row_step + g.out0.row_off;
+        if (r0 < g.out0.row_lo || r0 >= g.out0.row_hi || r1 < g.out0.row_lo || r1 >= g.out0.row_hi) return AEW_E_ARG;
     }
-    if (g.impl == 2 && g.dtype == AEW_BF16) {
-        if (g_fn_enable_flag() && fn_supported(g)) {
-            const int es2 = 2;
-            int ks = 0;
-            for (int s = 0; s < g.n_segs; ++s) {
-                const int rc = check_seg(g.seg[s], es2, 64);
-                if (rc) return rc;
-                ks += g.seg[s].k_len;
-            }
-            if (ks != g.K_total || g.N > g.N_pad || (g.N & 7)) return AEW_E_ARG;
-            return launch_fn(g, st);
-        }
-        aew_gemm_nt_t a = g;                                  // not covered: the tiled kernel (same results)
-        a.impl = 0;
-        return launch_gemm_nt(a, st);
-    }
-    const int es = g.dtype == AEW_BF16 ? 2 : 4;
-    const int kt = g.dtype == AEW_BF16 ? 64 : NF_BK;        // ABI contract: bf16 segments are 64-aligned
-    const int ntile = g.dtype == AEW_BF16 ? NT_BN : NF_BN;
+    const bool bf = g.dtype == AEW_BF16;
+    const int ntile = bf ? NT_BN : NF_BN;
     int ksum = 0;
     for (int s = 0; s < g.n_segs; ++s) {
-        const int rc = check_seg(g.seg[s], es, kt);
+        const int rc = check_seg(g.seg[s], bf ? 2 : 4, bf ? 64 : NF_BK);      // ABI contract: bf16 segments are 64-aligned
         if (rc) return rc;
         ksum += g.seg[s].k_len;
     }
-    if (ksum != g.K_total || g.N_pad % ntile || g.N > g.N_pad || (g.N & (g.dtype == AEW_BF16 ? 7 : 3))) return AEW_E_ARG;
+    if (ksum != g.K_total || g.N > g.N_pad || (g.N & (bf ? 7 : 3))) return AEW_E_ARG;
+    nt_pick(g, T, p);
+    if (p->kernel == 2) return 0;                            // (fn_supported has looked at the rest)
+    if (g.N_pad % ntile) return AEW_E_ARG;
     if (g.epi == AEW_EPI_RES_SKIP && (g.n_split % ntile)) return AEW_E_ARG;
-    if (g.epi != AEW_EPI_STORE && g.dtype != AEW_BF16) return AEW_E_UNSUP;
-    if (g.dtype == AEW_BF16 && g.impl != 1 && (g.epi == AEW_EPI_STORE || g.epi == AEW_EPI_DFG) &&
+    if (g.epi != AEW_EPI_STORE && !bf) return AEW_E_UNSUP;
+    if (bf && g.impl != 1 && (g.epi == AEW_EPI_STORE || g.epi == AEW_EPI_DFG) &&
         ((g.aux0.ptr && g.aux0.dtype != AEW_BF16) || (g.aux1.ptr && g.aux1.dtype != AEW_BF16)))
         return AEW_E_UNSUP;                                  // the MFMA epilogues prefetch aux rows as bf16
-    if (g.dtype == AEW_BF16 && g.impl != 1 && g.epi == AEW_EPI_STORE && (g.flags & AEW_EF_OUT2_COPY))
+    if (bf && g.impl != 1 && g.epi == AEW_EPI_STORE && (g.flags & AEW_EF_OUT2_COPY))
         return AEW_E_UNSUP;                                  // the copy output exists in the fp32 / check epilogues only
-    if (g.impl == 1) {
-        const int nq = (g.epi == AEW_EPI_GATED) ? g.N_pad / 8 : g.N_pad / 4;
-        dim3 grid((nq + 63) / 64, g.M, g.batch);
-        if (g.dtype == AEW_BF16) hipLaunchKernelGGL(k_gemm_nt_check<uint16_t>, grid, dim3(64), 0, st, g);
-        else hipLaunchKernelGGL(k_gemm_nt_check<float>, grid, dim3(64), 0, st, g);
-    } else if (g.dtype == AEW_BF16) {
-        const int rc = ensure_big_lds();
-        if (rc) return rc;
-        bool zspan = true;                                   // masked rows stream from aew_zero_region
-        for (int s = 0; s < g.n_segs; ++s) zspan = zspan && g.seg[s].k_len * 2 <= AEW_ZERO_SPAN;
-        const bool wide = AEW_T().nt_wave_rows == 256 && g.N_pad % 256 == 0 && !(g.epi == AEW_EPI_RES_SKIP && g.n_split % 256);
-        const bool p64 = wide && AEW_T().nt_pipe == 2 && zspan;    // 256 x 256 tiles, K tiles of 64
-        // 256 x 256 tiles as SIXTEEN waves of 64 x 64 (A/B, round 6: the A operand staged once per two N tiles, with the wave
-        // count of two 8-wave blocks - what the 8-fat-wave form of this tile lacks); one block per CU, 3 x 32 KiB ring
-        const bool wide16 = AEW_T().nt_wave_rows == 512 && g.N_pad % 256 == 0 && g.epi != AEW_EPI_RES_SKIP;
-        // launches that would be a small fraction of one tile wave use 64-row tiles (default shape only)
-        const int tiles256 = ((g.M + NT_BM - 1) / NT_BM) * g.batch * (g.N_pad / NT_BN);
-        const bool p64r = AEW_T().nt_wave_rows == 64 && AEW_T().nt_small_tiles > 0 && tiles256 <= AEW_T().nt_small_tiles && zspan;
-        // memory-bound launches (the K loop of G2 is 8 steps, dz carries 100 MB of epilogue operands): 128-row tiles, so
-        // that the launch is several tile waves and one block's stores run under another's K loop
-        const bool memb = AEW_T().nt_mem128 && AEW_T().nt_wave_rows == 64 && !p64r && !win_dwp(g) && zspan &&
-                          (g.epi == AEW_EPI_DFG || (g.epi == AEW_EPI_STORE && g.K_total <= 256));
-        const bool t128 = memb && AEW_T().nt_mem128 == 1;
-        const bool p128 = !p64r && (AEW_T().nt_wave_rows == 0 || (memb && AEW_T().nt_mem128 == 2)) && zspan;      // 128 x 128 tiles, K tiles of 64
-        const bool p256 = AEW_T().nt_wave_rows == 1 && zspan;      // 256 x 128 tiles, K tiles of 64, one block per CU
-        // 192-row tiles (8 waves of 48 x 64) where they shorten the launch.  Blocks spread over the 256 CUs before
-        // they double up, and a CU is MFMA-bound with one block already, so a launch costs about
-        // ceil(tiles / 256) * rows-per-tile; the 192-row shape is ~5 % less efficient per row (12 MFMAs per wave
-        // and K step instead of 16), hence the margin.
-        bool t192 = false;
-        if (AEW_T().nt_wave_rows == 64 && !p64r && AEW_T().nt_rows192 && !memb) {
-            const int tiles192 = ((g.M + 191) / 192) * g.batch * (g.N_pad / NT_BN);
-            const int c256 = ((tiles256 + 255) / 256) * 256, c192 = ((tiles192 + 255) / 256) * 192;
-            t192 = AEW_T().nt_rows192 == 2 || c192 * 10 < c256 * 9;
-        }
-        const bool deep2 = (AEW_T().nt_deep == 2 || AEW_T().nt_deep == 3) && AEW_T().nt_wave_rows == 64 && !p64r && !memb && g.N_pad % 256 == 0 &&
-                           !(g.epi == AEW_EPI_RES_SKIP && g.n_split % 256);
-        const bool deep1 = (AEW_T().nt_deep == 1 || AEW_T().nt_deep == 2) && !deep2 && AEW_T().nt_wave_rows == 64 && !p64r && !memb;
-        if (deep1 || deep2) t192 = false;
-        if (!p64r && AEW_T().nt_wave_rows == 64 && !deep1 && !deep2) {   // both taps of a dilated pair from one LDS window
-            const int dwp = win_dwp(g);
-            if (dwp) return launch_win(g, dwp, t192, st);
-        }
-        // 64 x 64 tiles for launches of very few 64 x 128 blocks (see the p64 kernel's table)
-        int blocks64 = 0;
-        const bool p64n = nt_small64(g, &blocks64);
-        const int bm = p64r ? 64 : ((p128 || t128) ? 128 : (t192 ? 192 : NT_BM)), bn = p64n ? 64 : ((p128 || p64r) ? 128 : ((wide || deep2 || wide16) ? 256 : NT_BN));
-        const int row_tiles = ((g.M + bm - 1) / bm) * g.batch;
-        dim3 grid(((row_tiles + 7) / 8) * 8 * (g.N_pad / bn));
-        // split-K of a small launch: honoured by the 64 x 64 shape (every other shape contracts the whole K axis; the
-        // plan's slabs then stay unused).  bf16 has no canonical order to keep: the partial sums are added in ascending order
-        if (g.k_split > 1 && p64n && !(AEW_FN_ABLATE && g.reserved)) {
-            const int64_t need = (int64_t)g.k_split * grid.x * (P64Cfg<1, 4, 1>::NW * 4 * 64 * 16);
-            if (g.k_split > 8 || g.K_total % (64 * g.k_split) || !g.ksplit_ws || !g.ksplit_tickets || ((uintptr_t)g.ksplit_ws & 15) ||
-                need > 0x7fffffff)
-                return AEW_E_ARG;
-            grid.x *= g.k_split;
-        }
-#define AEW_NT_GO(EPI, ABL)                                                                                   \
-    do {                                                                                                      \
-        if (!ABL && deep2)                                                                                     \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, false, 8, 2, 256, 5>), grid, dim3((NtCfg<8, 2>::THREADS)), (5 * NtCfg<8, 2, 256>::STAGE_BYTES), st, g); \
-        else if (!ABL && deep1)                                                                                \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, false, 4, 1, 256, 6>), grid, dim3((NtCfg<4>::THREADS)), (6 * NtCfg<4, 1, 256>::STAGE_BYTES), st, g); \
-        else if (!ABL && t192)                                                                                 \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, false, 3, 1, 192>), grid, dim3((NtCfg<3, 1, 192>::THREADS)), (NtCfg<3, 1, 192>::LDS_BYTES), st, g); \
-        else if (!ABL && t128)                                                                                 \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, false, 4, 1, 128>), grid, dim3((NtCfg<4, 1, 128>::THREADS)), (NtCfg<4, 1, 128>::LDS_BYTES), st, g); \
-        else if (!ABL && p64n)                                                                                 \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 1, 4, 1, 5>), grid, dim3(256), (5 * P64Cfg<1, 4, 1>::STAGE_BYTES), st, g); \
-        else if (!ABL && p64r && (int)grid.x <= AEW_T().nt_small_deep && AEW_T().nt_small_w8)                              \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 1, 4, 2, 5>), grid, dim3(512), (5 * P64Cfg<1, 4, 2>::STAGE_BYTES), st, g); \
-        else if (!ABL && p64r && (int)grid.x <= AEW_T().nt_small_deep)                                               \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 4, 1, 2, 5>), grid, dim3(128), (5 * P64Cfg<4, 1, 2>::STAGE_BYTES), st, g); \
-        else if (!ABL && p64r)                                                                                 \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 4, 1, 2>), grid, dim3(128), (P64Cfg<4, 1, 2>::LDS_BYTES), st, g); \
-        else if (!ABL && p256)                                                                                 \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 4, 4, 2>), grid, dim3(512), (P64Cfg<4, 4, 2>::LDS_BYTES), st, g); \
-        else if (!ABL && p128)                                                                                 \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 4, 2, 2>), grid, dim3(256), (P64Cfg<4, 2, 2>::LDS_BYTES), st, g); \
-        else if (!ABL && p64)                                                                                  \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_p64<EPI, 8, 2, 4>), grid, dim3(512), (P64Cfg<8, 2, 4>::LDS_BYTES), st, g); \
-        else if (!ABL && wide16)                                                                               \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, false, 4, 2>), grid, dim3((NtCfg<4, 2>::THREADS)), (NtCfg<4, 2>::LDS_BYTES), st, g); \
-        else if (!ABL && AEW_T().nt_pipe && wide)                                                                   \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_pipe<EPI, 2>), grid, dim3((NtCfg<8, 2>::THREADS)), (NtCfg<8, 2>::LDS_BYTES), st, g); \
-        else if (!ABL && AEW_T().nt_pipe && AEW_T().nt_wave_rows == 128)                                                  \
-            hipLaunchKernelGGL((k_gemm_nt_bf16_pipe<EPI, 1>), grid, dim3((NtCfg<8, 1>::THREADS)), (NtCfg<8, 1>::LDS_BYTES), st, g); \
-        else if (wide)                                                                                        \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, ABL, 8, 2>), grid, dim3((NtCfg<8, 2>::THREADS)), (NtCfg<8, 2>::LDS_BYTES), st, g); \
-        else if (AEW_T().nt_wave_rows == 128)                                                                       \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, ABL, 8>), grid, dim3(NtCfg<8>::THREADS), NT_LDS_BYTES, st, g); \
-        else                                                                                                  \
-            hipLaunchKernelGGL((k_gemm_nt_bf16<EPI, ABL, 4>), grid, dim3(NtCfg<4>::THREADS), NT_LDS_BYTES, st, g); \
-    } while (0)
-        switch (g.epi) {
-            case AEW_EPI_STORE:
-#if AEW_FN_ABLATE
-                if (g.reserved && AEW_T().nt_wave_rows == 64) { AEW_NT_GO(AEW_EPI_STORE, true); break; }
-#endif
-                AEW_NT_GO(AEW_EPI_STORE, false);
-                break;
-            case AEW_EPI_GATED:
-#if AEW_FN_ABLATE
-                if (g.reserved) { AEW_NT_GO(AEW_EPI_GATED, true); break; }
-#endif
-                AEW_NT_GO(AEW_EPI_GATED, false);
-                break;
-            case AEW_EPI_RES_SKIP: AEW_NT_GO(AEW_EPI_RES_SKIP, false); break;
-            case AEW_EPI_DFG:
-#if AEW_FN_ABLATE
-                if (g.reserved && AEW_T().nt_wave_rows == 64) { AEW_NT_GO(AEW_EPI_DFG, true); break; }
-#endif
-                AEW_NT_GO(AEW_EPI_DFG, false);
-                break;
-            default: return AEW_E_UNSUP;
-        }
-#undef AEW_NT_GO
-    } else {
-        const int rc = ensure_big_lds();
-        if (rc) return rc;
-        // shape by block count (see the kernel's header): one block per CU with the whole LDS as ring where the launch
-        // is that small - 16-row tiles first (more, shorter chains), else 32-row tiles - and the 3-blocks-per-CU shape
-        // for anything larger
-        const int rows = g.M * g.batch, n_nt = g.N_pad / NF_BN;
-        const int ksp = g.k_split > 1 ? g.k_split : 1;
-        if (ksp > 1) {
-            if ((ksp != 2 && ksp != 4) || g.impl != 0 || g.epi != AEW_EPI_STORE || !g.ksplit_ws || !g.ksplit_tickets ||
-                g.K_total % (NF_BK * ksp) || ((uintptr_t)g.ksplit_ws & 15) || (int64_t)ksp * ((rows + 31) & ~31) * g.N_pad * 4 > 0x7fffffff)
-                return AEW_E_ARG;
-        }
-        // (workgroups: tiles x k ranges; the shape thresholds see the whole grid)
-        const int tiles1 = ((rows + 15) / 16) * n_nt * ksp, tiles2 = ((rows + 31) / 32) * n_nt * ksp;
-#define AEW_NF_GO(RT, S, GRID)                                                                                       \
-    do {                                                                                                             \
-        if (AEW_T().nf_loaders) hipLaunchKernelGGL((k_gemm_nt_f32<RT, S, 1>), dim3(GRID), dim3(512), (NfCfg<RT, S>::LDS_BYTES), st, g); \
-        else hipLaunchKernelGGL((k_gemm_nt_f32<RT, S, 0>), dim3(GRID), dim3(256), (NfCfg<RT, S>::LDS_BYTES), st, g);  \
-    } while (0)
-        // split-K launches: 64-row tiles (four chains per wave share one W fragment: four times the MFMAs per weight byte
-        // staged; the k ranges restore the workgroup count), two workgroups per CU on a 4-stage ring
-        if (ksp > 1 && rows >= 64) AEW_NF_GO(4, 4, ((rows + 63) / 64) * n_nt * ksp);
-        else if (AEW_T().nf_deep && tiles1 <= AEW_T().nf_deep) AEW_NF_GO(1, 14, tiles1);
-        else if (AEW_T().nf_deep && tiles2 <= AEW_T().nf_deep) AEW_NF_GO(2, 12, tiles2);
-        else AEW_NF_GO(1, 7, tiles1);
-#undef AEW_NF_GO
+    if (g.impl == 1) return 0;
+    if (!bf) {
+        const int ksp = g.k_split, rows = g.M * g.batch;
+        return ksp > 1 && ((ksp != 2 && ksp != 4) || g.impl != 0 || !g.ksplit_ws || !g.ksplit_tickets || g.K_total % (NF_BK * ksp) ||
+                           ((uintptr_t)g.ksplit_ws & 15) || (int64_t)ksp * ((rows + 31) & ~31) * g.N_pad * 4 > 0x7fffffff) ? AEW_E_ARG : 0;
     }
+    // the split-K operands of a small launch the pick honours the hint for (grid: every K range's tiles)
+    if (p->k_split > 1 && (g.k_split > 8 || g.K_total % (64 * g.k_split) || !g.ksplit_ws || !g.ksplit_tickets || ((uintptr_t)g.ksplit_ws & 15) ||
+                           (int64_t)p->grid * (P64Cfg<1, 4, 1>::NW * 4 * 64 * 16) > 0x7fffffff))
+        return AEW_E_ARG;
+    return (g.epi >= AEW_EPI_STORE && g.epi <= AEW_EPI_DFG) ? 0 : AEW_E_UNSUP;
+}
+
+extern "C" int aew_gemm_nt_small_split(const aew_gemm_nt_t* g, int target_blocks, int* k_split, int64_t* ws_bytes, int* n_tickets) {
+    if (!g || !k_split || !ws_bytes || !n_tickets) return AEW_E_ARG;
+    *k_split = 1; *ws_bytes = 0; *n_tickets = 0;
+    // the 64 x 64 shape of launches of very few blocks (see the p64 kernel's table): does the launcher take it for g, under
+    // the calling thread's tuning record?  (impl = 0 descriptors only get the hint)
+    if (g->dtype != AEW_BF16 || g->impl != 0 || g->N_pad % 128) return 0;
+    NtPick p;
+    nt_pick(*g, AEW_T(), &p);
+    if (p.kernel != 1 || p.bn != 64) return 0;
+    const int blocks = ((((g->M + p.bm - 1) / p.bm) * g->batch + 7) / 8) * 8 * (g->N_pad / p.bn);      // its grid, one K range
+    const int kt = g->K_total / 64;
+    int best = 1;
+    for (int S = 2; S <= 8; ++S)                             // at least four K tiles per range: the ring is five deep
+        if (kt % S == 0 && kt / S >= 4 && blocks * S <= target_blocks) best = S;
+    if (best == 1) return 0;
+    *k_split = best; *n_tickets = blocks * P64Cfg<1, 4, 1>::NW;
+    *ws_bytes = (int64_t)best * blocks * (P64Cfg<1, 4, 1>::NW * 4 * 64 * 16);
+    return 0;
+}
+
+static int launch_gemm_nt(const aew_gemm_nt_t& g, hipStream_t st) {
+    NtPick p;
+    int rc = nt_check(g, AEW_T(), &p);
+    if (rc) return rc;
+    if (g.W2 && !nt_takes_fn(g, AEW_T())) {
+        // unfused execution with the same result: GATED, then a STORE | ADD_AUX0 GEMM over the z it wrote
+        aew_gemm_nt_t a = g; a.W2 = nullptr;
+        rc = launch_gemm_nt(a, st);
+        if (rc) return rc;
+        aew_gemm_nt_t b2 = {};
+        b2.dtype = AEW_BF16; b2.impl = g.impl == 2 ? 0 : g.impl;
+        b2.M = g.M; b2.N = g.N2; b2.N_pad = g.N2_pad; b2.batch = g.batch;
+        b2.n_segs = 1; b2.K_total = g.N_pad / 2;
+        b2.seg[0].ptr = g.out0.ptr; b2.seg[0].batch_stride = g.out0.batch_stride; b2.seg[0].row_pitch = g.out0.row_pitch;
+        b2.seg[0].row_step = g.out0.row_step; b2.seg[0].row_off = g.out0.row_off;
+        b2.seg[0].row_lo = g.out0.row_lo; b2.seg[0].row_hi = g.out0.row_hi; b2.seg[0].k_len = g.N_pad / 2;
+        b2.W = g.W2; b2.epi = AEW_EPI_STORE; b2.flags = g.aux0.ptr ? AEW_EF_ADD_AUX0 : 0;
+        b2.out0 = g.out3; b2.aux0 = g.aux0;
+        return launch_gemm_nt(b2, st);
+    }
+    if (p.kernel == 2) return launch_fn(g, st);
+    const NtRow& r = g_nt_rows[p.variant];
+    if (r.lds && (rc = ensure_big_lds())) return rc;
+    void* args[] = {const_cast<aew_gemm_nt_t*>(&g)};
+    (void)hipLaunchKernel(r.fn, g.impl == 1 ? dim3(p.grid, g.M, g.batch) : dim3(p.grid), dim3(r.threads), args, r.lds, st);
     return (int)hipGetLastError();
+}
+
+// Which kernel launch_gemm_nt runs for this descriptor under the current settings (the codes: aewavenet.h; bench.py groups
+// its per-kernel rooflines by it), or the launcher's refusal
+extern "C" int aew_nt_kernel(const aew_gemm_nt_t* g) {
+    NtPick p;
+    const int rc = g ? nt_check(*g, AEW_T(), &p) : AEW_E_ARG;
+    return rc ? rc : p.kernel;
+}
+
+// ... and everything else the launcher decides: the launch_gemm_nt return code without launching; *out on 0
+extern "C" int aew_nt_pick(const aew_gemm_nt_t* g, aew_nt_pick_t* out) {
+    NtPick p;
+    const int rc = g && out ? nt_check(*g, AEW_T(), &p) : AEW_E_ARG;
+    if (rc) return rc;
+    *out = aew_nt_pick_t{p.kernel, p.variant, p.bm, p.bn, p.threads, p.lds_bytes, p.grid, p.k_split, p.dwp, {0}};
+    const char* s = p.variant >= 0 ? g_nt_rows[p.variant].name + 1 : "k_fn)";      // the row's kernel, its parentheses and blanks dropped
+    for (int n = 0; s[1] && n < (int)sizeof(out->name) - 1; ++s)
+        if (*s != ' ') out->name[n++] = *s;
+    return 0;
 }
 
 

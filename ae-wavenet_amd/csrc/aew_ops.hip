@@ -2038,8 +2038,9 @@ static int launch_lc_gather(const aew_lc_gather_t& p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 #define AEW_LC_SCATTER_DET_MAXN 4096
+extern "C" int aew_lc_scatter_needs_zero(int n) { return n > AEW_LC_SCATTER_DET_MAXN; }
 static int launch_lc_scatter(const aew_lc_scatter_t& p, hipStream_t st) {
-    if (p.N <= AEW_LC_SCATTER_DET_MAXN) {                      // every element of dsrc[b][j][0:C] is written: no zeroing needed
+    if (!aew_lc_scatter_needs_zero(p.N)) {                    // every element of dsrc[b][j][0:C] is written: no zeroing needed
         hipLaunchKernelGGL(k_lc_scatter_det, dim3(cdiv64((int64_t)p.B * p.N * p.C, 256)), dim3(256), 0, st, p);
         return (int)hipGetLastError();
     }

@@ -30,6 +30,8 @@ struct WinCfg {
     static constexpr int W_OFF = NXP * 1024;                 // tap 0 W rows; tap 1 follows 8 KiB later
     static constexpr int STAGE_BYTES = W_OFF + 2 * NT_BN * NT_ROWB;
     static constexpr int LDS_BYTES = 2 * STAGE_BYTES;
+    static constexpr int BN = NT_BN, THREADS = 512;          // (the launcher's table reads tile and block here)
+    static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU");
     static_assert(NFULL >= 1 && NFULL <= 2 && (NFULL < 2 || REM <= 8) && NXP <= 24, "three pieces per wave at most");
 };
 
@@ -252,48 +254,17 @@ __global__ __launch_bounds__(512, 4) void k_gemm_nt_bf16_win(const aew_gemm_nt_t
 // ---- host side ----------------------------------------------------------------------------------------------
 
 // window pieces beyond the tile's own that the descriptor needs (1 | 4), or 0 if it cannot use the window kernel
-static int win_dwp(const aew_gemm_nt_t& g) {
-    if (!AEW_T().nt_window || g.dtype != AEW_BF16 || g.impl != 0 || g.n_segs < 2 || g.W2) return 0;
+// (under T; the caller - nt_pick, the chain builder - has settled that g runs on the tiled bf16 kernels)
+static int win_dwp(const aew_gemm_nt_t& g, const aew_tuning_t& T) {
+    if (!T.nt_window || g.dtype != AEW_BF16 || g.n_segs < 2) return 0;
     if (g.epi != AEW_EPI_GATED && g.epi != AEW_EPI_STORE) return 0;
     const aew_seg_t &a = g.seg[0], &c = g.seg[1];
     if (a.ptr != c.ptr || a.batch_stride != c.batch_stride || a.row_pitch != c.row_pitch || a.row_step != 1 ||
         c.row_step != 1 || a.row_lo != c.row_lo || a.row_hi != c.row_hi || a.k_len != c.k_len)
         return 0;
     const int d = a.row_off > c.row_off ? a.row_off - c.row_off : c.row_off - a.row_off;
-    if (d < 1 || d > 64 || d > AEW_T().nt_window) return 0;
+    if (d < 1 || d > 64 || d > T.nt_window) return 0;
     for (int s = 0; s < g.n_segs; ++s)
         if (g.seg[s].k_len % NT_BK || g.seg[s].k_len * 2 > AEW_ZERO_SPAN) return 0;
     return d <= 16 ? 1 : 4;
-}
-
-template <int EPI, int MT, int DWP>
-static int win_launch(const aew_gemm_nt_t& g, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_done{0};          // one bit per device (function attributes are per device)
-    typedef WinCfg<MT, DWP> Cfg;
-    constexpr int lds = Cfg::LDS_BYTES;
-    static_assert(2 * lds <= 160 * 1024, "two blocks per CU");
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {      // (racing threads both set it: harmless)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_bf16_win<EPI, MT, DWP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    const int row_tiles = ((g.M + Cfg::BM - 1) / Cfg::BM) * g.batch;
-    dim3 grid(((row_tiles + 7) / 8) * 8 * (g.N_pad / NT_BN));
-    hipLaunchKernelGGL((k_gemm_nt_bf16_win<EPI, MT, DWP>), grid, dim3(512), lds, st, g);
-    return (int)hipGetLastError();
-}
-
-// t192: 192-row tiles (the launcher's per-CU cost model); they always take the 256-row window (DWP = 4: 16 pieces,
-// two per wave)
-static int launch_win(const aew_gemm_nt_t& g, int dwp, bool t192, hipStream_t st) {
-    if (g.epi == AEW_EPI_GATED) {
-        if (t192) return win_launch<AEW_EPI_GATED, 3, 4>(g, st);
-        return dwp == 1 ? win_launch<AEW_EPI_GATED, 4, 1>(g, st) : win_launch<AEW_EPI_GATED, 4, 4>(g, st);
-    }
-    if (t192) return win_launch<AEW_EPI_STORE, 3, 4>(g, st);
-    return dwp == 1 ? win_launch<AEW_EPI_STORE, 4, 1>(g, st) : win_launch<AEW_EPI_STORE, 4, 4>(g, st);
 }

@@ -79,6 +79,7 @@ extern "C" int aew_sizeof(int which) {
         case 13: return (int)sizeof(aew_uw_chunk_t);
         case 14: return (int)sizeof(aew_uw_track_t);
         case 15: return (int)sizeof(aew_update_ratio_t);
+        case 16: return (int)sizeof(aew_nt_pick_t);
         default: return -1;
     }
 }

@@ -1012,8 +1012,8 @@ class DecoderPlan:
                                        [dlc1.seg(Cp, row_off=-t) for t in range(3)], self.WlcT.ptr,
                                        out0=self.dlcj.view(), impl=impl), "d.lc_conv", TAG_UPS)
         # ---- jitter scatter back to the LC source
-        if self.Ne > 4096:                                         # (up to 4096 conditioning vectors per window the scatter runs in
-            plan.zero(self.ws, self.dlc_src.name)                  #  its gather form, which writes every element: no atomics, no zeroing)
+        if L.load().aew_lc_scatter_needs_zero(self.Ne):            # (short windows: the scatter runs in its gather form, which
+            plan.zero(self.ws, self.dlc_src.name)                  #  writes every element: no atomics, no zeroing)
         sc = L.LcScatter()
         sc.d, sc.d_bs, sc.d_pitch = self.dlcj.ptr, self.dlcj.bs, self.dlcj.pitch
         sc.jitter, sc.jit_pitch = self.jitter.data_ptr(), self.jitter.shape[1]

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 22
+#define AEW_ABI_VERSION 23
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -328,6 +328,9 @@ typedef struct {                 /* transpose of the gather: dsrc[b][j][c] += d[
     int32_t B, N, C;
     int32_t take_compat;
 } aew_lc_scatter_t;
+/* 1: an AEW_OP_LC_SCATTER over n conditioning vectors ADDS into dsrc (atomics: the plan zeroes dsrc in front of it);
+ * 0: it runs in its gather form, which writes every element of dsrc[b][j][0:C] (no zeroing needed).  Host-only. */
+int aew_lc_scatter_needs_zero(int n);
 
 typedef struct {                 /* per-(batch,layer) gated bias incl. speaker term           */
     /* bias[b][l][pack(co)] = conv_bias_l[co] + sum_j V_l[co][C_lc + j] * gc[b][j]
@@ -755,7 +758,7 @@ typedef struct {
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
@@ -851,8 +854,25 @@ int aew_set_fn_ring3(int min_k_tiles);   /* plain full-N GEMMs of >= this many 6
                                             operand ring (default 16; 0 = never).  Same results either way.       */
 /* Which kernel a GEMM_NT descriptor dispatches to under the current settings: 0 k_gemm_nt_bf16 (256- / 192-row tiles),
  * 1 k_gemm_nt_bf16_p64 (64-row tiles, small launches), 2 k_fn, 3 k_gemm_nt_f32, 4 the scalar check kernel, 5 an A/B
- * shape.  Measurement aid: lets a caller group per-op times by kernel the way a rocprofv3 kernel trace does. */
+ * shape, 6 the one-window kernel - or the error code the launch would return for a descriptor it refuses.  Measurement
+ * aid: lets a caller group per-op times by kernel the way a rocprofv3 kernel trace does. */
 int aew_nt_kernel(const aew_gemm_nt_t* g);
+/* ABI 23, test and measurement aid: everything the launcher decides for g under the current settings, without launching.
+ * Returns what the launch would return for a malformed / unsupported descriptor (*out untouched), else 0 and
+ *   kernel      the aew_nt_kernel code (6: the one-window kernel)
+ *   variant     row of the library's table of NT kernel instantiations (-1: a full-N kernel, chosen by its own launcher:
+ *               name "k_fn", lds_bytes 0)
+ *   bm, bn      output tile of that row; threads, lds_bytes: its block and dynamic LDS
+ *   grid        grid.x of the launch (k_split copies of the tile grid)
+ *   k_split     K ranges the launch runs (1 unless the shape honours aew_gemm_nt_t.k_split)
+ *   dwp         extra 16-row window pieces of the one-window kernel (1 | 4), 0 for every other kernel
+ *   name        the instantiation as written in the table, blanks removed: "k_gemm_nt_bf16<0,false,4>"
+ * Of a fused gated layer (W2) that runs unfused it describes the first launch, the GATED one. */
+typedef struct {
+    int32_t kernel, variant, bm, bn, threads, lds_bytes, grid, k_split, dwp;
+    char name[96];
+} aew_nt_pick_t;
+int aew_nt_pick(const aew_gemm_nt_t* g, aew_nt_pick_t* out);
 /* Default shape only: memory-bound plain launches (DFG epilogue, or K_total <= 256: wavenet.py:103-109 and the backward of
  * :100-102) as 128-row tiles - 0 the 256- / 192-row tiles, 1 128 x 128 tiles with K tiles of 32 (4 waves, three blocks
  * per CU), 2 128 x 128 tiles with K tiles of 64 (two blocks per CU).  Bit-identical results. */

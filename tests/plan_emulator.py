@@ -346,7 +346,7 @@ class Emu:
                + torch.arange(p.C)[None, None, :])
         gsrc = self.rd(p.d, idx)
         t, off = self.flat(p.dsrc)
-        if p.N <= 4096:
+        if not L.load().aew_lc_scatter_needs_zero(p.N):
             # gather form (k_lc_scatter_det): every element of dsrc[b][j][0:C] is WRITTEN, the plan does not zero the target
             tgt = (torch.arange(p.B)[:, None, None] * p.dsrc_bs + torch.arange(p.N)[None, :, None] * p.dsrc_pitch
                    + torch.arange(p.C)[None, None, :])

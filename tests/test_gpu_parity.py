@@ -124,11 +124,12 @@ def test_gemm_nt(dtype, epi):
     lib = L.load()
     try:
         # impl 0 under every tile / wave shape of the bf16 kernel (64: 8 waves of 64x64, 128: 4 waves of
-        # 128x64, 256: 256x256 tiles where N_pad allows); the shapes must agree bit for bit
+        # 128x64, 256: 256x256 tiles where N_pad allows, 512: those as 16 waves of 64x64 - RES_SKIP stays on the default
+        # body); the shapes must agree bit for bit
         # (impl, shape, pipe, small): small = tile-count threshold of the 64-row tiles (0: plain 256x128)
         # small < 0: 192-row tiles forced (small tiles off)
         for impl, shape, pipe, small in ((0, 64, 1, 0), (1, 64, 1, 0), (0, 64, 1, 128), (0, 64, 1, -1), (0, 0, 1, 0), (0, 1, 1, 0),
-                                         (0, 128, 1, 0), (0, 128, 0, 0), (0, 256, 0, 0), (0, 256, 1, 0), (0, 256, 2, 0)):
+                                         (0, 128, 1, 0), (0, 128, 0, 0), (0, 256, 0, 0), (0, 256, 1, 0), (0, 256, 2, 0), (0, 512, 1, 0)):
             lib.aew_set_nt_rows192(2 if small < 0 else 0)
             small = max(small, 0)
             lib.aew_set_nt_wave_rows(shape)
