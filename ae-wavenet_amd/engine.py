@@ -17,7 +17,7 @@ Reference arithmetic restated by these plans (citations into the reference check
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -145,10 +145,38 @@ def _gate_groups(D: int):
         yield full * 16, 1, D % 16
 
 
+class Piece(NamedTuple):
+    """One rectangular piece of the index map between a parameter tensor and a packed matrix, stated once for both
+    directions: p_* address the parameter (elements, relative to it), m_* the matrix.  A weight-gradient slab with the
+    matrix's layout is unpacked by the pieces that pack the matrix."""
+    pname: str
+    p_off: int
+    p_strides: Sequence[int]
+    dims: Sequence[int]
+    m_off: int
+    m_strides: Sequence[int]
+
+    def at(self, m_off: int, m_strides: Sequence[int]) -> "Piece":
+        """The same parameter elements in another matrix layout (dgrad copies of a weight)."""
+        return self._replace(m_off=m_off, m_strides=m_strides)
+
+
+# where a weight gradient lands: `slabs` fp32 partial results `stride` elements apart, summed into the flat gradients by table `tbl`
+WGrad = NamedTuple("WGrad", [("ptr", int), ("stride", int), ("slabs", int), ("tbl", CopyTableBuilder)])
+
+
+def wgrad_slab(ws: Workspace, name: str, t: "L.GemmTN", slabs: int, tbl: CopyTableBuilder) -> WGrad:
+    """Allocates the result of a TN descriptor (`slabs` partial sums of N_pad x K_total) and points the descriptor at it."""
+    stride = t.N_pad * t.K_total
+    ptr = ws.alloc(name, slabs * stride, torch.float32).data_ptr()
+    t.out, t.out_batch_stride = ptr, stride
+    return WGrad(ptr, stride, slabs, tbl)
+
+
 class Packer:
-    """Emits strided-copy records in both directions for one packed matrix:
+    """Emits strided-copy records in both directions for the pieces of packed matrices:
     pack   params(fp32)        -> packed weights (bf16 / f32)
-    unpack wgrad slabs (fp32)  -> flat grads (fp32), summing `slabs` partials."""
+    unpack wgrad slabs (fp32)  -> flat grads (fp32), summing the slabs."""
 
     def __init__(self, ps: ParamStore, pack_tbl: CopyTableBuilder, unpack_tbl: CopyTableBuilder,
                  late_tbl: Optional[CopyTableBuilder] = None, first_tbl: Optional[CopyTableBuilder] = None):
@@ -156,25 +184,18 @@ class Packer:
         self.late_tbl = late_tbl            # packs that only the backward reads (dgrad layouts): off the forward's start
         self.first_tbl = first_tbl          # packs the very first GEMM of the step needs (first=True): the only ones it waits for
 
-    def rec(self, pname: str, p_off: int, p_strides: Sequence[int], dims: Sequence[int],
-            w_mat: Optional[Mat], w_off: int, w_strides: Sequence[int],
-            g_ptr: int = 0, g_strides: Optional[Sequence[int]] = None, slabs: int = 0, slab_stride: int = 0,
-            g_off: Optional[int] = None, late: bool = False, first: bool = False):
-        """One rectangular piece.  p_* address the parameter tensor (elements, relative to the
-        parameter), w_* the packed forward matrix, g_* the wgrad slab (defaults to the same
-        layout as the packed matrix)."""
-        ps = self.ps
-        if w_mat is not None:
-            tbl = self.late_tbl if (late and self.late_tbl is not None) else self.pack_tbl
-            if first and not late and self.first_tbl is not None:
-                tbl = self.first_tbl
-            tbl.add(ps.ptr(pname) + 4 * p_off, w_mat.ptr + w_off * ESIZE[w_mat.dtype],
-                    dims, p_strides, w_strides, F3, w_mat.dtype)
-        if g_ptr:
-            gs = list(g_strides if g_strides is not None else w_strides)
-            go = w_off if g_off is None else g_off
-            self.unpack_tbl.add(g_ptr + 4 * go, ps.ptr(pname, grad=True) + 4 * p_off, dims, gs,
-                                p_strides, F3, F3, red_n=slabs, red_stride=slab_stride)
+    def pack(self, pc: Piece, w_mat: Mat, late: bool = False, first: bool = False):
+        tbl = self.late_tbl if (late and self.late_tbl is not None) else self.pack_tbl
+        if first and not late and self.first_tbl is not None:
+            tbl = self.first_tbl
+        tbl.add(self.ps.ptr(pc.pname) + 4 * pc.p_off, w_mat.ptr + pc.m_off * ESIZE[w_mat.dtype],
+                pc.dims, pc.p_strides, pc.m_strides, F3, w_mat.dtype)
+
+    def unpack(self, pieces: Sequence[Piece], g: WGrad):
+        """The gradients of the pieces out of result g (the table is g's: the router's choice, or this packer's own)."""
+        for pc in pieces:
+            g.tbl.add(g.ptr + 4 * pc.m_off, self.ps.ptr(pc.pname, grad=True) + 4 * pc.p_off, pc.dims, pc.m_strides,
+                      pc.p_strides, F3, F3, red_n=g.slabs, red_stride=g.stride)
 
 
 # ------------------------------------------------------------------------------------------
@@ -279,6 +300,10 @@ class DecoderPlan:
         self.NL = len(geom.layers)
         self.T, self.w = geom.dec_in_len, geom.n_win
         self.Ne = geom.embed_len
+        self.peak_ptrs = None               # (per-position peak log-probability, arg-max) the forward softmax writes (set by TrainEngine)
+        self.unpack_early_tbl: Optional[CopyTableBuilder] = None    # build_backward's early table, as given
+        self.hi_first_layer: Optional[int] = None   # build_backward: layers from here up are final mid-chain (WgradRouter)
+        self.tail_lane_used, self._lane_rr = 0, 0   # build_backward: tail_lane as applied; _next_lane's rotation
         self._alloc()
         self._pack_records()
 
@@ -346,9 +371,13 @@ class DecoderPlan:
     def _wmat(self, name, rows, cols, dt=BF) -> Mat:
         return Mat.new(self.ws, self.pre + "wp." + name, 1, rows, cols, dt)
 
-    def _gslab(self, name, rows, cols, slabs) -> Tuple[int, int]:
-        t = self.ws.alloc(self.pre + "wg." + name, slabs * rows * cols, torch.float32)
-        return t.data_ptr(), rows * cols
+    def _chains(self, plan: Plan, n_chains: int):
+        """One stage of n_chains half-batch chains: per chain c sets its lane - 4 + c, unless split_one_lane interleaves two
+        chains on the main lane - and yields (c, first batch element, label suffix); back on the main lane afterwards."""
+        for c in range(n_chains):
+            plan.lane = (4 + c) if (n_chains > 1 and not self.split_one_lane) else 0
+            yield c, c * (self.B // n_chains), (f".c{c}" if n_chains > 1 else "")
+        plan.lane = 0
 
     # -- packed weight matrices and their pack/unpack records ------------------------------
     def _pack_records(self):
@@ -358,8 +387,9 @@ class DecoderPlan:
         Cc = Clc + self.Gc
         NL = self.NL
         self.Wfg, self.Wrs, self.WrsT, self.WfgT = [], [], [], []
-        self.tn: Dict[str, L.GemmTN] = {}         # wgrad ops by name (built in build_backward)
-        self.gbuf: Dict[str, Tuple[int, int, int]] = {}  # name -> (ptr, slab stride, slabs)
+        # name of a weight gradient -> the pieces of the packed matrix whose layout its slab has (packed here, unpacked
+        # by build_backward from the same pieces)
+        self.lay: Dict[str, List[Piece]] = {}
         Kfg = 2 * Rp + Cp
         # the 20-segment GEMMs (skip sum, cond gradient) run as two halves: the half whose inputs exist
         # mid-chain goes to a side lane (fills tile-wave tails), the other half adds it as aux
@@ -369,49 +399,59 @@ class DecoderPlan:
         self.VfgT_hi = self._wmat("VfgT_hi", Cp, max(n_hi, 1) * 2 * Dp)
         self.Wskp_lo = self._wmat("skp_lo", Sp, n_lo * Dp)
         self.Wskp_hi = self._wmat("skp_hi", Sp, max(n_hi, 1) * Dp)
-        # base layer as a row gather: transposed fp32 copy [Q][Rp] (wavenet.py:348-351)
+        # base layer as a row gather: transposed fp32 copy [Q][Rp] (wavenet.py:348-351).  (Its gradient comes out of a TN
+        # GEMM over the one-hot matrix as [Rp][Qp], not in this layout: build_backward states that map itself.)
         self.Wbase_t = self._wmat("base_t", Q, Rp, F3)
-        pk.rec(p + "base_layer.weight", 0, [Q, 1], [R, Q], self.Wbase_t, 0, [1, Rp])
+        pk.pack(Piece(p + "base_layer.weight", 0, [Q, 1], [R, Q], 0, [1, Rp]), self.Wbase_t)
         for l in range(NL):
             last = l == NL - 1
             q = p + f"conv_layers.{l}."
             Wfg = self._wmat(f"fg{l}", 2 * Dp, Kfg)
             WfgT = self._wmat(f"fgT{l}", Rp, 4 * Dp)
             self.Wfg.append(Wfg); self.WfgT.append(WfgT)
+            Vt, lv, nv = (self.VfgT_lo, l, n_lo) if l < n_lo else (self.VfgT_hi, l - n_lo, n_hi)
+            fg = self.lay[f"fg{l}"] = []
             for gate, nm in ((0, "signal"), (1, "gate")):
                 for co0, ng, gl in _gate_groups(D):
                     row0 = (co0 // 16) * 32 + 16 * gate
                     # conv weight [D][R][2] -> Wfg rows, tap-major K; and WfgT (dgrad) layout
-                    pk.rec(q + f"conv_{nm}.weight", co0 * R * 2, [16 * R * 2, R * 2, 2, 1], [ng, gl, R, 2],
-                           Wfg, row0 * Kfg, [32 * Kfg, Kfg, 1, Rp])
-                    pk.rec(q + f"conv_{nm}.weight", co0 * R * 2, [16 * R * 2, R * 2, 2, 1], [ng, gl, R, 2],
-                           WfgT, row0, [32, 1, 4 * Dp, 2 * Dp])
+                    conv = Piece(q + f"conv_{nm}.weight", co0 * R * 2, [16 * R * 2, R * 2, 2, 1], [ng, gl, R, 2],
+                                 row0 * Kfg, [32 * Kfg, Kfg, 1, Rp])
                     # conditioning projection [D][Cc][1], first Clc columns only
-                    pk.rec(q + f"proj_{nm}.weight", co0 * Cc, [16 * Cc, Cc, 1], [ng, gl, Clc],
-                           Wfg, row0 * Kfg + 2 * Rp, [32 * Kfg, Kfg, 1])
-                    Vt, lv, nv = (self.VfgT_lo, l, self.n_lo) if l < self.n_lo else (self.VfgT_hi, l - self.n_lo, NL - self.n_lo)
-                    pk.rec(q + f"proj_{nm}.weight", co0 * Cc, [16 * Cc, Cc, 1], [ng, gl, Clc],
-                           Vt, lv * 2 * Dp + row0, [32, 1, nv * 2 * Dp])
+                    proj = Piece(q + f"proj_{nm}.weight", co0 * Cc, [16 * Cc, Cc, 1], [ng, gl, Clc],
+                                 row0 * Kfg + 2 * Rp, [32 * Kfg, Kfg, 1])
+                    fg += [conv, proj]
+                    pk.pack(conv, Wfg)
+                    pk.pack(conv.at(row0, [32, 1, 4 * Dp, 2 * Dp]), WfgT)
+                    pk.pack(proj, Wfg)
+                    pk.pack(proj.at(lv * 2 * Dp + row0, [32, 1, nv * 2 * Dp]), Vt)
             # residual 1x1 (forward) and [res | skip]^T (backward dz); the skip 1x1s of ALL layers
             # form one matrix Wskp [Sp][NL*Dp] for the deferred skip GEMM (wavenet.py:103,357)
             Nrs = Sp if last else Rp + Sp
             Wrs = None if last else self._wmat(f"rs{l}", Rp, Dp)
             WrsT = self._wmat(f"rsT{l}", Dp, Nrs)
             self.Wrs.append(Wrs); self.WrsT.append(WrsT)
-            so = 0 if last else Rp
             if not last:
-                pk.rec(q + "dil_res.weight", 0, [D, 1], [R, D], Wrs, 0, [Dp, 1])
-                pk.rec(q + "dil_res.weight", 0, [D, 1], [R, D], WrsT, 0, [1, Nrs])
-            Ws, ls, ns = (self.Wskp_lo, l, self.n_lo) if l < self.n_lo else (self.Wskp_hi, l - self.n_lo, NL - self.n_lo)
-            pk.rec(q + "dil_skp.weight", 0, [D, 1], [S, D], Ws, ls * Dp, [ns * Dp, 1])
-            pk.rec(q + "dil_skp.weight", 0, [D, 1], [S, D], WrsT, so, [1, Nrs])
+                res = Piece(q + "dil_res.weight", 0, [D, 1], [R, D], 0, [Dp, 1])
+                self.lay[f"res{l}"] = [res]
+                pk.pack(res, Wrs)
+                pk.pack(res.at(0, [1, Nrs]), WrsT)
+            # (the skip gradient spans all NL layers in ONE matrix whatever split_multiseg does to the packed pair:
+            # _skip_piece states its map)
+            Ws, ls, ns = (self.Wskp_lo, l, n_lo) if l < n_lo else (self.Wskp_hi, l - n_lo, n_hi)
+            skp = self._skip_piece(l, ls, ns)
+            pk.pack(skp, Ws)
+            pk.pack(skp.at(0 if last else Rp, [1, Nrs]), WrsT)
         # post network
         self.Wp1, self.Wp1T = self._wmat("p1", Pp, Sp), self._wmat("p1T", Sp, Pp)
         self.Wp2, self.Wp2T = self._wmat("p2", Qp, Pp), self._wmat("p2T", Pp, Qp)
-        pk.rec(p + "post1.weight", 0, [S, 1], [P, S], self.Wp1, 0, [Sp, 1])
-        pk.rec(p + "post1.weight", 0, [S, 1], [P, S], self.Wp1T, 0, [1, Pp])
-        pk.rec(p + "post2.weight", 0, [P, 1], [Q, P], self.Wp2, 0, [Pp, 1])
-        pk.rec(p + "post2.weight", 0, [P, 1], [Q, P], self.Wp2T, 0, [1, Qp])
+        p1 = Piece(p + "post1.weight", 0, [S, 1], [P, S], 0, [Sp, 1])
+        p2 = Piece(p + "post2.weight", 0, [P, 1], [Q, P], 0, [Pp, 1])
+        self.lay["p1"], self.lay["p2"] = [p1], [p2]
+        pk.pack(p1, self.Wp1)
+        pk.pack(p1.at(0, [1, Pp]), self.Wp1T)
+        pk.pack(p2, self.Wp2)
+        pk.pack(p2.at(0, [1, Qp]), self.Wp2T)
         # fp32 bias vectors padded to N_pad
         self.bias_vec: Dict[str, int] = {}
         for nm, n, npad in (("post1", P, Pp), ("post2", Q, Qp), ("lc_conv", Clc, Cp)):
@@ -422,11 +462,12 @@ class DecoderPlan:
         # LC conv [Clc][n_lc_in][3]
         nin = self.n_lc_in
         self.Wlc, self.WlcT = self._wmat("lc", Cp, 3 * Lp), self._wmat("lcT", Lp, 3 * Cp)
-        pk.rec(p + "lc_conv.weight", 0, [nin * 3, 3, 1], [Clc, nin, 3], self.Wlc, 0, [3 * Lp, 1, Lp])
-        pk.rec(p + "lc_conv.weight", 0, [nin * 3, 3, 1], [Clc, nin, 3], self.WlcT, 0, [1, 3 * Cp, Cp])
+        lc = Piece(p + "lc_conv.weight", 0, [nin * 3, 3, 1], [Clc, nin, 3], 0, [3 * Lp, 1, Lp])
+        self.lay["lc"] = [lc]
+        pk.pack(lc, self.Wlc)
+        pk.pack(lc.at(0, [1, 3 * Cp, Cp]), self.WlcT)
         # upsamplers: ConvTranspose1d weight [ci][co][k]
-        self.Wup: List[List[Mat]] = []
-        self.WupT: List[Mat] = []
+        self.Wup, self.Wup_all, self.WupT = [], [], []          # per stage: [phase matrices], all phases as one, dgrad layout
         for i, (f, s) in enumerate(zip(self.hps.lc_upsample_filt_sizes, self.hps.lc_upsample_strides)):
             nm = p + f"lc_upsample.{i}.tconv.weight"
             phases = []
@@ -435,19 +476,26 @@ class DecoderPlan:
             for ph in range(s):
                 Wm = Mat(self.ws, Wall.name, 1, Cp, Kph, BF, base_off=ph * Cp * Kph)
                 # [co][j*Cp + ci] <- W[ci][co][ph + s*j]
-                pk.rec(nm, ph, [f, Clc * f, s], [Clc, Clc, f // s], Wm, 0, [(f // s) * Cp, 1, Cp])
+                pk.pack(Piece(nm, ph, [f, Clc * f, s], [Clc, Clc, f // s], 0, [(f // s) * Cp, 1, Cp]), Wm)
                 phases.append(Wm)
             self.Wup.append(phases)
-            self.Wup_all = getattr(self, "Wup_all", []) + [Wall]
+            self.Wup_all.append(Wall)
             WT = self._wmat(f"upT{i}", Cp, f * Cp)
-            # [ci][k*Cp + co] <- W[ci][co][k]
-            pk.rec(nm, 0, [Clc * f, f, 1], [Clc, Clc, f], WT, 0, [f * Cp, 1, Cp])
+            # [ci][k*Cp + co] <- W[ci][co][k]: the dgrad matrix, and the layout of the weight gradient
+            up = Piece(nm, 0, [Clc * f, f, 1], [Clc, Clc, f], 0, [f * Cp, 1, Cp])
+            self.lay[f"up{i}"] = [up]
+            pk.pack(up, WT)
             self.WupT.append(WT)
             t = self.ws.alloc(p + f"wp.bias.up{i}", s * Cp, torch.float32)     # the bias once per phase
             self.bias_vec[f"up{i}"] = t.data_ptr()
             for ph in range(s):
                 pk.pack_tbl.add(ps.ptr(p + f"lc_upsample.{i}.tconv.bias"), t.data_ptr() + 4 * ph * Cp, [Clc], [1], [1],
                                 F3, F3)
+
+    def _skip_piece(self, l: int, col_layer: int, n_layers: int) -> Piece:
+        """dil_skp of layer l as columns [col_layer * Dp, +D) of a skip matrix that holds n_layers layers side by side."""
+        return Piece(self.pre + f"conv_layers.{l}.dil_skp.weight", 0, [self.D, 1], [self.S, self.D],
+                     col_layer * self.Dp, [n_layers * self.Dp, 1])
 
     # -- forward ---------------------------------------------------------------------------
     def build_forward(self, plan: Plan, need_onehot: bool = True, after_logits=None, after_nll=None):
@@ -545,15 +593,12 @@ class DecoderPlan:
             last = l == NL - 1
             x = self.x[l]
             P_l = lg.out_len
-            for c in range(n_chains):
-                b0 = c * nb
+            for c, b0, sfx in self._chains(plan, n_chains):
                 # two chains: BOTH on side lanes (4 and 5: the ones aew_set_lanes(2) honours alone).  A side op is ordered after every main-lane op emitted before
                 # it, so a chain left on the main lane would hold the other one back at every layer; with no main-lane op
                 # between the first layer and the skip sum the two lanes run free
-                plan.lane = (4 + c) if (n_chains > 1 and not self.split_one_lane) else 0
                 segs = [x.seg(Rp, b0=b0), x.seg(Rp, row_off=lg.dil, b0=b0),
                         self.cond.seg(Cp, row_off=lg.cond_lead, b0=b0)]
-                sfx = f".c{c}" if n_chains > 1 else ""
                 gkw = dict(epi=L.EPI_GATED, out0=self.z[l].view(b0=b0), out1=self.pf[l].view(b0=b0),
                            out2=self.pg[l].view(b0=b0),
                            bias_ptr=self.bias_bl.data_ptr() + 4 * (l * 2 * Dp + b0 * NL * 2 * Dp), bias_bs=NL * 2 * Dp)
@@ -622,13 +667,6 @@ class DecoderPlan:
         sb.B, sb.L, sb.D, sb.D_pad, sb.C_lc, sb.G = self.B, self.NL, self.D, self.Dp, self.Clc, self.Gc
         sb.n_speakers = self.hps.n_speakers
 
-    def _spk_det(self, sb: "L.SpkBwd", tag: str):
-        """Scratch + ticket of the deterministic speaker-embedding sums (aew_spk_bwd_t.det_scratch: one [16][16] block of terms
-        per (layer, filt | gate, chunk of 16 batch elements), added in a fixed order by the last block)."""
-        chunks = (self.B + 15) // 16
-        sb.det_scratch = self.ws.alloc(self.pre + f"det.spk_{tag}.scratch", self.NL * 2 * chunks * 256, torch.float32).data_ptr()
-        sb.det_tickets = self.ws.alloc(self.pre + f"det.spk_{tag}.tickets", 4, torch.int32, zero=True).data_ptr()
-
     def _softmax(self, backward: bool, scale: float) -> L.SoftmaxNll:
         sm = L.SoftmaxNll()
         sm.logits, sm.bs, sm.pitch = self.logits.ptr, self.logits.bs, self.logits.pitch
@@ -637,380 +675,205 @@ class DecoderPlan:
         sm.nll, sm.ptgt = self.nll.data_ptr(), self.ptgt.data_ptr()
         sm.dlogits, sm.dl_bs, sm.dl_pitch = self.dlogits.ptr, self.dlogits.bs, self.dlogits.pitch
         sm.scale, sm.backward = scale, int(backward)
-        if not backward and getattr(self, "peak_ptrs", None):
+        if not backward and self.peak_ptrs:
             sm.peak, sm.amax = self.peak_ptrs
         if backward and self.gmul_ptr:
             sm.gmul = self.gmul_ptr
         return sm
 
     # -- backward --------------------------------------------------------------------------
-    def _colsum(self, plan: Plan, X: Mat, M: int, N: int, out_ptr: int, out_bs: int = 0,
-                row_off: int = 0, label: str = "colsum"):
-        cs = L.Colsum()
-        cs.x = X.seg(128, row_off=row_off)
-        cs.dtype, cs.M, cs.N, cs.batch = X.dtype, M, N, self.B
-        cs.out, cs.out_bs, cs.accumulate = out_ptr, out_bs, 1      # target pre-zeroed by the plan
-        det_colsum(self.ws, cs, self.pre + "det." + label)
+    def _colsum(self, plan: Plan, X: Mat, M: int, N: int, out_ptr: int, out_bs: int = 0, label: str = "colsum"):
+        cs = colsum_op(self.ws, X.seg(128), X.dtype, M, N, self.B, out_ptr, out_bs, self.pre + "det." + label)
         with plan.side(self._next_lane()):
             plan.add(L.OP_COLSUM, cs, label, TAG_MISC)
 
-    def _wgrad_tile(self) -> int:
-        if self.wgrad_tile:
-            return self.wgrad_tile
-        n128 = self.NL * ((2 * self.Dp // 128) * ((2 * self.Rp + self.Cp) // 128) + (self.Rp // 128) * (self.Dp // 128))
-        return 256 if n128 > TnGroupBuilder.CURSOR_AUTO_TILES else 128
-
-    def _next_lane(self, kind: str = "") -> int:
+    def _next_lane(self) -> int:
         n = min(self.n_side_lanes, Plan.N_SIDE, 3)             # lanes 4 / 5 are for explicit branches (tail_lane, split_chains)
-        self._lane_rr = getattr(self, "_lane_rr", 0) % max(1, n) + 1
+        self._lane_rr = self._lane_rr % max(1, n) + 1
         return self._lane_rr
 
-    def _wgrad(self, plan: Plan, name: str, dtype: int, Mc: int, N: int, N_pad: int, gseg: L.Seg,
-               segs: Sequence[L.Seg], tag: int) -> Tuple[int, int, int]:
-        t = make_tn(dtype, Mc, self.B, N, N_pad, gseg, segs, impl=self.impl)
-        slabs = L.tn_slabs(t)
-        ptr, stride = self._gslab(name, N_pad, t.K_total, slabs)
-        t.out, t.out_batch_stride = ptr, stride
-        with plan.side(self._next_lane(name)):                     # off the dgrad chain
-            plan.add(L.OP_GEMM_TN, t, "wgrad." + name, tag)
-        self.gbuf[name] = (ptr, stride, slabs)
-        return ptr, stride, slabs
+    def _tn(self, Mc: int, N: int, N_pad: int, gseg: L.Seg, segs: Sequence[L.Seg]) -> L.GemmTN:
+        return make_tn(BF, Mc, self.B, N, N_pad, gseg, segs, impl=self.impl)
 
-    def build_backward(self, plan: Plan, nll_scale: float):
-        """nll_scale = d(loss)/d(per-position nll): 1/(B*(w-1)) for mean-type losses, 1 for
-        sum-type (times the upstream gradient)."""
-        B, g, hps, p, ps = self.B, self.g, self.hps, self.pre, self.ps
-        R, D, S, P, Q, Clc = self.R, self.D, self.S, self.P, self.Q, self.Clc
-        Rp, Dp, Sp, Pp, Qp, Cp, Lp = self.Rp, self.Dp, self.Sp, self.Pp, self.Qp, self.Cp, self.Lp
-        impl, NL, w, T = self.impl, self.NL, self.w, self.T
-        pk = self.pk
-        plan.add(L.OP_SOFTMAX_NLL, self._softmax(True, nll_scale), "softmax_grad", TAG_LOSS)
-        plan.zero(self.ws, p + "colsum_fg")
-        # gradients of the post network and of the upper half of the stack are unpacked mid-chain (side
-        # lane), so that less unpack work is left when the chain ends (shorter drain before the encoder
-        # backward / before a data-parallel caller may start reducing the decoder gradients)
-        early_tbl = getattr(self, "unpack_early_tbl", None)
-        late_tbl = pk.unpack_tbl
-        if early_tbl is not None:
-            pk.unpack_tbl = early_tbl
-        # grouped weight gradients (wgrad_group layers per launch, impl 0 only: the check kernels keep one op per
-        # matrix).  A group is emitted right after the dz GEMM of its lowest layer, on a side lane; the last one after
-        # the chain, together with the skip and post-network weight gradients.  With the ones channel in x the fg
-        # descriptors also deliver the running per-batch column sums of dfg.
-        grouped = self.wgrad_group > 0 and self.impl == 0
-        # running per-batch column sums of dfg out of the grouped launch: column R of the weight gradient where x carries
-        # the ones channel (R < Rp), else the launch's own all-ones operand (aew_gemm_tn_t.snap_k = -1)
-        snap_ok = grouped
-        grp: Optional[TnGroupBuilder] = None
-        n_groups = 0
-        tail_descs = []                                        # (name, descriptor): join the last group
-        # Several groups (wgrad_group < NL; data parallel: AEW_WGRAD_GROUP=NL/2): the post-network and skip weight
-        # gradients - operands complete before the chain starts - join the FIRST group instead of the last, and their
-        # results are unpacked with it.  Every gradient from layer NL - wgrad_group up (the tail of the flat buffer,
-        # `hi_first_layer`) is then final right after "unpack grads (decoder, upper layers)": a data-parallel caller
-        # starts its reduce-scatter there, under the second half of the chain (TrainEngine.bwd_a1 / bwd_a2).
-        multi = grouped and self.wgrad_group < NL
-        if multi and self.wgrad_split_layers > 0:
-            # (the upper-layers spk_bwd differences RUNNING column sums; layers kept as split-K ops deliver per-batch sums)
-            raise ValueError("wgrad_split_layers > 0 cannot be combined with several grouped weight-gradient launches (wgrad_group < layers)")
-        self.hi_first_layer = NL - self.wgrad_group if (multi and early_tbl is not None and snap_ok) else None
-        self._spk_hi_from = None
-        layers_in_grp = 0
+    def _spk_bwd(self, first: int, count: int, running: int, det_tag: str) -> "L.SpkBwd":
+        """Speaker-embedding / gated-bias gradients of layers [first, first + count) (count 0: all) from colsum_fg, whose
+        first `running` layers hold running sums over the batch (the grouped launch's snapshots)."""
+        sb = L.SpkBwd()
+        self._fill_spk(sb)
+        sb.colsum, sb.gc, sb.grads = self.colsum_fg.data_ptr(), self.gc.data_ptr(), self.ps.grads.data_ptr()
+        sb.colsum_running = running
+        if count:
+            sb.layer_range = first | (count << 16)
+        # scratch + ticket of the deterministic speaker-embedding sums (aew_spk_bwd_t.det_scratch: one [16][16] block of terms
+        # per (layer, filt | gate, chunk of 16 batch elements), added in a fixed order by the last block)
+        chunks = (self.B + 15) // 16
+        sb.det_scratch = self.ws.alloc(self.pre + f"det.spk_{det_tag}.scratch", self.NL * 2 * chunks * 256, torch.float32).data_ptr()
+        sb.det_tickets = self.ws.alloc(self.pre + f"det.spk_{det_tag}.tickets", 4, torch.int32, zero=True).data_ptr()
+        return sb
 
-        def group_add(name, t, tag):
-            nonlocal grp
-            if grp is None:
-                grp = TnGroupBuilder(self.ws, p + f"tng{n_groups}", self._wgrad_tile())
-                grp.cursor = self.wgrad_cursor
-            ptr, stride = self._gslab(name, t.N_pad, t.K_total, 1)
-            t.out, t.out_batch_stride = ptr, stride
-            grp.add(t, "wgrad." + name)
-            self.gbuf[name] = (ptr, stride, 1)
-            return ptr, stride, 1
-
-        def wgrad_late(name, dtype, Mc, N, N_pad, gseg, segs, tag, bias_grad=0):
-            """A weight gradient whose operands exist early but whose result is only needed at the end: grouped mode
-            defers it into the last group (one result, unpacked by the late table).  bias_grad: address of the layer's
-            bias gradient = column sums of the G operand, a by-product of the grouped launch (0: none)."""
-            if not grouped:
-                return self._wgrad(plan, name, dtype, Mc, N, N_pad, gseg, segs, tag) + (pk.unpack_tbl,)
-            t = make_tn(dtype, Mc, B, N, N_pad, gseg, segs)
-            t.colsum_out = bias_grad or None
-            if multi and name != "base":                       # (the base layer's needs dx of layer 0: last group)
-                return group_add(name, t, tag) + (pk.unpack_tbl,)
-            ptr, stride = self._gslab(name, t.N_pad, t.K_total, 1)
-            t.out, t.out_batch_stride = ptr, stride
-            tail_descs.append((name, t))
-            self.gbuf[name] = (ptr, stride, 1)
-            return ptr, stride, 1, late_tbl
-
-        # ---- post network
-        if ps.has(p + "post2.bias") and not grouped:
-            self._colsum(plan, self.dlogits, w, Q, ps.ptr(p + "post2.bias", True), label="db.post2")
-        gp, gs, gn, tbl = wgrad_late("p2", BF, w, Q, Qp, self.dlogits.seg(Qp), [self.h1.seg(Pp)], TAG_POST,
-                                     bias_grad=ps.ptr(p + "post2.bias", True) if ps.has(p + "post2.bias") else 0)
-        keep_tbl, pk.unpack_tbl = pk.unpack_tbl, tbl
-        pk.rec(p + "post2.weight", 0, [P, 1], [Q, P], None, 0, [Pp, 1], g_ptr=gp, slabs=gn, slab_stride=gs)
-        pk.unpack_tbl = keep_tbl
-        plan.add(L.OP_GEMM_NT, make_nt(BF, w, Pp, Pp, B, [self.dlogits.seg(Qp)], self.Wp2T.ptr,
-                                       flags=L.EF_MUL_POS1, out0=self.dh1.view(), aux1=self.h1.view(),
-                                       impl=impl), "d.post2", TAG_POST)
-        if ps.has(p + "post1.bias") and not grouped:
-            self._colsum(plan, self.dh1, w, P, ps.ptr(p + "post1.bias", True), label="db.post1")
-        gp, gs, gn, tbl = wgrad_late("p1", BF, w, P, Pp, self.dh1.seg(Pp), [self.h0.seg(Sp)], TAG_POST,
-                                     bias_grad=ps.ptr(p + "post1.bias", True) if ps.has(p + "post1.bias") else 0)
-        keep_tbl, pk.unpack_tbl = pk.unpack_tbl, tbl
-        pk.rec(p + "post1.weight", 0, [S, 1], [P, S], None, 0, [Sp, 1], g_ptr=gp, slabs=gn, slab_stride=gs)
-        pk.unpack_tbl = keep_tbl
-        plan.add(L.OP_GEMM_NT, make_nt(BF, w, Sp, Sp, B, [self.dh1.seg(Pp)], self.Wp1T.ptr,
-                                       flags=L.EF_MUL_POS1, out0=self.dskp.view(), aux1=self.h0.view(),
-                                       impl=impl), "d.post1", TAG_POST)
-        skp = None
-        if multi:
-            # skip weights of all layers (see below) into the first group: dskp and every z exist already
-            skp = wgrad_late("skp_all", BF, w, S, Sp, self.dskp.seg(Sp),
-                             [self.z[l].seg(Dp, row_off=g.layers[l].skip_lead) for l in range(NL)], TAG_WG_RS)
-            for l in range(NL):
-                pk.rec(p + f"conv_layers.{l}.dil_skp.weight", 0, [D, 1], [S, D], None, 0, [NL * Dp, 1],
-                       g_ptr=skp[0], slabs=skp[2], slab_stride=skp[1], g_off=l * Dp)
-        # ---- gated stack, last layer first
-        Kfg = 2 * Rp + Cp
-        Cc = Clc + self.Gc
-        dx_next: Optional[Mat] = None
-        colsum_tbl = CopyTableBuilder(self.ws, p + "tbl.colsum")
+    def build_backward(self, plan: Plan, nll_scale: float, early_tbl: Optional[CopyTableBuilder] = None):
+        """nll_scale = d(loss)/d(per-position nll): 1/(B*(w-1)) for mean-type losses, 1 for sum-type (times the upstream
+        gradient).  early_tbl: gradients of the post network and of the upper half of the stack are unpacked mid-chain by this table
+        (side lane), so that less unpack work is left when the chain ends (shorter drain before the encoder backward /
+        before a data-parallel caller may start reducing the decoder gradients); the caller emits the packer's own."""
+        self.unpack_early_tbl, self.hi_first_layer = early_tbl, None
+        rt = WgradRouter(self, plan, early_tbl)
         # split_chains_bwd: the dz / dx chain as two independent half-batch chains on lanes 4 / 5 (the mirror of the
-        # forward's split_chains; grouped weight gradients only, so that nothing else sits inside the chain)
-        n_chains = 2 if (self.split_chains_bwd and grouped and not multi and snap_ok and self.wgrad_split_layers == 0
-                         and B % 2 == 0 and self.n_lo >= NL) else 1
-        nb = B // n_chains
+        # forward's split_chains; ONE grouped weight-gradient launch only, so that nothing else sits inside the chain)
+        n_chains = 2 if (self.split_chains_bwd and rt.grouped and not rt.multi and self.wgrad_split_layers == 0
+                         and self.B % 2 == 0 and self.n_lo >= self.NL) else 1
         # (the tail branch is for the one-chain plan only: queued behind a chain on lane 4 it needs lanes 4 and 5 to wait
         # for each other in turn, and capturing that shape crashes inside the runtime - ROCm 7.2)
         tail = self.tail_lane_used = self.tail_lane if n_chains == 1 else 0
+        self._bwd_post(plan, rt, nll_scale)
+        dx0, colsum_tbl = self._bwd_stack(plan, rt, n_chains)
+        self._bwd_base_skip(plan, rt, dx0, tail, n_chains)
+        # tail_lane: the speaker / gated-bias gradients right behind the last grouped launch, before any main-lane op, so
+        # that the branch needs no second edge from the main lane
+        if tail:
+            self._bwd_spk(plan, rt, colsum_tbl, tail)
+        self._bwd_cond(plan, n_chains)
+        if not tail:
+            self._bwd_spk(plan, rt, colsum_tbl, tail)
+        self._bwd_ups(plan, rt)
+
+    def _bwd_post(self, plan: Plan, rt: "WgradRouter", nll_scale: float):
+        """Loss gradient and post network (wavenet.py:359-360, 543-547)."""
+        B, p, w, impl, Sp, Pp, Qp = self.B, self.pre, self.w, self.impl, self.Sp, self.Pp, self.Qp
+        plan.add(L.OP_SOFTMAX_NLL, self._softmax(True, nll_scale), "softmax_grad", TAG_LOSS)
+        plan.zero(self.ws, p + "colsum_fg")
+        rt.add("p2", self._tn(w, self.Q, Qp, self.dlogits.seg(Qp), [self.h1.seg(Pp)]), TAG_POST, rt.LATE,
+               bias=(p + "post2.bias", self.dlogits, "db.post2"))
+        plan.add(L.OP_GEMM_NT, make_nt(BF, w, Pp, Pp, B, [self.dlogits.seg(Qp)], self.Wp2T.ptr, flags=L.EF_MUL_POS1,
+                                       out0=self.dh1.view(), aux1=self.h1.view(), impl=impl), "d.post2", TAG_POST)
+        rt.add("p1", self._tn(w, self.P, Pp, self.dh1.seg(Pp), [self.h0.seg(Sp)]), TAG_POST, rt.LATE,
+               bias=(p + "post1.bias", self.dh1, "db.post1"))
+        plan.add(L.OP_GEMM_NT, make_nt(BF, w, Sp, Sp, B, [self.dh1.seg(Pp)], self.Wp1T.ptr, flags=L.EF_MUL_POS1,
+                                       out0=self.dskp.view(), aux1=self.h0.view(), impl=impl), "d.post1", TAG_POST)
+        if rt.multi:
+            self._bwd_skip_wgrad(rt)                           # into the first group: dskp and every z exist already
+
+    def _bwd_skip_wgrad(self, rt: "WgradRouter"):
+        """Skip weights of all layers: ONE wgrad with NL segments (mirror of the deferred skip GEMM):
+        dW_skp[s][l*Dp + k] = sum_t dskp[t][s] * z_l[t + skip_lead_l][k].  640 tiles x batch fill the chip without row
+        splits, so it writes B slabs instead of ~128 per layer.  The gradient always spans all NL layers, while the
+        packed matrix may be two (split_multiseg): its per-layer map is stated here, not taken from the pack."""
+        segs = [self.z[l].seg(self.Dp, row_off=self.g.layers[l].skip_lead) for l in range(self.NL)]
+        rt.add("skp_all", self._tn(self.w, self.S, self.Sp, self.dskp.seg(self.Sp), segs), TAG_WG_RS, rt.LATE,
+               pieces=[self._skip_piece(l, l, self.NL) for l in range(self.NL)])
+
+    def _bwd_stack(self, plan: Plan, rt: "WgradRouter", n_chains: int) -> Tuple[Mat, CopyTableBuilder]:
+        """Gated stack, last layer first: the dz / dx chain with each layer's weight gradients routed beside it.  Returns
+        dx of layer 0 and the table that gathers per-batch column sums of dfg out of split-K weight gradients."""
+        B, g, p, impl, NL = self.B, self.g, self.pre, self.impl, self.NL
+        R, Rp, Dp, Sp, Cp = self.R, self.Rp, self.Dp, self.Sp, self.Cp
+        Kfg = 2 * Rp + Cp
+        dx_next: Optional[Mat] = None
+        colsum_tbl = CopyTableBuilder(self.ws, p + "tbl.colsum")
+        nb = B // n_chains
         for l in range(NL - 1, -1, -1):
-            lg = g.layers[l]
-            last = l == NL - 1
+            lg, last = g.layers[l], l == NL - 1
             P_l, d = lg.out_len, lg.dil
-            q = p + f"conv_layers.{l}."
-            segs = []
-            if not last:
-                segs.append(dx_next.seg(Rp, hi=P_l))
-            segs.append(self.dskp.seg(Sp, row_off=-lg.skip_lead))
-            for c in range(n_chains):
-                b0 = c * nb
-                plan.lane = (4 + c) if (n_chains > 1 and not self.split_one_lane) else 0
-                csegs = segs if n_chains == 1 else \
-                    ([] if last else [dx_next.seg(Rp, hi=P_l, b0=b0)]) + [self.dskp.seg(Sp, row_off=-lg.skip_lead, b0=b0)]
-                plan.add(L.OP_GEMM_NT, make_nt(BF, P_l, Dp, Dp, nb, csegs, self.WrsT[l].ptr, epi=L.EPI_DFG,
+            for c, b0, sfx in self._chains(plan, n_chains):
+                segs = ([] if last else [dx_next.seg(Rp, hi=P_l, b0=b0)]) + [self.dskp.seg(Sp, row_off=-lg.skip_lead, b0=b0)]
+                plan.add(L.OP_GEMM_NT, make_nt(BF, P_l, Dp, Dp, nb, segs, self.WrsT[l].ptr, epi=L.EPI_DFG,
                                                aux0=self.pf[l].view(b0=b0), aux1=self.pg[l].view(b0=b0),
-                                               out0=self.dfg[l].view(b0=b0), impl=self._impl("dz")),
-                         f"dz.{l}" + (f".c{c}" if n_chains > 1 else ""), TAG_DZ)
-            plan.lane = 0
+                                               out0=self.dfg[l].view(b0=b0), impl=self._impl("dz")), f"dz.{l}" + sfx, TAG_DZ)
             if self.n_lo < NL and l == self.n_lo:
                 hsegs = [self.dfg[k].seg(2 * Dp, row_off=-g.layers[k].cond_lead) for k in range(self.n_lo, NL)]
                 with plan.side(self.EARLY_LANE):               # upper half of the cond gradient: inputs complete
-                    plan.add(L.OP_GEMM_NT, make_nt(BF, T, Cp, Cp, B, hsegs, self.VfgT_hi.ptr,
+                    plan.add(L.OP_GEMM_NT, make_nt(BF, self.T, Cp, Cp, B, hsegs, self.VfgT_hi.ptr,
                                                    out0=self.dcond_part.view(), impl=impl), "dcond_hi", TAG_DCOND)
             x = self.x[l]
-            fg_segs = [x.seg(Rp), x.seg(Rp, row_off=d), self.cond.seg(Cp, row_off=lg.cond_lead)]
-            if grouped and l < NL - self.wgrad_split_layers:
-                if not last:
-                    gp, gs, gn = group_add(f"res{l}", make_tn(BF, P_l, B, R, Rp, dx_next.seg(Rp, hi=P_l),
-                                                              [self.z[l].seg(Dp)]), TAG_WG_RS)
-                    pk.rec(q + "dil_res.weight", 0, [D, 1], [R, D], None, 0, [Dp, 1], g_ptr=gp, slabs=gn, slab_stride=gs)
-                t = make_tn(BF, P_l, B, 2 * Dp, 2 * Dp, self.dfg[l].seg(2 * Dp), fg_segs)
-                if snap_ok:
-                    t.snap_out, t.snap_bs, t.snap_k = self.colsum_fg.data_ptr() + 4 * l * 2 * Dp, NL * 2 * Dp, (R if self.R < Rp else -1)
-                gp, gs, gn = group_add(f"fg{l}", t, TAG_WG_FG)
-            else:
-                if not last:
-                    gp, gs, gn = self._wgrad(plan, f"res{l}", BF, P_l, R, Rp, dx_next.seg(Rp, hi=P_l),
-                                             [self.z[l].seg(Dp)], TAG_WG_RS)
-                    pk.rec(q + "dil_res.weight", 0, [D, 1], [R, D], None, 0, [Dp, 1], g_ptr=gp, slabs=gn, slab_stride=gs)
-                gp, gs, gn = self._wgrad(plan, f"fg{l}", BF, P_l, 2 * Dp, 2 * Dp, self.dfg[l].seg(2 * Dp), fg_segs,
-                                         TAG_WG_FG)
-            spb = gn // B if (gn % B == 0 and gn >= B) else 0     # slabs per batch (0: batch folded)
-            if snap_ok and l < NL - self.wgrad_split_layers:
-                pass                                               # running column sums come from the grouped wgrad
-            elif self.R < Rp and spb > 0:
+            if not last:
+                rt.add(f"res{l}", self._tn(P_l, R, Rp, dx_next.seg(Rp, hi=P_l), [self.z[l].seg(Dp)]), TAG_WG_RS, l)
+            t = self._tn(P_l, 2 * Dp, 2 * Dp, self.dfg[l].seg(2 * Dp),
+                         [x.seg(Rp), x.seg(Rp, row_off=d), self.cond.seg(Cp, row_off=lg.cond_lead)])
+            colsum_l = self.colsum_fg.data_ptr() + 4 * l * 2 * Dp
+            if rt.in_group(l):
+                # running per-batch column sums of dfg out of the grouped launch: column R of the weight gradient where x
+                # carries the ones channel (R < Rp), else the launch's own all-ones operand (aew_gemm_tn_t.snap_k = -1)
+                t.snap_out, t.snap_bs, t.snap_k = colsum_l, NL * 2 * Dp, (R if R < Rp else -1)
+            wg = rt.add(f"fg{l}", t, TAG_WG_FG, l)
+            spb = wg.slabs // B if (wg.slabs % B == 0 and wg.slabs >= B) else 0     # slabs per batch (0: batch folded)
+            if rt.in_group(l):
+                pass                                               # (its running column sums come from the grouped launch)
+            elif R < Rp and spb > 0:
                 # x carries a constant 1.0 in pad channel R (base_gather ones_channel), so column R
                 # of this wgrad is sum_t dfg[t][n]: gather it per batch for the bias / speaker grads
-                colsum_tbl.add(gp + 4 * R, self.colsum_fg.data_ptr() + 4 * l * 2 * Dp, [B, 2 * Dp],
-                               [spb * gs, Kfg], [NL * 2 * Dp, 1], F3, F3, red_n=spb, red_stride=gs)
+                colsum_tbl.add(wg.ptr + 4 * R, colsum_l, [B, 2 * Dp], [spb * wg.stride, Kfg], [NL * 2 * Dp, 1], F3, F3,
+                               red_n=spb, red_stride=wg.stride)
             else:
-                self._colsum(plan, self.dfg[l], P_l, 2 * Dp, self.colsum_fg.data_ptr() + 4 * l * 2 * Dp,
-                             out_bs=NL * 2 * Dp, label=f"colsum.dfg{l}")
-            for gate, nm in ((0, "signal"), (1, "gate")):
-                for co0, ng, gl in _gate_groups(D):
-                    row0 = (co0 // 16) * 32 + 16 * gate
-                    pk.rec(q + f"conv_{nm}.weight", co0 * R * 2, [16 * R * 2, R * 2, 2, 1], [ng, gl, R, 2],
-                           None, row0 * Kfg, [32 * Kfg, Kfg, 1, Rp], g_ptr=gp, slabs=gn, slab_stride=gs)
-                    pk.rec(q + f"proj_{nm}.weight", co0 * Cc, [16 * Cc, Cc, 1], [ng, gl, Clc],
-                           None, row0 * Kfg + 2 * Rp, [32 * Kfg, Kfg, 1], g_ptr=gp, slabs=gn, slab_stride=gs)
-            if grouped and l < NL - self.wgrad_split_layers:
-                layers_in_grp += 1
-            if grouped and grp is not None and layers_in_grp >= self.wgrad_group and l > 0:
-                layers_in_grp = 0
-                with plan.side(self._next_lane("tng")):
-                    grp.emit(plan, f"wgrad.group{n_groups} (layers {l}.., skip, post)" if n_groups == 0 else
-                             f"wgrad.group{n_groups} (layers {l}..)", TAG_WG_FG)
-                grp = None
-                n_groups += 1
-                if early_tbl is not None:
-                    if multi and snap_ok:
-                        # gated-bias / speaker-projection gradients of the layers in this group (from the running column
-                        # sums it just wrote): everything of layers >= l is final after the unpack below
-                        sb_hi = L.SpkBwd()
-                        self._fill_spk(sb_hi)
-                        sb_hi.colsum, sb_hi.gc, sb_hi.grads = self.colsum_fg.data_ptr(), self.gc.data_ptr(), ps.grads.data_ptr()
-                        sb_hi.colsum_running = NL
-                        sb_hi.layer_range = l | ((NL - l) << 16)
-                        self._spk_det(sb_hi, "hi")
-                        self._spk_hi_from = l
-                        with plan.side(1):
-                            plan.add(L.OP_SPK_BWD, sb_hi, "spk_bwd (upper layers)", TAG_MISC, join=True)
-                    with plan.side(1):                             # the first group's gradients: unpacked mid-chain
-                        early_tbl.emit(plan, "unpack grads (decoder, upper layers)", join=True)
-                    pk.unpack_tbl = late_tbl
-                    early_tbl = None
+                self._colsum(plan, self.dfg[l], P_l, 2 * Dp, colsum_l, out_bs=NL * 2 * Dp, label=f"colsum.dfg{l}")
+            rt.layer_done(l)
             dx = self.dx[l]
-            for c in range(n_chains):
-                b0 = c * nb
-                plan.lane = (4 + c) if (n_chains > 1 and not self.split_one_lane) else 0
+            for c, b0, sfx in self._chains(plan, n_chains):
                 segs = [self.dfg[l].seg(2 * Dp, b0=b0), self.dfg[l].seg(2 * Dp, row_off=-d, b0=b0)]
                 plan.add(L.OP_GEMM_NT, make_nt(
-                    BF, lg.in_len, Rp, Rp, nb, segs, self.WfgT[l].ptr,
-                    flags=0 if last else L.EF_ADD_AUX0,
-                    out0=dx.view(hi=lg.in_len, b0=b0),
-                    aux0=null_view() if last else dx_next.view(row_off=-d, hi=P_l, b0=b0), impl=self._impl("dx")),
-                    f"dx.{l}" + (f".c{c}" if n_chains > 1 else ""), TAG_DX)
-            plan.lane = 0
+                    BF, lg.in_len, Rp, Rp, nb, segs, self.WfgT[l].ptr, flags=0 if last else L.EF_ADD_AUX0,
+                    out0=dx.view(hi=lg.in_len, b0=b0), aux0=null_view() if last else dx_next.view(row_off=-d, hi=P_l, b0=b0),
+                    impl=self._impl("dx")), f"dx.{l}" + sfx, TAG_DX)
             dx_next = dx
-            if not grouped and early_tbl is not None and l == NL // 2:
-                with plan.side(1):                                 # after the wgrads issued so far, on any lane
-                    early_tbl.emit(plan, "unpack grads (decoder, upper layers)", join=True)
-                pk.unpack_tbl = late_tbl
-                early_tbl = None
-        pk.unpack_tbl = late_tbl
-        dx0 = dx_next
-        # ---- skip weights of all layers: ONE wgrad with NL segments (mirror of the deferred skip GEMM):
-        # dW_skp[s][l*Dp + k] = sum_t dskp[t][s] * z_l[t + skip_lead_l][k].  640 tiles x batch fill the
-        # chip without row splits, so it writes B slabs instead of ~128 per layer.
-        # ---- base layer (wavenet.py:351)
-        # (as a TN GEMM over a materialised one-hot matrix: 0.044 ms + 29 MB written by base_gather.  The scatter-add form
-        # - rows of dx0 added into LDS images per 64 channels, AEW-internal experiment of round 2 - took 0.58 ms: the
-        # rows have to be fetched one dependent (wav[t] -> dx0[t]) load pair at a time and the partial images merged
-        # with ~10 M global atomics; the GEMM streams the same bytes at full rate)
-        has_bb = ps.has(p + "base_layer.bias")
-        if has_bb and not grouped:
-            self._colsum(plan, dx0, T, R, ps.ptr(p + "base_layer.bias", True), label="db.base")
-        gp_b, gs_b, gn_b, _tbl = wgrad_late("base", BF, T, R, Rp, dx0.seg(Rp), [self.onehot.seg(Qp)], TAG_MISC,
-                                            bias_grad=ps.ptr(p + "base_layer.bias", True) if has_bb else 0)
-        pk.rec(p + "base_layer.weight", 0, [Q, 1], [R, Q], None, 0, [Qp, 1], g_ptr=gp_b, slabs=gn_b, slab_stride=gs_b)
-        if skp is None:
-            gp, gs, gn, _tbl = wgrad_late("skp_all", BF, w, S, Sp, self.dskp.seg(Sp),
-                                          [self.z[l].seg(Dp, row_off=g.layers[l].skip_lead) for l in range(NL)], TAG_WG_RS)
-        if grouped:
-            for name, t in tail_descs:
-                if grp is None:
-                    grp = TnGroupBuilder(self.ws, p + f"tng{n_groups}", self._wgrad_tile())
-                    grp.cursor = self.wgrad_cursor
-                grp.add(t, "wgrad." + name)
-            with plan.side(tail or self._next_lane("tng")):
-                grp.emit(plan, f"wgrad.group{n_groups} (last layers, skip, post)" if not multi else
-                         f"wgrad.group{n_groups} (layers 0.., base)", TAG_WG_FG, join=n_chains > 1)
-            grp = None
-            if early_tbl is not None:                              # a single group: nothing was unpacked mid-chain
-                pk.unpack_tbl = late_tbl
-                late_tbl.recs.extend(early_tbl.recs)
-                early_tbl = None
-        for l in range(NL if skp is None else 0):
-            pk.rec(p + f"conv_layers.{l}.dil_skp.weight", 0, [D, 1], [S, D], None, 0, [NL * Dp, 1],
-                   g_ptr=gp, slabs=gn, slab_stride=gs, g_off=l * Dp)
-        # ---- speaker / gated-bias gradients (tail_lane: right behind the last grouped launch, before any main-lane op,
-        # so that the branch needs no second edge from the main lane)
-        def emit_spk():
-            sbw = L.SpkBwd()
-            self._fill_spk(sbw)
-            sbw.colsum, sbw.gc, sbw.grads = self.colsum_fg.data_ptr(), self.gc.data_ptr(), ps.grads.data_ptr()
-            sbw.colsum_running = max(0, NL - self.wgrad_split_layers) if snap_ok else 0
-            if getattr(self, "_spk_hi_from", None):                    # the upper layers were done after the first group
-                sbw.layer_range = 0 | (self._spk_hi_from << 16)
-            self._spk_det(sbw, "lo")
-            with plan.side(tail or 1):                                 # reads the side lanes' wgrad slabs: side join
-                colsum_tbl.emit(plan, "colsum.dfg (from wgrad column R)", join=True)
-                plan.add(L.OP_SPK_BWD, sbw, "spk_bwd", TAG_MISC, join=not colsum_tbl.recs)
-        if tail:
-            emit_spk()
-        # ---- conditioning gradient over all layers' dfg (wavenet.py:100-101 cond terms).  With split_multiseg the
-        # layers [n_lo, NL) were summed on a side lane mid-chain (dcond_part); this GEMM adds them.
-        lo = self.n_lo
-        if lo < NL:
-            segs = [self.dfg[l].seg(2 * Dp, row_off=-g.layers[l].cond_lead) for l in range(lo)]
-            plan.add(L.OP_GEMM_NT, make_nt(BF, T, Cp, Cp, B, segs, self.VfgT_lo.ptr, flags=L.EF_ADD_AUX0,
-                                           out0=self.dcond.view(), aux0=self.dcond_part.view(), impl=impl),
-                     "dcond", TAG_DCOND, join=("lane", self.EARLY_LANE))
-        else:
-            segs = [self.dfg[l].seg(2 * Dp, row_off=-lg.cond_lead) for l, lg in enumerate(g.layers)]
-            plan.add(L.OP_GEMM_NT, make_nt(BF, T, Cp, Cp, B, segs, self.VfgT_lo.ptr, out0=self.dcond.view(),
-                                           impl=self._impl("dcond")), "dcond", TAG_DCOND,
-                     join=n_chains > 1)          # two chains: the main lane meets them here at the latest (every lane mode)
-        if not tail:
-            emit_spk()
-        # ---- upsamplers, last stage first (wavenet.py:154)
+            rt.dx_done(l)
+        return dx_next, colsum_tbl
+
+    def _bwd_base_skip(self, plan: Plan, rt: "WgradRouter", dx0: Mat, tail: int, n_chains: int):
+        """Base layer (wavenet.py:351), the skip weights unless the first of several groups took them, the last grouped launch.
+        (Base layer as a TN GEMM over a materialised one-hot matrix: 0.044 ms + 29 MB written by base_gather.  The
+        scatter-add form - rows of dx0 added into LDS images per 64 channels, AEW-internal experiment of round 2 - took
+        0.58 ms: the rows have to be fetched one dependent (wav[t] -> dx0[t]) load pair at a time and the partial images
+        merged with ~10 M global atomics; the GEMM streams the same bytes at full rate)"""
+        p = self.pre
+        # (the gradient is [Rp][Qp]; the packed form is the transposed fp32 gather table [Q][Rp]: no shared layout)
+        rt.add("base", self._tn(self.T, self.R, self.Rp, dx0.seg(self.Rp), [self.onehot.seg(self.Qp)]), TAG_MISC, rt.LAST,
+               bias=(p + "base_layer.bias", dx0, "db.base"),
+               pieces=[Piece(p + "base_layer.weight", 0, [self.Q, 1], [self.R, self.Q], 0, [self.Qp, 1])])
+        rt.merge_early()
+        if not rt.multi:
+            self._bwd_skip_wgrad(rt)
+        rt.emit_last(tail, join=n_chains > 1)
+
+    def _bwd_spk(self, plan: Plan, rt: "WgradRouter", colsum_tbl: CopyTableBuilder, tail: int):
+        """Speaker / gated-bias gradients (of the layers the first of several groups has not done already)."""
+        running = max(0, self.NL - self.wgrad_split_layers) if rt.grouped else 0
+        sb = self._spk_bwd(0, self.hi_first_layer or 0, running, "lo")
+        with plan.side(tail or 1):                                 # reads the side lanes' wgrad slabs: side join
+            colsum_tbl.emit(plan, "colsum.dfg (from wgrad column R)", join=True)
+            plan.add(L.OP_SPK_BWD, sb, "spk_bwd", TAG_MISC, join=not colsum_tbl.recs)
+
+    def _bwd_cond(self, plan: Plan, n_chains: int):
+        """Conditioning gradient over all layers' dfg (wavenet.py:100-101 cond terms).  With split_multiseg the layers
+        [n_lo, NL) were summed on a side lane mid-chain (dcond_part); this GEMM adds them."""
+        g, Dp, Cp, half = self.g, self.Dp, self.Cp, self.n_lo < self.NL
+        segs = [self.dfg[l].seg(2 * Dp, row_off=-g.layers[l].cond_lead) for l in range(self.n_lo)]
+        plan.add(L.OP_GEMM_NT, make_nt(BF, self.T, Cp, Cp, self.B, segs, self.VfgT_lo.ptr, flags=L.EF_ADD_AUX0 if half else 0,
+                                       out0=self.dcond.view(), aux0=self.dcond_part.view() if half else None,
+                                       impl=self.impl if half else self._impl("dcond")), "dcond", TAG_DCOND,
+                 # (two chains: the main lane meets them here at the latest, in every lane mode)
+                 join=("lane", self.EARLY_LANE) if half else n_chains > 1)
+
+    def _bwd_ups(self, plan: Plan, rt: "WgradRouter"):
+        """Upsamplers, last stage first (wavenet.py:154), LC conv (wavenet.py:337) and the jitter scatter."""
+        B, g, hps, p, ps, impl = self.B, self.g, self.hps, self.pre, self.ps, self.impl
+        Clc, Cp, Lp = self.Clc, self.Cp, self.Lp
         n_ups = len(hps.lc_upsample_strides)
-        ugrp = TnGroupBuilder(self.ws, p + "tng_ups", 128) if grouped else None     # upsampler + LC-conv wgrads: one launch
-
-        def wgrad_ups(name, Mc, N, N_pad, gseg, segs, bias_grad=0, gmat=None):
-            """One or a few output tiles with up to 8 x 1780 rows to contract: cut into chunks of ~512 rows (one block
-            and one slab each) unless the whole contraction is that short (then the column-sum by-product is available)."""
-            if ugrp is None:
-                return self._wgrad(plan, name, BF, Mc, N, N_pad, gseg, segs, TAG_UPS)
-            t = make_tn(BF, Mc, B, N, N_pad, gseg, segs)
-            split = Mc * B > self.ups_split_rows
-            if not split:
-                t.colsum_out = bias_grad or None
-            elif bias_grad:
-                # a split descriptor has no block that sees every row: the bias gradient (column sums of the G
-                # operand) comes from a column-sum op, as in the ungrouped plan
-                self._colsum(plan, gmat, Mc, N, bias_grad, label="db." + name)
-            slabs = ugrp.set_split(t, 512) if split else 1
-            ptr, stride = self._gslab(name, t.N_pad, t.K_total, slabs)
-            t.out, t.out_batch_stride = ptr, stride
-            ugrp.add(t, "wgrad." + name)
-            self.gbuf[name] = (ptr, stride, slabs)
-            return ptr, stride, slabs
-
         for i in range(n_ups - 1, -1, -1):
             f, s = hps.lc_upsample_filt_sizes[i], hps.lc_upsample_strides[i]
-            pad = f - s
             X, dX = self.ups_in[i], self.dups[i]
             last = i == n_ups - 1
             dY = self.dcond if last else self.dups[i + 1]
             trim0 = g.trim_ups_out[0] if last else 0
-            self._colsum(plan, dY, dY.rows, Clc, ps.ptr(p + f"lc_upsample.{i}.tconv.bias", True),
-                         label=f"db.up{i}")
-            segs = [dY.seg(Cp, row_step=s, row_off=k - pad - trim0) for k in range(f)]
-            gp, gs, gn = wgrad_ups(f"up{i}", X.rows, Clc, Cp, X.seg(Cp), segs)
-            pk.rec(p + f"lc_upsample.{i}.tconv.weight", 0, [Clc * f, f, 1], [Clc, Clc, f], None, 0,
-                   [f * Cp, 1, Cp], g_ptr=gp, slabs=gn, slab_stride=gs)
+            self._colsum(plan, dY, dY.rows, Clc, ps.ptr(p + f"lc_upsample.{i}.tconv.bias", True), label=f"db.up{i}")
+            segs = [dY.seg(Cp, row_step=s, row_off=k - (f - s) - trim0) for k in range(f)]
+            rt.add(f"up{i}", self._tn(X.rows, Clc, Cp, X.seg(Cp), segs), TAG_UPS, rt.UPS)
             plan.add(L.OP_GEMM_NT, make_nt(BF, X.rows, Cp, Cp, B, segs, self.WupT[i].ptr, out0=dX.view(),
                                            impl=impl), f"d.ups{i}", TAG_UPS)
-        # ---- LC conv (wavenet.py:337)
         dlc1, lc1 = self.dups[0], self.ups_in[0]
-        has_lb = ps.has(p + "lc_conv.bias")
-        if has_lb and ugrp is None:
-            self._colsum(plan, dlc1, lc1.rows, Clc, ps.ptr(p + "lc_conv.bias", True), label="db.lc")
-        nin = self.n_lc_in
-        gp, gs, gn = wgrad_ups("lc", lc1.rows, Clc, Cp, dlc1.seg(Cp), [self.lcj.seg(Lp, row_off=t) for t in range(3)],
-                               bias_grad=ps.ptr(p + "lc_conv.bias", True) if has_lb else 0, gmat=dlc1)
-        if ugrp is not None:
-            with plan.side(self._next_lane("tng")):
-                ugrp.emit(plan, "wgrad.group (upsamplers, lc conv)", TAG_UPS)
-        pk.rec(p + "lc_conv.weight", 0, [nin * 3, 3, 1], [Clc, nin, 3], None, 0, [3 * Lp, 1, Lp],
-               g_ptr=gp, slabs=gn, slab_stride=gs)
-        plan.add(L.OP_GEMM_NT, make_nt(BF, self.Ne, ru(nin, 8), Lp, B,
-                                       [dlc1.seg(Cp, row_off=-t) for t in range(3)], self.WlcT.ptr,
-                                       out0=self.dlcj.view(), impl=impl), "d.lc_conv", TAG_UPS)
+        rt.add("lc", self._tn(lc1.rows, Clc, Cp, dlc1.seg(Cp), [self.lcj.seg(Lp, row_off=t) for t in range(3)]),
+               TAG_UPS, rt.UPS, bias=(p + "lc_conv.bias", dlc1, "db.lc"))
+        rt.emit_ups()
+        plan.add(L.OP_GEMM_NT, make_nt(BF, self.Ne, ru(self.n_lc_in, 8), Lp, B, [dlc1.seg(Cp, row_off=-t) for t in range(3)],
+                                       self.WlcT.ptr, out0=self.dlcj.view(), impl=impl), "d.lc_conv", TAG_UPS)
         # ---- jitter scatter back to the LC source
         if L.load().aew_lc_scatter_needs_zero(self.Ne):            # (short windows: the scatter runs in its gather form, which
             plan.zero(self.ws, self.dlc_src.name)                  #  writes every element: no atomics, no zeroing)
@@ -1018,8 +881,144 @@ class DecoderPlan:
         sc.d, sc.d_bs, sc.d_pitch = self.dlcj.ptr, self.dlcj.bs, self.dlcj.pitch
         sc.jitter, sc.jit_pitch = self.jitter.data_ptr(), self.jitter.shape[1]
         sc.dsrc, sc.dsrc_bs, sc.dsrc_pitch = self.dlc_src.ptr, self.dlc_src.bs, self.dlc_src.pitch
-        sc.B, sc.N, sc.C, sc.take_compat = B, self.Ne, nin, int(self.take_compat)
+        sc.B, sc.N, sc.C, sc.take_compat = B, self.Ne, self.n_lc_in, int(self.take_compat)
         plan.add(L.OP_LC_SCATTER, sc, "lc_scatter", TAG_UPS)
+
+
+class WgradRouter:
+    """Where each weight gradient of one decoder backward plan runs, and which table unpacks it.
+    Destinations: its own split-K TN op on the next rotating side lane (wgrad_group 0, the check kernels, the top
+    wgrad_split_layers layers); the current grouped launch (AEW_OP_GEMM_TN_GROUP; impl 0 only) of wgrad_group layers,
+    emitted on a side lane right after the dz GEMM of its lowest layer; the last grouped launch, after the chain; the
+    upsampler group, where long contractions are cut into row chunks.
+    Several groups (wgrad_group < NL; data parallel: AEW_WGRAD_GROUP = NL / 2): the post-network and skip weight gradients -
+    operands complete before the chain starts - join the FIRST group instead of the last and are unpacked with it.  Every
+    gradient from layer NL - wgrad_group up (the tail of the flat buffer, `hi_first_layer`) is then final right after
+    "unpack grads (decoder, upper layers)": a data-parallel caller starts its reduce-scatter there, under the second half
+    of the chain (TrainEngine.bwd_a1 / bwd_a2).
+    Tables: what is final mid-chain goes to the early table - emitted after the first of several groups or, ungrouped,
+    after layer NL // 2 - the rest to the packer's own, which also takes the early records of a single group."""
+    LATE, LAST, UPS = -1, -2, -3      # placements other than a layer index: operands exist early, the result is needed at the
+                                      # end | needs dx of layer 0: last group | upsampler / LC-conv group
+
+    def __init__(self, dec: DecoderPlan, plan: Plan, early_tbl: Optional[CopyTableBuilder]):
+        self.dec, self.plan = dec, plan
+        self.grouped = dec.wgrad_group > 0 and dec.impl == 0
+        self.multi = self.grouped and dec.wgrad_group < dec.NL
+        if self.multi and dec.wgrad_split_layers > 0:
+            # (the upper-layers spk_bwd differences RUNNING column sums; layers kept as split-K ops deliver per-batch sums)
+            raise ValueError("wgrad_split_layers > 0 cannot be combined with several grouped weight-gradient launches (wgrad_group < layers)")
+        self.late = dec.pk.unpack_tbl
+        self.early = early_tbl                                 # until it is emitted or merged
+        self.tbl = self.late if early_tbl is None else early_tbl      # table of a result that is final now
+        self.grp: Optional[TnGroupBuilder] = None
+        self.n_groups = self.layers_in_grp = 0
+        self.tail: List[Tuple[L.GemmTN, str]] = []             # (descriptor, label): join the last group
+        self.ups = TnGroupBuilder(dec.ws, dec.pre + "tng_ups", 128) if self.grouped else None
+
+    def in_group(self, l: int) -> bool:
+        """Layer l's weight gradients go to a grouped launch (which then also delivers its running column sums of dfg)."""
+        return self.grouped and l < self.dec.NL - self.dec.wgrad_split_layers
+
+    def _group(self) -> TnGroupBuilder:
+        dec = self.dec
+        if self.grp is None:
+            n128 = dec.NL * ((2 * dec.Dp // 128) * ((2 * dec.Rp + dec.Cp) // 128) + (dec.Rp // 128) * (dec.Dp // 128))   # (wgrad_tile)
+            tile = dec.wgrad_tile or (256 if n128 > TnGroupBuilder.CURSOR_AUTO_TILES else 128)
+            self.grp = TnGroupBuilder(dec.ws, dec.pre + f"tng{self.n_groups}", tile)
+            self.grp.cursor = dec.wgrad_cursor
+        return self.grp
+
+    def add(self, name: str, t: "L.GemmTN", tag: int, place: int, bias: Optional[Tuple[str, Mat, str]] = None,
+            pieces: Optional[Sequence[Piece]] = None) -> WGrad:
+        """Routes descriptor t (place: layer index | LATE | LAST | UPS), allocates `<pre>wg.<name>`, points t at it and
+        writes the unpack records (pieces: the result's index map; default: the packed matrix's, DecoderPlan.lay[name]).
+        bias = (bias parameter, G operand, label): the bias gradient is the column sums of the G operand - a by-product
+        of a grouped descriptor, a column-sum op where there is no block that sees every row (split-K, row-split)."""
+        dec = self.dec
+        if not self.grouped:
+            dest = None
+        elif place == self.UPS:
+            dest = self.ups
+        elif place >= 0:
+            dest = self._group() if self.in_group(place) else None
+        else:
+            dest = self._group() if (self.multi and place == self.LATE) else self.tail
+        # upsampler group: one or a few output tiles with up to 8 x 1780 rows to contract, cut into chunks of ~512 rows
+        # (one block and one slab each) unless the whole contraction is that short
+        split = dest is self.ups and dest is not None and t.Mc * t.batch > dec.ups_split_rows
+        bias_ptr = dec.ps.ptr(bias[0], True) if (bias and dec.ps.has(bias[0])) else 0
+        if dest is None or split:
+            if bias_ptr:
+                dec._colsum(self.plan, bias[1], t.Mc, t.N, bias_ptr, label=bias[2])
+        else:
+            t.colsum_out = bias_ptr or None
+        slabs = L.tn_slabs(t) if dest is None else (dest.set_split(t, 512) if split else 1)
+        g = wgrad_slab(dec.ws, dec.pre + "wg." + name, t, slabs, self.late if dest is self.tail else self.tbl)
+        dec.pk.unpack(dec.lay[name] if pieces is None else pieces, g)
+        if dest is None:
+            with self.plan.side(dec._next_lane()):             # off the dgrad chain
+                self.plan.add(L.OP_GEMM_TN, t, "wgrad." + name, tag)
+        elif dest is self.tail:
+            self.tail.append((t, "wgrad." + name))
+        else:
+            dest.add(t, "wgrad." + name)
+        return g
+
+    def _unpack_early(self):
+        with self.plan.side(1):                                # after the wgrads issued so far, on any lane
+            self.early.emit(self.plan, "unpack grads (decoder, upper layers)", join=True)
+        self.early, self.tbl = None, self.late
+
+    def layer_done(self, l: int):
+        """After layer l's weight gradients: a group that holds wgrad_group layers is emitted (never at layer 0: what is
+        left goes with the last group), and the first one is followed by the early unpack."""
+        dec, plan = self.dec, self.plan
+        self.layers_in_grp += self.in_group(l)
+        if self.grp is None or self.layers_in_grp < dec.wgrad_group or l == 0:
+            return
+        self.layers_in_grp = 0
+        with plan.side(dec._next_lane()):
+            self.grp.emit(plan, f"wgrad.group{self.n_groups} (layers {l}.., skip, post)" if self.n_groups == 0 else
+                          f"wgrad.group{self.n_groups} (layers {l}..)", TAG_WG_FG)
+        self.grp, self.n_groups = None, self.n_groups + 1
+        if self.early is not None:
+            # gated-bias / speaker-projection gradients of the layers in this group (from the running column sums it just
+            # wrote): everything of layers >= l = NL - wgrad_group is final after the unpack below
+            dec.hi_first_layer = l
+            sb = dec._spk_bwd(l, dec.NL - l, dec.NL, "hi")
+            with plan.side(1):
+                plan.add(L.OP_SPK_BWD, sb, "spk_bwd (upper layers)", TAG_MISC, join=True)
+            self._unpack_early()
+
+    def dx_done(self, l: int):
+        """After dx of layer l: the ungrouped plan unpacks the upper half's gradients here; after the chain nothing is early."""
+        if not self.grouped and self.early is not None and l == self.dec.NL // 2:
+            self._unpack_early()
+        if l == 0:
+            self.tbl = self.late
+
+    def merge_early(self):
+        """A plan that unpacked nothing mid-chain (a single group): its early records join the packer's table here."""
+        if self.early is not None:
+            self.late.recs.extend(self.early.recs)
+            self.early = None
+
+    def emit_last(self, lane: int, join: bool):
+        """The last grouped launch: the layers left, and what was deferred to it."""
+        if not self.grouped:
+            return
+        for t, label in self.tail:
+            self._group().add(t, label)
+        with self.plan.side(lane or self.dec._next_lane()):
+            self.grp.emit(self.plan, f"wgrad.group{self.n_groups} (last layers, skip, post)" if not self.multi else
+                          f"wgrad.group{self.n_groups} (layers 0.., base)", TAG_WG_FG, join=join)
+        self.grp = None
+
+    def emit_ups(self):
+        if self.ups is not None:
+            with self.plan.side(self.dec._next_lane()):
+                self.ups.emit(self.plan, "wgrad.group (upsamplers, lc conv)", TAG_UPS)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1029,11 +1028,19 @@ def det_colsum(ws: Workspace, cs: "L.Colsum", name: str):
     """Scratch + tickets of the deterministic form of a column-sum op (aew_colsum_t.det_scratch / det_tickets: partial sums per
     row chunk, added in a fixed order by the last arriver - no fp32 atomics).  The tickets start at zero and every launch
     leaves them at zero."""
-    import ctypes as _C
-    nf, nt = _C.c_int64(0), _C.c_int32(0)
-    L.check(L.load().aew_colsum_det_size(_C.byref(cs), _C.byref(nf), _C.byref(nt)), "aew_colsum_det_size")
+    nf, nt = C.c_int64(0), C.c_int32(0)
+    L.check(L.load().aew_colsum_det_size(C.byref(cs), C.byref(nf), C.byref(nt)), "aew_colsum_det_size")
     cs.det_scratch = ws.alloc(name + ".scratch", max(4, nf.value), torch.float32).data_ptr()
     cs.det_tickets = ws.alloc(name + ".tickets", max(4, nt.value), torch.int32, zero=True).data_ptr()
+
+
+def colsum_op(ws: Workspace, x: "L.Seg", dtype: int, M: int, N: int, batch: int, out_ptr: int, out_bs: int, det: str) -> "L.Colsum":
+    """Column sums of x [batch][M][N] added into out (pre-zeroed by the plan), deterministic (det_colsum, buffers `det`.*)."""
+    cs = L.Colsum()
+    cs.x, cs.dtype, cs.M, cs.N, cs.batch = x, dtype, M, N, batch
+    cs.out, cs.out_bs, cs.accumulate = out_ptr, out_bs, 1
+    det_colsum(ws, cs, det)
+    return cs
 
 
 def exact_split_args(ws: Workspace, name: str, S: int, cin: int, k_total: int, rows: int, n_pad: int) -> dict:
@@ -1093,28 +1100,26 @@ class EncoderPlan:
         for i, (f, s) in enumerate(zip(G.ENCODER_FILTERS, G.ENCODER_STRIDES)):
             nm = f"encoder.net.{i}.conv."
             Wm = Mat.new(ws, f"enc.wp.{i}", 1, Ep, f * cinp, F3)
-            packer.rec(nm + "weight", 0, [cin * f, f, 1], [E, cin, f], Wm, 0, [f * cinp, 1, cinp], first=(i == 0))
+            packer.pack(self._w_piece(i, cinp), Wm, first=(i == 0))
             self.W.append(Wm)
-            # dgrad layouts, bf16: [ci][k*Eb + co] <- W[co][ci][k]  (per output phase for strided layers)
-            if s == 1:
-                WT = Mat.new(ws, f"enc.wpT.{i}", 1, cinb, f * Eb, BF)
-                packer.rec(nm + "weight", 0, [cin * f, f, 1], [E, cin, f], WT, 0, [1, f * Eb, Eb], late=True)
-                self.WT.append([WT])
-            else:
-                phs = []
-                for ph in range(s):
-                    WT = Mat.new(ws, f"enc.wpT.{i}.{ph}", 1, cinb, (f // s) * Eb, BF)
-                    # [ci][j*Eb + co] <- W[co][ci][ph + s*j]
-                    packer.rec(nm + "weight", ph, [cin * f, f, s], [E, cin, f // s], WT, 0, [1, (f // s) * Eb, Eb],
-                               late=True)
-                    phs.append(WT)
-                self.WT.append(phs)
+            # dgrad layouts, bf16, per output phase ph < s: [ci][j*Eb + co] <- W[co][ci][ph + s*j]
+            phs = []
+            for ph in range(s):
+                WT = Mat.new(ws, f"enc.wpT.{i}" + (f".{ph}" if s > 1 else ""), 1, cinb, (f // s) * Eb, BF)
+                packer.pack(Piece(nm + "weight", ph, [cin * f, f, s], [E, cin, f // s], 0, [1, (f // s) * Eb, Eb]), WT, late=True)
+                phs.append(WT)
+            self.WT.append(phs)
             bt = ws.alloc(f"enc.wp.bias{i}", Ep, torch.float32)
             (packer.first_tbl if (i == 0 and packer.first_tbl is not None) else packer.pack_tbl).add(
                 ps.ptr(nm + "bias"), bt.data_ptr(), [E], [1], [1], F3, F3)
             self.bias.append(bt)
             cin, cinp, cinb = E, Ep, Eb
-        self.gbuf = {}
+
+    def _w_piece(self, i: int, pitch: int) -> Piece:
+        """Layer i's conv weight [E][cin][f] as [E][f * pitch], tap-major with the input channels padded to `pitch`: the
+        forward's fp32 matrix (pitch = channels rounded up to 64) and the weight gradient (to 128, the bf16 operand's)."""
+        cin, f = (self.n_mel if i == 0 else self.E), G.ENCODER_FILTERS[i]
+        return Piece(f"encoder.net.{i}.conv.weight", 0, [cin * f, f, 1], [self.E, cin, f], 0, [f * pitch, 1, pitch])
 
     def build_forward(self, plan: Plan, join_before_layer1=False):
         """join_before_layer1: join spec (see Plan.add) for the layer-1 GEMM - the side lane that packs the weights of
@@ -1152,24 +1157,17 @@ class EncoderPlan:
             t = make_tn(BF, Lo, B, E, Eb, dpre.seg(Eb), [X.seg(cinb, row_step=s, row_off=k) for k in range(f)],
                         impl=impl)
             if grp is None:
-                cs = L.Colsum()
-                cs.x = dpre.seg(128)
-                cs.dtype, cs.M, cs.N, cs.batch = BF, Lo, E, B
-                cs.out, cs.out_bs, cs.accumulate = ps.ptr(f"encoder.net.{i}.conv.bias", True), 0, 1
-                det_colsum(self.ws, cs, f"det.db.enc{i}")
+                cs = colsum_op(self.ws, dpre.seg(128), BF, Lo, E, B, ps.ptr(f"encoder.net.{i}.conv.bias", True), 0, f"det.db.enc{i}")
                 with plan.side(1 + (2 * i) % DecoderPlan.n_side_lanes):
                     plan.add(L.OP_COLSUM, cs, f"db.enc{i}", TAG_ENC)
-            slabs = L.tn_slabs(t) if grp is None else 1
-            gt = self.ws.alloc(f"enc.wg.{i}", slabs * Eb * t.K_total, torch.float32)
-            t.out, t.out_batch_stride = gt.data_ptr(), Eb * t.K_total
+            wg = wgrad_slab(self.ws, f"enc.wg.{i}", t, L.tn_slabs(t) if grp is None else 1, pk.unpack_tbl)
             if grp is None:
                 with plan.side(1 + (2 * i + 1) % DecoderPlan.n_side_lanes):
                     plan.add(L.OP_GEMM_TN, t, f"wgrad.enc{i}", TAG_ENC)
             else:
                 t.colsum_out = ps.ptr(f"encoder.net.{i}.conv.bias", True)
                 grp.add(t, f"wgrad.enc{i}")
-            pk.rec(f"encoder.net.{i}.conv.weight", 0, [cin * f, f, 1], [E, cin, f], None, 0,
-                   [f * cinb, 1, cinb], g_ptr=gt.data_ptr(), slabs=slabs, slab_stride=Eb * t.K_total)
+            pk.unpack([self._w_piece(i, cinb)], wg)
             if i == 0 and not need_input_grad:
                 continue
             dX = self.dy[i]

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib as L
 from . import geometry as G
-from .engine import (BF, F3, DecoderPlan, EncoderPlan, Packer, ParamStore, TAG_ADAM, TAG_ENC, det_colsum, exact_split_args,
+from .engine import (BF, F3, DecoderPlan, EncoderPlan, Packer, ParamStore, Piece, wgrad_slab, TAG_ADAM, TAG_ENC, colsum_op, exact_split_args,
                      TAG_LOSS, TAG_MISC, TAG_PACK, TAG_VQ, bottleneck_param_specs,
                      decoder_param_specs, encoder_param_specs)
 from .plan import CopyTableBuilder, Mat, Plan, Workspace, insert_nt_chains, make_nt, make_tn, null_view, ru, split_small_nt
@@ -162,7 +162,6 @@ class TrainEngine:
             lc_src = self.mel_cl
         self.dec = DecoderPlan(ws, ps, hps, g, B, dec_pre, hps.n_lc_in, lc_src, self.in_wav, self.in_voice,
                                self.in_jitter, take_compat, self.pk_dec, impl, wgrad_group=self.wgrad_group)
-        self.dec.unpack_early_tbl = CopyTableBuilder(ws, "tbl.unpack_dec_early")
         self._build()
         self.adam_state = None
         self.step_count = 0
@@ -180,8 +179,9 @@ class TrainEngine:
         self.lin = Mat.new(ws, "bn.lin", B, Ne, self.nlin_p, F3)          # ze / (mu|logvar)
         self.Wl = Mat.new(ws, "bn.wp.lin", 1, self.nlin_p, Ep, F3)
         self.WlT = Mat.new(ws, "bn.wp.linT", 1, Ep, self.nlin_p, F3)
-        self.pk.rec("bottleneck.linear.weight", 0, [E, 1], [nlin, E], self.Wl, 0, [Ep, 1])
-        self.pk.rec("bottleneck.linear.weight", 0, [E, 1], [nlin, E], self.WlT, 0, [1, self.nlin_p])
+        self.lin_piece = Piece("bottleneck.linear.weight", 0, [E, 1], [nlin, E], 0, [Ep, 1])     # Wl, and its gradient
+        self.pk.pack(self.lin_piece, self.Wl)
+        self.pk.pack(self.lin_piece.at(0, [1, self.nlin_p]), self.WlT)
         self.dlin = Mat.new(ws, "bn.dlin", B, Ne, self.nlin_p, F3)
         if bn in ("vqvae-ema", "vqvae"):
             K = hps.bn_vq_n_embed
@@ -400,7 +400,7 @@ class TrainEngine:
         nll_scale = (1.0 / n_pos) if mean else 1.0
         if bn == "vqvae-ema" and self.loss_mode == "head":
             nll_scale = 0.0
-        self.dec.build_backward(bw, nll_scale)
+        self.dec.build_backward(bw, nll_scale, early_tbl=CopyTableBuilder(ws, "tbl.unpack_dec_early"))
         if self.nt_chain_bwd_used >= 2:
             heads = ("d.post2", "d.post1")[int(self.nt_chain_bwd_phase):]    # (phase 1: pairs are (dx.l, dz.l-1), not (dz.l, dx.l))
             insert_nt_chains(bw, ws, "chain.bwd", lambda lab: lab.startswith(heads + ("dz.", "dx.")),
@@ -416,7 +416,7 @@ class TrainEngine:
             mo.out = self.gstat.data_ptr() + 4 * slot
             with bw.side(1):
                 bw.add(L.OP_MOMENTS, mo, f"grad stats ({nm})", TAG_LOSS)
-        with bw.side(getattr(self.dec, "tail_lane_used", 0) or 1):                 # after every decoder wgrad on any side lane
+        with bw.side(self.dec.tail_lane_used or 1):                 # after every decoder wgrad on any side lane
             self.unpack_dec.emit(bw, "unpack grads (decoder)", join=True)
         if self.enc is not None:
             moments(self.dec.dlc_src, hps.bn_n_out, 4, "bn")
@@ -440,22 +440,15 @@ class TrainEngine:
                 bw.add(L.OP_VAE, self._vae_op(True, dcode), "vae.bwd", TAG_VQ)
             elif bn == "ae":
                 bw.add(L.OP_AE_NORM, self._ae_norm_op(True, dcode), "ae.norm.bwd", TAG_VQ)
-                cs = L.Colsum()
-                cs.x = self.dlin.seg(64)
-                cs.dtype, cs.M, cs.N, cs.batch = F3, g.embed_len, self.d, B
-                cs.out, cs.out_bs, cs.accumulate = ps.ptr("bottleneck.linear.bias", True), 0, 1
-                det_colsum(ws, cs, "det.db.bn")
+                cs = colsum_op(ws, self.dlin.seg(64), F3, g.embed_len, self.d, B, ps.ptr("bottleneck.linear.bias", True), 0, "det.db.bn")
                 with bw.side():
                     bw.add(L.OP_COLSUM, cs, "db.bn", TAG_VQ)
             # linear wgrad / dgrad
             t = make_tn(F3, g.embed_len, B, self.nlin, self.nlin_p, self.dlin.seg(64), [y9.seg(Ep)], impl=impl)
-            slabs = L.tn_slabs(t)
-            gt = ws.alloc("bn.wg.lin", slabs * self.nlin_p * Ep, torch.float32)
-            t.out, t.out_batch_stride = gt.data_ptr(), self.nlin_p * Ep
+            wg = wgrad_slab(ws, "bn.wg.lin", t, L.tn_slabs(t), self.unpack_tbl)
             with bw.side():
                 bw.add(L.OP_GEMM_TN, t, "wgrad.bn.linear", TAG_VQ)
-            self.pk.rec("bottleneck.linear.weight", 0, [hps.enc_n_out, 1], [self.nlin, hps.enc_n_out], None, 0,
-                        [Ep, 1], g_ptr=gt.data_ptr(), slabs=slabs, slab_stride=self.nlin_p * Ep)
+            self.pk.unpack([self.lin_piece], wg)
             bw.add(L.OP_GEMM_NT, make_nt(F3, g.embed_len, hps.enc_n_out, Ep, B, [self.dlin.seg(self.nlin_p)],
                                          self.WlT.ptr, flags=L.EF_OUT1_POS1, out0=self.enc.dy[9].view(),
                                          out1=self.enc.dpre[9].view(), aux1=self.enc.r[9].view(), impl=impl),
@@ -505,7 +498,7 @@ class TrainEngine:
         # the flat buffer from dec_hi_offset) is final, so that exchange starts under the second half of the chain
         self.bwd_a1 = self.bwd_a2 = None
         self.dec_hi_offset = None
-        hi = getattr(self.dec, "hi_first_layer", None)
+        hi = self.dec.hi_first_layer
         lab_hi = "unpack grads (decoder, upper layers)"
         if hi is not None and lab_hi in bw.labels[:cut]:
             c1 = bw.labels.index(lab_hi) + 1
