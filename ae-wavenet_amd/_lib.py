@@ -23,7 +23,7 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO) = range(1, 28)
+ OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP) = range(1, 29)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -180,7 +180,13 @@ class Reduce(C.Structure):
 class Adam(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("lr", f32),
                 ("beta1", f32), ("beta2", f32), ("eps", f32), ("bc1", f32), ("bc2", f32),
-                ("grad_scale", f32), ("pad_", i32), ("guard", vp), ("clip", vp), ("track", vp)]
+                ("grad_scale", f32), ("pad_", i32), ("guard", vp), ("clip", vp), ("track", vp),
+                ("avg", vp), ("avg_rate", f32), ("pad2_", i32)]
+
+
+class Swap(C.Structure):
+    """aew_swap_t: exchange two flat fp32 buffers in place (the parameters and their average, Adam.avg)."""
+    _fields_ = [("a", vp), ("b", vp), ("n", i64)]
 
 
 UW_CHUNK = 4096
@@ -259,7 +265,7 @@ class _OpU(C.Union):
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
-                ("ratio", UpdateRatio)]
+                ("ratio", UpdateRatio), ("swap", Swap)]
 
 
 class Op(C.Structure):
@@ -272,7 +278,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_BASE_GATHER: "base", OP_SOFTMAX_NLL: "sm", OP_COLSUM: "cs", OP_REDUCE: "red",
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
-            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio"}
+            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap"}
 
 
 
@@ -373,12 +379,12 @@ def load():
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
-                       (15, UpdateRatio), (16, NtPick)):
+                       (15, UpdateRatio), (16, NtPick), (17, Swap)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 23:
+    if lib.aew_abi_version() != 24:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib

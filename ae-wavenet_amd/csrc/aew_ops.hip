@@ -1202,8 +1202,13 @@ __device__ __forceinline__ void adam_elem(const aew_adam_t& a, const float gs, c
     v = a.beta2 * v + (1.f - a.beta2) * gr * gr;
     p -= step * m / (sqrtf(v) * inv_sqrt_bc2 + a.eps);
 }
+// The averaged weights (aew_adam_t.avg): s += rate * (p_new - s) in three round-to-nearest operations - the intrinsics
+// keep the compiler from contracting them into an FMA, so a host restatement in fp32 gives the same bits.
+__device__ __forceinline__ float avg_elem(const float s, const float rate, const float p_new) {
+    return __fadd_rn(s, __fmul_rn(rate, __fsub_rn(p_new, s)));
+}
 
-template <bool CLIP>
+template <bool CLIP, bool AVG>
 __global__ void k_adam(const aew_adam_t a) {
     const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i4 >= a.n) return;
@@ -1220,18 +1225,45 @@ __global__ void k_adam(const aew_adam_t a) {
         float4 g = *reinterpret_cast<const float4*>(a.g + i4);
         float4 m = *reinterpret_cast<float4*>(a.m + i4);
         float4 v = *reinterpret_cast<float4*>(a.v + i4);
-        float* pp = &p.x; float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
+        float4 s;
+        if (AVG) s = *reinterpret_cast<const float4*>(a.avg + i4);
+        float* pp = &p.x; float* gp = &g.x; float* mp = &m.x; float* vp = &v.x; float* sp = &s.x;
 #pragma unroll
         for (int r = 0; r < 4; ++r) adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pp[r], gp[r], mp[r], vp[r]);
         *reinterpret_cast<float4*>(a.p + i4) = p;
         *reinterpret_cast<float4*>(a.m + i4) = m;
         *reinterpret_cast<float4*>(a.v + i4) = v;
+        if (AVG) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sp[r] = avg_elem(sp[r], a.avg_rate, pp[r]);
+            *reinterpret_cast<float4*>(a.avg + i4) = s;
+        }
     } else {
         for (int64_t i = i4; i < a.n; ++i) {
             float p = a.p[i], m = a.m[i], v = a.v[i];
             adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, p, a.g[i], m, v);
             a.m[i] = m; a.v[i] = v;
             a.p[i] = p;
+            if (AVG) a.avg[i] = avg_elem(a.avg[i], a.avg_rate, p);
+        }
+    }
+}
+
+// =============================================================================================
+// swap (aew_swap_t): a[i] <-> b[i], one pass, 16-byte loads and stores, scalar tail in the thread behind the last float4
+// =============================================================================================
+__global__ __launch_bounds__(256) void k_swap(const aew_swap_t p) {
+    const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 >= p.n) return;
+    if (i4 + 4 <= p.n) {
+        const float4 x = *reinterpret_cast<const float4*>(p.a + i4);
+        const float4 y = *reinterpret_cast<const float4*>(p.b + i4);
+        *reinterpret_cast<float4*>(p.a + i4) = y;
+        *reinterpret_cast<float4*>(p.b + i4) = x;
+    } else {
+        for (int64_t i = i4; i < p.n; ++i) {
+            const float x = p.a[i], y = p.b[i];
+            p.a[i] = y; p.b[i] = x;
         }
     }
 }
@@ -1338,7 +1370,7 @@ __global__ __launch_bounds__(256) void k_grad_norm(const aew_grad_norm_t p) {
 // update / weight ratios (aew_uw_track_t, aew_update_ratio_t; chassis.py:162-185): the Adam launch with one block per
 // chunk of the host's chunk table, fp64 sums of (p_old - p_new)^2 and p_old^2 per chunk, then one block per tensor
 // =============================================================================================
-template <bool CLIP>
+template <bool CLIP, bool AVG>
 __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_uw_chunk_t* __restrict__ chunks, double* part,
                                                  const int64_t base, const int chunk0) {
     constexpr int IT = AEW_UW_CHUNK / 1024;            // float4 rounds of the block over a whole chunk
@@ -1361,7 +1393,7 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
     const float inv_sqrt_bc2 = rsqrtf(a.bc2);
     const float step = a.lr / a.bc1;
     double sd = 0.0, sw = 0.0;                         // one chain per sum and thread, elements ascending
-    float4 p[IT], g[IT], m[IT], v[IT];
+    float4 p[IT], g[IT], m[IT], v[IT], sa[IT];
 #pragma unroll
     for (int it = 0; it < IT; ++it) {                  // every load of the block's part in flight first
         const int64_t i4 = s + (int64_t)(it * 256 + tid) * 4;
@@ -1371,6 +1403,7 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
                 g[it] = *reinterpret_cast<const float4*>(a.g + i4);
                 m[it] = *reinterpret_cast<const float4*>(a.m + i4);
                 v[it] = *reinterpret_cast<const float4*>(a.v + i4);
+                if (AVG) sa[it] = *reinterpret_cast<const float4*>(a.avg + i4);
             }
         }
     }
@@ -1387,6 +1420,12 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
                 *reinterpret_cast<float4*>(a.p + i4) = p[it];
                 *reinterpret_cast<float4*>(a.m + i4) = m[it];
                 *reinterpret_cast<float4*>(a.v + i4) = v[it];
+                if (AVG) {
+                    float* sp = &sa[it].x;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sp[r] = avg_elem(sp[r], a.avg_rate, pp[r]);
+                    *reinterpret_cast<float4*>(a.avg + i4) = sa[it];
+                }
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -1406,6 +1445,7 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
                 adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pn, a.g[i], mm, vv);
                 a.m[i] = mm; a.v[i] = vv;
                 a.p[i] = pn;
+                if (AVG) a.avg[i] = avg_elem(a.avg[i], a.avg_rate, pn);
             }
             if (i < e_sum) {
                 const float d = old - pn;
@@ -2197,8 +2237,9 @@ static int launch_adam_tracked(const aew_adam_t& p, hipStream_t st) {
         if (int rc = launch_zero(z, st)) return rc;
     }
     const dim3 grid((unsigned)(c1 - c0 + 1));
-    if (p.clip) hipLaunchKernelGGL(k_adam_uw<true>, grid, dim3(256), 0, st, p, t.chunks, t.part, t.base, (int)c0);
-    else hipLaunchKernelGGL(k_adam_uw<false>, grid, dim3(256), 0, st, p, t.chunks, t.part, t.base, (int)c0);
+    auto k = p.clip ? (p.avg ? k_adam_uw<true, true> : k_adam_uw<true, false>)
+                    : (p.avg ? k_adam_uw<false, true> : k_adam_uw<false, false>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, p, t.chunks, t.part, t.base, (int)c0);
     return (int)hipGetLastError();
 }
 static int launch_update_ratio(const aew_update_ratio_t& p, hipStream_t st) {
@@ -2211,9 +2252,23 @@ static int launch_update_ratio(const aew_update_ratio_t& p, hipStream_t st) {
 }
 static int launch_adam(const aew_adam_t& p, hipStream_t st) {
     if (((uintptr_t)p.p | (uintptr_t)p.g | (uintptr_t)p.m | (uintptr_t)p.v) & 15) return AEW_E_ALIGN;
+    if (p.avg) {
+        if ((uintptr_t)p.avg & 15) return AEW_E_ALIGN;
+        if (!(p.avg_rate >= 0.f && p.avg_rate <= 1.f)) return AEW_E_ARG;
+    }
     if (p.track) return launch_adam_tracked(p, st);
-    if (p.clip) hipLaunchKernelGGL(k_adam<true>, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_adam<false>, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
+    auto k = p.clip ? (p.avg ? k_adam<true, true> : k_adam<true, false>) : (p.avg ? k_adam<false, true> : k_adam<false, false>);
+    hipLaunchKernelGGL(k, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
+    return (int)hipGetLastError();
+}
+static int launch_swap(const aew_swap_t& p, hipStream_t st) {
+    if (p.n < 0 || (p.n > 0 && (!p.a || !p.b))) return AEW_E_ARG;
+    if (p.n == 0) return 0;
+    if (((uintptr_t)p.a | (uintptr_t)p.b) & 15) return AEW_E_ALIGN;
+    if (p.a < p.b ? p.a + p.n > p.b : p.b + p.n > p.a) return AEW_E_ARG;      // overlapping buffers: not an exchange
+    const int64_t blocks = cdiv64((p.n + 3) / 4, 256);
+    if (blocks > 0x7fffffff) return AEW_E_ARG;
+    hipLaunchKernelGGL(k_swap, dim3((unsigned)blocks), dim3(256), 0, st, p);
     return (int)hipGetLastError();
 }
 static int grad_norm_blocks(const aew_grad_norm_t& p, int64_t* blocks) {

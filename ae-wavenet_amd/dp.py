@@ -35,6 +35,13 @@ replicated remainders (equal on every rank: counted once); the per-tensor fp64 p
 finalizing launch takes norms and ratios from them, so every rank holds the same ratios while the parameter all-gathers
 are still in flight.  The reference's clone-and-norm loop around optim.step() must NOT be used with the sharded schedule:
 after the step p.data is complete only once those all-gathers are.
+
+Averaged weights (avg_rate in the Adam keywords; aew_adam_t.avg): the Adam launch averages the elements it updates.
+All-reduce schedule: every rank runs the same whole-buffer step, nothing else to do.  Sharded schedule: a rank averages
+its own shards and the replicated remainders - like the moments, its average is complete for its own shards only until
+gather_moments() / sync_optimizer_state() all-gathers adam_avg along with them; FusedAdam.averaged_weights() refuses to
+swap in an incomplete average.  A copy of the parameters updated with torch._foreach_lerp_ behind optim.step() must NOT
+be used with the sharded schedule: p.data is complete only once the parameter all-gathers are.
 """
 from __future__ import annotations
 
@@ -440,14 +447,15 @@ class DataParallel:
         return [(hi, n), (lo, hi), (0, lo)] if hi is not None else [(lo, n), (0, lo)]
 
     def gather_moments(self, eng):
-        """All-gather the Adam moments (each rank holds valid moments for its own shards only under the sharded step).
-        COLLECTIVE: every rank must call it."""
+        """All-gather the Adam moments (each rank holds valid moments for its own shards only under the sharded step) and,
+        where the optimizer keeps them, the averaged weights, which follow the same rule.  COLLECTIVE: every rank must
+        call it."""
         if self._solo():
             return
         for a, b in self._regions(eng):
             s, rem = self._split(a, b)
             if s > 0:
-                for buf in (eng.adam_m, eng.adam_v):
+                for buf in (eng.adam_m, eng.adam_v) + ((eng.adam_avg,) if eng.avg_live else ()):
                     dist.all_gather_into_tensor(buf[a:a + self.world * s], buf[a + self.rank * s: a + (self.rank + 1) * s].clone(),
                                                 group=self.group)
         self.moments_step = eng.step_count

@@ -596,6 +596,16 @@ class TrainEngine:
         ur.part, ur.first, ur.n_tensors, ur.finalize = self.uw_part.data_ptr(), self.uw_first.data_ptr(), P, 1
         ur.sums, ur.out = self.uw_sums.data_ptr(), self.uw_out.data_ptr()
         self.ratio.add(L.OP_UPDATE_RATIO, ur, "update ratio", TAG_ADAM)
+        # ===== averaged (EMA) weights (aew_adam_t.avg: updated only when adam_step() is given avg_rate) and the swap
+        # that puts them in the parameters' place for sampling / evaluation
+        self.adam_avg = None              # flat like adam_m / adam_v; allocated by the first use (_avg_buffer): an engine that
+                                          # never averages holds neither the 4 bytes per parameter nor the swap op.
+                                          # INVARIANT: avg_live implies adam_avg is allocated - set avg_live only behind
+                                          # _avg_buffer(); readers (dp.gather_moments, the surface's carry) test avg_live
+        self.avg_steps = 0                # averaged steps taken so far (a skipped step counts, like step_count)
+        self.avg_live = False             # adam_avg holds an average (started by a step, or restored by the module surface)
+        self.averaged_in = False          # the average sits in ps.params, the raw parameters in adam_avg
+        self.swap = Plan("swap")          # one op over ps.params / adam_avg, added with the buffer
 
     def _vae_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.Vae:
         va = L.Vae()
@@ -904,7 +914,7 @@ class TrainEngine:
 
     def adam_step(self, lr: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                   lo: int = 0, hi: Optional[int] = None, count: bool = True, max_grad_norm: Optional[float] = None,
-                  norm_done: bool = False, track: bool = False):
+                  norm_done: bool = False, track: bool = False, avg_rate: Optional[float] = None):
         """One Adam step over the flat buffer, or over its element range [lo, hi) (multiples of 4): a
         data-parallel caller updates the decoder tail while the encoder gradients are still being
         reduced (`count=False` on all but the first range of a step).
@@ -915,13 +925,30 @@ class TrainEngine:
         itself (sharded data parallel).  None: the op reads no clip word - the step of an engine without clipping.
         track: the launch also sums (p_old - p_new)^2 and p_old^2 per chunk of the parameter tensors it covers
         (aew_uw_track_t); the first tracked call of a step clears the sums, a whole-buffer step reduces them to
-        update_ratios() right away, range calls leave that to the accessor.  False: the op carries no record."""
+        update_ratios() right away, range calls leave that to the accessor.  False: the op carries no record.
+        avg_rate: the launch also moves the averaged weights (adam_avg, aew_adam_t.avg) of the elements it updates towards
+        their new values, avg += avg_rate * (p_new - avg), avg_rate = 1 - decay of this step; the first averaged call of
+        an engine without an average starts it from the parameters in front of that step.  A step the device skips leaves
+        the average alone; avg_steps advances with count like step_count.  None: the op carries no average."""
+        if self.averaged_in:
+            raise L.AewError("adam_step() while the averaged weights are swapped in: the step would update the average "
+                             "in the parameters' place (leave FusedAdam.averaged_weights() / call swap_averaged() first)")
+        if avg_rate is not None and not 0.0 <= float(avg_rate) <= 1.0:
+            raise ValueError(f"Invalid avg_rate: {avg_rate} (1 - decay, within [0, 1])")
+        hi = self.ps.numel if hi is None else hi
+        assert lo % 4 == 0 and (hi % 4 == 0 or hi == self.ps.numel) and 0 <= lo < hi <= self.ps.numel
+        # every argument is checked by here: a refused call leaves the counters and the average as they were
+        if avg_rate is not None:
+            if not self.avg_live:
+                n = self.ps.numel
+                self._avg_buffer()[:n].copy_(self.ps.params[:n])
+                self.avg_live = True
+            if count:
+                self.avg_steps += 1
         if count:
             self.step_count += 1
             self._uw_zero = True
         self.weights_version += 1
-        hi = self.ps.numel if hi is None else hi
-        assert lo % 4 == 0 and (hi % 4 == 0 or hi == self.ps.numel) and 0 <= lo < hi <= self.ps.numel
         if max_grad_norm is not None and count and not norm_done:
             self.grad_norm_step([(0, self.ps.numel)], max_grad_norm, grad_scale)
         a = self.opt.array()[0].u.adam
@@ -933,6 +960,7 @@ class TrainEngine:
         a.bc2 = 1.0 - betas[1] ** self.step_count
         a.grad_scale = grad_scale
         a.clip = self.clip_out.data_ptr() + 4 if max_grad_norm is not None else None
+        a.avg, a.avg_rate = (self._avg_buffer().data_ptr() + 4 * lo, float(avg_rate)) if avg_rate is not None else (None, 0.0)
         a.track = None
         if track:
             self.uw_track.base, self.uw_track.zero = lo, int(self._uw_zero)
@@ -944,6 +972,26 @@ class TrainEngine:
                 self.ratio_step()
             else:
                 self._uw_stale = True
+
+    def _avg_buffer(self) -> torch.Tensor:
+        """adam_avg, allocated (and the swap plan completed) at its first use."""
+        if self.adam_avg is None:
+            self.adam_avg = self.ws.alloc("adam.avg", self.ps.numel, torch.float32)
+            sw = L.Swap()
+            sw.a, sw.b, sw.n = self.ps.params.data_ptr(), self.adam_avg.data_ptr(), self.ps.numel
+            self.swap.add(L.OP_SWAP, sw, "swap averaged weights", TAG_ADAM)
+        return self.adam_avg
+
+    def swap_averaged(self):
+        """Exchange the parameters with their average on the device (AEW_OP_SWAP, one pass, no third buffer): after an odd
+        number of calls forward / sampling / state_dict see the averaged weights and adam_avg holds the raw ones
+        (`averaged_in`); adam_step() refuses to run until they are swapped back.  Everything that keeps a packed copy of
+        the weights re-packs (weights_version)."""
+        if not self.avg_live:
+            raise L.AewError("no averaged weights yet: no optimizer step with an average has run on this engine")
+        self.swap.run(self._stream())
+        self.weights_version += 1
+        self.averaged_in = not self.averaged_in
 
     # --------------------------------------------------------------------------------------
     # views for the module surface / tests

@@ -5,7 +5,36 @@ Drop-in for the harness: `ss.optim = FusedAdam(model, lr)` in place of `t.optim.
 """
 from __future__ import annotations
 
+import contextlib
+
+import numpy as np
 import torch
+
+from . import _lib as L
+
+EMA_WARMUP_NUM, EMA_WARMUP_DEN = 1, 10       # decay of averaged step t with warm-up: min(ema_decay, (1 + t) / (10 + t))
+
+
+def _check_ema_decay(d):
+    if d is None:
+        return None
+    try:                                                     # like max_grad_norm: whatever float() takes (numpy scalars, 0-d tensors)
+        f = float(d)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if not (0.0 < f < 1.0):
+        raise ValueError(f"Invalid ema_decay: {d!r} (a number in (0, 1), or None for no averaged weights)")
+    return f
+
+
+def ema_decay_at(ema_decay: float, t: int, warmup: bool = True) -> float:
+    """Decay of the averaged step number t (t = averaged steps taken before it), in double."""
+    return min(float(ema_decay), (EMA_WARMUP_NUM + t) / (EMA_WARMUP_DEN + t)) if warmup else float(ema_decay)
+
+
+def ema_rate_at(ema_decay: float, t: int, warmup: bool = True) -> float:
+    """What the kernel multiplies by (aew_adam_t.avg_rate): 1 - decay in double, rounded to fp32 once."""
+    return float(np.float32(1.0 - ema_decay_at(ema_decay, t, warmup)))
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -28,19 +57,34 @@ class FusedAdam(torch.optim.Optimizer):
     progress step computes with a clone of every parameter in front of `step()` and a loop of norms behind it
     (chassis.py:162-163,180-183), here summed inside the Adam launch (aew_uw_track_t): no clone, no host
     synchronisation, one summation order, and right under the sharded data-parallel schedule.  Parameters and moments
-    are bit for bit those of an untracked step.  The value lives in `param_groups[0]["track_update_ratio"]`."""
+    are bit for bit those of an untracked step.  The value lives in `param_groups[0]["track_update_ratio"]`.
+
+    ema_decay: every step also moves an exponential moving average of the parameters towards their new values inside
+    the Adam launch (aew_adam_t.avg: avg += (1 - decay_t) * (p_new - avg), one more stream of that launch) - what a
+    second copy of the parameters and a `torch._foreach_lerp_` behind `step()` do, and right under the sharded
+    data-parallel schedule, where a rank owns its shards only at the moment of the update.  decay_t =
+    min(ema_decay, (1 + t) / (10 + t)) for the averaged step t = 0, 1, ... with ema_warmup (the default), ema_decay
+    without.  The average starts from the parameters in front of the first averaged step; a step the device skips leaves
+    it alone.  Parameters and moments are bit for bit those of a step without it.  `averaged_weights()` puts the average
+    in the parameters' place for sampling / evaluation.  A number in (0, 1), or None = off.  The values live in
+    `param_groups[0]["ema_decay"]` / `["ema_warmup"]`."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None,
-                 track_update_ratio=False):
+                 track_update_ratio=False, ema_decay=None, ema_warmup=True):
         if max_grad_norm is not None and not (float(max_grad_norm) > 0):
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (a positive number, or None for no clipping)")
         if not isinstance(track_update_ratio, (bool, int)) or track_update_ratio not in (0, 1):
             raise ValueError(f"Invalid track_update_ratio: {track_update_ratio!r} (True or False)")
+        ema_decay = _check_ema_decay(ema_decay)
+        if not isinstance(ema_warmup, (bool, int)) or ema_warmup not in (0, 1):
+            raise ValueError(f"Invalid ema_warmup: {ema_warmup!r} (True or False)")
         self.model = model
         params = list(model.parameters())
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
-                                      track_update_ratio=bool(track_update_ratio)))
+                                      track_update_ratio=bool(track_update_ratio), ema_decay=ema_decay,
+                                      ema_warmup=bool(ema_warmup)))
         self.grad_scale = grad_scale
+        self._averaged_in = False                                # inside averaged_weights()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -52,12 +96,44 @@ class FusedAdam(torch.optim.Optimizer):
         if c is not None and not (float(c) > 0):
             raise ValueError(f"Invalid max_grad_norm: {c}")
         track = bool(g.get("track_update_ratio"))
+        d = _check_ema_decay(g.get("ema_decay"))
+        if self._averaged_in or eng.averaged_in:
+            raise L.AewError("FusedAdam.step() inside averaged_weights(): the averaged weights sit in the parameters' place")
+        kw = {}
+        if d is not None:                                        # (off: the calls below are the ones of an optimizer without it)
+            kw["avg_rate"] = ema_rate_at(d, eng.avg_steps, bool(g.get("ema_warmup", True)))
         dp = getattr(self.model, "_dp", None)
         if dp is not None and dp.sharded and not dp._solo():
             # data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather
-            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track)
+            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track,
+                              **kw)
         else:
-            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"], max_grad_norm=c, track=track)
+            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"], max_grad_norm=c, track=track, **kw)
+
+    # ---- the averaged weights -------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block the model computes with the averaged weights: `model.sample`, `model.forward`, `model.run` and
+        `model.state_dict()` see them (one swap launch on the device; the sampler re-packs); `step()`, `load_state_dict()`,
+        `model.to()` and `model.override()` raise.  On exit - also by an exception - the swap is undone: parameters and
+        average are bit for bit what they were."""
+        model = self.model
+        if self._averaged_in:
+            raise L.AewError("averaged_weights() is already entered")
+        st = model._avg_state_flat()                             # (raises where this rank's average is incomplete: sharded DP)
+        if st is None or int(st[0]) < 1:
+            raise L.AewError("averaged_weights(): no averaged step has run yet (FusedAdam(..., ema_decay=...) and step())")
+        model._dp_finish()                                       # parameter all-gathers in flight write what the swap reads
+        # the swap is a launch on the engine's buffers: with none live (a restored checkpoint, model.to()) the sampling
+        # engine is built, which takes the carried average in
+        (model._engine or model._ensure_engine(1)).swap_averaged()
+        self._averaged_in = True
+        try:
+            yield self
+        finally:
+            self._averaged_in = False
+            model._engine.swap_averaged()                        # (sample() inside may have moved everything to the B = 1
+                                                                 #  engine; to() / override() are refused while swapped in)
 
     # ---- what the last clipped step saw (0-d device tensors: reading one is the caller's synchronisation) ----------
     def _clip_word(self, i):
@@ -127,6 +203,11 @@ class FusedAdam(torch.optim.Optimizer):
             group["max_grad_norm"] = g["max_grad_norm"]
         if g.get("track_update_ratio"):
             group["track_update_ratio"] = True
+        av = None
+        if g.get("ema_decay") is not None:                      # (off: the dictionary is the one of an optimizer without it)
+            av = self.model._avg_state_flat()
+            group["ema_decay"], group["ema_warmup"] = g["ema_decay"], bool(g.get("ema_warmup", True))
+            group["avg_steps"] = int(av[0]) if av is not None else 0
         state = {}
         st = self.model._opt_state_flat()
         if st is not None and int(st[0]) > 0:
@@ -135,9 +216,15 @@ class FusedAdam(torch.optim.Optimizer):
             for i, (n, o, k, shp) in enumerate(lay):
                 state[i] = {"step": torch.tensor(float(step)), "exp_avg": m[o:o + k].reshape(shp).clone(),
                             "exp_avg_sq": v[o:o + k].reshape(shp).clone()}
+            if av is not None and int(av[0]) > 0:
+                a = av[1].detach().cpu()
+                for i, (n, o, k, shp) in enumerate(lay):
+                    state[i]["param_avg"] = a[o:o + k].reshape(shp).clone()
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, state_dict):
+        if self._averaged_in or (self.model._engine is not None and self.model._engine.averaged_in):
+            raise L.AewError("load_state_dict() inside averaged_weights()")     # (before anything is changed)
         lay, total = self._layout()
         groups = state_dict["param_groups"]
         order = [i for g in groups for i in g["params"]]
@@ -151,8 +238,12 @@ class FusedAdam(torch.optim.Optimizer):
             self.param_groups[0]["max_grad_norm"] = g0["max_grad_norm"]
         if g0.get("track_update_ratio") is not None:            # absent: keep the constructor's
             self.param_groups[0]["track_update_ratio"] = bool(g0["track_update_ratio"])
+        if g0.get("ema_decay") is not None:                     # absent (a torch.optim.Adam checkpoint): keep the constructor's
+            self.param_groups[0]["ema_decay"] = _check_ema_decay(g0["ema_decay"])
+            self.param_groups[0]["ema_warmup"] = bool(g0.get("ema_warmup", True))
         st = state_dict.get("state", {})
         m, v = torch.zeros(total), torch.zeros(total)
+        avg, n_avg = torch.zeros(total), 0
         step, found = 0, False
         for pos, idx in enumerate(order):
             s = st.get(idx, st.get(str(idx)))
@@ -165,8 +256,15 @@ class FusedAdam(torch.optim.Optimizer):
             v[o:o + k] = s["exp_avg_sq"].detach().float().cpu().reshape(-1)
             step = max(step, int(float(s["step"])))
             found = True
+            if s.get("param_avg") is not None:
+                if tuple(s["param_avg"].shape) != shp:
+                    raise ValueError(f"param_avg of parameter {n} has shape {tuple(s['param_avg'].shape)}, expected {shp}")
+                avg[o:o + k] = s["param_avg"].detach().float().cpu().reshape(-1)
+                n_avg += 1
         if not found:
             return
+        if n_avg not in (0, len(order)):
+            raise ValueError(f"optimizer state has param_avg for {n_avg} of {len(order)} parameters")
         model = self.model
         model._opt_carry = (step, m.to(model._device), v.to(model._device))
         model._opt_carry_partial = False
@@ -178,6 +276,17 @@ class FusedAdam(torch.optim.Optimizer):
             eng.adam_m[:total].copy_(model._opt_carry[1])
             eng.adam_v[:total].copy_(model._opt_carry[2])
             eng.step_count = step
+        # the averaged weights: restored with their step count; a state without them (torch.optim.Adam's own, or written
+        # before the first averaged step) leaves none - the average then starts from the parameters at the next step
+        if n_avg:
+            model._avg_carry = (max(1, int(g0.get("avg_steps", step))), avg.to(model._device), False)
+            if eng is not None:
+                eng._avg_buffer()[:total].copy_(model._avg_carry[1])
+                eng.avg_steps, eng.avg_live = model._avg_carry[0], True
+        else:
+            model._avg_carry = None
+            if eng is not None:
+                eng.avg_steps, eng.avg_live = 0, False
 
     def zero_grad(self, set_to_none=True):
         # the backward plan rewrites the flat gradient buffer: "cleared" is a flag the next backward reads (no memset;

@@ -120,6 +120,8 @@ class HipModelBase(nn.Module):
         self._engine: Optional[TrainEngine] = None
         self._engines: Dict[int, TrainEngine] = {}      # engines by batch size (train B, sampling B = 1, ...)
         self._opt_carry = None                           # (step, exp_avg flat, exp_avg_sq flat) while no engine holds them
+        self._avg_carry = None                           # (averaged steps, averaged weights flat, swapped in?) beside it; the flag is set
+                                                         # only between two engines (another batch size inside averaged_weights())
         self._grads_cleared = True                       # no backward yet / FusedAdam.zero_grad() since the last one
         self._opt_carry_partial = False                  # carry saved from a sharded DP engine without a moment gather
         self._weights_epoch = 0                          # bumped whenever parameter values change behind torch's back
@@ -161,6 +163,8 @@ class HipModelBase(nn.Module):
     def override(self, n_win_batch=None):
         """mfcc_inverter.py:30-35 (checkpoint.py:46)."""
         if n_win_batch is not None and n_win_batch != self.window_batch_size:
+            if self._engine is not None:
+                self._refuse_while_averaged_in("override()")         # (before anything is changed)
             self.window_batch_size = n_win_batch
             self._set_geometry(n_win_batch)
             self._drop_engine()
@@ -253,6 +257,7 @@ class HipModelBase(nn.Module):
         # engine's flat buffer are copied out by this), then drop the engines; one is rebuilt
         # lazily on the next run() and the values (and the Adam moments) are copied back in.
         if self._engine is not None:
+            self._refuse_while_averaged_in("model.to() / a dtype change")
             self._dp_finish()
             self._sync_buffers_from_engine()
             self._save_opt_carry()
@@ -263,8 +268,17 @@ class HipModelBase(nn.Module):
         if self._opt_carry is not None:
             st, m, v = self._opt_carry
             self._opt_carry = (st, m.to(self._device), v.to(self._device))
+        if self._avg_carry is not None:
+            k, avg, swapped = self._avg_carry
+            self._avg_carry = (k, avg.to(self._device), swapped)
         self._anchor = torch.zeros((), requires_grad=True, device=self._device)
         return out
+
+    def _refuse_while_averaged_in(self, what):
+        """Inside FusedAdam.averaged_weights() the swap back is a launch on the live engine: the engine may change (another
+        batch size, sample()), it may not go away."""
+        if self._engine.averaged_in:
+            raise L.AewError(f"{what} inside FusedAdam.averaged_weights(): leave the context first")
 
     def _drop_engine(self):
         if self._engine is not None:
@@ -285,6 +299,10 @@ class HipModelBase(nn.Module):
             # sharded data parallel: unless the moments were just gathered this rank's copy is valid for its own shards
             # only - enough to continue training on a rebuilt engine (same shard layout), not to write a checkpoint
             self._opt_carry_partial = self._dp is not None and not self._dp.moments_complete(eng)
+        if eng is not None and eng.avg_live:
+            # the averaged weights move with the moments (sharded data parallel: complete where the moments are); while
+            # they are swapped in, adam_avg holds the raw parameters and the flag travels along
+            self._avg_carry = (eng.avg_steps, eng.adam_avg[:eng.ps.numel].detach().clone(), eng.averaged_in)
 
     def _opt_state_flat(self):
         """(step, exp_avg flat, exp_avg_sq flat) from the live engine, else from the carry, else None."""
@@ -300,6 +318,28 @@ class HipModelBase(nn.Module):
             raise L.AewError("the carried Adam moments were saved from a sharded data-parallel engine without "
                              "dp.sync_optimizer_state(model): they are complete for this rank's shards only")
         return self._opt_carry
+
+    def _avg_state_flat(self):
+        """(averaged steps, averaged weights flat) from the live engine, else from the carry, else None - under the rule
+        of _opt_state_flat for sharded data parallel: a rank averages its own shards only."""
+        eng = self._engine
+        if eng is not None:
+            if not eng.avg_live:
+                return None
+            if eng.averaged_in:
+                raise L.AewError("the averaged weights are swapped in (FusedAdam.averaged_weights()): leave the context "
+                                 "before reading optimizer state")
+            if self._dp is not None and not self._dp.moments_complete(eng):
+                raise L.AewError("the averaged weights are sharded across the data-parallel ranks (each rank averages its "
+                                 "own 1/world): call dp.sync_optimizer_state(model) on ALL ranks before reading them on "
+                                 "any of them")
+            return eng.avg_steps, eng.adam_avg[:eng.ps.numel]
+        if self._avg_carry is None:
+            return None
+        if getattr(self, "_opt_carry_partial", False):
+            raise L.AewError("the carried averaged weights were saved from a sharded data-parallel engine without "
+                             "dp.sync_optimizer_state(model): they are complete for this rank's shards only")
+        return self._avg_carry[0], self._avg_carry[1]
 
     def _pull_params_to_cpu(self):
         eng = self._engine
@@ -363,6 +403,12 @@ class HipModelBase(nn.Module):
             eng.adam_m[:n].copy_(m)
             eng.adam_v[:n].copy_(v)
             eng.step_count = int(st)
+        if self._avg_carry is not None:
+            k, avg, swapped = self._avg_carry
+            eng._avg_buffer()[:eng.ps.numel].copy_(avg)
+            eng.avg_steps, eng.avg_live, eng.averaged_in = int(k), True, bool(swapped)
+        else:
+            eng.avg_steps, eng.avg_live, eng.averaged_in = 0, False, False
         if self._dp is not None:
             self._dp.prepare_vae(eng)
         if eng.bn_type == "vae":

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 23
+#define AEW_ABI_VERSION 24
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -533,7 +533,27 @@ typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.op
                                     range per chunk (see above).  The chunks must cover [base, base + n): AEW_E_ARG otherwise,
                                     and for a NULL table / part or base < 0; AEW_E_ALIGN for base % 4 or part % 16.
                                     NULL = the launch of ABI 21, grid and bits.                                            */
+    float* avg;                  /* ABI 24, optional: device buffer with the offsets of p (16-byte aligned: AEW_E_ALIGN) that holds
+                                    an exponential moving average of the parameters.  The thread that updates an element also
+                                    updates its average from the new parameter it still holds in a register:
+                                        s = __fadd_rn(s, __fmul_rn(avg_rate, __fsub_rn(p_new, s)))
+                                    - three round-to-nearest fp32 operations that the compiler may not contract into an FMA, so
+                                    a numpy fp32 restatement gives the same bits.  Vector and scalar-tail paths alike, untracked
+                                    and tracked launch alike; the pad elements behind a tensor are averaged like they are updated,
+                                    and the tracked launch's sums (part[]) do not depend on it.  The per-element Adam arithmetic
+                                    is untouched: p / m / v come out bit for bit as with avg = NULL.  A step the device skips
+                                    (guard non-zero, clip[1] != 0) leaves avg untouched, like p / m / v.
+                                    NULL = the launch of ABI 23, grid and bits.                                            */
+    float avg_rate;              /* 1 - decay of this step, rounded to fp32 once by the host; with avg set it must lie in [0, 1]
+                                    (AEW_E_ARG).  0 leaves avg as it is; 1 gives p_new up to the rounding of p_new - s.        */
+    int32_t pad2_;
 } aew_adam_t;
+
+/* Exchange two flat fp32 buffers in place (ABI 24): a[i] <-> b[i] for i in [0, n).  One pass, float4 loads and stores with a
+ * scalar tail; every element is read once and written once per buffer, no third buffer.  The engine swaps the parameters with
+ * their average (aew_adam_t.avg) around sampling / evaluation.  n = 0 is a no-op.
+ * AEW_E_ARG: n < 0, a NULL pointer with n > 0, buffers that overlap; AEW_E_ALIGN: a or b not 16-byte aligned. */
+typedef struct { float* a; float* b; int64_t n; } aew_swap_t;
 
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
@@ -726,7 +746,8 @@ enum {
     AEW_OP_VQ_EMA, AEW_OP_VQ_BWD, AEW_OP_LC_GATHER, AEW_OP_LC_SCATTER, AEW_OP_SPK_BIAS,
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
-    AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO
+    AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
+    AEW_OP_SWAP
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -752,13 +773,14 @@ typedef struct {
         aew_softmax_nll_t sm; aew_colsum_t cs; aew_reduce_t red; aew_adam_t adam; aew_zero_t zero;
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
+        aew_swap_t swap;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
