@@ -237,7 +237,7 @@ class DataParallel:
             if "enc" in work:
                 self._wait(work["enc"], "grads.encoder")
             eng.adam_step(lr, grad_scale, lo=0, hi=lo, count=False, **adam_kw)
-        self.moments_step = eng.step_count  # all-reduce schedule: every rank updates everything
+        self.moments_complete_at(eng.step_count)    # all-reduce schedule: every rank updates everything
 
     # ---- reduce-scatter + sharded Adam + all-gather ------------------------------------------------------------
     def _split(self, a: int, b: int):
@@ -382,33 +382,30 @@ class DataParallel:
         dec_gathers = [] if late else None
         self._guard_wait()
         clip = adam_kw.get("max_grad_norm")
+
+        def reduced(key, what):
+            """Wait for a region's reduction, then run its finishers; once per step (a second call finds nothing)."""
+            work, fin = st[key]
+            for w in work:
+                self._wait(w, what)
+            for f in fin:
+                f()
+            st[key] = ([], [])
+
         if clip is not None:
             for key, what in (("dec_hi", "grads.decoder_hi"), ("dec", "grads.decoder"), ("head", "grads.encoder")):
                 if key in st:
-                    for w in st[key][0]:
-                        self._wait(w, what)
-                    for f in st[key][1]:
-                        f()
-                    st[key] = ([], [])
+                    reduced(key, what)
             regions = ([(st["hi"], n), (lo, st["hi"])] if "dec_hi" in st else [(lo, n)]) + [(0, lo)]
             self._clip_norm_sharded(eng, regions, clip, grad_scale)
             adam_kw = dict(adam_kw, norm_done=True)
         if "dec_hi" in st:                               # the upper layers' region: reduced under the rest of the chain
-            for w in st["dec_hi"][0]:
-                self._wait(w, "grads.decoder_hi")
-            for f in st["dec_hi"][1]:
-                f()
+            reduced("dec_hi", "grads.decoder_hi")
             pend += [("dec", w) for w in self._update_region(eng, st["hi"], n, lr, grad_scale, True, adam_kw, dec_gathers)]
             counted, dec_end = False, st["hi"]
-        for w in st["dec"][0]:
-            self._wait(w, "grads.decoder")
-        for f in st["dec"][1]:
-            f()
+        reduced("dec", "grads.decoder")
         pend += [("dec", w) for w in self._update_region(eng, lo, dec_end, lr, grad_scale, counted, adam_kw, dec_gathers)]
-        for w in st["head"][0]:
-            self._wait(w, "grads.encoder")
-        for f in st["head"][1]:
-            f()
+        reduced("head", "grads.encoder")
         if lo > 0:
             pend += [("head", w) for w in self._update_region(eng, 0, lo, lr, grad_scale, False, adam_kw)]
         for g in dec_gathers or []:
@@ -455,10 +452,15 @@ class DataParallel:
         for a, b in self._regions(eng):
             s, rem = self._split(a, b)
             if s > 0:
-                for buf in (eng.adam_m, eng.adam_v) + ((eng.adam_avg,) if eng.avg_live else ()):
+                for buf in eng.opt_buffers():
                     dist.all_gather_into_tensor(buf[a:a + self.world * s], buf[a + self.rank * s: a + (self.rank + 1) * s].clone(),
                                                 group=self.group)
-        self.moments_step = eng.step_count
+        self.moments_complete_at(eng.step_count)
+
+    def moments_complete_at(self, step: int):
+        """Every rank holds ALL Adam moments (and the whole average) of this engine step: after a gather, after an
+        all-reduce step, after every rank restored the same complete state (FusedAdam.load_state_dict)."""
+        self.moments_step = int(step)
 
     def moments_complete(self, eng) -> bool:
         """Does this rank hold the Adam moments of ALL parameters for the engine's current step?  (Always under the

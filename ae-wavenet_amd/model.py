@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -26,6 +26,22 @@ MEAN_LOSS = {"none": True, "ae": True, "vae": True, "vqvae": False, "vqvae-ema":
 
 
 _SERIAL = [0]
+
+
+class OptState(NamedTuple):
+    """The optimizer state of a model away from an engine: what TrainEngine.opt_state() hands out and load_opt_state()
+    takes in, what the module surface carries between engines and what FusedAdam reads / restores checkpoints through."""
+    step: int                             # optimizer steps taken
+    m: torch.Tensor                       # first / second moments, flat fp32 [ps.numel]
+    v: torch.Tensor
+    avg_steps: int = 0                    # averaged steps taken
+    avg: Optional[torch.Tensor] = None    # averaged weights, flat like m / v; None = no average
+    averaged_in: bool = False             # the average sits in the parameters' place, `avg` holds the raw ones
+    complete: bool = True                 # False: taken from a sharded data-parallel engine without a gather - valid for
+                                          # that rank's shards only
+
+    def to(self, device) -> "OptState":
+        return self._replace(m=self.m.to(device), v=self.v.to(device), avg=None if self.avg is None else self.avg.to(device))
 
 
 class TrainEngine:
@@ -599,11 +615,9 @@ class TrainEngine:
         # ===== averaged (EMA) weights (aew_adam_t.avg: updated only when adam_step() is given avg_rate) and the swap
         # that puts them in the parameters' place for sampling / evaluation
         self.adam_avg = None              # flat like adam_m / adam_v; allocated by the first use (_avg_buffer): an engine that
-                                          # never averages holds neither the 4 bytes per parameter nor the swap op.
-                                          # INVARIANT: avg_live implies adam_avg is allocated - set avg_live only behind
-                                          # _avg_buffer(); readers (dp.gather_moments, the surface's carry) test avg_live
+                                          # never averages holds neither the 4 bytes per parameter nor the swap op
         self.avg_steps = 0                # averaged steps taken so far (a skipped step counts, like step_count)
-        self.avg_live = False             # adam_avg holds an average (started by a step, or restored by the module surface)
+        self.avg_live = False             # adam_avg holds an average (started by a step, or restored by load_opt_state)
         self.averaged_in = False          # the average sits in ps.params, the raw parameters in adam_avg
         self.swap = Plan("swap")          # one op over ps.params / adam_avg, added with the buffer
 
@@ -974,13 +988,38 @@ class TrainEngine:
                 self._uw_stale = True
 
     def _avg_buffer(self) -> torch.Tensor:
-        """adam_avg, allocated (and the swap plan completed) at its first use."""
+        """adam_avg, allocated (and the swap plan completed) at its first use; avg_live becomes True only behind a call."""
         if self.adam_avg is None:
             self.adam_avg = self.ws.alloc("adam.avg", self.ps.numel, torch.float32)
             sw = L.Swap()
             sw.a, sw.b, sw.n = self.ps.params.data_ptr(), self.adam_avg.data_ptr(), self.ps.numel
             self.swap.add(L.OP_SWAP, sw, "swap averaged weights", TAG_ADAM)
         return self.adam_avg
+
+    # ---- the optimizer state as one record: nothing outside this class writes step_count, avg_steps, avg_live,
+    # averaged_in or (but for dp.gather_moments, in place, through opt_buffers) the three flat buffers
+    def opt_buffers(self) -> tuple:
+        """The flat state buffers that hold values: adam_m, adam_v and, once there is an average, adam_avg."""
+        return (self.adam_m, self.adam_v) + ((self.adam_avg,) if self.avg_live else ())
+
+    def opt_state(self, clone: bool) -> OptState:
+        """The state as views of the engine's buffers, or as clones that outlive it."""
+        n = self.ps.numel
+        m, v, *avg = [b[:n].detach().clone() if clone else b[:n] for b in self.opt_buffers()]
+        return OptState(self.step_count, m, v, self.avg_steps, avg[0] if avg else None, self.averaged_in)
+
+    def load_opt_state(self, st: OptState):
+        """Take a record in (tensors from any device).  One without an average leaves the engine without one: the
+        average then starts again from the parameters at the next averaged step."""
+        n = self.ps.numel
+        self.adam_m[:n].copy_(st.m)
+        self.adam_v[:n].copy_(st.v)
+        self.step_count = int(st.step)
+        if st.avg is not None:
+            self._avg_buffer()[:n].copy_(st.avg)
+            self.avg_steps, self.avg_live, self.averaged_in = int(st.avg_steps), True, bool(st.averaged_in)
+        else:
+            self.avg_steps, self.avg_live, self.averaged_in = 0, False, False
 
     def swap_averaged(self):
         """Exchange the parameters with their average on the device (AEW_OP_SWAP, one pass, no third buffer): after an odd

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .model import OptState
 
 EMA_WARMUP_NUM, EMA_WARMUP_DEN = 1, 10       # decay of averaged step t with warm-up: min(ema_decay, (1 + t) / (10 + t))
 
@@ -25,6 +26,18 @@ def _check_ema_decay(d):
     if not (0.0 < f < 1.0):
         raise ValueError(f"Invalid ema_decay: {d!r} (a number in (0, 1), or None for no averaged weights)")
     return f
+
+
+def _check_max_grad_norm(c):
+    if c is not None and not (float(c) > 0):
+        raise ValueError(f"Invalid max_grad_norm: {c} (a positive number, or None for no clipping)")
+    return c
+
+
+def _check_flag(name, b):
+    if not isinstance(b, (bool, int)) or b not in (0, 1):
+        raise ValueError(f"Invalid {name}: {b!r} (True or False)")
+    return bool(b)
 
 
 def ema_decay_at(ema_decay: float, t: int, warmup: bool = True) -> float:
@@ -71,20 +84,12 @@ class FusedAdam(torch.optim.Optimizer):
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None,
                  track_update_ratio=False, ema_decay=None, ema_warmup=True):
-        if max_grad_norm is not None and not (float(max_grad_norm) > 0):
-            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (a positive number, or None for no clipping)")
-        if not isinstance(track_update_ratio, (bool, int)) or track_update_ratio not in (0, 1):
-            raise ValueError(f"Invalid track_update_ratio: {track_update_ratio!r} (True or False)")
-        ema_decay = _check_ema_decay(ema_decay)
-        if not isinstance(ema_warmup, (bool, int)) or ema_warmup not in (0, 1):
-            raise ValueError(f"Invalid ema_warmup: {ema_warmup!r} (True or False)")
+        defaults = dict(lr=lr, betas=betas, eps=eps, max_grad_norm=_check_max_grad_norm(max_grad_norm),
+                        track_update_ratio=_check_flag("track_update_ratio", track_update_ratio),
+                        ema_decay=_check_ema_decay(ema_decay), ema_warmup=_check_flag("ema_warmup", ema_warmup))
         self.model = model
-        params = list(model.parameters())
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm,
-                                      track_update_ratio=bool(track_update_ratio), ema_decay=ema_decay,
-                                      ema_warmup=bool(ema_warmup)))
+        super().__init__(list(model.parameters()), defaults)
         self.grad_scale = grad_scale
-        self._averaged_in = False                                # inside averaged_weights()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -92,12 +97,10 @@ class FusedAdam(torch.optim.Optimizer):
         if eng is None:
             raise RuntimeError("FusedAdam.step() before the first model.run()")
         g = self.param_groups[0]
-        c = g.get("max_grad_norm")
-        if c is not None and not (float(c) > 0):
-            raise ValueError(f"Invalid max_grad_norm: {c}")
+        c = _check_max_grad_norm(g.get("max_grad_norm"))
         track = bool(g.get("track_update_ratio"))
         d = _check_ema_decay(g.get("ema_decay"))
-        if self._averaged_in or eng.averaged_in:
+        if eng.averaged_in:
             raise L.AewError("FusedAdam.step() inside averaged_weights(): the averaged weights sit in the parameters' place")
         kw = {}
         if d is not None:                                        # (off: the calls below are the ones of an optimizer without it)
@@ -118,20 +121,19 @@ class FusedAdam(torch.optim.Optimizer):
         `model.to()` and `model.override()` raise.  On exit - also by an exception - the swap is undone: parameters and
         average are bit for bit what they were."""
         model = self.model
-        if self._averaged_in:
+        # (whether the average is swapped in is the engine's to say: inside the block an engine may change, not go away)
+        if model._engine is not None and model._engine.averaged_in:
             raise L.AewError("averaged_weights() is already entered")
-        st = model._avg_state_flat()                             # (raises where this rank's average is incomplete: sharded DP)
-        if st is None or int(st[0]) < 1:
+        st = model._opt_state(avg=True)                          # (raises where this rank's average is incomplete: sharded DP)
+        if st is None or st.avg_steps < 1:
             raise L.AewError("averaged_weights(): no averaged step has run yet (FusedAdam(..., ema_decay=...) and step())")
         model._dp_finish()                                       # parameter all-gathers in flight write what the swap reads
         # the swap is a launch on the engine's buffers: with none live (a restored checkpoint, model.to()) the sampling
         # engine is built, which takes the carried average in
         (model._engine or model._ensure_engine(1)).swap_averaged()
-        self._averaged_in = True
         try:
             yield self
         finally:
-            self._averaged_in = False
             model._engine.swap_averaged()                        # (sample() inside may have moved everything to the B = 1
                                                                  #  engine; to() / override() are refused while swapped in)
 
@@ -205,25 +207,24 @@ class FusedAdam(torch.optim.Optimizer):
             group["track_update_ratio"] = True
         av = None
         if g.get("ema_decay") is not None:                      # (off: the dictionary is the one of an optimizer without it)
-            av = self.model._avg_state_flat()
+            av = self.model._opt_state(avg=True)
             group["ema_decay"], group["ema_warmup"] = g["ema_decay"], bool(g.get("ema_warmup", True))
-            group["avg_steps"] = int(av[0]) if av is not None else 0
+            group["avg_steps"] = av.avg_steps if av is not None else 0
         state = {}
-        st = self.model._opt_state_flat()
-        if st is not None and int(st[0]) > 0:
-            step, m, v = st
-            m, v = m.detach().cpu(), v.detach().cpu()           # (synchronises with the stream that wrote them)
+        st = self.model._opt_state()
+        if st is not None and st.step > 0:
+            m, v = st.m.detach().cpu(), st.v.detach().cpu()     # (synchronises with the stream that wrote them)
             for i, (n, o, k, shp) in enumerate(lay):
-                state[i] = {"step": torch.tensor(float(step)), "exp_avg": m[o:o + k].reshape(shp).clone(),
+                state[i] = {"step": torch.tensor(float(st.step)), "exp_avg": m[o:o + k].reshape(shp).clone(),
                             "exp_avg_sq": v[o:o + k].reshape(shp).clone()}
-            if av is not None and int(av[0]) > 0:
-                a = av[1].detach().cpu()
+            if av is not None and av.avg_steps > 0:
+                a = av.avg.detach().cpu()
                 for i, (n, o, k, shp) in enumerate(lay):
                     state[i]["param_avg"] = a[o:o + k].reshape(shp).clone()
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, state_dict):
-        if self._averaged_in or (self.model._engine is not None and self.model._engine.averaged_in):
+        if self.model._engine is not None and self.model._engine.averaged_in:
             raise L.AewError("load_state_dict() inside averaged_weights()")     # (before anything is changed)
         lay, total = self._layout()
         groups = state_dict["param_groups"]
@@ -231,16 +232,14 @@ class FusedAdam(torch.optim.Optimizer):
         if len(order) != len(lay):
             raise ValueError(f"optimizer state has {len(order)} parameters, the model {len(lay)}")
         g0 = groups[0]
-        for k in ("lr", "betas", "eps"):
-            if k in g0:
-                self.param_groups[0][k] = tuple(g0[k]) if k == "betas" else g0[k]
-        if g0.get("max_grad_norm") is not None:                 # absent (a torch.optim.Adam checkpoint): keep the constructor's
-            self.param_groups[0]["max_grad_norm"] = g0["max_grad_norm"]
-        if g0.get("track_update_ratio") is not None:            # absent: keep the constructor's
-            self.param_groups[0]["track_update_ratio"] = bool(g0["track_update_ratio"])
-        if g0.get("ema_decay") is not None:                     # absent (a torch.optim.Adam checkpoint): keep the constructor's
-            self.param_groups[0]["ema_decay"] = _check_ema_decay(g0["ema_decay"])
-            self.param_groups[0]["ema_warmup"] = bool(g0.get("ema_warmup", True))
+        # the group's options; one that is absent (a torch.optim.Adam checkpoint) keeps the constructor's
+        opts = {k: tuple(g0[k]) if k == "betas" else g0[k] for k in ("lr", "betas", "eps") if k in g0}
+        if g0.get("max_grad_norm") is not None:
+            opts["max_grad_norm"] = g0["max_grad_norm"]
+        if g0.get("track_update_ratio") is not None:
+            opts["track_update_ratio"] = bool(g0["track_update_ratio"])
+        if g0.get("ema_decay") is not None:
+            opts["ema_decay"], opts["ema_warmup"] = _check_ema_decay(g0["ema_decay"]), bool(g0.get("ema_warmup", True))
         st = state_dict.get("state", {})
         m, v = torch.zeros(total), torch.zeros(total)
         avg, n_avg = torch.zeros(total), 0
@@ -261,32 +260,15 @@ class FusedAdam(torch.optim.Optimizer):
                     raise ValueError(f"param_avg of parameter {n} has shape {tuple(s['param_avg'].shape)}, expected {shp}")
                 avg[o:o + k] = s["param_avg"].detach().float().cpu().reshape(-1)
                 n_avg += 1
-        if not found:
-            return
         if n_avg not in (0, len(order)):
             raise ValueError(f"optimizer state has param_avg for {n_avg} of {len(order)} parameters")
-        model = self.model
-        model._opt_carry = (step, m.to(model._device), v.to(model._device))
-        model._opt_carry_partial = False
-        dp = getattr(model, "_dp", None)
-        if dp is not None:
-            dp.moments_step = step                               # every rank loads the complete state
-        eng = model._engine
-        if eng is not None:
-            eng.adam_m[:total].copy_(model._opt_carry[1])
-            eng.adam_v[:total].copy_(model._opt_carry[2])
-            eng.step_count = step
+        self.param_groups[0].update(opts)                        # every check has passed by here
+        if not found:
+            return
         # the averaged weights: restored with their step count; a state without them (torch.optim.Adam's own, or written
         # before the first averaged step) leaves none - the average then starts from the parameters at the next step
-        if n_avg:
-            model._avg_carry = (max(1, int(g0.get("avg_steps", step))), avg.to(model._device), False)
-            if eng is not None:
-                eng._avg_buffer()[:total].copy_(model._avg_carry[1])
-                eng.avg_steps, eng.avg_live = model._avg_carry[0], True
-        else:
-            model._avg_carry = None
-            if eng is not None:
-                eng.avg_steps, eng.avg_live = 0, False
+        self.model._load_opt_state(OptState(step, m, v, max(1, int(g0.get("avg_steps", step))), avg) if n_avg
+                                   else OptState(step, m, v))
 
     def zero_grad(self, set_to_none=True):
         # the backward plan rewrites the flat gradient buffer: "cleared" is a flag the next backward reads (no memset;

@@ -22,7 +22,7 @@ from torch import nn
 
 from . import _lib as L
 from . import geometry as G
-from .model import TrainEngine
+from .model import OptState, TrainEngine
 
 
 class _StepFn(torch.autograd.Function):
@@ -119,11 +119,8 @@ class HipModelBase(nn.Module):
         self.window_batch_size = hps.n_win_batch
         self._engine: Optional[TrainEngine] = None
         self._engines: Dict[int, TrainEngine] = {}      # engines by batch size (train B, sampling B = 1, ...)
-        self._opt_carry = None                           # (step, exp_avg flat, exp_avg_sq flat) while no engine holds them
-        self._avg_carry = None                           # (averaged steps, averaged weights flat, swapped in?) beside it; the flag is set
-                                                         # only between two engines (another batch size inside averaged_weights())
+        self._opt_carry: Optional[OptState] = None       # the optimizer state while no engine holds it
         self._grads_cleared = True                       # no backward yet / FusedAdam.zero_grad() since the last one
-        self._opt_carry_partial = False                  # carry saved from a sharded DP engine without a moment gather
         self._weights_epoch = 0                          # bumped whenever parameter values change behind torch's back
         self._device = torch.device("cpu")
         self._pending_state: Optional[Dict[str, torch.Tensor]] = None
@@ -266,11 +263,7 @@ class HipModelBase(nn.Module):
         self._engines = {}
         self._device = next(iter(self._parameters.values())).device
         if self._opt_carry is not None:
-            st, m, v = self._opt_carry
-            self._opt_carry = (st, m.to(self._device), v.to(self._device))
-        if self._avg_carry is not None:
-            k, avg, swapped = self._avg_carry
-            self._avg_carry = (k, avg.to(self._device), swapped)
+            self._opt_carry = self._opt_carry.to(self._device)
         self._anchor = torch.zeros((), requires_grad=True, device=self._device)
         return out
 
@@ -289,57 +282,47 @@ class HipModelBase(nn.Module):
         self._engines = {}
 
     def _save_opt_carry(self):
-        """Adam moments / step count live in the engine's flat buffers; keep them when the engine goes away
-        (model.to(), override(), a different batch size, sample()), so optimizer state survives exactly like
-        torch.optim.Adam's per-parameter state does in the reference's save / restore flow (checkpoint.py:82-102)."""
+        """The optimizer state lives in the engine's flat buffers; keep it when the engine goes away (model.to(),
+        override(), a different batch size, sample()), so it survives exactly like torch.optim.Adam's per-parameter state
+        does in the reference's save / restore flow (checkpoint.py:82-102)."""
         eng = self._engine
-        if eng is not None and (eng.step_count > 0 or self._opt_carry is None):
-            n = eng.ps.numel
-            self._opt_carry = (eng.step_count, eng.adam_m[:n].detach().clone(), eng.adam_v[:n].detach().clone())
-            # sharded data parallel: unless the moments were just gathered this rank's copy is valid for its own shards
-            # only - enough to continue training on a rebuilt engine (same shard layout), not to write a checkpoint
-            self._opt_carry_partial = self._dp is not None and not self._dp.moments_complete(eng)
-        if eng is not None and eng.avg_live:
-            # the averaged weights move with the moments (sharded data parallel: complete where the moments are); while
-            # they are swapped in, adam_avg holds the raw parameters and the flag travels along
-            self._avg_carry = (eng.avg_steps, eng.adam_avg[:eng.ps.numel].detach().clone(), eng.averaged_in)
+        # an engine that has neither stepped nor holds an average has nothing a carry (a restored checkpoint) lacks.
+        # While the average is swapped in, `avg` holds the raw parameters and the flag travels along: that happens only
+        # between two engines (another batch size inside averaged_weights()) - to() and override() are refused there
+        if eng is not None and (eng.step_count > 0 or eng.avg_live or self._opt_carry is None):
+            # sharded data parallel: unless the state was just gathered this rank's copy is valid for its own shards only
+            # - enough to continue training on a rebuilt engine (same shard layout), not to write a checkpoint
+            self._opt_carry = eng.opt_state(clone=True)._replace(complete=self._opt_complete(eng))
 
-    def _opt_state_flat(self):
-        """(step, exp_avg flat, exp_avg_sq flat) from the live engine, else from the carry, else None."""
-        eng = self._engine
-        if eng is not None:
-            if self._dp is not None and not self._dp.moments_complete(eng):
-                raise L.AewError("the Adam moments are sharded across the data-parallel ranks (each rank holds its own "
-                                 "1/world): call dp.sync_optimizer_state(model) - or checkpoint.save(...) - on ALL ranks "
-                                 "before reading optimizer state on any of them")
-            n = eng.ps.numel
-            return eng.step_count, eng.adam_m[:n], eng.adam_v[:n]
-        if self._opt_carry is not None and getattr(self, "_opt_carry_partial", False):
-            raise L.AewError("the carried Adam moments were saved from a sharded data-parallel engine without "
-                             "dp.sync_optimizer_state(model): they are complete for this rank's shards only")
-        return self._opt_carry
+    def _opt_complete(self, eng) -> bool:
+        return self._dp is None or self._dp.moments_complete(eng)
 
-    def _avg_state_flat(self):
-        """(averaged steps, averaged weights flat) from the live engine, else from the carry, else None - under the rule
-        of _opt_state_flat for sharded data parallel: a rank averages its own shards only."""
+    def _load_opt_state(self, st: OptState):
+        """FusedAdam.load_state_dict: a complete state that every rank restores - into the carry, and into the engine
+        where one is live."""
+        self._opt_carry = st.to(self._device)
+        if self._engine is not None:
+            self._engine.load_opt_state(self._opt_carry)
+        if self._dp is not None:
+            self._dp.moments_complete_at(st.step)
+
+    def _opt_state(self, avg: bool = False) -> Optional[OptState]:
+        """The optimizer state from the live engine (views), else from the carry, else None.  avg=False: for a reader of
+        step / m / v - they stay readable while the average is swapped in (the swap does not touch them).  avg=True: for a
+        reader of the average - None also where there is none, refused while it is swapped in."""
         eng = self._engine
-        if eng is not None:
-            if not eng.avg_live:
-                return None
-            if eng.averaged_in:
-                raise L.AewError("the averaged weights are swapped in (FusedAdam.averaged_weights()): leave the context "
-                                 "before reading optimizer state")
-            if self._dp is not None and not self._dp.moments_complete(eng):
-                raise L.AewError("the averaged weights are sharded across the data-parallel ranks (each rank averages its "
-                                 "own 1/world): call dp.sync_optimizer_state(model) on ALL ranks before reading them on "
-                                 "any of them")
-            return eng.avg_steps, eng.adam_avg[:eng.ps.numel]
-        if self._avg_carry is None:
+        st = self._opt_carry if eng is None else eng.opt_state(clone=False)._replace(complete=self._opt_complete(eng))
+        if st is None or (avg and st.avg is None):
             return None
-        if getattr(self, "_opt_carry_partial", False):
-            raise L.AewError("the carried averaged weights were saved from a sharded data-parallel engine without "
-                             "dp.sync_optimizer_state(model): they are complete for this rank's shards only")
-        return self._avg_carry[0], self._avg_carry[1]
+        if avg and st.averaged_in:
+            raise L.AewError("the averaged weights are swapped in (FusedAdam.averaged_weights()): leave the context "
+                             "before reading optimizer state")
+        if not st.complete:
+            raise L.AewError("the optimizer state is sharded across the data-parallel ranks (each rank holds the Adam "
+                             "moments and the averaged weights of its own 1/world): call dp.sync_optimizer_state(model) - "
+                             "or checkpoint.save(...) - on ALL ranks before reading it on any of them (and before the "
+                             "engine goes away: what the model then carries stays this rank's shards only)")
+        return st
 
     def _pull_params_to_cpu(self):
         eng = self._engine
@@ -376,7 +359,7 @@ class HipModelBase(nn.Module):
         if eng is not None:
             self._dp_finish()
             # another batch size (e.g. sample() uses B = 1 between training steps): parameters, EMA buffers and
-            # Adam moments move to the other engine; engines are kept per batch size so that switching back does
+            # optimizer state move to the other engine; engines are kept per batch size so that switching back does
             # not rebuild plans and graphs
             self._pull_params_to_cpu()
             self._save_opt_carry()
@@ -384,8 +367,11 @@ class HipModelBase(nn.Module):
         if new is None:
             new = TrainEngine(self.hps, B, self._device, n_win=self.window_batch_size, **self._opts)
             self._engines[B] = new
-        eng = new
-        # re-home the parameters into the flat buffer (values preserved)
+        return self._adopt_engine(new)
+
+    def _adopt_engine(self, eng):
+        """Make `eng` the live engine: the parameters become views into its flat buffer (values preserved), the buffers
+        and the carried optimizer state move in."""
         with torch.no_grad():
             for name, pname in self._pnames:
                 p = self._parameters[pname]
@@ -397,18 +383,8 @@ class HipModelBase(nn.Module):
         self._engine = eng
         self._weights_epoch += 1
         self._push_buffers_to_engine()
-        if self._opt_carry is not None:
-            st, m, v = self._opt_carry
-            n = eng.ps.numel
-            eng.adam_m[:n].copy_(m)
-            eng.adam_v[:n].copy_(v)
-            eng.step_count = int(st)
-        if self._avg_carry is not None:
-            k, avg, swapped = self._avg_carry
-            eng._avg_buffer()[:eng.ps.numel].copy_(avg)
-            eng.avg_steps, eng.avg_live, eng.averaged_in = int(k), True, bool(swapped)
-        else:
-            eng.avg_steps, eng.avg_live, eng.averaged_in = 0, False, False
+        if self._opt_carry is not None:                          # (none: the first engine of a model - it starts at zero)
+            eng.load_opt_state(self._opt_carry)
         if self._dp is not None:
             self._dp.prepare_vae(eng)
         if eng.bn_type == "vae":

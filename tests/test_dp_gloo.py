@@ -144,7 +144,8 @@ def _seed_engine(eng, seed=7):
     if eng.bn_type == "vqvae-ema":
         eng.emb.copy_(torch.randn(eng.emb.shape, generator=gen))
         eng.init_ema_from_emb()
-    eng.adam_m.zero_(); eng.adam_v.zero_(); eng.step_count = 0
+    zero = torch.zeros(n)
+    eng.load_opt_state(M.OptState(0, zero, zero))
 
 
 def _global_batch(eng_geom, n_mel, world, seed=3):
@@ -293,20 +294,6 @@ def test_dp_real_steps_match_single_process_global_batch(bn, world, wg):
 # sharded optimizer state at the module surface: sync_optimizer_state, the collective checkpoint.save, and the loud
 # error instead of one rank's shard posing as the whole state (round-2 ADVICE fix; chassis.py:171, checkpoint.py:82-102)
 # ----------------------------------------------------------------------------------------------
-def _home_engine(model, eng):
-    """What HipModelBase._ensure_engine does once it has an engine (it refuses to build one off the GPU): the
-    parameters become views into the engine's flat buffer."""
-    with torch.no_grad():
-        for name, pname in model._pnames:
-            p = model._parameters[pname]
-            view = eng.ps.view(name)
-            view.copy_(p.data)
-            p.data = view
-            p.grad = eng.ps.view(name, grad=True)
-    model._engine = eng
-    model._push_buffers_to_engine()
-
-
 def _state_worker(rank, world, port, tmpdir, q):
     from tests.plan_emulator import emulate
     from ae_wavenet_amd import _lib as L, autoencoder_model as ae, checkpoint as ckpt, optim
@@ -318,7 +305,7 @@ def _state_worker(rank, world, port, tmpdir, q):
         torch.manual_seed(5)                                       # the same initial weights on every rank
         model = ae.AutoEncoder(hps, n_mel=5)
         eng = emulate(M.TrainEngine(hps, B=1, device="cpu", n_mel=5))
-        _home_engine(model, eng)
+        model._adopt_engine(eng)          # (what _ensure_engine does once it has an engine: it refuses to build one off the GPU)
         d = dp.DataParallel()
         d.attach(model, sharded=True)
         opt = optim.FusedAdam(model, lr=1e-2)

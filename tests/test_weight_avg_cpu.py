@@ -112,7 +112,9 @@ def test_state_dict_round_trip_with_and_without_the_average():
             for k in ("exp_avg", "exp_avg_sq", "param_avg"):
                 assert torch.equal(o["state"][i][k], s[k]), (i, k)
             assert float(o["state"][i]["step"]) == float(s["step"])
-    assert m2._avg_carry[0] == 5 and m2._avg_carry[2] is False and m2._opt_carry[0] == 2 and len(m2._opt_carry) == 3
+    c = m2._opt_carry
+    assert c.avg_steps == 5 and c.averaged_in is False and c.step == 2 and c.avg is not None and c.complete is True
+    assert c._fields == ("step", "m", "v", "avg_steps", "avg", "averaged_in", "complete")
     # torch.optim.Adam reads the dictionary (extra keys travel along)
     stock = torch.optim.Adam([torch.nn.Parameter(torch.empty_like(p)) for p in m.parameters()])
     stock.load_state_dict(out)
@@ -120,7 +122,7 @@ def test_state_dict_round_trip_with_and_without_the_average():
     # any more - it starts again at the next step
     opt2.load_state_dict(ck["optim"])
     assert "ema_decay" not in ck["optim"]["param_groups"][0]
-    assert opt2.param_groups[0]["ema_decay"] == 0.99 and m2._avg_carry is None
+    assert opt2.param_groups[0]["ema_decay"] == 0.99 and m2._opt_carry.avg is None
     o3 = opt2.state_dict()
     assert o3["param_groups"][0]["avg_steps"] == 0
     for i, s in ck["optim"]["state"].items():
@@ -140,7 +142,7 @@ DECAY, STEPS = 0.9, 3
 
 def _avg_worker(rank, world, port, q):
     from ae_wavenet_amd import autoencoder_model as ae
-    from tests.test_dp_gloo import _global_batch, _home_engine, _seed_engine, _tiny
+    from tests.test_dp_gloo import _global_batch, _seed_engine, _tiny
     from tests.weight_avg_emulator import avg_update, emulate_avg
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -150,7 +152,7 @@ def _avg_worker(rank, world, port, q):
         torch.manual_seed(5)
         model = ae.AutoEncoder(hps, n_mel=5)
         eng = emulate_avg(M.TrainEngine(hps, B=1, device="cpu", n_mel=5, wgrad_group=1))
-        _home_engine(model, eng)
+        model._adopt_engine(eng)
         d = dp.DataParallel()
         d.attach(model, sharded=True)
         opt = optim.FusedAdam(model, lr=1e-2, ema_decay=DECAY)
@@ -224,3 +226,60 @@ def test_sharded_average_is_complete_after_the_sync_and_matches_a_single_process
         assert np.abs(p_raw - ref_p).max() <= 2e-5 * scale
         assert np.abs(full - ref_avg).max() <= 2e-5 * scale, (rank, np.abs(full - ref_avg).max(), scale)
     assert res[0][4].tobytes() == res[1][4].tobytes()               # the ranks hold the same average
+
+
+# ----------------------------------------------------------------------------------------------
+# the optimizer state as one record (model.OptState): out of one engine, into another
+# ----------------------------------------------------------------------------------------------
+def test_opt_state_record_moves_everything_between_engines():
+    """Engine A (B = 1) takes two averaged steps and swaps the average in; its record, cloned, goes into engine B (B = 2:
+    other plans, the same flat layout).  B then holds A's state bit for bit, refuses to step like A, and after swapping
+    back takes the third step exactly as a twin of A does whose state never moved.  adam_step reads the gradient buffer
+    alone, so the three gradients are written there: no forward / backward, and the batch size does not matter."""
+    from tests.test_dp_gloo import _seed_engine, _tiny
+    from tests.weight_avg_emulator import emulate_avg
+    hps = _tiny("vqvae-ema")
+    a, twin = (emulate_avg(M.TrainEngine(hps, B=1, device="cpu", n_mel=5)) for _ in range(2))
+    b = emulate_avg(M.TrainEngine(hps, B=2, device="cpu", n_mel=5))
+    n = a.ps.numel
+    assert b.ps.numel == n
+    grads = [torch.randn(n, generator=torch.Generator().manual_seed(20 + i)) for i in range(3)]
+    bits = lambda t: t.numpy().tobytes()
+
+    def step(eng, i):
+        eng.ps.grads[:n].copy_(grads[i])
+        eng.adam_step(1e-2, 1.0, avg_rate=optim.ema_rate_at(DECAY, eng.avg_steps))
+
+    for eng in (a, twin):
+        _seed_engine(eng)
+        step(eng, 0)
+        step(eng, 1)
+    a.swap_averaged()
+    st = a.opt_state(clone=True)
+    assert st._fields == ("step", "m", "v", "avg_steps", "avg", "averaged_in", "complete")
+    assert st.m.data_ptr() != a.adam_m.data_ptr() and st.avg.data_ptr() != a.adam_avg.data_ptr()      # clones ...
+    b.ps.params[:n].copy_(a.ps.params[:n])                          # (the parameters move beside the record)
+    b.load_opt_state(st)
+    got, want = b.opt_state(clone=False), a.opt_state(clone=False)
+    assert got.m.data_ptr() == b.adam_m.data_ptr() and got.avg.data_ptr() == b.adam_avg.data_ptr()    # ... and views
+    assert (got.step, got.avg_steps, got.averaged_in, got.complete) == (2, 2, True, True)
+    assert (want.step, want.avg_steps, want.averaged_in, want.complete) == (2, 2, True, True)
+    for f in ("m", "v", "avg"):
+        assert bits(getattr(got, f)) == bits(getattr(want, f)), f
+    assert bits(got.avg) != bits(b.ps.params[:n]) and float(got.m.abs().max()) > 0
+    for eng in (a, b):                                              # swapped in: no step, and nothing counted
+        with pytest.raises(L.AewError):
+            step(eng, 2)
+        assert (eng.step_count, eng.avg_steps) == (2, 2)
+    b.swap_averaged()
+    assert not b.averaged_in
+    step(b, 2)
+    step(twin, 2)
+    assert (b.step_count, b.avg_steps) == (twin.step_count, twin.avg_steps) == (3, 3)
+    for f in ("adam_m", "adam_v", "adam_avg"):
+        assert bits(getattr(b, f)[:n]) == bits(getattr(twin, f)[:n]), f
+    assert bits(b.ps.params[:n]) == bits(twin.ps.params[:n])
+    # a record without an average leaves an engine that holds one without
+    b.load_opt_state(st._replace(avg=None))
+    assert b.avg_live is False and b.avg_steps == 0 and b.averaged_in is False and b.step_count == 2
+    assert b.opt_state(clone=False).avg is None and len(b.opt_buffers()) == 2

@@ -29,7 +29,7 @@ state = {k: eng.ws.get(k).clone() for k in ("params", "adam.m", "adam.v", "bn.em
 def restore():
     for k, v in state.items():
         eng.ws.get(k).copy_(v)
-    eng.step_count = 0
+    eng.load_opt_state(eng.opt_state(clone=False)._replace(step=0))     # (the moments just restored, at step 0)
 restore()
 for it in range(2):
     eng.forward(); eng.backward(); eng.adam_step(1e-3)
