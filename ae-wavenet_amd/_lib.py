@@ -23,7 +23,7 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP) = range(1, 29)
+ OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART) = range(1, 30)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -189,6 +189,16 @@ class Swap(C.Structure):
     _fields_ = [("a", vp), ("b", vp), ("n", i64)]
 
 
+VQ_RESTART_MAX = 1024
+
+
+class VqRestart(C.Structure):
+    """aew_vq_restart_t: re-seed the codes whose EMA count fell under min_usage from rows of this step's encoder outputs."""
+    _fields_ = [("ze", vp), ("Q", i32), ("d", i32), ("d_pitch", i32), ("emb", vp), ("numer", vp), ("denom", vp),
+                ("K", i32), ("max_codes", i32), ("min_usage", f32), ("denom_init", f32),
+                ("seed", C.c_uint64), ("call", C.c_uint64), ("out", vp), ("pairs", vp), ("guard", vp)]
+
+
 UW_CHUNK = 4096
 
 
@@ -265,7 +275,7 @@ class _OpU(C.Union):
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
-                ("ratio", UpdateRatio), ("swap", Swap)]
+                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart)]
 
 
 class Op(C.Structure):
@@ -278,7 +288,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_BASE_GATHER: "base", OP_SOFTMAX_NLL: "sm", OP_COLSUM: "cs", OP_REDUCE: "red",
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
-            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap"}
+            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr"}
 
 
 
@@ -379,12 +389,12 @@ def load():
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
-                       (15, UpdateRatio), (16, NtPick), (17, Swap)):
+                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 24:
+    if lib.aew_abi_version() != 25:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib

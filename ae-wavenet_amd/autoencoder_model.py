@@ -17,8 +17,12 @@ from .surface import HipModelBase, _BottleneckFacade, _EncoderFacade
 
 class AutoEncoder(HipModelBase):
     def __init__(self, hps, loss_mode: str = "intended", take_compat: bool = False,
-                 update_codebook_every_step: bool = True, n_mel=None):
-        super().__init__(hps, "autoencoder", loss_mode, take_compat, update_codebook_every_step, n_mel)
+                 update_codebook_every_step: bool = True, n_mel=None, codebook_restart=None):
+        """codebook_restart: None, or dict(every=, min_usage=, max_codes=64, denom_init=1.0, seed=0) - vqvae-ema only:
+        every `every`-th training step re-seeds the codes whose EMA count fell under min_usage from distinct encoder
+        outputs of that step, on the device (bottleneck.restart_dead_codes() does it on demand)."""
+        super().__init__(hps, "autoencoder", loss_mode, take_compat, update_codebook_every_step, n_mel,
+                         codebook_restart=codebook_restart)
         self.encoder = _EncoderFacade()
         self.bottleneck = _BottleneckFacade(self)
         try:                                    # the reference's MFCC front-end, when importable

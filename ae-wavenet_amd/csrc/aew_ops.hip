@@ -507,6 +507,84 @@ __global__ void k_vq_ema_denom(const aew_vq_ema_t p) {
     p.denom[k] = __fadd_rn(__fmul_rn(p.gamma, p.denom[k]), __fmul_rn(p.gamma_comp, p.n_sum[k]));
 }
 
+// Restart dead codes (aew_vq_restart_t): ONE workgroup of 1024 threads, so the dead list, the rows and every write have
+// one order.  K is walked in chunks of 1024: a thread's rank among the dead of its wave comes from the ballot, the waves'
+// counts are scanned in ascending order through LDS, a running base carries over the chunks; the first min(Q, max_codes)
+// dead indices land in an LDS list.  A barrier separates the last read of denom from the first write to it; then wave w
+// takes restarts w, w + 16, ... and its lanes the d channels.
+// (the splitmix64 finaliser of the counter-based draws: the jitter op and the sampler use it too)
+__device__ __forceinline__ unsigned long long aew_mix64(unsigned long long z) {      // splitmix64 finaliser
+    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27; z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+__global__ __launch_bounds__(1024) void k_vq_restart(const aew_vq_restart_t p) {
+    __shared__ int s_list[AEW_VQ_RESTART_MAX];
+    __shared__ int s_cnt[16];
+    __shared__ unsigned s_ab[2];
+    if (p.guard && *p.guard) return;                       // the whole workgroup reads the same word: no barrier is split
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cap = min(p.Q, p.max_codes);
+    int n_dead = 0;
+    for (int64_t k0 = 0; k0 < p.K; k0 += 1024) {
+        const int64_t k = k0 + tid;
+        const bool dead = k < p.K && !(p.denom[k] >= p.min_usage);
+        const unsigned long long m = __ballot(dead);
+        if (lane == 0) s_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int c = s_cnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        const int pos = n_dead + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (dead && pos < cap) s_list[pos] = (int)k;
+        n_dead += total;
+        __syncthreads();                                   // s_cnt is rewritten by the next chunk; after the last chunk:
+    }                                                      // every read of denom is done, s_list is complete
+    if (tid == 0) {
+        const unsigned long long G = 0x9e3779b97f4a7c15ull, Q = (unsigned long long)p.Q;
+        const unsigned long long h = aew_mix64(aew_mix64(p.seed + G) ^ (p.call + G));
+        unsigned b = 1;
+        if (p.Q > 1) {
+            const unsigned b0 = (unsigned)(aew_mix64(h ^ 2ull) % (Q - 1));
+            for (unsigned i = 0;; ++i) {
+                b = 1u + (unsigned)(((unsigned long long)b0 + i) % (Q - 1));
+                unsigned x = b, y = (unsigned)p.Q;         // gcd(b, Q); b = 1 ends the search at the latest
+                while (y) { const unsigned t = x % y; x = y; y = t; }
+                if (x == 1) break;
+            }
+        }
+        s_ab[0] = (unsigned)(aew_mix64(h ^ 1ull) % Q);
+        s_ab[1] = b;
+    }
+    __syncthreads();
+    const int n = min(n_dead, cap);
+    const unsigned long long a = s_ab[0], b = s_ab[1];
+    for (int r = wave; r < n; r += 16) {
+        const int k = s_list[r];
+        const int64_t q = (int64_t)((a + (unsigned long long)r * b) % (unsigned long long)p.Q);
+        const float* z = p.ze + q * p.d_pitch;
+        for (int j = lane; j < p.d; j += 64) {
+            const float nu = __fmul_rn(z[j], p.denom_init);
+            p.numer[(int64_t)k * p.d + j] = nu;
+            p.emb[(int64_t)k * p.d + j] = __fdiv_rn(nu, p.denom_init);
+        }
+        if (lane == 0) p.denom[k] = p.denom_init;
+    }
+    if (p.pairs)
+        for (int r = tid; r < p.max_codes; r += 1024) {
+            p.pairs[2 * r] = r < n ? s_list[r] : -1;
+            p.pairs[2 * r + 1] = r < n ? (int)((a + (unsigned long long)r * b) % (unsigned long long)p.Q) : -1;
+        }
+    if (tid == 0) {
+        p.out[0] = n_dead; p.out[1] = n; p.out[2] += n; p.out[3] = 0;
+    }
+}
+
 // d(ze) = d(zq) [straight-through, vqema_bn.py:44-45] + coef * d(dist_min)/d(ze)
 //   scaled_l2: dist = u/v, u = ||z-q||, v = ||z|| + ||q||
 //       d dist/dz = (z-q)/(u v) - u z / (v^2 ||z||)
@@ -1544,12 +1622,6 @@ __global__ void k_ae_norm(const aew_ae_norm_t p) {
 // time-jitter indices (jitter.py:13-33): one thread per batch row (the documented rule is a
 // second-order chain; n is a few hundred at most)
 // =============================================================================================
-__device__ __forceinline__ unsigned long long aew_mix64(unsigned long long z) {      // splitmix64 finaliser
-    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
-    z ^= z >> 27; z *= 0x94d049bb133111ebull;
-    z ^= z >> 31;
-    return z;
-}
 __device__ __forceinline__ double aew_jitter_u(unsigned long long seed, unsigned long long step, int b, int t) {
     unsigned long long h = aew_mix64(seed + 0x9e3779b97f4a7c15ull);
     h = aew_mix64(h ^ (step + 0x9e3779b97f4a7c15ull));
@@ -2067,6 +2139,16 @@ static int launch_vq_stats(const aew_vq_stats_t& p, hipStream_t st) {
 static int launch_vq_ema(const aew_vq_ema_t& p, hipStream_t st) {
     hipLaunchKernelGGL(k_vq_ema, dim3(cdiv64((int64_t)p.K * p.d, 256)), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_vq_ema_denom, dim3(cdiv64(p.K, 256)), dim3(256), 0, st, p);
+    return (int)hipGetLastError();
+}
+static int launch_vq_restart(const aew_vq_restart_t& p, hipStream_t st) {
+    if (p.Q < 1 || p.K < 1 || p.d < 1 || p.d_pitch < p.d) return AEW_E_ARG;
+    if (p.max_codes < 1 || p.max_codes > AEW_VQ_RESTART_MAX) return AEW_E_ARG;
+    if (!(p.denom_init > 0.f) || __builtin_isinf(p.denom_init) || p.min_usage != p.min_usage) return AEW_E_ARG;
+    if (!p.ze || !p.emb || !p.numer || !p.denom || !p.out) return AEW_E_ARG;
+    if (((uintptr_t)p.ze | (uintptr_t)p.emb | (uintptr_t)p.numer | (uintptr_t)p.denom | (uintptr_t)p.out |
+         (uintptr_t)p.pairs | (uintptr_t)p.guard) & 3) return AEW_E_ALIGN;
+    hipLaunchKernelGGL(k_vq_restart, dim3(1), dim3(1024), 0, st, p);
     return (int)hipGetLastError();
 }
 static int launch_vq_bwd(const aew_vq_bwd_t& p, hipStream_t st) {

@@ -505,11 +505,30 @@ class DataParallel:
         dist.all_reduce(z_sum, op=dist.ReduceOp.SUM, group=self.group)
         dist.all_reduce(n_sum, op=dist.ReduceOp.SUM, group=self.group)
 
+    def broadcast_codebook(self, eng, src: int = 0):
+        """The EMA codebook state (emb, ema_numer, ema_denom) of rank `src` to every rank.  COLLECTIVE."""
+        if eng.bn_type == "vqvae-ema":
+            for t in (eng.emb, eng.ema_numer, eng.ema_denom):
+                dist.broadcast(t, src, group=self.group)
+
     def broadcast_params(self, eng, src: int = 0):
         self.finish()
         dist.broadcast(eng.ps.params, src, group=self.group)
-        if eng.bn_type == "vqvae-ema":
-            for t in (eng.emb, eng.ema_numer, eng.ema_denom):
+        self.broadcast_codebook(eng, src)
+
+    def restart_codes(self, eng, min_usage: float, call: int, src: int = 0, **kw):
+        """TrainEngine.restart_codes under data parallel.  COLLECTIVE: every rank runs the launch (the same plans on every
+        rank; ema_denom is replicated, so the dead list and the counts are the same everywhere) - only the rows differ,
+        each rank seeding from its own batch - and rank `src`'s codebook state is then broadcast: the replicas end up bit
+        equal to a single process that saw that rank's batch.  The counts and the (code, row) pairs travel with it: each
+        rank's launch is gated by its own chain_guard word, whose cross-rank maximum may still be in flight here, so on a
+        guarded step the ranks' own counts could differ - after the broadcast restart_out() / restart_pairs() describe, on
+        every rank, the codebook every rank holds.  The broadcasts are blocking collectives issued behind the launch on the
+        compute stream, like broadcast_params; they happen on restart steps only."""
+        eng.restart_codes(min_usage, call, **kw)
+        if not self._solo():
+            self.broadcast_codebook(eng, src)
+            for t in (eng.restart_out(), eng.restart_pairs()):
                 dist.broadcast(t, src, group=self.group)
 
     def attach(self, model, sharded: bool = False, bf16_grads: bool = False):

@@ -620,6 +620,12 @@ class TrainEngine:
         self.avg_live = False             # adam_avg holds an average (started by a step, or restored by load_opt_state)
         self.averaged_in = False          # the average sits in ps.params, the raw parameters in adam_avg
         self.swap = Plan("swap")          # one op over ps.params / adam_avg, added with the buffer
+        # ===== restart of dead codes (aew_vq_restart_t, vqvae-ema only): like the average, the counters, the pair list
+        # and the op exist from the first restart_codes() on
+        self.restart = Plan("restart")    # one op over bn.lin / emb / ema_numer / ema_denom, added with its buffers
+        self.restart_buf = None           # int32 [4]: dead, restarted, total restarted, 0 (restart_out())
+        self.restart_pairs_buf = None     # int32 [AEW_VQ_RESTART_MAX][2]: (code, row) per restart (restart_pairs())
+        self.lin_live = False             # a forward (or encode) of this engine has filled bn.lin
 
     def _vae_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.Vae:
         va = L.Vae()
@@ -708,6 +714,7 @@ class TrainEngine:
             stop = fa.labels.index("bn.linear") + 1
             self._encode_plan = self._sub_plan("encode", fa, lambda i, lab: i < stop)
         self._run(self._encode_plan, False)
+        self.lin_live = True
 
     def conditioning(self):
         """Encoder / bottleneck and the conditioning half of the decoder forward only (jitter gather, lc_conv,
@@ -817,6 +824,7 @@ class TrainEngine:
         self._chain_watch("check")
         self.finish_ema(timing)
         self._run(self.fwd_a, timing)
+        self.lin_live = True
         if before_decoder is not None:
             before_decoder()
         if ema_allreduce is not None and self.bn_type == "vqvae-ema":
@@ -875,6 +883,60 @@ class TrainEngine:
     def update_codebook(self):
         self.finish_ema()
         self.cb.run(self._stream())
+
+    def _restart_op(self) -> L.VqRestart:
+        """The restart op, allocated with its two output buffers (and the `restart` plan completed) at its first use."""
+        if self.bn_type != "vqvae-ema":
+            raise L.AewError(f"restarting codes needs the vqvae-ema bottleneck (this engine: {self.bn_type}): only its "
+                             "codebook carries a usage statistic")
+        if self.restart_buf is None:
+            self.restart_buf = self.ws.alloc("restart.out", 4, torch.int32)[:4]
+            self.restart_pairs_buf = self.ws.alloc("restart.pairs", 2 * L.VQ_RESTART_MAX, torch.int32)[:2 * L.VQ_RESTART_MAX] \
+                .view(L.VQ_RESTART_MAX, 2)
+            rs = L.VqRestart()
+            rs.ze, rs.Q, rs.d, rs.d_pitch = self.lin.ptr, self.Q, self.d, self.nlin_p
+            rs.emb, rs.numer, rs.denom = self.emb.data_ptr(), self.ema_numer.data_ptr(), self.ema_denom.data_ptr()
+            rs.K, rs.max_codes, rs.min_usage, rs.denom_init = self.K, 1, 0.0, 1.0
+            rs.out, rs.pairs = self.restart_buf.data_ptr(), self.restart_pairs_buf.data_ptr()
+            rs.guard = self.chain_guard.data_ptr()
+            self.restart.add(L.OP_VQ_RESTART, rs, "vq.restart", TAG_VQ)
+        return self.restart.array()[0].u.vqr
+
+    def restart_codes(self, min_usage: float, call: int, max_codes: int = 64, denom_init: float = 1.0, seed: int = 0):
+        """Re-seed dead codes on the device (AEW_OP_VQ_RESTART, one launch, no host synchronisation): every code k with
+        !(ema_denom[k] >= min_usage), ascending, at most min(Q, max_codes) of them, takes a distinct row of this step's
+        encoder outputs (bn.lin) chosen by the counter-based hash of (seed, call): ema_numer[k] = ze * denom_init,
+        emb[k] = ema_numer[k] / denom_init, ema_denom[k] = denom_init.  A pending EMA accumulation is applied first (it
+        would overwrite the restart); a raised chain_guard makes the launch a no-op.  Counts: restart_out()."""
+        if self.bn_type != "vqvae-ema":
+            self._restart_op()                                          # raises: nothing is allocated for a refused call
+        if not self.lin_live:
+            raise L.AewError("restart_codes() before any forward on this engine: bn.lin holds no encoder output yet")
+        if not 1 <= int(max_codes) <= L.VQ_RESTART_MAX:
+            raise ValueError(f"Invalid max_codes: {max_codes} (1 .. {L.VQ_RESTART_MAX})")
+        if not (math.isfinite(denom_init) and denom_init > 0.0):
+            raise ValueError(f"Invalid denom_init: {denom_init} (finite, > 0)")
+        if math.isnan(min_usage):
+            raise ValueError("Invalid min_usage: nan")
+        if call < 0 or seed < 0:
+            raise ValueError(f"Invalid call / seed: {call} / {seed} (unsigned 64-bit counters)")
+        self.finish_ema()
+        rs = self._restart_op()
+        rs.min_usage, rs.denom_init, rs.max_codes = float(min_usage), float(denom_init), int(max_codes)
+        rs.seed, rs.call = int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1)
+        self.restart.run(self._stream())
+
+    def restart_out(self) -> torch.Tensor:
+        """int32 [4] device view: dead codes found and codes restarted by the last restart_codes(), codes restarted since
+        the engine was built, 0.  Reading it is the caller's synchronisation."""
+        self._restart_op()
+        return self.restart_buf
+
+    def restart_pairs(self) -> torch.Tensor:
+        """int32 [AEW_VQ_RESTART_MAX][2] device view: (code, row of bn.lin) of the last launch's restarts in order, (-1, -1)
+        behind them up to its max_codes."""
+        self._restart_op()
+        return self.restart_pairs_buf
 
     def grad_norm_step(self, ranges, max_grad_norm: float, grad_scale: float = 1.0, finalize: bool = True,
                        add_partial: bool = False):

@@ -15,6 +15,8 @@ autograd traffic, and any torch optimizer — or the fused `optim.FusedAdam` —
 """
 from __future__ import annotations
 
+import math
+import operator
 from typing import Dict, Optional
 
 import torch
@@ -23,6 +25,50 @@ from torch import nn
 from . import _lib as L
 from . import geometry as G
 from .model import OptState, TrainEngine
+
+
+_RESTART_DEFAULTS = dict(max_codes=64, denom_init=1.0, seed=0)
+
+
+def _check_codebook_restart(opt):
+    """The `codebook_restart` constructor option: None, or dict(every=int >= 1, min_usage=float > 0, max_codes=64,
+    denom_init=1.0, seed=0) -> a complete dictionary of plain Python numbers."""
+    if opt is None:
+        return None
+    if not isinstance(opt, dict):
+        raise ValueError(f"Invalid codebook_restart: {opt!r} (None, or a dict with every, min_usage and optionally "
+                         "max_codes, denom_init, seed)")
+    unknown = set(opt) - {"every", "min_usage"} - set(_RESTART_DEFAULTS)
+    if unknown or "every" not in opt or "min_usage" not in opt:
+        raise ValueError(f"Invalid codebook_restart: {opt!r} (keys every and min_usage, optionally max_codes, denom_init, "
+                         "seed)")
+    out = dict(_RESTART_DEFAULTS, **opt)
+
+    def whole(name, lo, hi):
+        v = out[name]
+        try:                                                     # Python and numpy integers; no bool, no float
+            i = None if isinstance(v, bool) else operator.index(v)
+        except TypeError:
+            i = None
+        if i is None or not lo <= i <= hi:
+            raise ValueError(f"Invalid codebook_restart[{name!r}]: {v!r} (an integer in {lo} .. {hi})")
+        out[name] = i
+
+    def positive(name):
+        try:                                                     # whatever float() takes, like FusedAdam's options
+            f = float(out[name])
+        except (TypeError, ValueError):
+            f = float("nan")
+        if isinstance(out[name], bool) or not (math.isfinite(f) and f > 0.0):
+            raise ValueError(f"Invalid codebook_restart[{name!r}]: {out[name]!r} (a finite number > 0)")
+        out[name] = f
+
+    whole("every", 1, 2 ** 62)
+    whole("max_codes", 1, L.VQ_RESTART_MAX)
+    whole("seed", 0, 2 ** 64 - 1)
+    positive("min_usage")
+    positive("denom_init")
+    return out
 
 
 class _StepFn(torch.autograd.Function):
@@ -56,6 +102,7 @@ class _StepFn(torch.autograd.Function):
             if dp is not None:
                 dp.allreduce_kl(owner._engine)               # VAE: the clamp's gate sees the global KL
             owner._engine.backward()
+        owner._auto_restart()                                # (the deferred EMA and the codebook refresh are done by here)
         owner._after_backward(g)
         if prev is not None:
             eng = owner._engine
@@ -101,13 +148,45 @@ class _BottleneckFacade(nn.Module):
         if eng is not None and eng.bn_type == "vqvae-ema":
             eng.update_codebook()
 
+    def _restart_engine(self):
+        owner = self._owner
+        if owner.bn_type != "vqvae-ema":
+            raise L.AewError(f"restarting codes needs the vqvae-ema bottleneck (this model: {owner.bn_type}): only its "
+                             "codebook carries a usage statistic")
+        if owner._engine is None:
+            raise L.AewError("no engine yet: restarting codes takes rows of the last run()'s encoder outputs")
+        return owner._engine
+
+    def restart_dead_codes(self, min_usage=None, call=None):
+        """Re-seed the codes whose EMA count is under `min_usage` from distinct encoder outputs of the last run(), on the
+        device (TrainEngine.restart_codes; under data parallel every rank ends up with rank 0's codebook).  min_usage and
+        the other settings default to the model's `codebook_restart` option, `call` - the counter the choice of rows is
+        hashed from - to the engine's step count.  max_codes, denom_init and seed come from that option alone: a model
+        built without it restarts with max_codes=64, denom_init=1.0, seed=0 (TrainEngine.restart_codes takes them
+        directly).  Counts: `restart_counts`."""
+        owner, eng = self._owner, self._restart_engine()
+        opt = owner._restart
+        if min_usage is None:
+            if opt is None:
+                raise L.AewError("restart_dead_codes() needs a threshold: pass min_usage, or build the model with "
+                                 "codebook_restart=dict(every=..., min_usage=...)")
+            min_usage = opt["min_usage"]
+        owner._restart_codes(eng, float(min_usage), eng.step_count if call is None else int(call))
+
+    @property
+    def restart_counts(self) -> torch.Tensor:
+        """int32 [4] on the device: dead codes found and codes restarted by the last restart, codes restarted so far on
+        this engine, 0.  Reading it synchronises."""
+        return self._restart_engine().restart_out()
+
 
 class HipModelBase(nn.Module):
     """Common implementation; subclasses set `kind` and the parameter prefix layout."""
 
     def __init__(self, hps, kind: str, loss_mode: str = "intended", take_compat: bool = False,
-                 update_codebook_every_step: bool = True, n_mel: Optional[int] = None):
+                 update_codebook_every_step: bool = True, n_mel: Optional[int] = None, codebook_restart=None):
         super().__init__()
+        codebook_restart = _check_codebook_restart(codebook_restart)
         if hps.global_model != kind:
             hps = type(hps)(hps)
             hps["global_model"] = kind
@@ -116,6 +195,10 @@ class HipModelBase(nn.Module):
         self.bn_type = hps.bn_type if kind == "autoencoder" else "none"
         self._opts = dict(loss_mode=loss_mode, take_compat=take_compat,
                           update_codebook_every_step=update_codebook_every_step, n_mel=n_mel)
+        if codebook_restart is not None and self.bn_type != "vqvae-ema":
+            raise ValueError(f"codebook_restart needs the vqvae-ema bottleneck (this model: {self.bn_type}): only its "
+                             "codebook carries a usage statistic")
+        self._restart = codebook_restart                 # kept on the model: every engine it builds restarts by it
         self.window_batch_size = hps.n_win_batch
         self._engine: Optional[TrainEngine] = None
         self._engines: Dict[int, TrainEngine] = {}      # engines by batch size (train B, sampling B = 1, ...)
@@ -479,6 +562,23 @@ class HipModelBase(nn.Module):
                 prev[o:o + view.numel()].copy_(gr.detach().reshape(-1).to(prev))
         return prev
 
+    def _restart_codes(self, eng, min_usage: float, call: int):
+        """One restart launch with the model's settings; through the data-parallel path where ranks have to agree."""
+        kw = {k: (self._restart or _RESTART_DEFAULTS)[k] for k in _RESTART_DEFAULTS}
+        if self._dp is not None and not self._dp._solo():
+            self._dp.restart_codes(eng, min_usage, call, **kw)
+        else:
+            eng.restart_codes(min_usage, call, **kw)
+
+    def _auto_restart(self):
+        """codebook_restart: the backward of step t = step_count + 1 restarts dead codes when t % every == 0, with call = t
+        (step_count comes back from checkpoints: a resumed run restarts on the same steps with the same rows)."""
+        opt = self._restart
+        if opt is not None:
+            t = self._engine.step_count + 1
+            if t % opt["every"] == 0:
+                self._restart_codes(self._engine, opt["min_usage"], t)
+
     def _after_backward(self, g):
         eng = self._engine
         # re-attach .grad views (optim.zero_grad(set_to_none=True) detaches them)
@@ -515,6 +615,8 @@ class HipModelBase(nn.Module):
             m["min_ze"], m["max_ze"], m["min_emb"], m["max_emb"] = dg[0], dg[1], dg[2], dg[3]   # vqema_bn.py:254-257
             if eng.bn_type == "vqvae-ema":
                 m["hst_ent"], m["nunq"] = dg[4], dg[5]              # vqema_bn.py:258-260
+                if self._restart is not None:
+                    m["vq_restarted"] = eng.restart_out()[1]        # codes the last restart re-seeded
             else:
                 m["nunq"] = eng.ind[:eng.Q].unique().numel()
         elif eng.bn_type == "vae":

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 24
+#define AEW_ABI_VERSION 25
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -301,6 +301,38 @@ typedef struct {                 /* EMA + optional codebook refresh (vqema_bn.py
     float gamma, gamma_comp;
     const uint32_t* guard;       /* ABI 20, optional: device word; non-zero = the op does nothing (see aew_adam_t.guard) */
 } aew_vq_ema_t;
+
+/* Restart dead codebook entries from this step's encoder outputs (ABI 25; VQ-VAE-EMA only).  One workgroup of 1024
+ * threads, so every order is fixed; no atomics.
+ *   dead list : D = every k in [0, K) with !(denom[k] >= min_usage), ascending (a NaN denominator is dead);
+ *               n_dead = |D|, n = min(n_dead, Q, max_codes); only D[0 .. n) are restarted.
+ *   rows      : h = mix64(mix64(seed + G) ^ (call + G)), G = 0x9e3779b97f4a7c15 and mix64 the splitmix64 finaliser of
+ *               aew_jitter_t; a = mix64(h ^ 1) % Q; Q == 1: b = 1; otherwise b0 = mix64(h ^ 2) % (Q - 1) and b is the
+ *               first c_i = 1 + (b0 + i) % (Q - 1), i = 0, 1, ..., with gcd(c_i, Q) == 1 (c = 1 qualifies, so it ends).
+ *               Restart r takes row q_r = (a + r * b) % Q in 64-bit arithmetic: b is coprime to Q, so the n rows are
+ *               distinct - no two codes are seeded with the same vector.
+ *   writes    : numer[k][j] = __fmul_rn(ze[q][j], denom_init), emb[k][j] = __fdiv_rn(numer[k][j], denom_init) - the
+ *               expression of aew_vq_ema_t's codebook refresh, which therefore reproduces emb bit for bit - and
+ *               denom[k] = denom_init, for j < d.  denom_init = 1 makes the code the encoder output exactly.  Nothing
+ *               else in the three buffers changes.
+ * AEW_E_ARG: Q, K or d < 1, d_pitch < d, max_codes outside 1 .. AEW_VQ_RESTART_MAX, denom_init not finite or <= 0,
+ * min_usage NaN, a NULL ze / emb / numer / denom / out; AEW_E_ALIGN: a pointer that is not 4-byte aligned.  Both before
+ * any launch. */
+#define AEW_VQ_RESTART_MAX 1024
+typedef struct {
+    const float* ze; int32_t Q, d, d_pitch;   /* this step's encoder outputs [Q][d_pitch] (bn.lin)            */
+    float* emb; float* numer; float* denom;   /* [K][d], [K][d], [K]                                          */
+    int32_t K;
+    int32_t max_codes;                        /* 1 .. AEW_VQ_RESTART_MAX (1024): at most this many per launch  */
+    float min_usage;                          /* code k is dead iff !(denom[k] >= min_usage)  (NaN counts)     */
+    float denom_init;                         /* > 0, finite: the denominator a restarted code gets            */
+    uint64_t seed, call;                      /* counter-based choice of the rows: no state between launches   */
+    int32_t* out;                             /* [4]: dead codes found, codes restarted, running total of
+                                                 restarted codes (zeroed by the caller once), 0                */
+    int32_t* pairs;                           /* optional [max_codes][2]: (k, q) of each restart, r ascending;
+                                                 rows >= out[1] are written as (-1, -1)                        */
+    const uint32_t* guard;                    /* optional, like aew_vq_ema_t.guard: non-zero = nothing is written */
+} aew_vq_restart_t;
 
 typedef struct {                 /* d(ze) = d(zq) + gscale*gamma * d(min_dist)/d(ze)          */
     const float* ze; const float* emb; const int64_t* ind; const float* dzq;
@@ -747,7 +779,7 @@ enum {
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
-    AEW_OP_SWAP
+    AEW_OP_SWAP, AEW_OP_VQ_RESTART
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -773,14 +805,14 @@ typedef struct {
         aew_softmax_nll_t sm; aew_colsum_t cs; aew_reduce_t red; aew_adam_t adam; aew_zero_t zero;
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
-        aew_swap_t swap;
+        aew_swap_t swap; aew_vq_restart_t vqr;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
