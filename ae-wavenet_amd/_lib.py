@@ -62,6 +62,11 @@ class GemmTN(C.Structure):
                 ("grp_splits", i32), ("grp_rows", i32)]
 
 
+class TnPick(C.Structure):
+    """aew_tn_pick_t: what the TN launchers decide for an op or a grouped launch (aew_tn_pick / aew_tn_group_pick)."""
+    _fields_ = [(n, i32) for n in "row bk bn threads lds_bytes".split()] + [("grid", i32 * 3)] + [(n, i32) for n in "tile rc splits rows_per_split fold slabs cursor cursor_epoch cursor_slack".split()] + [("name", C.c_char * 96)]
+
+
 class GemmTNGroup(C.Structure):
     _fields_ = [("descs", vp), ("tile_map", vp), ("n_descs", i32), ("n_blocks", i32), ("tile", i32), ("cursor_stride", i32),
                 ("cursors", vp)]
@@ -365,8 +370,9 @@ def load():
     lib.aew_tn_slabs.argtypes = [C.c_void_p]
     lib.aew_tn_fold.argtypes = [C.c_void_p]
     lib.aew_tn_group_check.argtypes = [C.c_void_p]
+    lib.aew_tn_group_tiles.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.aew_nt_kernel.argtypes = [C.c_void_p]
-    lib.aew_nt_pick.argtypes = [C.c_void_p, C.c_void_p]
+    lib.aew_nt_pick.argtypes = lib.aew_tn_pick.argtypes = lib.aew_tn_group_pick.argtypes = [C.c_void_p, C.c_void_p]
     lib.aew_lc_scatter_needs_zero.argtypes = [C.c_int]
     lib.aew_graph_capture.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     lib.aew_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
@@ -389,12 +395,12 @@ def load():
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
-                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart)):
+                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 25:
+    if lib.aew_abi_version() != 26:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib
@@ -442,4 +448,4 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_set_tn_target_blocks", "aew_set_tn_small", "aew_set_nt_small_tiles", "aew_set_nt_small_deep", "aew_set_nt_small_waves", "aew_set_nf_deep", "aew_set_nf_loaders", "aew_set_nt_rows192",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
-           "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero")
+           "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles")

@@ -1775,6 +1775,55 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
     return v;
 }
 
+// By-products and tile store of tn_bf16_tile (NK = 4 k-direction MFMA tiles per wave) and tnb_tile (8); tn8_tile spells the same
+// three out.  acc[i][j][r] = dW[n = nb + j * 16 + (lane & 15)][k = kb + i * 16 + 4 * (lane >> 4) + r].  Grouped form (SNAP) only:
+// tn16_colsum - an all-ones A operand: every row of cs[j] is sum_m G[m][n]; tn16_snap - after batch element b, column srel of the
+// wave's k range (here) and / or the column sums so far (cs_here) to g.snap_out; tn16_store - the tile, the sums to g.colsum_out
+__device__ __forceinline__ void tn16_colsum(f32x4_t (&cs)[4], const bf16x8_t& ones, const bf16x8_t (&gf)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cs[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, gf[j], cs[j], 0, 0, 0);
+}
+
+template <int NK>
+__device__ __forceinline__ void tn16_snap(const aew_gemm_tn_t& g, const f32x4_t (&acc)[NK][4], const f32x4_t (&cs)[4], int b,
+                                          int nb, int srel, bool here, bool cs_here, int lane) {
+    if (here && (lane >> 4) == ((srel >> 2) & 3)) {
+        const int si = (srel >> 4) & (NK - 1), sr = srel & 3;
+        float* so = g.snap_out + (int64_t)b * g.snap_bs + nb + (lane & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v = 0.f;
+#pragma unroll
+            for (int i = 0; i < NK; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v = (i == si && r == sr) ? acc[i][j][r] : v;
+            so[j * 16] = v;
+        }
+    }
+    if (cs_here && (lane >> 4) == 0) {                 // every row of cs[j] is sum_m G[m][n] so far
+        float* so = g.snap_out + (int64_t)b * g.snap_bs + nb + (lane & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) so[j * 16] = cs[j][0];
+    }
+}
+
+template <int NK>
+__device__ __forceinline__ void tn16_store(const aew_gemm_tn_t& g, const f32x4_t (&acc)[NK][4], const f32x4_t (&cs)[4], float* out,
+                                           int nb, int kb, bool do_cs, int lane) {
+    const int q = lane & 15, gq = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = nb + j * 16 + q;
+#pragma unroll
+        for (int i = 0; i < NK; ++i) {
+            const int k = kb + i * 16 + 4 * gq;
+            *reinterpret_cast<float4*>(out + (int64_t)n * g.K_total + k) =
+                make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+        }
+        if (do_cs && g.colsum_out && gq == 0 && n < g.N) g.colsum_out[n] = cs[j][0];
+    }
+}
+
 template <int SAFE, bool SNAP, bool CUR = false>      // CUR: the row-cursor protocol is compiled in (its own kernel: the default path carries none of it)
 __device__ __forceinline__ void tn_bf16_tile(const aew_gemm_tn_t& g, char* smem, int kt, int nt, int b_lo, int b_hi,
                                              int r_lo, int r_hi, float* out, const TnCursor C = {nullptr, 0, 0, 0, 0}) {
@@ -1810,8 +1859,7 @@ __device__ __forceinline__ void tn_bf16_tile(const aew_gemm_tn_t& g, char* smem,
     const int srel = SNAP ? g.snap_k - tt.koff : -1;
     const bool snap_here = SNAP && g.snap_out && srel >= 0 && srel < TN_BT;
     int c_in_b = 0, bdone = b_lo;
-    // column sums of G (grouped form, first k tile, the two waves of k half 0): one more MFMA per n tile and stage with
-    // an all-ones A operand - every row of the result is sum_m G[m][n]
+    // column sums of G (tn16_colsum: grouped form, first k tile, the two waves of k half 0)
     const bool snap_cs = SNAP && g.snap_out && g.snap_k < 0;   // snap_k = -1: the running column sums of G themselves
     const bool do_cs = SNAP && (g.colsum_out != nullptr || snap_cs) && kt == 0 && wk == 0;
     f32x4_t cs[4];
@@ -1881,45 +1929,14 @@ __device__ __forceinline__ void tn_bf16_tile(const aew_gemm_tn_t& g, char* smem,
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], gf[j], acc[i][j], 0, 0, 0);
-        if (do_cs) {                                   // wave-uniform
-#pragma unroll
-            for (int j = 0; j < 4; ++j) cs[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, gf[j], cs[j], 0, 0, 0);
-        }
+        if (do_cs) tn16_colsum(cs, ones, gf);          // wave-uniform
         if (SNAP && ++c_in_b == nst) {                 // wave-uniform, once per batch element
             c_in_b = 0;
-            if (snap_here && wk == (srel >> 6) && (lane >> 4) == ((srel >> 2) & 3)) {
-                const int si = (srel >> 4) & 3, sr = srel & 3;
-                float* so = g.snap_out + (int64_t)bdone * g.snap_bs + n0 + wn * 64 + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = 0.f;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v = (i == si && r == sr) ? acc[i][j][r] : v;
-                    so[j * 16] = v;
-                }
-            }
-            if (snap_cs && do_cs && (lane >> 4) == 0) {          // every row of cs[j] is sum_m G[m][n] so far
-                float* so = g.snap_out + (int64_t)bdone * g.snap_bs + n0 + wn * 64 + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) so[j * 16] = cs[j][0];
-            }
+            tn16_snap<4>(g, acc, cs, bdone, n0 + wn * 64, srel, snap_here && wk == (srel >> 6), snap_cs && do_cs, lane);
             ++bdone;
         }
     }
-    const int q = lane & 15, gq = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + q;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = tt.koff + wk * 64 + i * 16 + 4 * gq;
-            *reinterpret_cast<float4*>(out + (int64_t)n * g.K_total + k) =
-                make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        }
-        if (do_cs && g.colsum_out && gq == 0 && n < g.N) g.colsum_out[n] = cs[j][0];
-    }
+    tn16_store<4>(g, acc, cs, out, n0 + wn * 64, tt.koff + wk * 64, do_cs, lane);
 }
 
 template <int SAFE>
@@ -2195,7 +2212,7 @@ __device__ __forceinline__ void tnb_issue(uint32_t lds_region, int r_end, int wa
 }
 
 // tnb_tile: one 256 x 256 output tile (kt, nt) contracted over rows [r_lo, r_hi) of the batch elements [b_lo, b_hi), in
-// that order, result to `out` ([N_pad][K_total] fp32).  SNAP as in tn_bf16_tile.
+// that order, result to `out` ([N_pad][K_total] fp32).  SNAP: the by-products (tn16_snap, tn16_colsum).
 template <bool SNAP>
 __device__ __forceinline__ void tnb_tile(const aew_gemm_tn_t& g, char* smem, int kt, int nt, int b_lo, int b_hi,
                                          int r_lo, int r_hi, float* out) {
@@ -2247,7 +2264,7 @@ __device__ __forceinline__ void tnb_tile(const aew_gemm_tn_t& g, char* smem, int
     const int srel = (SNAP && comp_valid) ? g.snap_k - ctt.koff : -1;
     const bool snap_here = SNAP && g.snap_out && srel >= 0 && srel < 128;
     int c_in_b = 0, bdone = b_lo;
-    // column sums of G (see tn_bf16_tile): the waves of k half 0 of the first k tile
+    // column sums of G (tn16_colsum): the waves of k half 0 of the first k tile
     const bool snap_cs = SNAP && g.snap_out && g.snap_k < 0;   // snap_k = -1: the running column sums of G themselves
     const bool do_cs = SNAP && (g.colsum_out != nullptr || snap_cs) && kt == 0 && wk == 0 && comp_valid;
     f32x4_t cs[4];
@@ -2278,47 +2295,16 @@ __device__ __forceinline__ void tnb_tile(const aew_gemm_tn_t& g, char* smem, int
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], gf[j], acc[i][j], 0, 0, 0);
-            if (do_cs) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) cs[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, gf[j], cs[j], 0, 0, 0);
-            }
+            if (do_cs) tn16_colsum(cs, ones, gf);
         }
         if (SNAP && ++c_in_b == nst) {                         // wave-uniform, once per batch element
             c_in_b = 0;
-            if (snap_here && (lane >> 4) == ((srel >> 2) & 3)) {
-                const int si = srel >> 4, sr = srel & 3;
-                float* so = g.snap_out + (int64_t)bdone * g.snap_bs + n128 * 128 + (wn & 1) * 64 + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = 0.f;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v = (i == si && r == sr) ? acc[i][j][r] : v;
-                    so[j * 16] = v;
-                }
-            }
-            if (snap_cs && do_cs && (lane >> 4) == 0) {
-                float* so = g.snap_out + (int64_t)bdone * g.snap_bs + n128 * 128 + (wn & 1) * 64 + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) so[j * 16] = cs[j][0];
-            }
+            tn16_snap<8>(g, acc, cs, bdone, n128 * 128 + (wn & 1) * 64, srel, snap_here, snap_cs && do_cs, lane);
             ++bdone;
         }
     }
     if (!comp_valid) return;
-    const int q = lane & 15, gq = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n128 * 128 + (wn & 1) * 64 + j * 16 + q;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int k = ctt.koff + i * 16 + 4 * gq;
-            *reinterpret_cast<float4*>(out + (int64_t)n * g.K_total + k) =
-                make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        }
-        if (do_cs && g.colsum_out && gq == 0 && n < g.N) g.colsum_out[n] = cs[j][0];
-    }
+    tn16_store<8>(g, acc, cs, out, n128 * 128 + (wn & 1) * 64, ctt.koff, do_cs, lane);
 }
 
 __global__ __launch_bounds__(TNB_THREADS, 2) void k_gemm_tn_bf16_big(const aew_gemm_tn_t g, int splits, int rows_per_split,
@@ -2718,6 +2704,20 @@ static const NtRow g_nt_rows[] = {AEW_NT_ROWS(AEW_ROW)};
 enum { AEW_NT_ROWS(AEW_ID) NTV_COUNT };                         // row of (id, sub): NTV_id_sub; NTV_SUB(id, sub) for a run-time sub
 #define NTV_SUB(ID, SUB) (NTV_##ID##_0 + (SUB) * (NTV_##ID##_1 - NTV_##ID##_0))
 
+// ---- the TN kernel table: ONE row per instantiation the two TN launchers can run; bm x bn: the output tile, k x n (GRP8: or 256 x 128)
+template <int BK, int BN_, int NT> struct TnCfg { static constexpr int BM = BK, BN = BN_, THREADS = NT; };
+typedef TnCfg<TN_BT, TN_BT, TN_THREADS> Tn128;
+#define AEW_TN_ROWS(X)                                                                                                       \
+    X(TN, 0, 0, (k_gemm_tn_bf16<0>), TN_LDS_BYTES, Tn128) X(TN, 1, 0, (k_gemm_tn_bf16<1>), TN_LDS_BYTES, Tn128)              \
+    X(TNGRP, 0, 0, (k_gemm_tn_bf16_grp), TN_LDS_BYTES, Tn128) X(TNCUR, 0, 0, (k_gemm_tn_bf16_grp_cur), TN_LDS_BYTES, Tn128)  \
+    X(TNGRP32, 0, 0, (k_gemm_tn_bf16_grp32), TN_LDS_BYTES, Tn128) X(TNGRP8, 0, 0, (k_gemm_tn_bf16_grp8), TN8_LDS_BYTES, TnCfg<128, 256, TN8_THREADS>) \
+    X(TNBIG, 0, 0, (k_gemm_tn_bf16_big), TNB_LDS_BYTES, TnCfg<256, 256, TNB_THREADS>)                                        \
+    X(TNBIGGRP, 0, 0, (k_gemm_tn_bf16_big_grp), TNB_LDS_BYTES, TnCfg<256, 256, TNB_THREADS>)                                 \
+    X(TNF32, 0, 0, (k_gemm_tn_f32), (2 * TF_STAGE_BYTES), TnCfg<TF_BT, TF_BT, 256>)                                          \
+    X(TNCHECK, 0, 0, (k_gemm_tn_check<uint16_t>), 0, TnCfg<64, 1, 64>) X(TNCHECK, 1, 0, (k_gemm_tn_check<float>), 0, TnCfg<64, 1, 64>)
+static const NtRow g_tn_rows[] = {AEW_TN_ROWS(AEW_ROW)};
+enum { AEW_TN_ROWS(AEW_ID) TNV_COUNT };
+
 // kernels using more than 64 KiB of dynamic LDS must opt in once per process
 static int ensure_big_lds() {
     static std::atomic<unsigned long long> done{0};               // one bit per device
@@ -2731,14 +2731,8 @@ static int ensure_big_lds() {
     if (e != hipSuccess) return (int)e;
     for (const NtRow& r : g_nt_rows)
         if (r.lds) { AEW_SET_LDS(r.fn, r.lds) }
-    AEW_SET_LDS(k_gemm_tn_bf16_big, TNB_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16<0>, TN_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16<1>, TN_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16_grp, TN_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16_grp_cur, TN_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16_big_grp, TNB_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16_grp8, TN8_LDS_BYTES)
-    AEW_SET_LDS(k_gemm_tn_bf16_grp32, TN_LDS_BYTES)
+    for (const NtRow& r : g_tn_rows)
+        if (r.lds) { AEW_SET_LDS(r.fn, r.lds) }
     AEW_SET_LDS((k_nt_chain<0>), CHAIN_LDS_BYTES)
     AEW_SET_LDS((k_nt_chain<1>), CHAIN_LDS_BYTES)
 #undef AEW_SET_LDS
@@ -2955,6 +2949,12 @@ static int launch_gemm_nt(const aew_gemm_nt_t& g, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
+// a table row's kernel as written there, its parentheses and blanks dropped (name: zeroed, 96 bytes)
+static void row_name(const char* s, char* name) {
+    for (int n = 0; *++s && s[1] && n < 95;)
+        if (*s != ' ') name[n++] = *s;
+}
+
 // Which kernel launch_gemm_nt runs for this descriptor under the current settings (the codes: aewavenet.h; bench.py groups
 // its per-kernel rooflines by it), or the launcher's refusal
 extern "C" int aew_nt_kernel(const aew_gemm_nt_t* g) {
@@ -2969,24 +2969,36 @@ extern "C" int aew_nt_pick(const aew_gemm_nt_t* g, aew_nt_pick_t* out) {
     const int rc = g && out ? nt_check(*g, AEW_T(), &p) : AEW_E_ARG;
     if (rc) return rc;
     *out = aew_nt_pick_t{p.kernel, p.variant, p.bm, p.bn, p.threads, p.lds_bytes, p.grid, p.k_split, p.dwp, {0}};
-    const char* s = p.variant >= 0 ? g_nt_rows[p.variant].name + 1 : "k_fn)";      // the row's kernel, its parentheses and blanks dropped
-    for (int n = 0; s[1] && n < (int)sizeof(out->name) - 1; ++s)
-        if (*s != ' ') out->name[n++] = *s;
+    row_name(p.variant >= 0 ? g_nt_rows[p.variant].name : "(k_fn)", out->name);
     return 0;
 }
 
-
-// does this op run on the big-tile kernel?  (bf16, MFMA path, at least one full 256 x 256 tile's worth of output)
-static bool tn_use_big(const aew_gemm_tn_t& g) {
-    return AEW_T().tn_big && !AEW_T().tn_safe && g.dtype == AEW_BF16 && g.impl != 1 && g.N_pad >= 256 && g.K_total >= 256 &&
-           (int64_t)g.Mc * g.batch > AEW_T().tn_fold_rows;
+// ---- TN (weight-gradient) launchers: one check (tn_check), one pick each (tn_pick, tn_group_pick), one table (g_tn_rows)
+typedef aew_tn_pick_t TnPick;                          // the picks answer in the exported record (aewavenet.h)
+static void tn_pick_row(TnPick* p, int row) {
+    const NtRow& r = g_tn_rows[row];
+    p->row = row; p->bk = r.bm; p->bn = r.bn; p->threads = r.threads; p->lds_bytes = r.lds;
+    row_name(r.name, p->name);
 }
 
-// split heuristic: aim for >= ~2 blocks per CU
-static void tn_plan(const aew_gemm_tn_t& g, int tile, int rc, int* splits, int* rps, int* fold) {
-    if (tn_use_big(g)) {
-        const int tiles = ((g.N_pad / 128 + 1) / 2) * ((g.K_total / 128 + 1) / 2);
-        int want = (AEW_T().tn_big_target + tiles * g.batch - 1) / (tiles * g.batch);
+// (k tiles, n tiles) of g's output: tile 256 = 2 x 2 halves of 128 columns, 384 = the 8-wave tile in g's orientation, else square
+static void tn_tile_grid(const aew_gemm_tn_t& g, int tile, int* nkt, int* nnt) {
+    const int k128 = g.K_total / 128, n128 = g.N_pad / 128, ori = tn8_ori(g.N_pad, g.K_total);
+    if (tile == 256) { *nkt = (k128 + 1) / 2; *nnt = (n128 + 1) / 2; }
+    else if (tile == 384) { *nkt = ori ? (k128 + 1) / 2 : k128; *nnt = ori ? n128 : (n128 + 1) / 2; }
+    else { *nkt = g.K_total / tile; *nnt = g.N_pad / tile; }
+}
+
+// does this op run on the big-tile kernel?  (bf16, MFMA path, at least one full 256 x 256 tile's worth of output)
+static bool tn_use_big(const aew_gemm_tn_t& g, const aew_tuning_t& T) {
+    return T.tn_big && !T.tn_safe && g.dtype == AEW_BF16 && g.impl != 1 && g.N_pad >= 256 && g.K_total >= 256 &&
+           (int64_t)g.Mc * g.batch > T.tn_fold_rows;
+}
+
+// split heuristic: aim for >= ~2 blocks per CU (tiles: output tiles of the kernel that runs, big: the big-tile kernel)
+static void tn_plan(const aew_gemm_tn_t& g, const aew_tuning_t& T, bool big, int tiles, int rc, int* splits, int* rps, int* fold) {
+    if (big) {
+        int want = (T.tn_big_target + tiles * g.batch - 1) / (tiles * g.batch);
         int max_sp = (g.Mc + 8 * rc - 1) / (8 * rc);       // keep >= 8 stages per block
         if (max_sp < 1) max_sp = 1;
         int sp = want < 1 ? 1 : (want > max_sp ? max_sp : want);
@@ -2996,13 +3008,12 @@ static void tn_plan(const aew_gemm_tn_t& g, int tile, int rc, int* splits, int* 
         *splits = sp; *rps = r; *fold = 0;
         return;
     }
-    const int tiles = (g.N_pad / tile) * (g.K_total / tile);
-    int f = ((int64_t)g.Mc * g.batch <= AEW_T().tn_fold_rows) ? 1 : 0;   // short contractions: fold the batch loop
+    int f = ((int64_t)g.Mc * g.batch <= T.tn_fold_rows) ? 1 : 0;   // short contractions: fold the batch loop
     int slabs_b = f ? 1 : g.batch;
     // small outputs (a handful of tiles) would need ~100 row splits to fill the chip on their own, and
     // every split is a slab that is written here and read again by the unpack; they run on the side lane
     // next to chip-filling kernels, so they are split much less
-    const int target = (tiles <= AEW_T().tn_small_tiles) ? AEW_T().tn_small_target : AEW_T().tn_target_blocks;
+    const int target = (tiles <= T.tn_small_tiles) ? T.tn_small_target : T.tn_target_blocks;
     int want = (target + tiles * slabs_b - 1) / (tiles * slabs_b);
     int max_sp = (g.Mc + 4 * rc - 1) / (4 * rc);        // keep >= 4 stages per block
     if (max_sp < 1) max_sp = 1;
@@ -3014,115 +3025,91 @@ static void tn_plan(const aew_gemm_tn_t& g, int tile, int rc, int* splits, int* 
     *splits = sp; *rps = r; *fold = f;
 }
 
-extern "C" int aew_tn_slabs(const aew_gemm_tn_t* g) {
-    // number of fp32 partial slabs the TN op writes (the unpack step sums them)
-    int sp, rps, fold;
-    const int tile = g->dtype == AEW_BF16 ? TN_BT : TF_BT;
-    const int rc = g->dtype == AEW_BF16 ? TN_RC : TF_RC;
-    tn_plan(*g, tile, rc, &sp, &rps, &fold);
-    return fold ? sp : g->batch * sp;
+// THE selection for a stand-alone op: kernel, grid, split-K plan.  Pure and total: it checks nothing (tn_check does)
+static void tn_pick(const aew_gemm_tn_t& g, const aew_tuning_t& T, TnPick* p) {
+    *p = TnPick{};
+    const bool bf = g.dtype == AEW_BF16, big = tn_use_big(g, T);
+    p->tile = bf ? TN_BT : TF_BT; p->rc = bf ? TN_RC : TF_RC;
+    int nkt, nnt;
+    tn_tile_grid(g, big ? 256 : p->tile, &nkt, &nnt);
+    const int tiles = nkt * nnt;
+    tn_plan(g, T, big, tiles, p->rc, &p->splits, &p->rows_per_split, &p->fold);
+    p->slabs = p->splits * (p->fold ? 1 : g.batch);          // one fp32 slab per (batch element | all of them, row split)
+    tn_pick_row(p, g.impl == 1 ? NTV_SUB(TNCHECK, !bf) : !bf ? NTV_TNF32_0 : big ? NTV_TNBIG_0 : NTV_SUB(TN, T.tn_safe != 0));
+    p->grid[0] = tiles; p->grid[1] = p->splits; p->grid[2] = p->fold ? 1 : g.batch;                   // fp32
+    if (g.impl == 1) { p->grid[0] = (g.K_total + 63) / 64; p->grid[1] = g.N_pad; p->grid[2] = p->slabs; }
+    else if (bf) { p->grid[0] = ((p->slabs + 7) / 8) * 8 * tiles; p->grid[1] = p->grid[2] = 1; }    // XCD-aware order, see the kernels
 }
 
-extern "C" int aew_tn_fold(const aew_gemm_tn_t* g) {
-    int sp, rps, fold;
-    const int tile = g->dtype == AEW_BF16 ? TN_BT : TF_BT;
-    const int rc = g->dtype == AEW_BF16 ? TN_RC : TF_RC;
-    tn_plan(*g, tile, rc, &sp, &rps, &fold);
-    return fold;
+// ... and for a grouped launch; tile 128 with progress words is paced by the row cursor unless T vetoes it (epoch -1; 0: 4 / 2)
+static int tn_group_pick(const aew_gemm_tn_group_t& g, const aew_tuning_t& T, TnPick* p) {
+    if (!g.descs || !g.tile_map || g.n_descs <= 0 || g.n_blocks <= 0 || (g.tile != 128 && g.tile != 256 && g.tile != 384)) return AEW_E_ARG;
+    *p = TnPick{};
+    const int te = T.tn_cursor_epoch;
+    p->cursor_epoch = te > 0 ? te : 4; p->cursor_slack = te > 0 ? T.tn_cursor_slack : 2;
+    p->cursor = g.tile == 128 && g.cursors && g.cursor_stride >= 64 && te >= 0 && p->cursor_epoch >= 3 && p->cursor_slack >= 1;
+    tn_pick_row(p, g.tile == 256 ? NTV_TNBIGGRP_0 : g.tile == 384 ? NTV_TNGRP8_0 : p->cursor ? NTV_TNCUR_0 : T.tn_mfma32 ? NTV_TNGRP32_0 : NTV_TNGRP_0);
+    p->tile = g.tile; p->rc = TN_RC; p->grid[0] = g.n_blocks; p->grid[1] = p->grid[2] = 1;
+    return 0;
 }
 
-extern "C" int aew_set_tn_fold_rows(int rows) { g_tune.tn_fold_rows = rows; return 0; }
-
-// host copy of a group's descriptors is not available (they live in device memory): the builder validated them with
-// aew_tn_group_check before uploading
-extern "C" int aew_tn_group_check(const aew_gemm_tn_t* g) {
-    if (!g) return AEW_E_ARG;
-    if (g->dtype != AEW_BF16 || g->n_segs < 1 || g->n_segs > AEW_MAX_SEGS || g->Mc <= 0 || g->batch <= 0 || !g->out)
-        return AEW_E_ARG;
+// descriptor checks of a stand-alone op | of one descriptor of a grouped launch (device table: aew_tn_group_check before upload)
+static int tn_check(const aew_gemm_tn_t& g, bool grouped) {
+    const bool bf = g.dtype == AEW_BF16;
+    if ((grouped && !bf) || g.n_segs < 1 || g.n_segs > AEW_MAX_SEGS || g.Mc <= 0 || g.batch <= 0 || !g.out) return AEW_E_ARG;
+    const int es = bf ? 2 : 4, tile = bf ? TN_BT : TF_BT;
     int ksum = 0;
-    for (int s = 0; s < g->n_segs; ++s) {
-        const int rc = check_seg(g->seg[s], 2, TN_BT);
+    for (int s = 0; s < g.n_segs; ++s) {
+        const int rc = check_seg(g.seg[s], es, tile);
         if (rc) return rc;
-        ksum += g->seg[s].k_len;
+        ksum += g.seg[s].k_len;
     }
-    aew_seg_t gg = g->g; gg.k_len = TN_BT;
-    const int rc = check_seg(gg, 2, TN_BT);
-    if (rc) return rc;
-    if (ksum != g->K_total || g->N_pad % TN_BT || (g->N_pad / TN_BT) * (g->K_total / TN_BT) > 0xfff) return AEW_E_ARG;
-    if (g->snap_out && (g->snap_k < -1 || g->snap_k >= g->K_total)) return AEW_E_ARG;
-    if (g->grp_splits < 0 || g->grp_splits * g->batch > 0x3ff) return AEW_E_ARG;
-    if (g->grp_splits > 0 && (g->grp_rows <= 0 || g->grp_rows % TN_RC || (int64_t)g->grp_splits * g->grp_rows < g->Mc ||
-                              g->snap_out || g->colsum_out))
+    aew_seg_t gg = g.g; gg.k_len = tile;
+    const int rc = check_seg(gg, es, tile);
+    if (rc || ksum != g.K_total || g.N_pad % tile) return rc ? rc : AEW_E_ARG;
+    if (!grouped) return 0;
+    // ---- grouped launches only: the tile map's 12-bit tile and 10-bit chunk fields, the by-products, the split rules
+    if ((g.N_pad / TN_BT) * (g.K_total / TN_BT) > 0xfff || (g.snap_out && (g.snap_k < -1 || g.snap_k >= g.K_total)) ||
+        g.grp_splits < 0 || g.grp_splits * g.batch > 0x3ff) return AEW_E_ARG;
+    if (g.grp_splits > 0 && (g.grp_rows <= 0 || g.grp_rows % TN_RC || (int64_t)g.grp_splits * g.grp_rows < g.Mc ||
+                             g.snap_out || g.colsum_out))
         return AEW_E_ARG;
     return 0;
 }
 
-static int launch_gemm_tn_group(const aew_gemm_tn_group_t& p, hipStream_t st) {
-    if (!p.descs || !p.tile_map || p.n_descs <= 0 || p.n_blocks <= 0) return AEW_E_ARG;
-    const int rc = ensure_big_lds();
-    if (rc) return rc;
-    if (p.tile == 256)
-        hipLaunchKernelGGL(k_gemm_tn_bf16_big_grp, dim3(p.n_blocks), dim3(TNB_THREADS), TNB_LDS_BYTES, st, p.descs, p.tile_map);
-    else if (p.tile == 384)
-        hipLaunchKernelGGL(k_gemm_tn_bf16_grp8, dim3(p.n_blocks), dim3(TN8_THREADS), TN8_LDS_BYTES, st, p.descs, p.tile_map);
-    else if (p.tile == 128) {
-        // row cursor: the caller provides one zeroed progress word per tile (64 per descriptor) when it wants the launch
-        // paced; the tuning record picks epoch / slack (0: the defaults 4 / 2) or vetoes it (-1).  Its own kernel: the
-        // unpaced launch carries none of it
-        const int te = AEW_T().tn_cursor_epoch;
-        const int e = te > 0 ? te : 4, d = te > 0 ? AEW_T().tn_cursor_slack : 2;
-        const bool on = p.cursors && p.cursor_stride >= 64 && te >= 0 && e >= 3 && d >= 1;
-        if (on)
-            hipLaunchKernelGGL(k_gemm_tn_bf16_grp_cur, dim3(p.n_blocks), dim3(TN_THREADS), TN_LDS_BYTES, st, p.descs, p.tile_map,
-                               p.cursors, p.cursor_stride, e, d);
-        else if (AEW_T().tn_mfma32)
-            hipLaunchKernelGGL(k_gemm_tn_bf16_grp32, dim3(p.n_blocks), dim3(TN_THREADS), TN_LDS_BYTES, st, p.descs, p.tile_map);
-        else
-            hipLaunchKernelGGL(k_gemm_tn_bf16_grp, dim3(p.n_blocks), dim3(TN_THREADS), TN_LDS_BYTES, st, p.descs, p.tile_map);
-    }
-    else
-        return AEW_E_ARG;
-    return (int)hipGetLastError();
+extern "C" int aew_tn_group_check(const aew_gemm_tn_t* g) { return g ? tn_check(*g, true) : AEW_E_ARG; }
+// number of fp32 partial slabs the TN op writes (the unpack step sums them); is its batch loop folded
+extern "C" int aew_tn_slabs(const aew_gemm_tn_t* g) { TnPick p; tn_pick(*g, AEW_T(), &p); return p.slabs; }
+extern "C" int aew_tn_fold(const aew_gemm_tn_t* g) { TnPick p; tn_pick(*g, AEW_T(), &p); return p.fold; }
+extern "C" int aew_set_tn_fold_rows(int rows) { g_tune.tn_fold_rows = rows; return 0; }
+extern "C" int aew_tn_pick(const aew_gemm_tn_t* g, aew_tn_pick_t* out) {
+    const int rc = g && out ? tn_check(*g, false) : AEW_E_ARG;
+    if (!rc) tn_pick(*g, AEW_T(), out);
+    return rc;
+}
+extern "C" int aew_tn_group_pick(const aew_gemm_tn_group_t* g, aew_tn_pick_t* out) { return g && out ? tn_group_pick(*g, AEW_T(), out) : AEW_E_ARG; }
+extern "C" int aew_tn_group_tiles(const aew_gemm_tn_t* g, int tile, int* nkt, int* nnt) {
+    if (!g || !nkt || !nnt || (tile != 128 && tile != 256 && tile != 384)) return AEW_E_ARG;
+    tn_tile_grid(*g, tile, nkt, nnt);
+    return 0;
 }
 
-static int launch_gemm_tn(const aew_gemm_tn_t& g, hipStream_t st) {
-    if (g.n_segs < 1 || g.n_segs > AEW_MAX_SEGS || g.Mc <= 0 || g.batch <= 0 || !g.out) return AEW_E_ARG;
-    const int es = g.dtype == AEW_BF16 ? 2 : 4;
-    const int tile = g.dtype == AEW_BF16 ? TN_BT : TF_BT;
-    const int rc = g.dtype == AEW_BF16 ? TN_RC : TF_RC;
-    int ksum = 0;
-    for (int s = 0; s < g.n_segs; ++s) {
-        const int rcode = check_seg(g.seg[s], es, tile);
-        if (rcode) return rcode;
-        ksum += g.seg[s].k_len;
-    }
-    aew_seg_t gg = g.g; gg.k_len = tile;
-    const int rcode = check_seg(gg, es, tile);
-    if (rcode) return rcode;
-    if (ksum != g.K_total || g.N_pad % tile) return AEW_E_ARG;
-    int sp, rps, fold;
-    tn_plan(g, tile, rc, &sp, &rps, &fold);
-    if (g.impl == 1) {
-        dim3 grid((g.K_total + 63) / 64, g.N_pad, fold ? sp : g.batch * sp);
-        if (g.dtype == AEW_BF16) hipLaunchKernelGGL(k_gemm_tn_check<uint16_t>, grid, dim3(64), 0, st, g, sp, rps, fold);
-        else hipLaunchKernelGGL(k_gemm_tn_check<float>, grid, dim3(64), 0, st, g, sp, rps, fold);
-    } else if (g.dtype == AEW_BF16) {
-        const int n_chunks = sp * (fold ? 1 : g.batch);
-        const int rc = ensure_big_lds();
-        if (rc) return rc;
-        if (tn_use_big(g)) {
-            const int tiles = ((g.N_pad / 128 + 1) / 2) * ((g.K_total / 128 + 1) / 2);
-            dim3 gridb(((n_chunks + 7) / 8) * 8 * tiles);
-            hipLaunchKernelGGL(k_gemm_tn_bf16_big, gridb, dim3(TNB_THREADS), TNB_LDS_BYTES, st, g, sp, rps, fold);
-            return (int)hipGetLastError();
-        }
-        dim3 grid(((n_chunks + 7) / 8) * 8 * (g.N_pad / TN_BT) * (g.K_total / TN_BT));
-        if (AEW_T().tn_safe) hipLaunchKernelGGL(k_gemm_tn_bf16<1>, grid, dim3(TN_THREADS), TN_LDS_BYTES, st, g, sp, rps, fold);
-        else hipLaunchKernelGGL(k_gemm_tn_bf16<0>, grid, dim3(TN_THREADS), TN_LDS_BYTES, st, g, sp, rps, fold);
-    } else {
-        dim3 grid((g.N_pad / TF_BT) * (g.K_total / TF_BT), sp, fold ? 1 : g.batch);
-        hipLaunchKernelGGL(k_gemm_tn_f32, grid, dim3(256), 2 * TF_STAGE_BYTES, st, g, sp, rps, fold);
-    }
+static int tn_launch(const TnPick& p, void** args, hipStream_t st) {
+    const int rc = p.lds_bytes ? ensure_big_lds() : 0;
+    if (rc) return rc;
+    (void)hipLaunchKernel(g_tn_rows[p.row].fn, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.threads), args, p.lds_bytes, st);
     return (int)hipGetLastError();
+}
+static int launch_gemm_tn_group(const aew_gemm_tn_group_t& g, hipStream_t st) {
+    TnPick p;
+    const int rc = tn_group_pick(g, AEW_T(), &p);
+    void* args[] = {(void*)&g.descs, (void*)&g.tile_map, (void*)&g.cursors, (void*)&g.cursor_stride, &p.cursor_epoch, &p.cursor_slack};   // (the last four: the cursor kernel's)
+    return rc ? rc : tn_launch(p, args, st);
+}
+static int launch_gemm_tn(const aew_gemm_tn_t& g, hipStream_t st) {
+    TnPick p;
+    const int rc = aew_tn_pick(&g, &p);
+    void* args[] = {(void*)&g, &p.splits, &p.rows_per_split, &p.fold};
+    return rc ? rc : tn_launch(p, args, st);
 }
 #endif  /* AEW_DEV_KERNELS_ONLY */

@@ -84,6 +84,7 @@ extern "C" int aew_sizeof(int which) {
         case 16: return (int)sizeof(aew_nt_pick_t);
         case 17: return (int)sizeof(aew_swap_t);
         case 18: return (int)sizeof(aew_vq_restart_t);
+        case 19: return (int)sizeof(aew_tn_pick_t);
         default: return -1;
     }
 }

@@ -274,11 +274,9 @@ class TnGroupBuilder:
 
     def _grid(self, t: L.GemmTN) -> Tuple[int, int]:
         """(k tiles, n tiles) of a descriptor's output in this builder's tile size."""
-        k128, n128 = t.K_total // 128, t.N_pad // 128
-        if self.tile == 384:              # orientation per descriptor (tn8_ori in csrc/aew_gemm.hip: the same rule)
-            ori = 1 if (t.K_total % 256 == 0 and t.N_pad % 256 != 0) else 0
-            return ((k128 + 1) // 2, n128) if ori else (k128, (n128 + 1) // 2)
-        return (k128, n128) if self.tile == 128 else ((k128 + 1) // 2, (n128 + 1) // 2)
+        nkt, nnt = C.c_int(), C.c_int()
+        L.check(L.load().aew_tn_group_tiles(C.byref(t), self.tile, C.byref(nkt), C.byref(nnt)), "aew_tn_group_tiles")
+        return nkt.value, nnt.value
 
     def set_split(self, t: L.GemmTN, chunk_rows: int) -> int:
         """Split the descriptor's contraction into chunks of about `chunk_rows` rows per batch element, one block and one

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 25
+#define AEW_ABI_VERSION 26
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -220,8 +220,8 @@ typedef struct {
                                     384 (ABI 20): EIGHT waves of 64 x 64 on a 128 (k) x 256 (n) tile - or 256 (k) x 128 (n)
                                          where K_total is a multiple of 256 and N_pad is not - two blocks per CU on a
                                          3 x 24 KiB ring (the NT kernels' shape: 1.5 x the MFMAs per staged byte of the
-                                         128-tile, four waves per SIMD); tile = nt * nkt + kt in that grid; no split
-                                         descriptors (grp_splits = 0), no cursor; results bit-identical to tile = 128 */
+                                         128-tile, four waves per SIMD); tile = nt * nkt + kt in that grid (aew_tn_group_tiles);
+                                         no split descriptors (grp_splits = 0), no cursor; results bit-identical to tile = 128 */
     int32_t cursor_stride;       /* words per descriptor in `cursors` (>= 64)                                          */
     /* Optional row cursor (ABI 18; tile = 128 only; non-NULL = pace this launch): device
      * [n_descs][cursor_stride] uint32, ZERO before every launch (epoch / slack: aew_set_tn_cursor); word i of a descriptor's row = the epoch tile i is
@@ -812,7 +812,7 @@ typedef struct {
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
@@ -971,6 +971,14 @@ int aew_set_tn_cursor(int epoch, int slack);
 
 /* Number of fp32 partial slabs a TN op writes into `out` (depends on the split heuristic). */
 int aew_tn_slabs(const aew_gemm_tn_t* g);
+/* ABI 26, test and measurement aid: what the TN launchers decide under the current settings, without launching.  Their return
+ * code for a descriptor / group they refuse (*out untouched), else 0 and the row of the library's table of TN kernel instantiations
+ * (name as written there; bk x bn its output tile), block, LDS, grid, the tile and rows per stage, the split-K plan | the cursor */
+typedef struct { int32_t row, bk, bn, threads, lds_bytes, grid[3], tile, rc, splits, rows_per_split, fold, slabs, cursor, cursor_epoch, cursor_slack; char name[96]; } aew_tn_pick_t;
+int aew_tn_pick(const aew_gemm_tn_t* g, aew_tn_pick_t* out);
+int aew_tn_group_pick(const aew_gemm_tn_group_t* p, aew_tn_pick_t* out);
+/* (k tiles, n tiles) of g's output under a group tile of 128 | 256 | 384: tile_map's tile = nt * *nkt + kt.  Host logic only. */
+int aew_tn_group_tiles(const aew_gemm_tn_t* g, int tile, int* nkt, int* nnt);
 /* Validate one descriptor of a grouped launch (aew_gemm_tn_group_t.descs lives in device memory, so the launcher
  * cannot): 0 or AEW_E_*.  Host logic only. */
 int aew_tn_group_check(const aew_gemm_tn_t* g);
