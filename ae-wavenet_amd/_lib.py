@@ -23,7 +23,7 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART) = range(1, 30)
+ OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC) = range(1, 31)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -204,6 +204,19 @@ class VqRestart(C.Structure):
                 ("seed", C.c_uint64), ("call", C.c_uint64), ("out", vp), ("pairs", vp), ("guard", vp)]
 
 
+EVAL_ACC_N, EVAL_OUT_N = 16, 16
+# finalize's out[i] by name (aew_eval_acc_t; Evaluator.result() hands them out under these names)
+EVAL_OUT_NAMES = ("loss", "nll", "bits_per_sample", "top1", "tprb", "dist", "code_entropy", "code_perplexity", "codes_used",
+                  "term1", "term2", "term3", "term4", "positions", "batches")
+
+
+class EvalAcc(C.Structure):
+    """aew_eval_acc_t: fold one evaluated batch into the running record on the device / turn the record into means."""
+    _fields_ = [("nll", vp), ("ptgt", vp), ("wav", vp), ("wav_pitch", i32), ("tgt_off", i32), ("B", i32), ("w", i32),
+                ("amax", vp), ("logits", vp), ("bs", i64), ("pitch", i32), ("n_quant", i32), ("ind", vp), ("dist", vp),
+                ("Q", i32), ("K", i32), ("loss", vp), ("acc", vp), ("hist", vp), ("finalize", i32), ("pad_", i32), ("out", vp)]
+
+
 UW_CHUNK = 4096
 
 
@@ -280,7 +293,7 @@ class _OpU(C.Union):
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
-                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart)]
+                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc)]
 
 
 class Op(C.Structure):
@@ -293,7 +306,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_BASE_GATHER: "base", OP_SOFTMAX_NLL: "sm", OP_COLSUM: "cs", OP_REDUCE: "red",
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
-            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr"}
+            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva"}
 
 
 
@@ -395,12 +408,12 @@ def load():
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
-                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick)):
+                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 26:
+    if lib.aew_abi_version() != 27:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib

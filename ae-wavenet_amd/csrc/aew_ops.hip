@@ -1211,6 +1211,112 @@ __global__ __launch_bounds__(1024) void k_reduce(const aew_reduce_t p) {
 }
 
 // =============================================================================================
+// evaluation accumulator (aew_eval_acc_t): one block of 1024 threads folds a batch into the running record; a second
+// kernel turns the record into the reported means.  Every floating sum follows THE order of the header: thread t adds
+// its elements t, t + 1024, ... ascending in double, then the halving tree below.  Plain loads and adds only.
+// =============================================================================================
+template <typename T>
+__device__ __forceinline__ T eval_tree(T* sh, T v) {      // all 1024 threads call; returns sh[0] to every thread
+    __syncthreads();                                      // (a previous tree's readers are done with sh)
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sh[0];
+}
+__global__ __launch_bounds__(1024) void k_eval_acc(const aew_eval_acc_t p) {
+    __shared__ double sh[1024];
+    const int t = threadIdx.x;
+    const int64_t wl = p.w - 1, n_pos = (int64_t)p.B * wl;
+    double s_nll = 0.0, s_pt = 0.0, s_hit = 0.0, s_d = 0.0;
+    // four positions per thread and pass, loads first (thread t still adds positions t, t + 1024, ... in that order)
+    for (int64_t i0 = t; i0 < n_pos; i0 += 4096) {
+        float vn[4], vp[4], hit[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t i = i0 + 1024 * r;
+            vn[r] = vp[r] = hit[r] = 0.f;
+            if (i >= n_pos) continue;
+            const int64_t b = i / wl, u = i - b * wl;
+            const int64_t pos = b * p.w + u;
+            vn[r] = p.nll[pos];
+            vp[r] = p.ptgt[pos];
+            const int tgt = (int)p.wav[b * p.wav_pitch + p.tgt_off + u + 1];
+            int am = 0;
+            if (p.amax) am = p.amax[pos];
+            else {
+                const float* lg = p.logits + b * p.bs + u * p.pitch;
+                float best = lg[0];
+                for (int c = 1; c < p.n_quant; ++c) {
+                    const float v = lg[c];
+                    if (v > best) { best = v; am = c; }    // strictly greater: the lowest class keeps a tie
+                }
+            }
+            hit[r] = am == tgt ? 1.f : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (i0 + 1024 * r < n_pos) { s_nll += (double)vn[r]; s_pt += (double)vp[r]; s_hit += (double)hit[r]; }
+    }
+    if (p.ind)
+        for (int64_t q = t; q < p.Q; q += 1024) {
+            if (p.dist) s_d += (double)p.dist[q];
+            const int64_t k = p.ind[q];
+            if (k >= 0 && k < p.K) atomicAdd(p.hist + k, 1u);      // integer: exact whatever the order
+        }
+    const double b_nll = eval_tree(sh, s_nll), b_pt = eval_tree(sh, s_pt), b_hit = eval_tree(sh, s_hit);
+    const double b_d = eval_tree(sh, s_d);
+    if (t == 0) {
+        p.acc[0] += 1.0;
+        p.acc[1] += (double)n_pos;
+        p.acc[2] += b_nll;
+        p.acc[3] += b_pt;
+        p.acc[4] += b_hit;
+        if (p.ind) { p.acc[5] += (double)p.Q; p.acc[6] += b_d; }
+        if (p.loss) {
+            p.acc[7] += (double)p.loss[0];
+            for (int j = 0; j < 4; ++j) p.acc[8 + j] += (double)p.loss[1 + j];
+        }
+    }
+}
+__global__ __launch_bounds__(1024) void k_eval_finalize(const aew_eval_acc_t p) {
+    __shared__ double shd[1024];
+    __shared__ unsigned long long shn[1024];
+    const int t = threadIdx.x;
+    unsigned long long n = 0, used = 0;
+    if (p.hist)
+        for (int k = t; k < p.K; k += 1024) { const uint32_t h = p.hist[k]; n += h; used += h > 0u ? 1u : 0u; }
+    const unsigned long long total = eval_tree(shn, n), n_used = eval_tree(shn, used);
+    double e = 0.0;
+    if (p.hist && total > 0)
+        for (int k = t; k < p.K; k += 1024) {
+            const uint32_t h = p.hist[k];
+            if (h > 0u) { const double pr = (double)h / (double)total; e -= pr * log2(pr); }
+        }
+    const double ent = eval_tree(shd, e);
+    if (t != 0) return;
+    const double* a = p.acc;
+    const double nb = a[0], np_ = a[1], nq = a[5];
+    auto div = [](double x, double y) { return y > 0.0 ? x / y : 0.0; };
+    const double nll = div(a[2], np_);
+    p.out[0] = (float)div(a[7], nb);
+    p.out[1] = (float)nll;
+    p.out[2] = (float)(nll / 0.693147180559945309417232121458);
+    p.out[3] = (float)div(a[4], np_);
+    p.out[4] = (float)div(a[3], np_);
+    p.out[5] = (float)div(a[6], nq);
+    p.out[6] = (float)ent;
+    p.out[7] = total > 0 ? (float)exp2(ent) : 0.f;
+    p.out[8] = (float)n_used;
+    for (int j = 0; j < 4; ++j) p.out[9 + j] = (float)div(a[8 + j], nb);
+    p.out[13] = (float)np_;
+    p.out[14] = (float)nb;
+    p.out[15] = 0.f;
+}
+
+// =============================================================================================
 // mean / unbiased std of a channels-last view (gradient statistics of run(), autoencoder_model.py:252-257)
 // =============================================================================================
 __global__ __launch_bounds__(1024) void k_moments(const aew_moments_t p) {
@@ -2265,6 +2371,22 @@ extern "C" int aew_colsum_det_size(const aew_colsum_t* c, int64_t* floats, int32
 static int launch_reduce(const aew_reduce_t& p, hipStream_t st) {
     if (p.n_terms < 1 || p.n_terms > 4) return AEW_E_ARG;
     hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, st, p);
+    return (int)hipGetLastError();
+}
+static int launch_eval_acc(const aew_eval_acc_t& p, hipStream_t st) {
+    if (!p.acc) return AEW_E_ARG;
+    if (p.finalize) {
+        if (!p.out || (p.hist && p.K < 1)) return AEW_E_ARG;
+    } else {
+        if (p.B < 1 || p.w < 2 || !p.nll || !p.ptgt || !p.wav) return AEW_E_ARG;
+        if (!p.amax && (!p.logits || p.n_quant < 1)) return AEW_E_ARG;
+        if (p.ind && (p.K < 1 || p.Q < 1 || !p.hist)) return AEW_E_ARG;
+    }
+    if (((uintptr_t)p.acc | (uintptr_t)p.ind) & 7) return AEW_E_ALIGN;
+    if (((uintptr_t)p.nll | (uintptr_t)p.ptgt | (uintptr_t)p.wav | (uintptr_t)p.amax | (uintptr_t)p.logits | (uintptr_t)p.dist |
+         (uintptr_t)p.loss | (uintptr_t)p.hist | (uintptr_t)p.out) & 3) return AEW_E_ALIGN;
+    if (p.finalize) hipLaunchKernelGGL(k_eval_finalize, dim3(1), dim3(1024), 0, st, p);
+    else hipLaunchKernelGGL(k_eval_acc, dim3(1), dim3(1024), 0, st, p);
     return (int)hipGetLastError();
 }
 static int launch_moments(const aew_moments_t& p, hipStream_t st) {

@@ -531,6 +531,34 @@ class DataParallel:
             for t in (eng.restart_out(), eng.restart_pairs()):
                 dist.broadcast(t, src, group=self.group)
 
+    def sum_eval_record(self, acc: torch.Tensor, hist: torch.Tensor):
+        """The ranks' evaluation records (aew_eval_acc_t: acc float64 [16], hist uint32 counts held as int32 [K]) summed
+        in ONE all-reduce.  COLLECTIVE.  The counts are widened to int64 (the int32 tensor holds unsigned words) and
+        travel in the float64 buffer of the sums, where integers under 2^53 - and so their sum - are exact.  Returns
+        (acc float64 [16], hist int64 [K]); the arguments are left alone."""
+        n = acc.numel()
+        buf = self._buf("eval", 0, n + hist.numel(), torch.float64, acc.device)
+        buf[:n].copy_(acc)
+        buf[n:].copy_(hist.to(torch.int64) & 0xffffffff)
+        if not self._solo():
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
+        return buf[:n].clone(), buf[n:].to(torch.int64)
+
+    def eval_finish(self, eng) -> torch.Tensor:
+        """TrainEngine.eval_finish over the sum of every rank's record.  COLLECTIVE: the summed record takes the place of
+        this rank's own for the finalize launch and the rank's own is put back behind it (all on the compute stream), so
+        evaluation may go on and a second call does not count anything twice.  Counts saturate at 2^32 - 1."""
+        eng.eval_plans()
+        own = eng.eval_acc.clone(), eng.eval_hist.clone()
+        acc, hist = self.sum_eval_record(*own)
+        hist = hist.clamp_(max=0xffffffff)
+        eng.eval_acc.copy_(acc)
+        eng.eval_hist.copy_(torch.where(hist >= 2 ** 31, hist - 2 ** 32, hist))       # back to unsigned words in int32
+        out = eng.eval_finish().clone()
+        eng.eval_acc.copy_(own[0])
+        eng.eval_hist.copy_(own[1])
+        return out
+
     def attach(self, model, sharded: bool = False, bf16_grads: bool = False):
         """Hook the collectives into the module surface.  sharded=False: loss.backward() leaves the fully reduced
         gradients in every .grad (any optimizer).  sharded=True: backward issues the reduce-scatter, FusedAdam.step()

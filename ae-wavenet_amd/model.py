@@ -626,6 +626,54 @@ class TrainEngine:
         self.restart_buf = None           # int32 [4]: dead, restarted, total restarted, 0 (restart_out())
         self.restart_pairs_buf = None     # int32 [AEW_VQ_RESTART_MAX][2]: (code, row) per restart (restart_pairs())
         self.lin_live = False             # a forward (or encode) of this engine has filled bn.lin
+        # ===== held-out evaluation (evaluate() / aew_eval_acc_t): like the restart, its buffers and plans exist from the
+        # first use on (eval_plans())
+        self.act_epoch = 0                # bumped by everything that overwrites the activations a backward reads
+        self.eval_a = self.eval_b = self.eval_fin = None      # the forward plans minus EVAL_DROP (+ loss, accumulate); finalize
+        self.eval_acc = self.eval_hist = self.eval_out = self.eval_loss = None
+
+    # ops of the training forward that an evaluation leaves out: they write what the next training step (or the caller,
+    # through objective.metrics) reads - the EMA statistics and accumulators, the index histogram, the diagnostics, the
+    # loss word - or serve the backward alone
+    EVAL_DROP = ("vq.stats", "n_sum -> diagnostics copy", "vq.ema", "pack weights (backward layouts)",
+                 "diagnostics (codebook)", "diagnostics (peak)", "metrics", "loss")
+
+    def eval_plans(self):
+        """Held-out evaluation, built once at its first use: the forward plans without EVAL_DROP (the same op records,
+        order, lanes and chained launches), the loss reduction once more into a word of its own, and the accumulator
+        (aew_eval_acc_t) that folds the batch into the running record eval_acc (float64 [16]) / eval_hist (uint32 [K],
+        held as int32).  eval_fin turns the record into eval_out.  Returns (eval_a, eval_b, eval_fin)."""
+        if self.eval_fin is not None:
+            return self.eval_a, self.eval_b, self.eval_fin
+        ws, fb = self.ws, self.fwd_b
+        K = getattr(self, "K", 0) if self.bn_type in ("vqvae-ema", "vqvae") else 0
+        self.eval_acc = ws.alloc("eval.acc", L.EVAL_ACC_N, torch.float64)[:L.EVAL_ACC_N]
+        self.eval_hist = ws.alloc("eval.hist", max(K, 1), torch.int32)[:max(K, 1)]     # (uint32 counts)
+        self.eval_out = ws.alloc("eval.out", L.EVAL_OUT_N, torch.float32)[:L.EVAL_OUT_N]
+        self.eval_loss = ws.alloc("eval.loss", 8, torch.float32)
+        keep = lambda i, lab: lab not in self.EVAL_DROP
+        self.eval_a = self._sub_plan("eval_a", self.fwd_a, keep)
+        self.eval_b = self._sub_plan("eval_b", fb, keep)
+        red = L.Reduce.from_buffer_copy(fb.ops[fb.labels.index("loss")].u.red)     # the same terms (and device-side anneal weight)
+        red.out = self.eval_loss.data_ptr()
+        self.eval_b.add(L.OP_REDUCE, red, "eval.loss", TAG_LOSS)
+        sm = fb.ops[fb.labels.index("softmax_nll")].u.sm
+        ev = L.EvalAcc()
+        ev.nll, ev.ptgt, ev.wav, ev.wav_pitch, ev.tgt_off, ev.B, ev.w = sm.nll, sm.ptgt, sm.wav, sm.wav_pitch, sm.tgt_off, sm.B, sm.w
+        if sm.amax:
+            ev.amax = sm.amax
+        else:
+            ev.logits, ev.bs, ev.pitch, ev.n_quant = sm.logits, sm.bs, sm.pitch, sm.Q
+        if K:
+            ev.ind, ev.dist, ev.Q, ev.K = self.ind.data_ptr(), self.min_dist.data_ptr(), self.Q, K
+            ev.hist = self.eval_hist.data_ptr()
+        ev.loss, ev.acc, ev.out = self.eval_loss.data_ptr(), self.eval_acc.data_ptr(), self.eval_out.data_ptr()
+        self.eval_b.add(L.OP_EVAL_ACC, ev, "eval.accumulate", TAG_LOSS)
+        fin = L.EvalAcc.from_buffer_copy(ev)
+        fin.finalize = 1
+        self.eval_fin = Plan("eval_fin")
+        self.eval_fin.add(L.OP_EVAL_ACC, fin, "eval.finalize", TAG_LOSS)
+        return self.eval_a, self.eval_b, self.eval_fin
 
     def _vae_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.Vae:
         va = L.Vae()
@@ -839,6 +887,34 @@ class TrainEngine:
         if not timing:
             self._chain_watch("fwd")
         return self.loss_buf[0]
+
+    def evaluate(self):
+        """The loss of the batch in the inputs WITHOUT a training step: the forward plans minus EVAL_DROP, the loss into
+        `eval_loss` and the batch folded into the running record (eval_acc / eval_hist, one launch).  Writes none of emb,
+        ema_numer, ema_denom, ind_hist, z_sum, n_sum, n_sum_diag, loss_buf, met_buf, diag, diag_pk, gstat, the
+        parameters, gradients, Adam moments or average, step_count, weights_version.  It DOES overwrite the activations,
+        code indices and logits: a backward of an earlier forward() is no longer possible (act_epoch).  A deferred EMA
+        accumulation is applied first, as forward() does; no host synchronisation.  Returns the 0-d device loss."""
+        ea, eb, _ = self.eval_plans()
+        self._chain_watch("check")
+        self.finish_ema()
+        self.act_epoch += 1
+        self._run(ea, False)
+        self._run(eb, False)
+        self._chain_watch("fwd")
+        return self.eval_loss[0]
+
+    def eval_reset(self):
+        """Start a new record (zeroes eval_acc / eval_hist on the device)."""
+        self.eval_plans()
+        self.eval_acc.zero_()
+        self.eval_hist.zero_()
+
+    def eval_finish(self) -> torch.Tensor:
+        """Finalize launch: the record as means -> eval_out (float [16] device view, _lib.EVAL_OUT_NAMES); the record itself
+        is left as it is, so more batches may follow.  Reading the view is the caller's synchronisation."""
+        self._run(self.eval_plans()[2], False)
+        return self.eval_out
 
     def finish_ema(self, timing=False):
         """Deferred vq.ema (see forward): wait for the statistics' all-reduce, then accumulate."""

@@ -15,6 +15,7 @@ autograd traffic, and any torch optimizer — or the fused `optim.FusedAdam` —
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import operator
 from typing import Dict, Optional
@@ -82,6 +83,7 @@ class _StepFn(torch.autograd.Function):
             loss = dp.forward(owner._engine)                 # the decoder's parameter all-gather stays in flight under the encoder
         else:
             loss = owner._engine.forward(owner._ema_allreduce)
+        ctx.act = (owner._engine.serial, owner._engine.act_epoch)    # whose activations, and which, the backward reads
         return loss.clone()
 
     @staticmethod
@@ -93,6 +95,11 @@ class _StepFn(torch.autograd.Function):
         # path the reference harness never takes (it zeroes every step, chassis.py:157-160; FusedAdam.zero_grad() /
         # zero_grad(set_to_none=True) cost nothing here).
         owner = ctx.owner
+        eng = owner._engine
+        if eng is None or (eng.serial, eng.act_epoch) != ctx.act:
+            raise L.AewError("loss.backward() after model.evaluate(): the evaluation overwrote the activations (and code "
+                             "indices, logits) this loss was computed from, so its gradients would be those of another "
+                             "batch.  Call backward() before evaluating, or run() the batch again.  No gradient was written")
         owner._engine.set_upstream_grad(g)
         dp = owner._dp
         prev = owner._grads_carried()
@@ -112,6 +119,29 @@ class _StepFn(torch.autograd.Function):
         if z is None or z.device != owner._anchor.device:
             z = owner._anchor_zero = torch.zeros_like(owner._anchor)
         return z, None
+
+
+class Evaluator:
+    """What `model.evaluation()` yields: the running record of the model.evaluate() calls made inside the block."""
+
+    def __init__(self, model):
+        self._model = model
+
+    def result(self) -> Dict[str, torch.Tensor]:
+        """The record so far as 0-d device tensors (one finalize launch, no host synchronisation; reading a value is the
+        caller's): loss (mean per batch), nll (nats per position), bits_per_sample, top1, tprb (mean target probability),
+        dist, code_entropy (bits), code_perplexity, codes_used, term1 .. term4 (the loss's terms, mean per batch),
+        positions, batches.  The codebook entries are zero for models without a codebook.  Under data parallel the ranks'
+        records are summed first (ONE all-reduce; COLLECTIVE: every rank calls it, every rank gets the same values).  More
+        evaluate() calls may follow; each result() covers everything since the block was entered."""
+        m = self._model
+        eng = m._engine
+        if eng is None:
+            raise L.AewError("Evaluator.result(): no engine - nothing has been evaluated on this device yet")
+        dp = m._dp
+        with torch.no_grad():
+            out = (dp.eval_finish(eng) if dp is not None and not dp._solo() else eng.eval_finish()).clone()
+        return {name: out[i] for i, name in enumerate(L.EVAL_OUT_NAMES)}
 
 
 class Objective:
@@ -450,6 +480,10 @@ class HipModelBase(nn.Module):
         if new is None:
             new = TrainEngine(self.hps, B, self._device, n_win=self.window_batch_size, **self._opts)
             self._engines[B] = new
+        if eng is not None and eng.eval_acc is not None:         # the evaluation record moves along (device copies)
+            new.eval_plans()
+            new.eval_acc.copy_(eng.eval_acc)
+            new.eval_hist.copy_(eng.eval_hist)
         return self._adopt_engine(new)
 
     def _adopt_engine(self, eng):
@@ -492,6 +526,29 @@ class HipModelBase(nn.Module):
         target = wav[:, g.wav_out_off + 1: g.wav_out_off + w]
         self._fill_forward_metrics(eng)
         return pred, target, loss
+
+    def evaluate(self, wav, mel, voice, jitter, eps=None):
+        """The loss of a held-out batch, computed without a training step: nothing the next run() / backward() / step()
+        reads is written - not the EMA statistics, the code histogram, the diagnostics behind `objective.metrics`, the
+        loss word, parameters, gradients or optimizer state (TrainEngine.evaluate).  Inside
+        `FusedAdam.averaged_weights()` it uses the averaged weights.  It does overwrite the activations: a pending
+        `loss.backward()` of an earlier run() raises afterwards.  Every call also folds the batch into the running record
+        `model.evaluation()` reads; outside such a block that record is simply never read.  No collectives, no host
+        synchronisation.  Returns the 0-d device loss."""
+        with torch.no_grad():
+            eng = self._ensure_engine(wav.shape[0])
+            self._dp_finish()
+            eng.set_inputs(wav, mel, voice, jitter, eps=eps)
+            return eng.evaluate().clone()
+
+    @contextlib.contextmanager
+    def evaluation(self):
+        """`with model.evaluation() as ev:` - the record starts at zero, every model.evaluate() inside adds its batch,
+        `ev.result()` returns the means (Evaluator.result).  The record follows the model when another batch size makes
+        another engine the live one."""
+        if self._engine is not None and self._engine.eval_acc is not None:     # (else: the record is allocated as zeros)
+            self._engine.eval_reset()
+        yield Evaluator(self)
 
     def forward(self, wav, mel, voice, jitter):
         """train(): logits (B, Q, w) for the batch (teacher-forced).  eval(): the reference's inference call

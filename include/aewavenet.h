@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 26
+#define AEW_ABI_VERSION 27
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -498,6 +498,58 @@ typedef struct {                 /* v_i = scale_i * sum(x_i[0:n_i]);  out[1+i] =
 } aew_reduce_t;
 
 /* ---------------------------------------------------------------------------------------
+ * Evaluation accumulator (ABI 27): folds one evaluated batch into a running record that stays on the device - what a
+ * validation loop needs (held-out loss, bits per sample, top-1 accuracy, code perplexity) without a host synchronisation
+ * per batch and without touching anything a training step reads.  One launch per batch, ONE workgroup of 1024 threads.
+ *
+ * finalize == 0 (accumulate).  With P = B * (w - 1) positions that carry loss, i = b * (w - 1) + u (u = w - 1 is dropped),
+ * element [b][u] of the [B][w] arrays:
+ *   acc[0] += 1                      batches
+ *   acc[1] += P                      positions
+ *   acc[2] += S(nll)                 acc[3] += S(ptgt)
+ *   acc[4] += S(arg-max class == target class, as 1.0 / 0.0), target[b][u] = (int)wav[b * wav_pitch + tgt_off + u + 1]
+ *                                    (the target of aew_softmax_nll_t); the arg-max class is amax[b][u] or, with amax
+ *                                    NULL, the LOWEST class c < n_quant holding the maximum of logits[b * bs + u * pitch + c]
+ *                                    (a later class replaces an earlier one only where it is strictly greater: the rule
+ *                                    of aew_softmax_nll_t.amax)
+ *   acc[5] += Q                      acc[6] += S(dist[0:Q])      (ind != NULL only; dist may be NULL: nothing is added)
+ *   acc[7] += loss[0]                acc[8 + j] += loss[1 + j], j < 4                       (loss != NULL only)
+ *   hist[ind[q]] += 1 for q < Q      (integer atomics: exact in any order; an index outside [0, K) is not counted)
+ *   acc[12..15] are not touched.
+ * THE order of every floating sum S(x) over n elements: thread t (of 1024) adds the elements i = t, t + 1024, ...
+ * ascending to a double that starts at 0.0, each element converted to double first; the 1024 partial sums go to LDS and
+ * are folded by the halving tree  for (o = 512; o > 0; o >>= 1) s[t] += s[t + o] for t < o;  s[0] is the batch's sum,
+ * and thread 0 adds it to acc with one double addition.  No floating atomics.
+ *
+ * finalize != 0: nothing is accumulated; out[0..15] are written from acc and hist (n / 0 = 0 throughout):
+ *   out[0] acc[7] / acc[0]  mean loss per batch          out[1] acc[2] / acc[1]  nll per position (nats)
+ *   out[2] out[1] / ln 2    bits per sample              out[3] acc[4] / acc[1]  top-1 accuracy
+ *   out[4] acc[3] / acc[1]  mean target probability      out[5] acc[6] / acc[5]  mean dist
+ *   out[6] entropy in bits of hist / sum(hist): -S(p_k log2 p_k) over the k with hist[k] > 0, in double, in THE order
+ *   out[7] 2^out[6] (0 while sum(hist) == 0)              out[8] number of k with hist[k] > 0
+ *   out[9 + j] acc[8 + j] / acc[0], j < 4  mean terms    out[13] acc[1]   out[14] acc[0]   out[15] 0
+ * every quotient taken in double and rounded to fp32 once.  With hist == NULL out[6..8] are 0.
+ *
+ * Before any launch - accumulate: AEW_E_ARG for B < 1, w < 2 (no position left), a NULL acc / nll / ptgt / wav, neither
+ * amax nor logits (or logits with n_quant < 1), ind with K < 1, Q < 1 or a NULL hist; finalize: AEW_E_ARG for a NULL
+ * acc / out, hist with K < 1.  AEW_E_ALIGN (both): acc or ind not 8-byte aligned, any other pointer not 4-byte aligned. */
+#define AEW_EVAL_ACC_N 16
+#define AEW_EVAL_OUT_N 16
+typedef struct {
+    const float* nll; const float* ptgt;                    /* [B][w], as aew_softmax_nll_t wrote them                */
+    const float* wav; int32_t wav_pitch; int32_t tgt_off;   /* the targets, as in aew_softmax_nll_t                   */
+    int32_t B, w;
+    const int32_t* amax;                                    /* [B][w] (aew_softmax_nll_t.amax), or NULL:              */
+    const float* logits; int64_t bs; int32_t pitch; int32_t n_quant;   /* fp32 [B][w][>= n_quant]                     */
+    const int64_t* ind; const float* dist; int32_t Q, K;    /* optional: code index / distance per query [Q]           */
+    const float* loss;                                      /* optional [5]: aew_reduce_t.out of the evaluation's loss */
+    double* acc;                                            /* [AEW_EVAL_ACC_N] the running record                     */
+    uint32_t* hist;                                         /* [K] code counts (with ind; finalize: optional)          */
+    int32_t finalize; int32_t pad_;
+    float* out;                                             /* [AEW_EVAL_OUT_N], written by finalize only              */
+} aew_eval_acc_t;
+
+/* ---------------------------------------------------------------------------------------
  * Per-parameter update / weight ratios (ABI 22): what the reference's training loop computes around optim.step()
  * (chassis.py:162-185: clone every parameter, step, norm(clone - p) / norm(clone) per tensor) - here from inside the
  * Adam launch, which holds the old and the new value of every element in registers: no clone, no extra pass over
@@ -779,7 +831,7 @@ enum {
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
-    AEW_OP_SWAP, AEW_OP_VQ_RESTART
+    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -805,14 +857,14 @@ typedef struct {
         aew_softmax_nll_t sm; aew_colsum_t cs; aew_reduce_t red; aew_adam_t adam; aew_zero_t zero;
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
-        aew_swap_t swap; aew_vq_restart_t vqr;
+        aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
