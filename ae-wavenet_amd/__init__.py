@@ -10,5 +10,13 @@ Package layout:
   mfcc_inverter.py      drop-in ``MfccInverter(hps)`` module surface
   optim.py              fused Adam on the flat parameter buffer
   dp.py                 data-parallel helpers (RCCL via torch.distributed)
+  corpus.py             the training corpus in device memory, batches cut on the device (DeviceCorpus, DeviceBatches)
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):                          # ae_wavenet_amd.DeviceCorpus / .DeviceBatches, imported on first use
+    if name in ("DeviceCorpus", "DeviceBatches"):
+        from . import corpus
+        return getattr(corpus, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -23,7 +23,7 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC) = range(1, 31)
+ OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER) = range(1, 32)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -217,6 +217,13 @@ class EvalAcc(C.Structure):
                 ("Q", i32), ("K", i32), ("loss", vp), ("acc", vp), ("hist", vp), ("finalize", i32), ("pad_", i32), ("out", vp)]
 
 
+class WindowGather(C.Structure):
+    """aew_window_gather_t: cut the next batch's windows out of the device-resident corpus (corpus.DeviceCorpus)."""
+    _fields_ = [("snd", vp), ("n_snd", i64), ("snd_bytes", i32), ("B", i32), ("starts", vp), ("voices", vp), ("N", i64),
+                ("order", vp), ("n_order", i32), ("num_replicas", i32), ("rank", i32), ("advance", i32), ("counter", vp),
+                ("slice_size", i32), ("wav_pitch", i32), ("wav", vp), ("voice", vp), ("index", vp), ("position", vp)]
+
+
 UW_CHUNK = 4096
 
 
@@ -293,7 +300,7 @@ class _OpU(C.Union):
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
-                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc)]
+                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather)]
 
 
 class Op(C.Structure):
@@ -306,7 +313,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_BASE_GATHER: "base", OP_SOFTMAX_NLL: "sm", OP_COLSUM: "cs", OP_REDUCE: "red",
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
-            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva"}
+            OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
+            OP_WINDOW_GATHER: "wgat"}
 
 
 
@@ -404,16 +412,19 @@ def load():
     lib.aew_gemm_nt_small_split.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     lib.aew_colsum_det_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.aew_grad_norm_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.aew_corpus_locate.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.aew_uw_chunks.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
-                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc)):
+                       (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
+                       (21, WindowGather)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 27:
+    if lib.aew_abi_version() != 28:
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib
@@ -461,4 +472,5 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_set_tn_target_blocks", "aew_set_tn_small", "aew_set_nt_small_tiles", "aew_set_nt_small_deep", "aew_set_nt_small_waves", "aew_set_nf_deep", "aew_set_nf_loaders", "aew_set_nt_rows192",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
-           "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles")
+           "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles",
+           "aew_corpus_locate")

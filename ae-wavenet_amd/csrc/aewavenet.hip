@@ -5,6 +5,7 @@
 #include "aew_fn.hip"
 #include "aew_ops.hip"
 #include "aew_sampler.hip"
+#include "aew_corpus.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -57,6 +58,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_SWAP: return launch_swap(op.u.swap, st);
         case AEW_OP_VQ_RESTART: return launch_vq_restart(op.u.vqr, st);
         case AEW_OP_EVAL_ACC: return launch_eval_acc(op.u.eva, st);
+        case AEW_OP_WINDOW_GATHER: return launch_window_gather(op.u.wgat, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -87,6 +89,7 @@ extern "C" int aew_sizeof(int which) {
         case 18: return (int)sizeof(aew_vq_restart_t);
         case 19: return (int)sizeof(aew_tn_pick_t);
         case 20: return (int)sizeof(aew_eval_acc_t);
+        case 21: return (int)sizeof(aew_window_gather_t);
         default: return -1;
     }
 }

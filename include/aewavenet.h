@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define AEW_ABI_VERSION 27
+#define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
 /* error codes (negative; positive values are hipError_t) */
@@ -741,6 +741,59 @@ typedef struct {                 /* time-jitter indices on the device (jitter.py
 } aew_jitter_t;
 
 /* ---------------------------------------------------------------------------------------
+ * Device-resident training corpus (ABI 28): the batch's windows are cut out of a corpus that lives in device memory, in
+ * ONE op, with no host work and no host synchronisation (the reference: data.py SliceDataset / LoopingRandomSampler /
+ * TrackerDataset, a Python loop per item under a DataLoader).  The op reads how many items this rank has consumed from
+ * a DEVICE counter, so a captured graph that holds it yields the next batch at every replay.
+ *
+ *   snd      the corpus: n_snd elements of snd_bytes = 1 (uint8), 2 (int16) or 4 (int32) bytes (data.py:35-40).
+ *            CONTRACT: the base is 16-byte aligned and at least 16 bytes are readable past the last element.
+ *   starts   int64 [N], voices int32 [N]: the reference's in_start table (slice start in elements, speaker), its order.
+ *   order    int32 [2][n_order]: the permutation of this rank's slice list range(rank, N, num_replicas) for two
+ *            consecutive sampler epochs; epoch e reads row e & 1 (a batch may straddle two epochs).
+ *            n_order = len(range(rank, N, num_replicas)) = (N - rank + num_replicas - 1) / num_replicas.
+ *   counter  uint64 [1]: items this rank has consumed since the start.
+ *
+ * With t0 = *counter, R = num_replicas, for batch item b < B:
+ *   j = t0 + b;  e = j / n_order;  p = j % n_order;  i = rank + R * order[e & 1][p]
+ *   wav[b * wav_pitch + k] = (float)snd[starts[i] + k], k < slice_size     (data.py:229; int32 rounds to nearest even;
+ *                                                        columns slice_size..wav_pitch-1 are NOT written)
+ *   voice[b] = voices[i];  index[b] = i
+ * and with P = ceil(N / R), t = t0 + B:
+ *   position[0] = t / P;  position[1] = (t % P) * R      (what TrackerDataset reports for the LAST item of the batch:
+ *                                                        step += R per item, at step >= N: epoch += 1, step = 0)
+ * After every block has read the counter - a second launch of one thread inside the same launcher, no grid-wide wait -
+ * *counter = t0 + B when advance != 0 (advance == 0: the same batch again at the next launch).
+ * A table entry that would leave the corpus (an order value outside [0, n_order), i >= N, starts[i] < 0 or
+ * starts[i] + slice_size > n_snd) is not followed: that row of wav reads as zeros, voice[b] = -1, index[b] = -1.
+ *
+ * Kernel: grid (ceil(slice_size / (4096 / snd_bytes)), B), 256 threads; a lane converts 16 source bytes (16 / 8 / 4
+ * elements) and writes them with 16-byte stores.  Slice starts have every alignment: the lane reads the two ALIGNED
+ * 16-byte quantities that hold its 16 bytes and realigns them in registers, so the stores are aligned to the row of wav
+ * and there is no element-wise head; the slice_size % (16 / snd_bytes) elements at the end are read and written one
+ * by one.  Nothing below snd is read and nothing beyond the 16 bytes of slack the contract grants.
+ *
+ * Before any launch: AEW_E_ARG for B < 1 or B > 65535 (grid rows), slice_size <= 0, snd_bytes outside {1, 2, 4}, num_replicas < 1, rank outside
+ * [0, num_replicas), N < 1, n_order < B, n_order != len(range(rank, N, num_replicas)), n_snd < slice_size,
+ * wav_pitch < slice_size or not a multiple of 4, a NULL pointer; then AEW_E_ALIGN for snd or wav not 16-byte aligned,
+ * starts / counter / voice / position not 8-byte aligned, voices / order / index not 4-byte aligned. */
+typedef struct {
+    const void* snd; int64_t n_snd; int32_t snd_bytes; int32_t B;
+    const int64_t* starts; const int32_t* voices; int64_t N;
+    const int32_t* order; int32_t n_order; int32_t num_replicas; int32_t rank; int32_t advance;
+    uint64_t* counter;
+    int32_t slice_size; int32_t wav_pitch;
+    float* wav; int64_t* voice; int32_t* index; int64_t* position;
+} aew_window_gather_t;
+
+/* The index arithmetic of aew_window_gather_t for item b of the batch that starts at counter value t0, from the same
+ * helper the kernel calls: *epoch = e, *p = p, (*pos_epoch, *pos_step) = position.  Host-only, no device needed.
+ * AEW_E_ARG for a NULL output, B < 1, b outside [0, B), N < 1, n_order < 1, R < 1, rank outside [0, R), or an epoch
+ * that does not fit an int. */
+int aew_corpus_locate(uint64_t t0, int b, int B, int64_t N, int n_order, int R, int rank, int* epoch, int* p,
+                      int64_t* pos_epoch, int64_t* pos_step);
+
+/* ---------------------------------------------------------------------------------------
  * Chained NT launch (ABI 19): a run of DEPENDENT bf16 NT ops - the gated stack's G1 / G2 pairs (wavenet.py:100-109,
  * 354-357: the layer loop) or its backward's dz / dx pairs - as ONE kernel launch.  The tiles of all stages form one
  * grid in stage order; a tile of stage s starts once the tiles of earlier stages that produce the rows it reads have
@@ -831,7 +884,7 @@ enum {
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
-    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC
+    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -857,14 +910,14 @@ typedef struct {
         aew_softmax_nll_t sm; aew_colsum_t cs; aew_reduce_t red; aew_adam_t adam; aew_zero_t zero;
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
-        aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva;
+        aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
