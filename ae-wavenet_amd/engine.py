@@ -1190,3 +1190,342 @@ class EncoderPlan:
         if grp is not None:
             with plan.side(1):
                 grp.emit(plan, "wgrad.group (encoder)", TAG_ENC)
+
+
+# ------------------------------------------------------------------------------------------
+# bottleneck (fp32): the shared linear + one subclass per type
+# ------------------------------------------------------------------------------------------
+def reduce_op(terms: Sequence[Tuple[int, int, float]], out_ptr: int) -> "L.Reduce":
+    """out[0] = sum_i scale_i * sum(x_i[:n_i]), out[1 + i] = term i (aew_reduce_t) over terms [(x_ptr, n, scale), ...]."""
+    red = L.Reduce()
+    red.n_terms = len(terms)
+    for i, (p_, n_, s_) in enumerate(terms):
+        red.x[i], red.n[i], red.scale[i], red.post_scale[i] = p_, n_, s_, 1.0
+    red.out = out_ptr
+    return red
+
+
+class BottleneckPlan:
+    """Bottleneck between the encoder and the decoder's conditioning input.  This class owns what every type shares: the
+    linear (bn.lin = y9 @ Wl^T, its packed weights, its weight / data gradient).  A subclass per type states, each once:
+    its buffers (_alloc), its ops in fwd_a / fwd_b (_forward, build_diag), its loss and metric terms, its nll scale, its
+    backward op (_backward), its part of the module surface's metric map (metrics) and - vqvae-ema - the codebook plan
+    (build_codebook) and the restart op.  make() is the one place that reads the type string.  The mfcc inverter has no bottleneck."""
+
+    K = 0                     # codes; the evaluation accumulates code statistics iff K > 0 (then ind / min_dist are buffers)
+    ind = min_dist = None
+    eps = None                # vae: the noise the caller supplies (TrainEngine.set_inputs)
+    lin_outs = 1              # outputs of the linear per code dimension
+    lin_flags, lin_bias_ptr = 0, 0      # epilogue flags and bias of the bn.linear op
+    names = ("d", "dp", "Q", "nlin_p", "lin", "code")     # what TrainEngine republishes as its own attributes
+
+    @staticmethod
+    def make(bn_type: str, *args, **kw) -> "BottleneckPlan":
+        types = {"vqvae-ema": VqEmaBottleneck, "vqvae": VqBottleneck, "vae": VaeBottleneck, "ae": AeBottleneck}
+        if bn_type not in types:
+            raise ValueError(f"unknown bn_type {bn_type}")
+        return types[bn_type](*args, **kw)
+
+    def __init__(self, ws: Workspace, ps: ParamStore, hps, geom: G.ModelGeom, B: int, enc: "EncoderPlan", packer: Packer,
+                 impl: int = 0, loss_mode: str = "intended"):
+        self.ws, self.ps, self.hps, self.g, self.B, self.enc, self.pk, self.impl = ws, ps, hps, geom, B, enc, packer, impl
+        E, d, Ne = hps.enc_n_out, hps.bn_n_out, geom.embed_len
+        self.loss_mode, self.E, self.Ep = loss_mode, E, ru(E, 64)
+        self.d, self.dp, self.Q, Ep = d, ru(d, 64), B * Ne, self.Ep
+        self.nlin = nlin = self.lin_outs * d
+        self.nlin_p = ru(nlin, 64)
+        self.lin = Mat.new(ws, "bn.lin", B, Ne, self.nlin_p, F3)          # ze / (mu|logvar)
+        self.Wl = Mat.new(ws, "bn.wp.lin", 1, self.nlin_p, Ep, F3)
+        self.WlT = Mat.new(ws, "bn.wp.linT", 1, Ep, self.nlin_p, F3)
+        self.lin_piece = Piece("bottleneck.linear.weight", 0, [E, 1], [nlin, E], 0, [Ep, 1])     # Wl, and its gradient
+        packer.pack(self.lin_piece, self.Wl)
+        packer.pack(self.lin_piece.at(0, [1, self.nlin_p]), self.WlT)
+        self.dlin = Mat.new(ws, "bn.dlin", B, Ne, self.nlin_p, F3)
+        # words of the engine that the ops read: the loss record, the upstream gradient, the chained launches' sticky guard
+        self.loss_ptr, self.gmul_ptr, self.guard_ptr = ws.ptr("loss"), ws.ptr("loss.gmul"), ws.ptr("chain.guard")
+        self._alloc()
+
+    # -- forward --------------------------------------------------------------------------
+    def build_forward(self, fa: Plan, fb: Plan):
+        """bn.linear and the type's ops behind it into fwd_a; side work that only the next step reads into fwd_b."""
+        B, Ne, Ep, impl = self.B, self.g.embed_len, self.Ep, self.impl
+        skw = exact_split_args(self.ws, "bn.ks", EncoderPlan.k_split if impl == 0 else 0, self.E, Ep, Ne * B, self.nlin_p)
+        fa.add(L.OP_GEMM_NT, make_nt(F3, Ne, ru(self.nlin, 4), self.nlin_p, B, [self.enc.y[9].seg(Ep)],
+                                     self.Wl.ptr, flags=self.lin_flags, out0=self.lin.view(),
+                                     bias_ptr=self.lin_bias_ptr, impl=impl, **skw),
+               "bn.linear", TAG_VQ)
+        self._forward(fa, fb)
+
+    def build_diag(self, fb: Plan, lane: int, w: int, scratch: torch.Tensor, out: torch.Tensor):
+        """Codebook / encoder-output statistics (vqema_bn.py:254-260) on a side lane of fwd_b: the VQ types."""
+
+    def metric_terms(self) -> List[Tuple[int, int, float]]:
+        """Terms of the forward's metrics reduction behind rec and tprb_m."""
+        return []
+
+    def loss_op(self, nll: Tuple[int, int, float]) -> "L.Reduce":
+        """The loss reduction: `nll` is the decoder's term (pointer, count, mean or sum scale: model.MEAN_LOSS)."""
+        return reduce_op(self.loss_terms(nll), self.loss_ptr)
+
+    def nll_scale(self, scale: float) -> float:
+        """The factor at which the NLL gradient enters the backward, given the loss's mean / sum scale."""
+        return scale
+
+    def metrics(self, met: torch.Tensor, diag: torch.Tensor, loss: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The type's part of objective.metrics: name -> view of the metrics / diagnostics / loss records."""
+        return {}
+
+    # -- backward -------------------------------------------------------------------------
+    def build_backward(self, bw: Plan, dcode: Mat):
+        """d(loss)/d(code) [B][Ne][dp] -> dlin (the type's op), then the linear's weight and data gradient; leaves dy[9] and
+        dpre[9] of the encoder written."""
+        B, Ne, Ep, impl, enc = self.B, self.g.embed_len, self.Ep, self.impl, self.enc
+        self._backward(bw, dcode)
+        t = make_tn(F3, Ne, B, self.nlin, self.nlin_p, self.dlin.seg(64), [enc.y[9].seg(Ep)], impl=impl)
+        wg = wgrad_slab(self.ws, "bn.wg.lin", t, L.tn_slabs(t), self.pk.unpack_tbl)
+        with bw.side():
+            bw.add(L.OP_GEMM_TN, t, "wgrad.bn.linear", TAG_VQ)
+        self.pk.unpack([self.lin_piece], wg)
+        bw.add(L.OP_GEMM_NT, make_nt(F3, Ne, self.E, Ep, B, [self.dlin.seg(self.nlin_p)],
+                                     self.WlT.ptr, flags=L.EF_OUT1_POS1, out0=enc.dy[9].view(),
+                                     out1=enc.dpre[9].view(), aux1=enc.r[9].view(), impl=impl),
+               "d.bn.linear", TAG_VQ)
+
+    def build_codebook(self):
+        """vqvae-ema: the plan `cb` that refreshes the codebook after the backward."""
+
+
+class VqBottleneck(BottleneckPlan):
+    """vq_bn.py:28-61, 72-115: the codebook is a parameter; the loss sums NLL + (1 + gamma) * ||ze - emb[ind]||^2."""
+    metric = 1                # aew_vq_nearest_t.metric / aew_vq_bwd_t.metric
+    names = BottleneckPlan.names + ("K", "ind", "min_dist", "emb")
+
+    def _alloc(self):
+        ws, B, Ne = self.ws, self.B, self.g.embed_len
+        self.K = self.hps.bn_vq_n_embed
+        self.code = Mat.new(ws, "bn.zq", B, Ne, self.dp, F3)
+        self.ind = ws.alloc("bn.ind", self.Q, torch.int64)
+        self.min_dist = ws.alloc("bn.min_dist", self.Q, torch.float32)
+        self._alloc_codebook()
+
+    def _alloc_codebook(self):
+        self.emb, self.demb_ptr = self.ps.view("bottleneck.emb"), self.ps.ptr("bottleneck.emb", True)
+
+    def _forward(self, fa: Plan, fb: Plan):
+        vq = L.VqNearest()
+        vq.ze, vq.emb = self.lin.ptr, self.emb.data_ptr()
+        vq.Q, vq.K, vq.d, vq.d_pitch = self.Q, self.K, self.d, self.nlin_p
+        vq.metric = self.metric
+        vq.ind, vq.dist, vq.zq = self.ind.data_ptr(), self.min_dist.data_ptr(), self.code.ptr
+        vq.n_split = max(1, min(16, self.K // 256))       # each block scans >= 256 codes (one per thread)
+        if vq.n_split > 1:
+            vq.scratch = self.ws.alloc("bn.vq_part", 2 * self.Q * vq.n_split, torch.float32).data_ptr()
+        assert self.dp == self.nlin_p
+        fa.add(L.OP_VQ_NEAREST, vq, "vq.nearest", TAG_VQ)
+
+    def _diag_op(self, w: int, scratch: torch.Tensor, out: torch.Tensor) -> "L.VqDiag":
+        dv = L.VqDiag()
+        dv.ze, dv.Q, dv.d, dv.d_pitch = self.lin.ptr, self.Q, self.d, self.lin.pitch
+        dv.K, dv.emb = self.K, self.emb.data_ptr()
+        dv.B, dv.w, dv.n_quant = self.B, w, self.hps.n_quant
+        dv.scratch, dv.out = scratch.data_ptr(), out.data_ptr()
+        return dv
+
+    def build_diag(self, fb, lane, w, scratch, out):
+        with fb.side(lane):
+            fb.add(L.OP_VQ_DIAG, self._diag_op(w, scratch, out), "diagnostics (codebook)", TAG_LOSS)
+
+    def metric_terms(self):
+        return [(self.min_dist.data_ptr(), self.Q, float(self.hps.bn_vq_gamma) / self.Q)]              # com
+
+    def loss_terms(self, nll):
+        return [nll, (self.min_dist.data_ptr(), self.Q, 1.0 + float(self.hps.bn_vq_gamma))]
+
+    def metrics(self, met, diag, loss):
+        m = {"com": met[3], "min_ze": diag[0], "max_ze": diag[1], "min_emb": diag[2], "max_emb": diag[3]}   # vqema_bn.py:254-257
+        m.update(self._usage_metrics(diag))
+        return m
+
+    def _usage_metrics(self, diag):
+        return {"nunq": self.ind[:self.Q].unique().numel()}
+
+    def _backward(self, bw: Plan, dcode: Mat):
+        vb = L.VqBwd()
+        vb.ze, vb.emb, vb.ind, vb.dzq = self.lin.ptr, self.emb.data_ptr(), self.ind.data_ptr(), dcode.ptr
+        vb.Q, vb.d, vb.d_pitch = self.Q, self.d, self.nlin_p
+        vb.metric = self.metric
+        vb.coef = float(self.hps.bn_vq_gamma)
+        vb.demb_coef = 1.0
+        vb.dze = self.dlin.ptr
+        vb.demb = self.demb_ptr
+        vb.gmul = self.gmul_ptr
+        bw.add(L.OP_VQ_BWD, vb, "vq.bwd", TAG_VQ)
+
+
+class VqEmaBottleneck(VqBottleneck):
+    """vqema_bn.py:125-222, 231-266: the codebook follows exponential averages of the encoder outputs assigned to each
+    code; the loss sums NLL + gamma * commitment (loss_mode "head": the commitment alone, vqema_bn.py:246)."""
+    metric = 0
+    names = VqBottleneck.names + ("ema_numer", "ema_denom", "zn_sum", "z_sum", "n_sum", "ind_hist", "n_sum_diag", "cb")
+
+    def _alloc_codebook(self):
+        ws, K, d = self.ws, self.K, self.d
+        self.emb = ws.alloc("bn.emb", K * d, torch.float32)[:K * d].view(K, d)
+        self.ema_numer = ws.alloc("bn.ema_numer", K * d, torch.float32)[:K * d].view(K, d)
+        self.ema_denom = ws.alloc("bn.ema_denom", K, torch.float32)[:K]
+        # one buffer so that the data-parallel exchange of the EMA statistics is ONE all-reduce
+        self.zn_sum = ws.alloc("bn.zn_sum", K * d + K, torch.float32)[:K * d + K]
+        self.z_sum = self.zn_sum[:K * d].view(K, d)
+        self.n_sum = self.zn_sum[K * d:]
+        self.ind_hist = ws.alloc("bn.ind_hist", K, torch.float32)[:K]
+        self.demb_ptr = None                                             # (the codebook takes no gradient)
+
+    def _ema_op(self, z_sum: int, n_sum: int, update_codebook: int, gamma: float) -> "L.VqEma":
+        em = L.VqEma()
+        em.numer, em.denom = self.ema_numer.data_ptr(), self.ema_denom.data_ptr()
+        em.z_sum, em.n_sum, em.emb = z_sum, n_sum, self.emb.data_ptr()
+        em.K, em.d, em.update_codebook = self.K, self.d, update_codebook
+        em.gamma, em.gamma_comp = gamma, float(1.0 - gamma)
+        em.guard = self.guard_ptr
+        return em
+
+    def _forward(self, fa, fb):
+        super()._forward(fa, fb)
+        st = L.VqStats()
+        st.ze, st.ind = self.lin.ptr, self.ind.data_ptr()
+        st.Q, st.K, st.d, st.d_pitch = self.Q, self.K, self.d, self.nlin_p
+        st.z_sum, st.n_sum, st.hist = self.z_sum.data_ptr(), self.n_sum.data_ptr(), self.ind_hist.data_ptr()
+        fa.add(L.OP_VQ_STATS, st, "vq.stats", TAG_VQ)
+        # the diagnostics op (side lane of fwd_b) reads this step's LOCAL code counts; a data-parallel
+        # caller all-reduces zn_sum in place while fwd_b runs, so it gets its own copy
+        self.n_sum_diag = self.ws.alloc("bn.n_sum_diag", self.K, torch.float32)
+        ntbl = CopyTableBuilder(self.ws, "tbl.nsum")
+        ntbl.add(self.n_sum.data_ptr(), self.n_sum_diag.data_ptr(), [self.K], [1], [1], F3, F3)
+        ntbl.emit(fa, "n_sum -> diagnostics copy")
+        # EMA runs at the START of part B (after the optional cross-rank sum); the
+        # codebook refresh is deferred to after backward so that forward and backward
+        # of one step see the same emb
+        em = self._ema_op(self.z_sum.data_ptr(), self.n_sum.data_ptr(), 0, float(self.hps.bn_vq_ema_gamma))
+        with fb.side(3):                                   # nothing in the forward / backward reads the accumulators
+            fb.add(L.OP_VQ_EMA, em, "vq.ema", TAG_VQ)
+
+    def _diag_op(self, w, scratch, out):
+        dv = super()._diag_op(w, scratch, out)
+        dv.hist, dv.n_sum = self.ind_hist.data_ptr(), self.n_sum_diag.data_ptr()
+        return dv
+
+    def loss_terms(self, nll):
+        com = (self.min_dist.data_ptr(), self.Q, float(self.hps.bn_vq_gamma))
+        return [com] if self.loss_mode == "head" else [nll, com]
+
+    def nll_scale(self, scale):
+        return 0.0 if self.loss_mode == "head" else scale
+
+    def _usage_metrics(self, diag):
+        return {"hst_ent": diag[4], "nunq": diag[5]}        # vqema_bn.py:258-260
+
+    def build_codebook(self):
+        """Deferred codebook refresh (vqema_bn.py:216-222): emb = numer / denom, the accumulators unchanged."""
+        self.cb = Plan("codebook")
+        z0 = self.ws.alloc("bn.zero_k", self.K * self.d, torch.float32)
+        self.cb.add(L.OP_VQ_EMA, self._ema_op(z0.data_ptr(), z0.data_ptr(), 1, 1.0), "vq.codebook", TAG_VQ)
+
+    def restart_op(self) -> Tuple[torch.Tensor, torch.Tensor, "L.VqRestart"]:
+        """(int32 [4] counts, int32 [AEW_VQ_RESTART_MAX][2] pairs, the op over bn.lin / emb / ema_numer / ema_denom)."""
+        out = self.ws.alloc("restart.out", 4, torch.int32)[:4]
+        pairs = self.ws.alloc("restart.pairs", 2 * L.VQ_RESTART_MAX, torch.int32)[:2 * L.VQ_RESTART_MAX].view(L.VQ_RESTART_MAX, 2)
+        rs = L.VqRestart()
+        rs.ze, rs.Q, rs.d, rs.d_pitch = self.lin.ptr, self.Q, self.d, self.nlin_p
+        rs.emb, rs.numer, rs.denom = self.emb.data_ptr(), self.ema_numer.data_ptr(), self.ema_denom.data_ptr()
+        rs.K, rs.max_codes, rs.min_usage, rs.denom_init = self.K, 1, 0.0, 1.0
+        rs.out, rs.pairs = out.data_ptr(), pairs.data_ptr()
+        rs.guard = self.guard_ptr
+        return out, pairs, rs
+
+
+class VaeBottleneck(BottleneckPlan):
+    """vae_bn.py:26-62, 76-125: sample = mu + eps * sigma; the loss is the mean NLL + anneal * max(KL, free nats)."""
+    lin_outs = 2              # mu | logvar
+    names = BottleneckPlan.names + ("eps", "kl_terms", "anneal_weight", "dp_world")
+
+    def _alloc(self):
+        ws, B, Ne, d = self.ws, self.B, self.g.embed_len, self.d
+        self.code = Mat.new(ws, "bn.sample", B, Ne, self.dp, F3)
+        self.eps = ws.alloc("bn.eps", self.Q * d, torch.float32)[:self.Q * d].view(B, Ne, d)
+        self.kl_terms = ws.alloc("bn.kl_terms", self.Q, torch.float32)
+        self.anneal_weight = 0.0
+        self.dp_world = 1                                                # set by dp.DataParallel (see set_anneal_weight)
+        self.anneal_buf = ws.alloc("bn.anneal", 4, torch.float32)[:1]   # read by the loss op
+        self.anneal_bwd = ws.alloc("bn.anneal_bwd", 4, torch.float32)[:1]   # read by the KL-gradient op
+
+    def _op(self, backward: bool, dcode: Optional[Mat] = None) -> "L.Vae":
+        va = L.Vae()
+        va.lin, va.lin_pitch, va.eps = self.lin.ptr, self.nlin_p, self.eps.data_ptr()
+        va.Q, va.d, va.d_pitch = self.Q, self.d, self.dp
+        va.sample, va.kl_terms = self.code.ptr, self.kl_terms.data_ptr()
+        va.backward = int(backward)
+        if backward:
+            va.dsample = dcode.ptr
+            va.kl_coef = float(self.anneal_weight)
+            va.kl_coef_dev = self.anneal_bwd.data_ptr()
+            va.kl_value = self.loss_ptr + 4 * 2                  # out[1 + term 1]
+            va.free_nats = float(self.hps.bn_free_nats)
+            va.dlin = self.dlin.ptr
+            va.gmul = self.gmul_ptr
+        return va
+
+    def _forward(self, fa, fb):
+        fa.add(L.OP_VAE, self._op(False), "vae.sample", TAG_VQ)
+
+    def loss_terms(self, nll):
+        return [nll, (self.kl_terms.data_ptr(), self.Q, -0.5)]
+
+    def loss_op(self, nll):
+        red = super().loss_op(nll)                               # the KL term clamped at the free nats, times the device-side
+        red.clamp[1], red.clamp_min[1], red.post_scale[1] = 1, float(self.hps.bn_free_nats), 0.0     # anneal weight
+        red.post_scale_dev[1] = self.anneal_buf.data_ptr()
+        return red
+
+    def metrics(self, met, diag, loss):
+        return {"kl_div_loss": loss[2], "log_pred_loss": met[1]}
+
+    def _backward(self, bw, dcode):
+        bw.add(L.OP_VAE, self._op(True, dcode), "vae.bwd", TAG_VQ)
+
+
+class AeBottleneck(BottleneckPlan):
+    """ae_bn.py:11-16, 29-46: the code is the (biased) linear's output; the loss is the mean NLL + 0.001 * mean ||ze||^2."""
+    lin_flags = L.EF_BIAS
+
+    def _alloc(self):
+        self.code = self.lin
+        self.norm_terms = self.ws.alloc("bn.norm_terms", self.Q, torch.float32)
+        bt = self.ws.alloc("bn.wp.bias", self.nlin_p, torch.float32)
+        self.pk.pack_tbl.add(self.ps.ptr("bottleneck.linear.bias"), bt.data_ptr(), [self.d], [1], [1], F3, F3)
+        self.lin_bias_ptr = bt.data_ptr()
+
+    def _op(self, backward: bool, dcode: Optional[Mat] = None) -> "L.AeNorm":
+        an = L.AeNorm()
+        an.ze, an.Q, an.d, an.d_pitch = self.lin.ptr, self.Q, self.d, self.nlin_p
+        an.term = self.norm_terms.data_ptr()
+        an.backward = int(backward)
+        if backward:
+            an.dze_in, an.coef, an.dze = dcode.ptr, 0.001 / self.Q, self.dlin.ptr
+            an.gmul = self.gmul_ptr
+        return an
+
+    def _forward(self, fa, fb):
+        fa.add(L.OP_AE_NORM, self._op(False), "ae.norm", TAG_VQ)
+
+    def loss_terms(self, nll):
+        return [nll, (self.norm_terms.data_ptr(), self.Q, 0.001 / self.Q)]
+
+    def metrics(self, met, diag, loss):
+        return {"norm": loss[2]}
+
+    def _backward(self, bw, dcode):
+        bw.add(L.OP_AE_NORM, self._op(True, dcode), "ae.norm.bwd", TAG_VQ)
+        cs = colsum_op(self.ws, self.dlin.seg(64), F3, self.g.embed_len, self.d, self.B,
+                       self.ps.ptr("bottleneck.linear.bias", True), 0, "det.db.bn")
+        with bw.side():
+            bw.add(L.OP_COLSUM, cs, "db.bn", TAG_VQ)

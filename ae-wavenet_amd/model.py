@@ -11,16 +11,15 @@ import ctypes as C
 import os
 
 import math
-from typing import Dict, List, NamedTuple, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
 from . import _lib as L
 from . import geometry as G
-from .engine import (BF, F3, DecoderPlan, EncoderPlan, Packer, ParamStore, Piece, wgrad_slab, TAG_ADAM, TAG_ENC, colsum_op, exact_split_args,
-                     TAG_LOSS, TAG_MISC, TAG_PACK, TAG_VQ, bottleneck_param_specs,
-                     decoder_param_specs, encoder_param_specs)
-from .plan import CopyTableBuilder, Mat, Plan, Workspace, insert_nt_chains, make_nt, make_tn, null_view, ru, split_small_nt
+from .engine import (F3, BottleneckPlan, DecoderPlan, EncoderPlan, Packer, ParamStore, TAG_ADAM, TAG_LOSS, TAG_PACK, TAG_VQ,
+                     bottleneck_param_specs, decoder_param_specs, encoder_param_specs, reduce_op)
+from .plan import CopyTableBuilder, Mat, Plan, Workspace, insert_nt_chains, ru, split_small_nt
 
 MEAN_LOSS = {"none": True, "ae": True, "vae": True, "vqvae": False, "vqvae-ema": False}
 
@@ -55,7 +54,7 @@ class TrainEngine:
     """
     DIAG_LANE = 3             # codebook diagnostics (behind vq.ema on the same lane; read at the end of the forward)
     LANE_PACK_DEC = 1         # side lane of the decoder's forward-layout weight pack (joined by the end of fwd_a) ...
-    pack_dec_late = True      # the decoder's weight pack at the head of fwd_b instead of fwd_a (see build: data-parallel overlap)
+    pack_dec_late = True      # the decoder's weight pack at the head of fwd_b instead of fwd_a (see _place_decoder_pack: data-parallel overlap)
     small_split = 0           # > 0: bf16 NT launches of few 64 x 64 blocks contract K as up to 8 ranges on separate workgroups, as
                               # long as ranges x blocks stays at or under this (aew_gemm_nt_t.k_split hint, plan.split_small_nt)
     merge_packs = None        # True: all weight-layout packs of a step as ONE copy-table launch at the head of fwd_a (three launches
@@ -169,162 +168,85 @@ class TrainEngine:
                         [self.n_mel * g.mel_len, 1, g.mel_len], [self.mel_cl.bs, Mp, 1], F3, F3)
         # ---- sub-plans
         self.enc: Optional[EncoderPlan] = None
+        self.bn: Optional[BottleneckPlan] = None                   # (the mfcc inverter has neither)
         if with_enc:
             self.enc = EncoderPlan(ws, ps, hps, g, B, self.n_mel, self.mel_cl, self.pk, impl, in_tbl=self.in_tbl,
                                    in_mel=self.in_mel, wgrad_group=self.wgrad_group)
-            self._alloc_bottleneck()
-            lc_src = self.code
-        else:
-            lc_src = self.mel_cl
-        self.dec = DecoderPlan(ws, ps, hps, g, B, dec_pre, hps.n_lc_in, lc_src, self.in_wav, self.in_voice,
-                               self.in_jitter, take_compat, self.pk_dec, impl, wgrad_group=self.wgrad_group)
+            self.bn = BottleneckPlan.make(self.bn_type, ws, ps, hps, g, B, self.enc, self.pk, impl, loss_mode)
+        self.dec = DecoderPlan(ws, ps, hps, g, B, dec_pre, hps.n_lc_in, self.bn.code if with_enc else self.mel_cl, self.in_wav,
+                               self.in_voice, self.in_jitter, take_compat, self.pk_dec, impl, wgrad_group=self.wgrad_group)
         self._build()
+        # the bottleneck's buffers (and the codebook plan `cb`) under the names the module surface, the data-parallel
+        # wrapper, bench.py and the tests read: plain attributes, present exactly where the type has them
+        for name in self.bn.names if self.bn is not None else ():
+            setattr(self, name, getattr(self.bn, name))
         self.adam_state = None
         self.step_count = 0
 
     # --------------------------------------------------------------------------------------
-    def _alloc_bottleneck(self):
-        ws, hps, B, g = self.ws, self.hps, self.B, self.geom
-        bn, E, d = self.bn_type, hps.enc_n_out, hps.bn_n_out
-        self.d, self.dp = d, ru(d, 64)
-        Ne = g.embed_len
-        self.Q = B * Ne
-        Ep = ru(E, 64)
-        nlin = 2 * d if bn == "vae" else d
-        self.nlin, self.nlin_p = nlin, ru(nlin, 64)
-        self.lin = Mat.new(ws, "bn.lin", B, Ne, self.nlin_p, F3)          # ze / (mu|logvar)
-        self.Wl = Mat.new(ws, "bn.wp.lin", 1, self.nlin_p, Ep, F3)
-        self.WlT = Mat.new(ws, "bn.wp.linT", 1, Ep, self.nlin_p, F3)
-        self.lin_piece = Piece("bottleneck.linear.weight", 0, [E, 1], [nlin, E], 0, [Ep, 1])     # Wl, and its gradient
-        self.pk.pack(self.lin_piece, self.Wl)
-        self.pk.pack(self.lin_piece.at(0, [1, self.nlin_p]), self.WlT)
-        self.dlin = Mat.new(ws, "bn.dlin", B, Ne, self.nlin_p, F3)
-        if bn in ("vqvae-ema", "vqvae"):
-            K = hps.bn_vq_n_embed
-            self.K = K
-            self.code = Mat.new(ws, "bn.zq", B, Ne, self.dp, F3)
-            self.ind = ws.alloc("bn.ind", self.Q, torch.int64)
-            self.min_dist = ws.alloc("bn.min_dist", self.Q, torch.float32)
-            if bn == "vqvae-ema":
-                self.emb = ws.alloc("bn.emb", K * d, torch.float32)[:K * d].view(K, d)
-                self.ema_numer = ws.alloc("bn.ema_numer", K * d, torch.float32)[:K * d].view(K, d)
-                self.ema_denom = ws.alloc("bn.ema_denom", K, torch.float32)[:K]
-                # one buffer so that the data-parallel exchange of the EMA statistics is ONE all-reduce
-                self.zn_sum = ws.alloc("bn.zn_sum", K * d + K, torch.float32)[:K * d + K]
-                self.z_sum = self.zn_sum[:K * d].view(K, d)
-                self.n_sum = self.zn_sum[K * d:]
-                self.ind_hist = ws.alloc("bn.ind_hist", K, torch.float32)[:K]
-            else:
-                self.emb = self.ps.view("bottleneck.emb")
-        elif bn == "vae":
-            self.code = Mat.new(ws, "bn.sample", B, Ne, self.dp, F3)
-            self.eps = ws.alloc("bn.eps", self.Q * d, torch.float32)[:self.Q * d].view(B, Ne, d)
-            self.kl_terms = ws.alloc("bn.kl_terms", self.Q, torch.float32)
-            self.anneal_weight = 0.0
-            self.dp_world = 1                                                # set by dp.DataParallel (see set_anneal_weight)
-            self.anneal_buf = ws.alloc("bn.anneal", 4, torch.float32)[:1]   # read by the loss op
-            self.anneal_bwd = ws.alloc("bn.anneal_bwd", 4, torch.float32)[:1]   # read by the KL-gradient op
-        elif bn == "ae":
-            self.code = self.lin
-            self.norm_terms = ws.alloc("bn.norm_terms", self.Q, torch.float32)
-            bt = ws.alloc("bn.wp.bias", self.nlin_p, torch.float32)
-            self.pack_tbl.add(self.ps.ptr("bottleneck.linear.bias"), bt.data_ptr(), [d], [1], [1], F3, F3)
-            self.lin_bias = bt
-        else:
-            raise ValueError(f"unknown bn_type {bn}")
-
+    # plan construction: _build runs the stages below in the order of the workspace allocations they make (device
+    # addresses; pinned with every op they emit by tests/data/plan_parent.json)
     # --------------------------------------------------------------------------------------
     def _build(self):
-        ws, hps, B, g, ps, impl = self.ws, self.hps, self.B, self.geom, self.ps, self.impl
-        bn = self.bn_type
-        w = self.n_win
-        n_pos = B * (w - 1)
-        # ===== forward, part A: pack, inputs, encoder, bottleneck up to the EMA statistics
-        self.fwd_a = fa = Plan("fwd_a")
-        self.fwd_b = fb = Plan("fwd_b")
-        pack_slot = len(fa.ops)
+        B, w = self.B, self.n_win
+        self.fwd_a, self.fwd_b, self.bwd = Plan("fwd_a"), Plan("fwd_b"), Plan("bwd")
+        nll = (self.dec.nll.data_ptr(), B * w, 1.0 / (B * (w - 1)) if MEAN_LOSS[self.bn_type] else 1.0)   # the loss's NLL term
+        chain_kw = self._chain_args()
+        self._build_forward_a()
+        self._build_forward_b(nll, chain_kw)
+        self._build_backward(nll[2], chain_kw)
+        self._split_small()
+        dec_packed = self._place_decoder_pack()
+        self._cut_plans()
+        if self.bn is not None:
+            self.bn.build_codebook()
+        self._place_packs(dec_packed)
+        self._build_optimizer()
+        self._declare_lazy()
+
+    def _chain_args(self) -> dict:
+        """Stages per chained launch of the forward / backward as applied (nt_chain_used / nt_chain_bwd_used) and the
+        keywords every insert_nt_chains call of this engine shares."""
+        # AEW_NT_CHAIN = "f" or "f,b": stages per chained launch of the forward / backward (A/B and bisecting aid)
+        env = os.environ.get("AEW_NT_CHAIN")
+        n_f, n_b = int(self.nt_chain), int(self.nt_chain_bwd)
+        if env is not None and env.strip():
+            try:
+                v = [int(x) for x in env.split(",") if x.strip()]
+            except ValueError:
+                raise ValueError(f"AEW_NT_CHAIN={env!r}: expected 'f' or 'f,b' (stages per chained launch, forward / backward)")
+            if v:
+                n_f, n_b = v[0], (v[1] if len(v) > 1 else 0)
+        self.nt_chain_used = n_f if self.impl == 0 else 0
+        self.nt_chain_bwd_used = n_b if self.impl == 0 else 0
+        return dict(force=bool(self.nt_chain_force), flags=int(self.nt_chain_flags), max_stage_tiles=int(self.nt_chain_max_stage_tiles),
+                    sticky_ptr=self.chain_guard.data_ptr(), tuning=self.tuning, spin_max=int(self.nt_chain_spin_max))
+
+    def _build_forward_a(self):
+        """fwd_a: inputs, encoder, bottleneck up to the EMA statistics (the weight packs go in front: _place_packs)."""
+        fa = self.fwd_a
         self.in_tbl.emit(fa, "mel->channels-last")
         if self.enc is not None:
             self.enc.build_forward(fa, join_before_layer1=("lane", self.PACK_LANE) if self.pack_first is not None else False)
-            E, Ep = hps.enc_n_out, ru(hps.enc_n_out, 64)
-            y9 = self.enc.y[9]
-            flags = L.EF_BIAS if bn == "ae" else 0
-            skw = exact_split_args(ws, "bn.ks", EncoderPlan.k_split if impl == 0 else 0, E, Ep, g.embed_len * B, self.nlin_p)
-            fa.add(L.OP_GEMM_NT, make_nt(F3, g.embed_len, ru(self.nlin, 4), self.nlin_p, B, [y9.seg(Ep)],
-                                         self.Wl.ptr, flags=flags, out0=self.lin.view(),
-                                         bias_ptr=self.lin_bias.data_ptr() if bn == "ae" else 0, impl=impl, **skw),
-                   "bn.linear", TAG_VQ)
-            if bn in ("vqvae-ema", "vqvae"):
-                vq = L.VqNearest()
-                vq.ze, vq.emb = self.lin.ptr, self.emb.data_ptr()
-                vq.Q, vq.K, vq.d, vq.d_pitch = self.Q, self.K, self.d, self.nlin_p
-                vq.metric = 0 if bn == "vqvae-ema" else 1
-                vq.ind, vq.dist, vq.zq = self.ind.data_ptr(), self.min_dist.data_ptr(), self.code.ptr
-                vq.n_split = max(1, min(16, self.K // 256))       # each block scans >= 256 codes (one per thread)
-                if vq.n_split > 1:
-                    vq.scratch = ws.alloc("bn.vq_part", 2 * self.Q * vq.n_split, torch.float32).data_ptr()
-                assert self.dp == self.nlin_p
-                fa.add(L.OP_VQ_NEAREST, vq, "vq.nearest", TAG_VQ)
-                if bn == "vqvae-ema":
-                    st = L.VqStats()
-                    st.ze, st.ind = self.lin.ptr, self.ind.data_ptr()
-                    st.Q, st.K, st.d, st.d_pitch = self.Q, self.K, self.d, self.nlin_p
-                    st.z_sum, st.n_sum, st.hist = self.z_sum.data_ptr(), self.n_sum.data_ptr(), self.ind_hist.data_ptr()
-                    fa.add(L.OP_VQ_STATS, st, "vq.stats", TAG_VQ)
-                    # the diagnostics op (side lane of fwd_b) reads this step's LOCAL code counts; a data-parallel
-                    # caller all-reduces zn_sum in place while fwd_b runs, so it gets its own copy
-                    self.n_sum_diag = ws.alloc("bn.n_sum_diag", self.K, torch.float32)
-                    ntbl = CopyTableBuilder(ws, "tbl.nsum")
-                    ntbl.add(self.n_sum.data_ptr(), self.n_sum_diag.data_ptr(), [self.K], [1], [1], F3, F3)
-                    ntbl.emit(fa, "n_sum -> diagnostics copy")
-                    em = L.VqEma()
-                    em.numer, em.denom = self.ema_numer.data_ptr(), self.ema_denom.data_ptr()
-                    em.z_sum, em.n_sum, em.emb = self.z_sum.data_ptr(), self.n_sum.data_ptr(), self.emb.data_ptr()
-                    em.K, em.d, em.update_codebook = self.K, self.d, 0
-                    em.gamma = float(hps.bn_vq_ema_gamma)
-                    em.gamma_comp = float(1.0 - hps.bn_vq_ema_gamma)
-                    em.guard = self.chain_guard.data_ptr()
-                    # EMA runs at the START of part B (after the optional cross-rank sum); the
-                    # codebook refresh is deferred to after backward so that forward and backward
-                    # of one step see the same emb
-                    with fb.side(3):                           # nothing in the forward / backward reads the accumulators
-                        fb.add(L.OP_VQ_EMA, em, "vq.ema", TAG_VQ)
-            elif bn == "vae":
-                va = self._vae_op(False)
-                fa.add(L.OP_VAE, va, "vae.sample", TAG_VQ)
-            elif bn == "ae":
-                an = self._ae_norm_op(False)
-                fa.add(L.OP_AE_NORM, an, "ae.norm", TAG_VQ)
-        # ===== forward, part B: decoder + loss
-        if not self.merge_packs:
-            with fb.side(self.LANE_PACK_LATE):                 # only the backward reads these: hidden under the decoder
-                self.pack_late.emit(fb, "pack weights (backward layouts)")
-            for op in fb.ops[-1:] if self.pack_late.recs else []:
-                op.tag = TAG_PACK
-        # Per-step diagnostics (what the reference's loss modules report, vqema_bn.py:251-264, chassis.py:266-270) are
-        # side-lane ops placed where their inputs become final, not after the plan's last op (a side op starts after
-        # every main-lane op that precedes it in the plan: appended at the end they were ~0.09 ms of exposed tail):
-        #   codebook / encoder-output statistics  right here, under the whole decoder forward
-        #   peak log-probability statistics       after the logits GEMM, under the softmax
-        #   rec / tprb_m / com                    after the softmax, under the loss reduction
+            self.bn.build_forward(fa, self.fwd_b)
+
+    def _build_diagnostics(self):
+        """Per-step diagnostics (what the reference's loss modules report, vqema_bn.py:251-264, chassis.py:266-270): side-lane
+        ops placed where their inputs become final, not after the plan's last op (a side op starts after every main-lane
+        op that precedes it in the plan: appended at the end they were ~0.09 ms of exposed tail):
+          codebook / encoder-output statistics  right here, under the whole decoder forward
+          peak log-probability statistics       after the logits GEMM, under the softmax
+          rec / tprb_m / com                    after the softmax, under the loss reduction
+        Returns the two hooks (after_logits, after_nll) that place the latter two."""
+        ws, hps, B, w, fb = self.ws, self.hps, self.B, self.n_win, self.fwd_b
         n_pos_m = B * (w - 1)
         self.diag = ws.alloc("diag.out", 16, torch.float32)              # [0..5] (vqema_bn.py:254-260)
         self.diag_pk = ws.alloc("diag.peak", 16, torch.float32)          # [6..8] (vqema_bn.py:261-263)
         self.diag_scratch = ws.alloc("scratch.diag", 512, torch.float32)
         self.diag_scratch_pk = ws.alloc("scratch.diag_pk", 512, torch.float32)   # (the two diagnostics ops may overlap on lanes)
         self.met_buf = ws.alloc("diag.metrics", 8, torch.float32)        # [1] rec, [2] tprb_m, [3] com
-        if bn in ("vqvae-ema", "vqvae"):
-            dv = L.VqDiag()
-            dv.ze, dv.Q, dv.d, dv.d_pitch = self.lin.ptr, self.Q, hps.bn_n_out, self.lin.pitch
-            dv.K = hps.bn_vq_n_embed
-            dv.emb = self.emb.data_ptr() if bn == "vqvae-ema" else ps.ptr("bottleneck.emb")
-            if bn == "vqvae-ema":
-                dv.hist, dv.n_sum = self.ind_hist.data_ptr(), self.n_sum_diag.data_ptr()
-            dv.B, dv.w, dv.n_quant = B, w, hps.n_quant
-            dv.scratch, dv.out = self.diag_scratch.data_ptr(), self.diag.data_ptr()
-            with fb.side(self.DIAG_LANE):                       # not lane 1: decoder layer 0 waits for that one
-                fb.add(L.OP_VQ_DIAG, dv, "diagnostics (codebook)", TAG_LOSS)
-
+        if self.bn is not None:
+            self.bn.build_diag(fb, self.DIAG_LANE, w, self.diag_scratch, self.diag)   # not lane 1: decoder layer 0 waits for that one
         # peak statistics of the predicted distribution (vqema_bn.py:261-263).  With the reference's 256 classes the
         # softmax kernel has each row in registers and writes the per-position peak log-probability / arg-max next to the
         # nll; the diagnostics op then reduces 2 x 160 KB instead of reading the 41 MB of logits a second time
@@ -351,76 +273,44 @@ class TrainEngine:
         def after_nll(plan):
             if fused_peak:
                 peak_diag(plan)
-            met = L.Reduce()
             mterms = [(self.dec.nll.data_ptr(), B * w, 1.0 / n_pos_m), (self.dec.ptgt.data_ptr(), B * w, 1.0 / n_pos_m)]
-            if bn in ("vqvae-ema", "vqvae"):
-                mterms.append((self.min_dist.data_ptr(), self.Q, float(hps.bn_vq_gamma) / self.Q))
-            met.n_terms = len(mterms)
-            for i, (p_, n_, s_) in enumerate(mterms):
-                met.x[i], met.n[i], met.scale[i], met.post_scale[i] = p_, n_, s_, 1.0
-            met.out = self.met_buf.data_ptr()
+            if self.bn is not None:
+                mterms += self.bn.metric_terms()
             with plan.side(1):
-                plan.add(L.OP_REDUCE, met, "metrics", TAG_LOSS)
+                plan.add(L.OP_REDUCE, reduce_op(mterms, self.met_buf.data_ptr()), "metrics", TAG_LOSS)
+        return after_logits, after_nll
 
+    def _build_forward_b(self, nll, chain_kw: dict):
+        """fwd_b (behind the bottleneck's vq.ema): backward-layout weight pack, diagnostics, decoder, chained launches, loss."""
+        fb = self.fwd_b
+        if not self.merge_packs:
+            late = Plan("pack_late")
+            with late.side(self.LANE_PACK_LATE):               # only the backward reads these: hidden under the decoder
+                self.pack_late.emit(late, "pack weights (backward layouts)")
+            fb.splice(len(fb.ops), late, TAG_PACK)
+        hooks = self._build_diagnostics()
         if self.diag_early:
-            self.dec.build_forward(fb, after_logits=after_logits, after_nll=after_nll)
+            self.dec.build_forward(fb, after_logits=hooks[0], after_nll=hooks[1])
         else:                                                  # A/B: all of them after the plan's last main-lane op
             self.dec.build_forward(fb)
-            self._diag_tail = (after_logits, after_nll)
-        # AEW_NT_CHAIN = "f" or "f,b": stages per chained launch of the forward / backward (A/B and bisecting aid)
-        env = os.environ.get("AEW_NT_CHAIN")
-        n_f, n_b = int(self.nt_chain), int(self.nt_chain_bwd)
-        if env is not None and env.strip():
-            try:
-                v = [int(x) for x in env.split(",") if x.strip()]
-            except ValueError:
-                raise ValueError(f"AEW_NT_CHAIN={env!r}: expected 'f' or 'f,b' (stages per chained launch, forward / backward)")
-            if v:
-                n_f, n_b = v[0], (v[1] if len(v) > 1 else 0)
-        self.nt_chain_used = n_f if impl == 0 else 0
-        self.nt_chain_bwd_used = n_b if impl == 0 else 0
-        ckw = dict(force=bool(self.nt_chain_force), flags=int(self.nt_chain_flags), max_stage_tiles=int(self.nt_chain_max_stage_tiles),
-                   sticky_ptr=self.chain_guard.data_ptr(), tuning=self.tuning, spin_max=int(self.nt_chain_spin_max))
         if self.nt_chain_used >= 2:
-            insert_nt_chains(fb, ws, "chain.fwd", lambda lab: lab.startswith(("G1.", "G2.", "post1", "post2")), max_len=self.nt_chain_used, **ckw)
-        red = L.Reduce()
-        nll_ptr = self.dec.nll.data_ptr()
-        terms = []
-        if bn in ("none",):
-            terms = [(nll_ptr, B * w, 1.0 / n_pos)]
-        elif bn == "vqvae-ema":
-            com = (self.min_dist.data_ptr(), self.Q, float(hps.bn_vq_gamma))
-            terms = [com] if self.loss_mode == "head" else [(nll_ptr, B * w, 1.0), com]
-        elif bn == "vqvae":
-            terms = [(nll_ptr, B * w, 1.0), (self.min_dist.data_ptr(), self.Q, 1.0 + float(hps.bn_vq_gamma))]
-        elif bn == "vae":
-            terms = [(nll_ptr, B * w, 1.0 / n_pos), (self.kl_terms.data_ptr(), self.Q, -0.5)]
-        elif bn == "ae":
-            terms = [(nll_ptr, B * w, 1.0 / n_pos), (self.norm_terms.data_ptr(), self.Q, 0.001 / self.Q)]
-        red.n_terms = len(terms)
-        for i, (p_, n_, s_) in enumerate(terms):
-            red.x[i], red.n[i], red.scale[i] = p_, n_, s_
-            red.post_scale[i] = 1.0
-        if bn == "vae":
-            red.clamp[1], red.clamp_min[1], red.post_scale[1] = 1, float(hps.bn_free_nats), 0.0
-            red.post_scale_dev[1] = self.anneal_buf.data_ptr()
-            self._red_index = len(fb.ops)
-        red.out = self.loss_buf.data_ptr()
+            insert_nt_chains(fb, self.ws, "chain.fwd", lambda lab: lab.startswith(("G1.", "G2.", "post1", "post2")),
+                             max_len=self.nt_chain_used, **chain_kw)
+        red = self.bn.loss_op(nll) if self.bn is not None else reduce_op([nll], self.loss_buf.data_ptr())
         fb.add(L.OP_REDUCE, red, "loss", TAG_LOSS)
-        for hook in getattr(self, "_diag_tail", ()):
+        for hook in () if self.diag_early else hooks:
             hook(fb)
-        # ===== backward
-        self.bwd = bw = Plan("bwd")
+
+    def _build_backward(self, scale: float, chain_kw: dict):
+        """bwd: decoder, bottleneck, encoder, the gradient unpacks and statistics.  scale: the loss's mean / sum factor."""
+        ws, hps, B, bw = self.ws, self.hps, self.B, self.bwd
         bw.zero(ws, "grads")
-        mean = MEAN_LOSS[bn]
-        nll_scale = (1.0 / n_pos) if mean else 1.0
-        if bn == "vqvae-ema" and self.loss_mode == "head":
-            nll_scale = 0.0
+        nll_scale = self.bn.nll_scale(scale) if self.bn is not None else scale
         self.dec.build_backward(bw, nll_scale, early_tbl=CopyTableBuilder(ws, "tbl.unpack_dec_early"))
         if self.nt_chain_bwd_used >= 2:
             heads = ("d.post2", "d.post1")[int(self.nt_chain_bwd_phase):]    # (phase 1: pairs are (dx.l, dz.l-1), not (dz.l, dx.l))
             insert_nt_chains(bw, ws, "chain.bwd", lambda lab: lab.startswith(heads + ("dz.", "dx.")),
-                             max_len=self.nt_chain_bwd_used, **ckw)
+                             max_len=self.nt_chain_bwd_used, **chain_kw)
         # gradient statistics of run() (autoencoder_model.py:252-257 mel_grad_sd / bn_grad_sd; mfcc_inverter.py:100-106
         # mel_grad_sd / mel_grad_mean): by-products of this backward, reduced on a side lane as soon as their input is
         # final (d(loss)/d(code) here, under the encoder backward)
@@ -435,80 +325,50 @@ class TrainEngine:
         with bw.side(self.dec.tail_lane_used or 1):                 # after every decoder wgrad on any side lane
             self.unpack_dec.emit(bw, "unpack grads (decoder)", join=True)
         if self.enc is not None:
-            moments(self.dec.dlc_src, hps.bn_n_out, 4, "bn")
-        if self.enc is not None:
             dcode = self.dec.dlc_src                      # d(loss)/d(code) [B][Ne][dp]
-            Ep = ru(hps.enc_n_out, 64)
-            y9 = self.enc.y[9]
-            if bn in ("vqvae-ema", "vqvae"):
-                vb = L.VqBwd()
-                vb.ze, vb.emb, vb.ind, vb.dzq = self.lin.ptr, self.emb.data_ptr(), self.ind.data_ptr(), dcode.ptr
-                vb.Q, vb.d, vb.d_pitch = self.Q, self.d, self.nlin_p
-                vb.metric = 0 if bn == "vqvae-ema" else 1
-                vb.coef = float(hps.bn_vq_gamma)
-                vb.demb_coef = 1.0
-                vb.dze = self.dlin.ptr
-                vb.demb = ps.ptr("bottleneck.emb", True) if bn == "vqvae" else None
-                vb.gmul = self.gmul.data_ptr()
-                bw.add(L.OP_VQ_BWD, vb, "vq.bwd", TAG_VQ)
-            elif bn == "vae":
-                self._vae_bwd_index = len(bw.ops)
-                bw.add(L.OP_VAE, self._vae_op(True, dcode), "vae.bwd", TAG_VQ)
-            elif bn == "ae":
-                bw.add(L.OP_AE_NORM, self._ae_norm_op(True, dcode), "ae.norm.bwd", TAG_VQ)
-                cs = colsum_op(ws, self.dlin.seg(64), F3, g.embed_len, self.d, B, ps.ptr("bottleneck.linear.bias", True), 0, "det.db.bn")
-                with bw.side():
-                    bw.add(L.OP_COLSUM, cs, "db.bn", TAG_VQ)
-            # linear wgrad / dgrad
-            t = make_tn(F3, g.embed_len, B, self.nlin, self.nlin_p, self.dlin.seg(64), [y9.seg(Ep)], impl=impl)
-            wg = wgrad_slab(ws, "bn.wg.lin", t, L.tn_slabs(t), self.unpack_tbl)
-            with bw.side():
-                bw.add(L.OP_GEMM_TN, t, "wgrad.bn.linear", TAG_VQ)
-            self.pk.unpack([self.lin_piece], wg)
-            bw.add(L.OP_GEMM_NT, make_nt(F3, g.embed_len, hps.enc_n_out, Ep, B, [self.dlin.seg(self.nlin_p)],
-                                         self.WlT.ptr, flags=L.EF_OUT1_POS1, out0=self.enc.dy[9].view(),
-                                         out1=self.enc.dpre[9].view(), aux1=self.enc.r[9].view(), impl=impl),
-                   "d.bn.linear", TAG_VQ)
+            moments(dcode, hps.bn_n_out, 4, "bn")
+            self.bn.build_backward(bw, dcode)
             self.enc.build_backward(bw, need_input_grad=True)
         # (mel gradient statistics: its input is the last thing the backward writes)
         moments(self.enc.dy[0] if self.enc is not None else self.dec.dlc_src, self.n_mel, 0, "mel")
         self.unpack_tbl.emit(bw, "unpack grads", join=True)        # reads the side-lane encoder wgrad slabs
-        # launches of a few dozen 64 x 64 blocks (the upsampler / encoder data gradients): split-K hint
+
+    def _split_small(self):
+        """Launches of a few dozen 64 x 64 blocks (the upsampler / encoder data gradients): split-K hint."""
         self.small_split_made = []
-        if int(self.small_split) > 0 and impl == 0:
-            for pl in (fa, fb, bw):
-                self.small_split_made += split_small_nt(pl, ws, "ks." + pl.name, int(self.small_split))
-        # Deferred EMA (data parallel): the EMA accumulators are not read again before the codebook
-        # refresh, so the cross-rank sum of z_sum | n_sum can run asynchronously under the whole
-        # decoder forward + backward; fwd_b_noema / ema_plan are fwd_b without / only its leading vq.ema op
-        # The decoder's weight layouts are packed at the head of fwd_b (behind vq.ema), not of fwd_a: nothing in fwd_a
-        # reads a decoder parameter, so a data-parallel caller lets the all-gather of the updated decoder shards run
-        # under the encoder forward and waits for it only between the two plans (forward(before_decoder=...)).  Serial
-        # plans: the same launches in the same total time.
-        if self.pack_dec_late and not self.merge_packs and self.pack_dec.recs:
-            pkd = Plan("pack_dec")
-            with pkd.side(self.LANE_PACK_DEC):
-                self.pack_dec.emit(pkd, "pack weights (decoder)")
-            at = 1 if (fb.labels and fb.labels[0] == "vq.ema") else 0
-            for op in pkd.ops:
-                op.tag = TAG_PACK
-            fb.ops[at:at] = pkd.ops
-            fb.labels[at:at] = pkd.labels
-            fb.keep += pkd.keep
-            self._pack_dec_emitted = True
+        if int(self.small_split) > 0 and self.impl == 0:
+            for pl in (self.fwd_a, self.fwd_b, self.bwd):
+                self.small_split_made += split_small_nt(pl, self.ws, "ks." + pl.name, int(self.small_split))
+
+    def _place_decoder_pack(self) -> bool:
+        """The decoder's weight layouts are packed at the head of fwd_b (behind vq.ema), not of fwd_a: nothing in fwd_a
+        reads a decoder parameter, so a data-parallel caller lets the all-gather of the updated decoder shards run
+        under the encoder forward and waits for it only between the two plans (forward(before_decoder=...)).  Serial
+        plans: the same launches in the same total time.  Returns whether the pack was placed here."""
+        fb = self.fwd_b
+        if not (self.pack_dec_late and not self.merge_packs and self.pack_dec.recs):
+            return False
+        pkd = Plan("pack_dec")
+        with pkd.side(self.LANE_PACK_DEC):
+            self.pack_dec.emit(pkd, "pack weights (decoder)")
+        fb.splice(1 if (fb.labels and fb.labels[0] == "vq.ema") else 0, pkd, TAG_PACK)
+        return True
+
+    def _cut_plans(self):
+        """The cuts of fwd_b and bwd a data-parallel caller runs in their place (the same op records: _sub_plan)."""
+        fb, bw, ps = self.fwd_b, self.bwd, self.ps
+        span = lambda a, b: (lambda i, lab: a <= i < b)
+        # Deferred EMA: the EMA accumulators are not read again before the codebook refresh, so the cross-rank sum of
+        # z_sum | n_sum can run asynchronously under the whole decoder forward + backward; fwd_b_noema / ema_plan are
+        # fwd_b without / only its leading vq.ema op
         self.fwd_b_noema, self.ema_plan = None, None
         if fb.labels and fb.labels[0] == "vq.ema":
-            self.fwd_b_noema, self.ema_plan = Plan("fwd_b_noema"), Plan("ema")
-            self.fwd_b_noema.ops, self.fwd_b_noema.labels = fb.ops[1:], fb.labels[1:]
-            self.ema_plan.ops, self.ema_plan.labels = fb.ops[:1], fb.labels[:1]
-        self._ema_work = None
+            self.fwd_b_noema, self.ema_plan = self._sub_plan("fwd_b_noema", fb, span(1, len(fb.ops))), self._sub_plan("ema", fb, span(0, 1))
         # The same ops as two plans, cut after the decoder's gradients are final: lets a data-parallel
         # caller start reducing the decoder gradients (the contiguous tail of the flat buffer) while the
         # bottleneck / encoder backward still runs (dp.DataParallel.backward_allreduce)
         cut = bw.labels.index("unpack grads (decoder)") + 1 if "unpack grads (decoder)" in bw.labels else len(bw.ops)
-        self.bwd_a, self.bwd_b = Plan("bwd_a"), Plan("bwd_b")
-        self.bwd_a.ops, self.bwd_a.labels = bw.ops[:cut], bw.labels[:cut]
-        self.bwd_b.ops, self.bwd_b.labels = bw.ops[cut:], bw.labels[cut:]
+        self.bwd_a, self.bwd_b = self._sub_plan("bwd_a", bw, span(0, cut)), self._sub_plan("bwd_b", bw, span(cut, len(bw.ops)))
         # ... and, with the stack's weight gradients as two grouped launches (wgrad_group < layers, e.g. AEW_WGRAD_GROUP=10),
         # bwd_a itself in two: after bwd_a1 every gradient from layer `hi_first_layer` up (+ the post network: the tail of
         # the flat buffer from dec_hi_offset) is final, so that exchange starts under the second half of the chain
@@ -518,9 +378,7 @@ class TrainEngine:
         lab_hi = "unpack grads (decoder, upper layers)"
         if hi is not None and lab_hi in bw.labels[:cut]:
             c1 = bw.labels.index(lab_hi) + 1
-            self.bwd_a1, self.bwd_a2 = Plan("bwd_a1"), Plan("bwd_a2")
-            self.bwd_a1.ops, self.bwd_a1.labels = bw.ops[:c1], bw.labels[:c1]
-            self.bwd_a2.ops, self.bwd_a2.labels = bw.ops[c1:cut], bw.labels[c1:cut]
+            self.bwd_a1, self.bwd_a2 = self._sub_plan("bwd_a1", bw, span(0, c1)), self._sub_plan("bwd_a2", bw, span(c1, cut))
             self.dec_hi_offset = min(ps.off[n] for n in ps.names() if n.startswith(self.dec.pre + f"conv_layers.{hi}."))
             later = [n for n in ps.names() if ps.off[n] >= self.dec_hi_offset]
             assert all(n.startswith(self.dec.pre + "post") or
@@ -530,44 +388,32 @@ class TrainEngine:
         self.dec_grad_offset = min(ps.off[n] for n in dec_names)
         assert all(ps.off[n] >= self.dec_grad_offset for n in dec_names) and \
             all(ps.off[n] < self.dec_grad_offset for n in ps.names() if n not in dec_names), "decoder params form the tail"
-        if bn == "vqvae-ema":
-            # deferred codebook refresh (vqema_bn.py:216-222)
-            self.cb = Plan("codebook")
-            em = L.VqEma()
-            em.numer, em.denom = self.ema_numer.data_ptr(), self.ema_denom.data_ptr()
-            z0 = ws.alloc("bn.zero_k", self.K * self.d, torch.float32)
-            em.z_sum, em.n_sum, em.emb = z0.data_ptr(), z0.data_ptr(), self.emb.data_ptr()
-            em.K, em.d, em.update_codebook = self.K, self.d, 1
-            em.gamma, em.gamma_comp = 1.0, 0.0     # numer/denom unchanged: emb = numer/denom
-            em.guard = self.chain_guard.data_ptr()
-            self.cb.add(L.OP_VQ_EMA, em, "vq.codebook", TAG_VQ)
-        # pack goes first in fwd_a (its table is complete only now)
+
+    def _place_packs(self, dec_packed: bool):
+        """The weight-layout packs go first in fwd_a (their tables are complete only now)."""
         pk_plan = Plan("pack")
         if self.merge_packs:
             # every weight layout of the step in ONE table launch at the head of fwd_a (serial plans: three launches fewer)
-            allp = CopyTableBuilder(ws, "tbl.pack_all")
+            allp = CopyTableBuilder(self.ws, "tbl.pack_all")
             for tb in (self.pack_first, self.pack_tbl, self.pack_dec, self.pack_late):
                 if tb is not None:
                     allp.recs.extend(tb.recs)
             allp.emit(pk_plan, "pack weights (all layouts)")
-        elif self.pack_first is not None and self.pack_first.recs:
-            if not getattr(self, "_pack_dec_emitted", False):
-                with pk_plan.side(self.LANE_PACK_DEC):         # joined by the end of fwd_a
-                    self.pack_dec.emit(pk_plan, "pack weights (decoder)")
-            self.pack_first.emit(pk_plan, "pack weights (encoder layer 0)")
-            with pk_plan.side(self.PACK_LANE):
-                self.pack_tbl.emit(pk_plan, "pack weights")
         else:
-            if not getattr(self, "_pack_dec_emitted", False):
+            if not dec_packed:
                 with pk_plan.side(self.LANE_PACK_DEC):         # joined by the end of fwd_a
                     self.pack_dec.emit(pk_plan, "pack weights (decoder)")
-            self.pack_tbl.emit(pk_plan, "pack weights")
-        fa.ops[pack_slot:pack_slot] = pk_plan.ops
-        fa.labels[pack_slot:pack_slot] = pk_plan.labels
-        for op in pk_plan.ops:
-            op.tag = TAG_PACK
-        fa.keep += pk_plan.keep
-        # ===== optimizer
+            if self.pack_first is not None and self.pack_first.recs:
+                self.pack_first.emit(pk_plan, "pack weights (encoder layer 0)")
+                with pk_plan.side(self.PACK_LANE):
+                    self.pack_tbl.emit(pk_plan, "pack weights")
+            else:
+                self.pack_tbl.emit(pk_plan, "pack weights")
+        self.fwd_a.splice(0, pk_plan, TAG_PACK)
+
+    def _build_optimizer(self):
+        """opt, clip and ratio: one op each, re-addressed per call by adam_step / grad_norm_step / ratio_step."""
+        ws, ps = self.ws, self.ps
         self.opt = Plan("adam")
         self.adam_m = ws.alloc("adam.m", ps.numel, torch.float32)
         self.adam_v = ws.alloc("adam.v", ps.numel, torch.float32)
@@ -612,6 +458,10 @@ class TrainEngine:
         ur.part, ur.first, ur.n_tensors, ur.finalize = self.uw_part.data_ptr(), self.uw_first.data_ptr(), P, 1
         ur.sums, ur.out = self.uw_sums.data_ptr(), self.uw_out.data_ptr()
         self.ratio.add(L.OP_UPDATE_RATIO, ur, "update ratio", TAG_ADAM)
+
+    def _declare_lazy(self):
+        """The state that later methods complete at its first use: declared here, empty."""
+        self._ema_work = None             # a deferred EMA exchange in flight (forward / finish_ema)
         # ===== averaged (EMA) weights (aew_adam_t.avg: updated only when adam_step() is given avg_rate) and the swap
         # that puts them in the parameters' place for sampling / evaluation
         self.adam_avg = None              # flat like adam_m / adam_v; allocated by the first use (_avg_buffer): an engine that
@@ -631,6 +481,9 @@ class TrainEngine:
         self.act_epoch = 0                # bumped by everything that overwrites the activations a backward reads
         self.eval_a = self.eval_b = self.eval_fin = None      # the forward plans minus EVAL_DROP (+ loss, accumulate); finalize
         self.eval_acc = self.eval_hist = self.eval_out = self.eval_loss = None
+        # ===== the encode / conditioning sub-plans (encode(), conditioning()) and the chained launches' host-side watch
+        self._encode_plan = self._cond_plan = self._cond_plan_a = None
+        self._chain_flag_views = self._chain_host = None
 
     # ops of the training forward that an evaluation leaves out: they write what the next training step (or the caller,
     # through objective.metrics) reads - the EMA statistics and accumulators, the index histogram, the diagnostics, the
@@ -646,7 +499,7 @@ class TrainEngine:
         if self.eval_fin is not None:
             return self.eval_a, self.eval_b, self.eval_fin
         ws, fb = self.ws, self.fwd_b
-        K = getattr(self, "K", 0) if self.bn_type in ("vqvae-ema", "vqvae") else 0
+        K = self.bn.K if self.bn is not None else 0
         self.eval_acc = ws.alloc("eval.acc", L.EVAL_ACC_N, torch.float64)[:L.EVAL_ACC_N]
         self.eval_hist = ws.alloc("eval.hist", max(K, 1), torch.int32)[:max(K, 1)]     # (uint32 counts)
         self.eval_out = ws.alloc("eval.out", L.EVAL_OUT_N, torch.float32)[:L.EVAL_OUT_N]
@@ -675,32 +528,6 @@ class TrainEngine:
         self.eval_fin.add(L.OP_EVAL_ACC, fin, "eval.finalize", TAG_LOSS)
         return self.eval_a, self.eval_b, self.eval_fin
 
-    def _vae_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.Vae:
-        va = L.Vae()
-        va.lin, va.lin_pitch, va.eps = self.lin.ptr, self.nlin_p, self.eps.data_ptr()
-        va.Q, va.d, va.d_pitch = self.Q, self.d, self.dp
-        va.sample, va.kl_terms = self.code.ptr, self.kl_terms.data_ptr()
-        va.backward = int(backward)
-        if backward:
-            va.dsample = dcode.ptr
-            va.kl_coef = float(self.anneal_weight)
-            va.kl_coef_dev = self.anneal_bwd.data_ptr()
-            va.kl_value = self.loss_buf.data_ptr() + 4 * 2       # out[1 + term 1]
-            va.free_nats = float(self.hps.bn_free_nats)
-            va.dlin = self.dlin.ptr
-            va.gmul = self.gmul.data_ptr()
-        return va
-
-    def _ae_norm_op(self, backward: bool, dcode: Optional[Mat] = None) -> L.AeNorm:
-        an = L.AeNorm()
-        an.ze, an.Q, an.d, an.d_pitch = self.lin.ptr, self.Q, self.d, self.nlin_p
-        an.term = self.norm_terms.data_ptr()
-        an.backward = int(backward)
-        if backward:
-            an.dze_in, an.coef, an.dze = dcode.ptr, 0.001 / self.Q, self.dlin.ptr
-            an.gmul = self.gmul.data_ptr()
-        return an
-
     # --------------------------------------------------------------------------------------
     # execution
     # --------------------------------------------------------------------------------------
@@ -716,7 +543,7 @@ class TrainEngine:
         self.in_mel.copy_(mel)
         self.in_voice.copy_(voice)
         self.in_jitter.copy_(jitter[:, :g.embed_len])
-        if self.bn_type == "vae":
+        if self.bn is not None and self.bn.eps is not None:          # (vae: the noise of the sample)
             if eps is None:
                 self.eps.normal_()
             else:
@@ -727,10 +554,10 @@ class TrainEngine:
         (chassis.py:148-149), so the ops read it from device memory (`anneal_buf`): no descriptor is
         patched and no captured graph is invalidated."""
         self.anneal_weight = float(a)
-        self.anneal_buf.fill_(float(a))
+        self.bn.anneal_buf.fill_(float(a))
         # Data parallel (dp.DataParallel): the optimizer scales the SUMMED gradient by 1/world (mean-type NLL), but
         # the KL term is a sum over all windows of the global batch, so its gradient must not be divided: pre-multiply
-        self.anneal_bwd.fill_(float(a) * float(getattr(self, "dp_world", 1)))
+        self.bn.anneal_bwd.fill_(float(a) * float(self.dp_world))
 
     def _run(self, plan, timing=False):
         # self.tuning: an aew_tuning_t of this engine's own (None: the process-wide switches).  Note that plan
@@ -757,7 +584,7 @@ class TrainEngine:
     def encode(self):
         """Encoder + bottleneck.linear only (what autoencoder_model.py:171-199 runs to collect k-means samples):
         no nearest-code search, no EMA statistics, no index histogram update.  Result in `self.lin`."""
-        if getattr(self, "_encode_plan", None) is None:
+        if self._encode_plan is None:
             fa = self.fwd_a
             stop = fa.labels.index("bn.linear") + 1
             self._encode_plan = self._sub_plan("encode", fa, lambda i, lab: i < stop)
@@ -769,7 +596,7 @@ class TrainEngine:
         upsampler, speaker bias): what the autoregressive sampler needs (wavenet.py:379-391).  No EMA statistics
         or update, no index histogram update (vq.stats is skipped), no loss.
         Returns (cond bf16 [B][T][Cp], gated bias fp32 [B][NL][2*Dp])."""
-        if getattr(self, "_cond_plan", None) is None:
+        if self._cond_plan is None:
             fb = self.fwd_b
             stop = fb.labels.index("G1.0") if "G1.0" in fb.labels else next(
                 i for i, l in enumerate(fb.labels) if l.startswith("G1.0"))
@@ -784,7 +611,7 @@ class TrainEngine:
     # ---- chained launches: a hand-off wait that gave up must not pass silently --------------------------------------
     def _chain_flags(self):
         """[(label, 1-element int32 view of the launch's timeout flag)] over the engine's chained launches."""
-        if getattr(self, "_chain_flag_views", None) is None:
+        if self._chain_flag_views is None:
             v = []
             for pl in (self.fwd_b, self.bwd):
                 for lab, (stages, cd) in getattr(pl, "nt_chains", {}).items():
@@ -810,7 +637,7 @@ class TrainEngine:
           for any point where the caller synchronises anyway."""
         if not self._chain_flags() or self.device.type != "cuda":
             return
-        st = getattr(self, "_chain_host", None)
+        st = self._chain_host
         if st is None:
             n = self.CHAIN_WATCH_SLOTS
             st = self._chain_host = {"buf": torch.zeros(n, dtype=torch.int32).pin_memory(),
@@ -857,7 +684,7 @@ class TrainEngine:
     def clear_chain_guard(self):
         """Re-arm after a reported timeout: clears the sticky word and forgets the copies in flight."""
         self.chain_guard.zero_()
-        if getattr(self, "_chain_host", None) is not None:
+        if self._chain_host is not None:
             torch.cuda.synchronize(self.device)
             self._chain_host["pending"].clear()
             self._chain_host["buf"].zero_()
@@ -875,9 +702,9 @@ class TrainEngine:
         self.lin_live = True
         if before_decoder is not None:
             before_decoder()
-        if ema_allreduce is not None and self.bn_type == "vqvae-ema":
+        if ema_allreduce is not None and self.ema_plan is not None:
             work = ema_allreduce(self.z_sum, self.n_sum)
-            if work is not None and self.ema_plan is not None:
+            if work is not None:
                 self._ema_work = work
                 self._run(self.fwd_b_noema, timing)
                 if not timing:
@@ -953,7 +780,7 @@ class TrainEngine:
         if not timing and self.nt_chain_bwd_used >= 2:
             self._chain_watch("bwd")
         self.finish_ema(timing)
-        if self.bn_type == "vqvae-ema" and self.update_codebook_every_step:
+        if self.update_codebook_every_step and self.ema_plan is not None:     # (the codebook that follows the EMA statistics)
             self._run(self.cb, timing)
 
     def update_codebook(self):
@@ -962,19 +789,11 @@ class TrainEngine:
 
     def _restart_op(self) -> L.VqRestart:
         """The restart op, allocated with its two output buffers (and the `restart` plan completed) at its first use."""
-        if self.bn_type != "vqvae-ema":
+        if self.ema_plan is None:
             raise L.AewError(f"restarting codes needs the vqvae-ema bottleneck (this engine: {self.bn_type}): only its "
                              "codebook carries a usage statistic")
         if self.restart_buf is None:
-            self.restart_buf = self.ws.alloc("restart.out", 4, torch.int32)[:4]
-            self.restart_pairs_buf = self.ws.alloc("restart.pairs", 2 * L.VQ_RESTART_MAX, torch.int32)[:2 * L.VQ_RESTART_MAX] \
-                .view(L.VQ_RESTART_MAX, 2)
-            rs = L.VqRestart()
-            rs.ze, rs.Q, rs.d, rs.d_pitch = self.lin.ptr, self.Q, self.d, self.nlin_p
-            rs.emb, rs.numer, rs.denom = self.emb.data_ptr(), self.ema_numer.data_ptr(), self.ema_denom.data_ptr()
-            rs.K, rs.max_codes, rs.min_usage, rs.denom_init = self.K, 1, 0.0, 1.0
-            rs.out, rs.pairs = self.restart_buf.data_ptr(), self.restart_pairs_buf.data_ptr()
-            rs.guard = self.chain_guard.data_ptr()
+            self.restart_buf, self.restart_pairs_buf, rs = self.bn.restart_op()
             self.restart.add(L.OP_VQ_RESTART, rs, "vq.restart", TAG_VQ)
         return self.restart.array()[0].u.vqr
 
@@ -984,7 +803,7 @@ class TrainEngine:
         encoder outputs (bn.lin) chosen by the counter-based hash of (seed, call): ema_numer[k] = ze * denom_init,
         emb[k] = ema_numer[k] / denom_init, ema_denom[k] = denom_init.  A pending EMA accumulation is applied first (it
         would overwrite the restart); a raised chain_guard makes the launch a no-op.  Counts: restart_out()."""
-        if self.bn_type != "vqvae-ema":
+        if self.ema_plan is None:
             self._restart_op()                                          # raises: nothing is allocated for a refused call
         if not self.lin_live:
             raise L.AewError("restart_codes() before any forward on this engine: bn.lin holds no encoder output yet")

@@ -155,6 +155,14 @@ class Plan:
         self._arr = None
         return op
 
+    def splice(self, at: int, other: "Plan", tag: Optional[int] = None):
+        """Insert the ops of `other` in front of op `at`, with their labels and kept tables; tag: set on every one of them."""
+        for op in other.ops if tag is not None else ():
+            op.tag = tag
+        self.ops[at:at], self.labels[at:at] = other.ops, other.labels
+        self.keep += other.keep
+        self._arr = None
+
     def zero(self, ws: Workspace, name: str, label: Optional[str] = None):
         z = L.Zero()
         t = ws.get(name)

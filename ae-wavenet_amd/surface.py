@@ -667,19 +667,10 @@ class HipModelBase(nn.Module):
         self.tprb_m = mb[2]                                        # chassis.py:266-270
         dg, pk = eng.diag, eng.diag_pk                             # AEW_OP_VQ_DIAG ops of the forward plan (side lanes)
         m["pk_m"], m["pk_sd"], m["pk_nuq"] = pk[6], pk[7], pk[8]    # vqema_bn.py:261-263
-        if eng.bn_type in ("vqvae-ema", "vqvae"):
-            m["com"] = mb[3]
-            m["min_ze"], m["max_ze"], m["min_emb"], m["max_emb"] = dg[0], dg[1], dg[2], dg[3]   # vqema_bn.py:254-257
-            if eng.bn_type == "vqvae-ema":
-                m["hst_ent"], m["nunq"] = dg[4], dg[5]              # vqema_bn.py:258-260
-                if self._restart is not None:
-                    m["vq_restarted"] = eng.restart_out()[1]        # codes the last restart re-seeded
-            else:
-                m["nunq"] = eng.ind[:eng.Q].unique().numel()
-        elif eng.bn_type == "vae":
-            m["kl_div_loss"], m["log_pred_loss"] = eng.loss_buf[2], m["rec"]
-        elif eng.bn_type == "ae":
-            m["norm"] = eng.loss_buf[2]
+        if eng.bn is not None:                                      # the bottleneck type's own terms (engine.BottleneckPlan.metrics)
+            m.update(eng.bn.metrics(mb, dg, eng.loss_buf))
+        if self._restart is not None:
+            m["vq_restarted"] = eng.restart_out()[1]                # codes the last restart re-seeded
         if eng.enc is not None and hasattr(self, "encoder"):
             az = eng.enc.zero_cnt[:9].double() / self._az_numel(eng)   # one division; the entries are views
             for i in range(9):

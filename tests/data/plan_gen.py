@@ -11,6 +11,12 @@ several configurations are stored once, and a plan whose ops are a slice of anot
 bwd, fwd_b_noema / ema of fwd_b) as [plan, start, stop].  The weight-pack plans are spliced into fwd_a / fwd_b by the
 engine and are recorded there.
 
+The configurations of late_configs() also pin the plans that the optimizer stage of TrainEngine._build and the lazily
+completed state make (LATE_PLANS: opt, clip, ratio, swap, restart, the evaluation plans, the encode and conditioning sub-plans), as
+built at the commit BEFORE the plan builder was split into stages and BottleneckPlan: after the record above is taken,
+complete() finishes that state on the "cpu" engine (nothing runs), and the same canonical form goes under the keys
+"late" and "alloc_late" (the allocation list once more, with the buffers the completion added).
+
     python tests/data/plan_gen.py            # rewrites plan_parent.json - ONLY from the commit the recording pins
 
 tests/test_plan_parent_cpu.py rebuilds the engines and compares; on a mismatch it prints canon_op() of the first
@@ -36,6 +42,10 @@ MODELS = {"mi": ("mi_tiny_jitter.npz", "mfcc_inverter", 7), "vqvae-ema": ("ae_ti
           "vae": ("ae_tiny_vae_random.npz", "autoencoder", None), "ae": ("ae_tiny_ae_identity.npz", "autoencoder", None),
           "vqvae": ("ae_tiny_vqvae_identity.npz", "autoencoder", None)}
 PLANS = ("fwd_a", "fwd_b", "bwd", "bwd_a", "bwd_a1", "bwd_a2", "bwd_b", "cb", "fwd_b_noema", "ema_plan")
+# name in the recording -> attribute of the engine
+LATE_PLANS = {"opt": "opt", "clip": "clip", "ratio": "ratio", "swap": "swap", "restart": "restart", "eval_a": "eval_a",
+              "eval_b": "eval_b", "eval_fin": "eval_fin", "encode": "_encode_plan", "conditioning_a": "_cond_plan_a",
+              "conditioning": "_cond_plan"}
 FN_ALL = frozenset(("layer", "G1", "dx", "dz", "skip", "dcond", "post"))
 FOLD_ROWS = 4096                                                        # the library's default (aew_set_tn_fold_rows)
 
@@ -108,6 +118,10 @@ def applied(cfg):
             os.environ.pop(k, None)
             if v is not None:
                 os.environ[k] = v
+
+
+def late_configs():
+    return [n for n in configs() if n.startswith(("default.", "dp."))]
 
 
 def build(cfg):
@@ -200,13 +214,24 @@ def allocations(eng):
     return [[n, t.numel(), str(t.dtype)] for n, t in eng.ws.bufs.items()]
 
 
-def record(eng):
-    """(allocation digest, {plan: [[label, digest], ...] or [plan, start, stop]}) of an engine."""
+def complete(eng):
+    """Everything an engine builds at first use, without running a plan: the evaluation plans, the average and its swap
+    op, the restart op, the encode and the conditioning sub-plans."""
+    eng._run = lambda *a, **k: None
+    eng.eval_plans()
+    eng._avg_buffer()
+    if getattr(eng, "cb", None) is not None:                             # (vqvae-ema)
+        eng._restart_op()
+    if eng.enc is not None:
+        eng.encode()
+    eng.conditioning()
+
+
+def _lines(eng, names, plans, ops_of):
+    """plans[name] for the plans `names` (name -> attribute) of the engine; ops_of: the op ids of plans stored in full."""
     R = Resolver(eng.ws)
-    alloc = digest(allocations(eng))
-    plans, ops_of = {}, {}
-    for nm in PLANS:
-        plan = getattr(eng, nm, None)
+    for nm, attr in names.items():
+        plan = getattr(eng, attr, None)
         if plan is None:
             continue
         ids = [id(op) for op in plan.ops]
@@ -218,23 +243,36 @@ def record(eng):
         else:
             plans[nm] = [[lab, digest(canon_op(eng, plan, i, R))] for i, lab in enumerate(plan.labels)]
             ops_of[nm] = ids
-    return alloc, plans
+    return plans
+
+
+def record(eng, late=False):
+    """(allocation digest, {plan: [[label, digest], ...] or [plan, start, stop]}) of an engine; late=True: the same pair
+    once more behind it, for LATE_PLANS after complete()."""
+    alloc, ops_of = digest(allocations(eng)), {}
+    plans = _lines(eng, {nm: nm for nm in PLANS}, {}, ops_of)
+    if not late:
+        return alloc, plans
+    complete(eng)
+    return alloc, plans, digest(allocations(eng)), _lines(eng, LATE_PLANS, {}, ops_of)
 
 
 def main():
     cfgs = configs()
     pool, out = {}, {}
     for name, cfg in cfgs.items():
-        alloc, plans = record(build(cfg))
-        ent = {}
-        for nm, lines in plans.items():
-            if lines and isinstance(lines[0], list):
-                key = digest(lines)
-                pool[key] = lines
-                ent[nm] = key
-            else:
-                ent[nm] = lines
-        out[name] = dict(alloc=alloc, plans=ent)
+        rec = record(build(cfg), late=name in late_configs())
+        out[name] = {}
+        for key_a, key_p, alloc, plans in zip(("alloc", "alloc_late"), ("plans", "late"), rec[0::2], rec[1::2]):
+            ent = {}
+            for nm, lines in plans.items():
+                if lines and isinstance(lines[0], list):
+                    key = digest(lines)
+                    pool[key] = lines
+                    ent[nm] = key
+                else:
+                    ent[nm] = lines
+            out[name].update({key_a: alloc, key_p: ent})
     with open(TABLE, "w") as f:
         f.write('{"configs": {\n')
         f.write(",\n".join(f' {json.dumps(k)}: {json.dumps(v, separators=(",", ":"))}' for k, v in out.items()))
@@ -248,6 +286,8 @@ def main():
 if __name__ == "__main__":
     if len(sys.argv) == 4:                                               # CONFIG PLAN INDEX: one op, field by field
         eng = build(configs()[sys.argv[1]])
-        print(json.dumps(canon_op(eng, getattr(eng, sys.argv[2]), int(sys.argv[3])), indent=1))
+        if sys.argv[2] in LATE_PLANS:
+            complete(eng)
+        print(json.dumps(canon_op(eng, getattr(eng, LATE_PLANS.get(sys.argv[2], sys.argv[2])), int(sys.argv[3])), indent=1))
     else:
         main()
