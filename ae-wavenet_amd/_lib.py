@@ -23,7 +23,8 @@ EF_OUT2_COPY = 1 << 10
 (OP_GEMM_NT, OP_GEMM_TN, OP_COPY_TABLE, OP_VQ_NEAREST, OP_VQ_STATS, OP_VQ_EMA, OP_VQ_BWD,
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
- OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER) = range(1, 32)
+ OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
+ OP_GRAD_WELFORD, OP_SEG_SELECT) = range(1, 34)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -224,6 +225,21 @@ class WindowGather(C.Structure):
                 ("slice_size", i32), ("wav_pitch", i32), ("wav", vp), ("voice", vp), ("index", vp), ("position", vp)]
 
 
+class GradWelford(C.Structure):
+    """aew_grad_welford_t: fold one gradient sample into the running mean / sum of squared deviations (flat fp32 buffers)."""
+    _fields_ = [("g", vp), ("mu", vp), ("s", vp), ("n", i64), ("first", i32), ("divisor", f32), ("chunks", vp),
+                ("chunks_host", vp), ("n_chunks", i64), ("part", vp)]
+
+
+SELECT_MAX_Q = 8
+
+
+class SegSelect(C.Structure):
+    """aew_seg_select_t: exact k-th smallest per tensor of a flat buffer, up to SELECT_MAX_Q ranks per tensor at once."""
+    _fields_ = [("s", vp), ("chunks", vp), ("n_chunks", i64), ("n_tensors", i32), ("Q", i32), ("k", vp), ("out", vp),
+                ("denom", f32), ("raw", i32), ("scratch", vp)]
+
+
 UW_CHUNK = 4096
 
 
@@ -300,7 +316,8 @@ class _OpU(C.Union):
                 ("sm", SoftmaxNll), ("cs", Colsum), ("red", Reduce), ("adam", Adam),
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
-                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather)]
+                ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
+                ("gwel", GradWelford), ("ssel", SegSelect)]
 
 
 class Op(C.Structure):
@@ -314,7 +331,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
-            OP_WINDOW_GATHER: "wgat"}
+            OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel"}
 
 
 
@@ -329,6 +346,13 @@ def uw_chunks(offs, lens):
     chunks = (UwChunk * max(nc.value, 1))()
     check(lib.aew_uw_chunks(o, ln, P, C.cast(chunks, C.c_void_p), nc.value, C.byref(nc), first), "aew_uw_chunks")
     return chunks, list(first)
+
+
+def select_key(bits: int) -> int:
+    """The order key AEW_OP_SEG_SELECT ranks the fp32 value with bit pattern `bits` by: aew_select_key, the kernels' own."""
+    key = C.c_uint32()
+    check(load().aew_select_key(bits & 0xFFFFFFFF, C.byref(key)), "aew_select_key")
+    return key.value
 
 
 # ---- autoregressive sampler (aew_actor_t / aew_sampler_t) ----
@@ -414,17 +438,19 @@ def load():
     lib.aew_grad_norm_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.aew_corpus_locate.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.aew_seg_select_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.aew_select_key.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
     lib.aew_uw_chunks.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
-                       (21, WindowGather)):
+                       (21, WindowGather), (22, GradWelford), (23, SegSelect)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
                            f"{want} in the library")
-    if lib.aew_abi_version() != 28:
+    if lib.aew_abi_version() != 28:            # (held at 28; the appended records are checked through aew_sizeof above)
         raise AewError("ABI version mismatch")
     _lib = lib
     return lib
@@ -473,4 +499,4 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
            "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles",
-           "aew_corpus_locate")
+           "aew_corpus_locate", "aew_seg_select_size", "aew_select_key")

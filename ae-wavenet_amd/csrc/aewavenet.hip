@@ -6,6 +6,7 @@
 #include "aew_ops.hip"
 #include "aew_sampler.hip"
 #include "aew_corpus.hip"
+#include "aew_gradstats.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -59,6 +60,8 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_VQ_RESTART: return launch_vq_restart(op.u.vqr, st);
         case AEW_OP_EVAL_ACC: return launch_eval_acc(op.u.eva, st);
         case AEW_OP_WINDOW_GATHER: return launch_window_gather(op.u.wgat, st);
+        case AEW_OP_GRAD_WELFORD: return launch_grad_welford(op.u.gwel, st);
+        case AEW_OP_SEG_SELECT: return launch_seg_select(op.u.ssel, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -90,6 +93,8 @@ extern "C" int aew_sizeof(int which) {
         case 19: return (int)sizeof(aew_tn_pick_t);
         case 20: return (int)sizeof(aew_eval_acc_t);
         case 21: return (int)sizeof(aew_window_gather_t);
+        case 22: return (int)sizeof(aew_grad_welford_t);
+        case 23: return (int)sizeof(aew_seg_select_t);
         default: return -1;
     }
 }

@@ -42,6 +42,11 @@
 extern "C" {
 #endif
 
+/* The number is held at 28 across the gradient-statistics additions (AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT): they are
+ * append-only - two op kinds behind the existing ones, two descriptors that fit the union's size, aew_sizeof indices 22
+ * and 23, two host functions; no existing record, op number or function changed - so a caller built against 28 runs
+ * unchanged.  A binding that wants the additions finds them through aew_sizeof(22) / aew_sizeof(23) (-1 in a library
+ * without them). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -794,6 +799,79 @@ int aew_corpus_locate(uint64_t t0, int b, int B, int64_t N, int n_order, int R, 
                       int64_t* pos_epoch, int64_t* pos_step);
 
 /* ---------------------------------------------------------------------------------------
+ * Gradient noise statistics (ABI 28, appended; aew_sizeof 22 / 23): what the reference's grad_analysis.py computes with six elementwise torch kernels per
+ * tensor and batch (mu_s_incr) and one kthvalue + .item() per tensor and quantile (quantiles) - here one launch per gradient
+ * sample over three flat fp32 buffers with the offsets of the parameters, and one op for every quantile of every tensor.
+ *
+ * AEW_OP_GRAD_WELFORD folds the gradient sample g into the running mean mu and the running sum of squared deviations s.
+ * Per element (grad_analysis.py:32-39), in round-to-nearest fp32 operations that the compiler may not contract, the
+ * division a true fp32 division - a numpy fp32 restatement gives the same bits:
+ *     first != 0 :  mu = g;  s = 0                                  (mu / s are not read)
+ *     first == 0 :  d = g - mu;  mu' = mu + d / divisor;  s' = s + d * (g - mu')
+ * float4 loads and stores with a scalar tail; every element of [0, n) is updated, the pad elements behind a tensor like
+ * any other (as Adam updates them).  `divisor` is the host's: the reference passes its loop index, the textbook the count.
+ * part != NULL: the launch runs one block per chunk of the chunk table (aew_uw_chunks; chunks = device copy, chunks_host =
+ * host copy, n_chunks records), exactly as the tracked Adam launch does, and also WRITES (plain stores: no two blocks
+ * share a chunk)
+ *     part[chunk] = {sum s', sum mu'^2}   over the chunk's own elements (pad elements enter no sum)
+ * in fp64 in the order aew_uw_track_t documents: per thread one chain per sum (the thread's float4 rounds ascending,
+ * components ascending), a fixed butterfly inside the wave, waves ascending.  AEW_OP_UPDATE_RATIO with finalize = 0 then
+ * yields the per-tensor sums [2][P].  The chunks and the pads behind them must cover [0, n) without a gap (AEW_E_ARG), so
+ * the mu / s bits do not depend on whether part is set - the two launches share one per-element device function.
+ * Before any launch - AEW_E_ARG: n < 0, a NULL g / mu / s with n > 0, first outside {0, 1}, divisor not > 0 with
+ * first == 0, buffers that overlap, with part a NULL / empty / non-covering chunk table; AEW_E_ALIGN: g, mu, s or part not
+ * 16-byte aligned.  n == 0 is a no-op. */
+typedef struct {
+    const float* g; float* mu; float* s;
+    int64_t n;
+    int32_t first;               /* 1: the first sample (mu = g, s = 0)                                                    */
+    float divisor;
+    const aew_uw_chunk_t* chunks;        /* device copy of the chunk table (with part)                                     */
+    const aew_uw_chunk_t* chunks_host;   /* host copy: the launcher checks the coverage of [0, n) in it                     */
+    int64_t n_chunks;
+    double* part;                /* optional device [n_chunks][2]                                                          */
+} aew_grad_welford_t;
+
+/* AEW_OP_SEG_SELECT: the exact k-th smallest element of every tensor of the flat buffer s, for Q <= AEW_SELECT_MAX_Q ranks
+ * per tensor at once, through the chunk table (a chunk's `tensor` names the row of k / out it belongs to; tensors of
+ * length 0 have no chunk).  The reference takes kthvalue(k) of sqrt(s / n_batch) (grad_analysis.py:42-50, 82-83); both are
+ * monotone, so the op selects on s and transforms only the winner.
+ *   order key : the fp32 bit pattern for s >= 0 (-0 counts as +0), 0xFFFFFFFF for s < 0 or NaN - the reference's sqrt makes
+ *               those NaN and kthvalue ranks NaN last.  aew_select_key is the function the kernels call.  (The key is that
+ *               of s alone: a negative s so small that s / denom underflows to -0 is -0 to the reference, NaN here.)
+ *   ranks     : k[t][q], device int32, 1-based, 1 <= k <= length of tensor t.
+ *   out[t][q] : with v = the value whose key is the k-th smallest:  raw != 0: v;  raw == 0: sqrt(v / denom), a true fp32
+ *               division and a correctly rounded root; NaN for the NaN key (raw or not), for a tensor of length 0 and for
+ *               a rank outside 1 .. length.
+ *   method    : radix select, four passes of 8 key bits.  Pass kernel: one block per chunk, an LDS histogram of the next 8
+ *               bits per live (tensor, rank) prefix (ranks that share a prefix share a histogram), non-zero bins added to
+ *               hist[t][q][256] with integer atomics.  Pick kernel: one block per tensor finds the bin that holds the
+ *               rank, narrows the prefix, reduces the rank, clears the bins.  Integer atomics only: exact in any order.
+ *   scratch   : aew_seg_select_size bytes, 16-byte aligned; the op zeroes what it needs itself, so two calls in a row give
+ *               the same bits without host work in between.
+ * Before any launch - AEW_E_ARG: Q outside 1..8, n_tensors < 1, a NULL k / out / scratch, a NULL s / chunks with
+ * n_chunks > 0, raw outside {0, 1}, denom not > 0 with raw == 0; AEW_E_ALIGN: s or scratch not 16-byte, chunks not 8-byte,
+ * k or out not 4-byte aligned. */
+#define AEW_SELECT_MAX_Q 8
+typedef struct {
+    const float* s;
+    const aew_uw_chunk_t* chunks;        /* device                                                                         */
+    int64_t n_chunks;
+    int32_t n_tensors;           /* P                                                                                      */
+    int32_t Q;                   /* 1 .. AEW_SELECT_MAX_Q ranks per tensor                                                  */
+    const int32_t* k;            /* device [P][Q]                                                                          */
+    float* out;                  /* device [P][Q]                                                                          */
+    float denom;
+    int32_t raw;
+    void* scratch;
+} aew_seg_select_t;
+/* Bytes of scratch the op needs (P and Q are read from *p).  Host logic only. */
+int aew_seg_select_size(const aew_seg_select_t* p, int64_t* bytes);
+/* *key = the order key of the value with fp32 bit pattern `bits`: the very function the kernels call.  Host-only, no
+ * device.  AEW_E_ARG for a NULL key. */
+int aew_select_key(uint32_t bits, uint32_t* key);
+
+/* ---------------------------------------------------------------------------------------
  * Chained NT launch (ABI 19): a run of DEPENDENT bf16 NT ops - the gated stack's G1 / G2 pairs (wavenet.py:100-109,
  * 354-357: the layer loop) or its backward's dz / dx pairs - as ONE kernel launch.  The tiles of all stages form one
  * grid in stage order; a tile of stage s starts once the tiles of earlier stages that produce the rows it reads have
@@ -884,7 +962,7 @@ enum {
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
-    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER
+    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -911,13 +989,14 @@ typedef struct {
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
         aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
+        aew_grad_welford_t gwel; aew_seg_select_t ssel;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
