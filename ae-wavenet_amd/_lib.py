@@ -24,7 +24,7 @@ EF_OUT2_COPY = 1 << 10
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
- OP_GRAD_WELFORD, OP_SEG_SELECT) = range(1, 34)
+ OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM) = range(1, 35)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -195,6 +195,14 @@ class Swap(C.Structure):
     _fields_ = [("a", vp), ("b", vp), ("n", i64)]
 
 
+ACCUM_FIRST, ACCUM_ADD, ACCUM_LAST = 0, 1, 2
+
+
+class Accum(C.Structure):
+    """aew_accum_t: fold the buffer a backward just wrote into a running sum (FIRST: acc = g, ADD: acc += g, LAST: g += acc)."""
+    _fields_ = [("acc", vp), ("g", vp), ("n", i64), ("mode", i32), ("pad_", i32)]
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -317,7 +325,7 @@ class _OpU(C.Union):
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
-                ("gwel", GradWelford), ("ssel", SegSelect)]
+                ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum)]
 
 
 class Op(C.Structure):
@@ -331,7 +339,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
-            OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel"}
+            OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum"}
 
 
 
@@ -445,7 +453,7 @@ def load():
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
-                       (21, WindowGather), (22, GradWelford), (23, SegSelect)):
+                       (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

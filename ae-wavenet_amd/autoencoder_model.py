@@ -17,12 +17,14 @@ from .surface import HipModelBase, _BottleneckFacade, _EncoderFacade
 
 class AutoEncoder(HipModelBase):
     def __init__(self, hps, loss_mode: str = "intended", take_compat: bool = False,
-                 update_codebook_every_step: bool = True, n_mel=None, codebook_restart=None):
+                 update_codebook_every_step: bool = True, n_mel=None, codebook_restart=None, accumulate=1):
         """codebook_restart: None, or dict(every=, min_usage=, max_codes=64, denom_init=1.0, seed=0) - vqvae-ema only:
         every `every`-th training step re-seeds the codes whose EMA count fell under min_usage from distinct encoder
-        outputs of that step, on the device (bottleneck.restart_dead_codes() does it on demand)."""
+        outputs of that step, on the device (bottleneck.restart_dead_codes() does it on demand).
+        accumulate: micro-batches per optimizer step, an integer >= 1 (HipModelBase.accumulate): gradients and EMA
+        statistics of k run() / backward() pairs are summed on the device, FusedAdam.step() acts on the k-th only."""
         super().__init__(hps, "autoencoder", loss_mode, take_compat, update_codebook_every_step, n_mel,
-                         codebook_restart=codebook_restart)
+                         codebook_restart=codebook_restart, accumulate=accumulate)
         self.encoder = _EncoderFacade()
         self.bottleneck = _BottleneckFacade(self)
         try:                                    # the reference's MFCC front-end, when importable

@@ -1453,6 +1453,31 @@ __global__ __launch_bounds__(256) void k_swap(const aew_swap_t p) {
 }
 
 // =============================================================================================
+// accumulate (aew_accum_t): fold g into the running sum acc, one pass like k_swap.  MODE 0: acc = g; 1: acc = acc + g;
+// 2: g = acc + g.  __fadd_rn: one IEEE addition per element that no contraction can merge with anything else
+// =============================================================================================
+template <int MODE>
+__global__ __launch_bounds__(256) void k_accum(const aew_accum_t p) {
+    const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 >= p.n) return;
+    if (i4 + 4 <= p.n) {
+        const float4 y = *reinterpret_cast<const float4*>(p.g + i4);
+        if (MODE == 0) {
+            *reinterpret_cast<float4*>(p.acc + i4) = y;
+        } else {
+            const float4 x = *reinterpret_cast<const float4*>(p.acc + i4);
+            const float4 s = make_float4(__fadd_rn(x.x, y.x), __fadd_rn(x.y, y.y), __fadd_rn(x.z, y.z), __fadd_rn(x.w, y.w));
+            *reinterpret_cast<float4*>((MODE == 1 ? p.acc : p.g) + i4) = s;
+        }
+    } else {
+        for (int64_t i = i4; i < p.n; ++i) {
+            if (MODE == 0) p.acc[i] = p.g[i];
+            else (MODE == 1 ? p.acc : p.g)[i] = __fadd_rn(p.acc[i], p.g[i]);
+        }
+    }
+}
+
+// =============================================================================================
 // global gradient norm + clip coefficient (aew_grad_norm_t; torch.nn.utils.clip_grad_norm_): one streaming read of the
 // flat gradient buffer, fp64 sums in ONE order, the coefficient stays on the device for k_adam<true>
 // =============================================================================================
@@ -2473,6 +2498,17 @@ static int launch_swap(const aew_swap_t& p, hipStream_t st) {
     const int64_t blocks = cdiv64((p.n + 3) / 4, 256);
     if (blocks > 0x7fffffff) return AEW_E_ARG;
     hipLaunchKernelGGL(k_swap, dim3((unsigned)blocks), dim3(256), 0, st, p);
+    return (int)hipGetLastError();
+}
+static int launch_accum(const aew_accum_t& p, hipStream_t st) {
+    if (p.n < 0 || (p.n > 0 && (!p.acc || !p.g)) || p.mode < 0 || p.mode > 2) return AEW_E_ARG;
+    if (p.n == 0) return 0;
+    if (((uintptr_t)p.acc | (uintptr_t)p.g) & 15) return AEW_E_ALIGN;
+    if (p.acc < p.g ? p.acc + p.n > p.g : p.g + p.n > p.acc) return AEW_E_ARG;      // overlapping buffers: not a fold
+    const int64_t blocks = cdiv64((p.n + 3) / 4, 256);
+    if (blocks > 0x7fffffff) return AEW_E_ARG;
+    auto k = p.mode == 0 ? k_accum<0> : p.mode == 1 ? k_accum<1> : k_accum<2>;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, st, p);
     return (int)hipGetLastError();
 }
 static int grad_norm_blocks(const aew_grad_norm_t& p, int64_t* blocks) {

@@ -62,6 +62,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_WINDOW_GATHER: return launch_window_gather(op.u.wgat, st);
         case AEW_OP_GRAD_WELFORD: return launch_grad_welford(op.u.gwel, st);
         case AEW_OP_SEG_SELECT: return launch_seg_select(op.u.ssel, st);
+        case AEW_OP_ACCUM: return launch_accum(op.u.accum, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -95,6 +96,7 @@ extern "C" int aew_sizeof(int which) {
         case 21: return (int)sizeof(aew_window_gather_t);
         case 22: return (int)sizeof(aew_grad_welford_t);
         case 23: return (int)sizeof(aew_seg_select_t);
+        case 25: return (int)sizeof(aew_accum_t);      // (24 is left unused: it answers -1)
         default: return -1;
     }
 }

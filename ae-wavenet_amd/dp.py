@@ -42,6 +42,14 @@ its own shards and the replicated remainders - like the moments, its average is 
 gather_moments() / sync_optimizer_state() all-gathers adam_avg along with them; FusedAdam.averaged_weights() refuses to
 swap in an incomplete average.  A copy of the parameters updated with torch._foreach_lerp_ behind optim.step() must NOT
 be used with the sharded schedule: p.data is complete only once the parameter all-gathers are.
+
+Gradient accumulation (`accumulate=k` on the model; aew_accum_t): the micro-batches 1 .. k-1 of a group exchange nothing -
+no gradient collective, no EMA-statistics collective (the VAE's KL all-reduce belongs to a micro-batch's own backward and
+stays).  The k-th micro-batch exchanges the group's sums, as often per group as a step does without accumulation.
+All-reduce schedule: allreduce_grads behind the fold that leaves the sum in the gradient buffer.  Sharded schedule:
+backward_exchange(accum_last=True) folds each region in front of its reduce-scatter, so the overlap with the encoder
+backward is kept.  The statistics all-reduce (sync or async, finish_ema unchanged) runs on the group's z_sum / n_sum; the
+parameter all-gathers follow real optimizer steps only.
 """
 from __future__ import annotations
 
@@ -318,30 +326,41 @@ class DataParallel:
         module surface does."""
         return eng.dec_grad_offset > 0 and bool(getattr(eng, "pack_dec_late", False)) and not getattr(eng, "merge_packs", False)
 
-    def forward(self, eng):
+    def forward(self, eng, accum=None):
         """The forward of a sharded step: the encoder part starts as soon as ITS parameters are complete, the decoder's
-        all-gather is waited for between the two forward plans."""
+        all-gather is waited for between the two forward plans.  accum: the micro-batch's fold in a group of accumulated
+        ones (TrainEngine.forward): FIRST / ADD issue no statistics collective, LAST all-reduces the group's sums."""
         late = self._late(eng)
         self._warn_merged_packs(eng)
         self.finish("head" if late else None)
-        return eng.forward(self.allreduce_ema_async, before_decoder=self.finish if late else None)
+        kw = {} if accum is None else {"accum": accum}
+        return eng.forward(self.allreduce_ema_async, before_decoder=self.finish if late else None, **kw)
 
-    def backward_exchange(self, eng, bf16_grads: bool = False):
+    def backward_exchange(self, eng, bf16_grads: bool = False, accum_last: bool = False):
         """Backward with the sharded gradient exchange issued as the regions become final: decoder tail (reduce-scatter
-        under the bottleneck / encoder backward), then the head.  optimizer_step() completes it."""
+        under the bottleneck / encoder backward), then the head.  optimizer_step() completes it.
+        accum_last: this is the last micro-batch of a group of accumulated ones - every region takes the group's running
+        sum in (TrainEngine.accum_grads, LAST, one launch over the region) in front of its reduce-scatter, so the
+        exchange still overlaps the rest of the backward.  The earlier micro-batches of a group run the plain backward
+        and exchange nothing."""
         n, lo = eng.ps.numel, eng.dec_grad_offset
         hi = getattr(eng, "dec_hi_offset", None)       # engines with two grouped wgrad launches: [hi, n) is final first
         flat = eng.ps.grads
         st = {"hi": hi}
 
+        def reduce(a, b):
+            if accum_last and b > a:
+                eng.accum_grads(2, a, b)                 # (AEW_ACCUM_LAST)
+            return self._reduce_region(flat, a, b, bf16_grads)
+
         def after_decoder_hi():
             self._guard_sync(eng)
-            st["dec_hi"] = self._reduce_region(flat, hi, n, bf16_grads)
+            st["dec_hi"] = reduce(hi, n)
 
         def after_decoder():
             if "dec_hi" not in st:
                 self._guard_sync(eng)
-            st["dec"] = self._reduce_region(flat, lo, n if "dec_hi" not in st else hi, bf16_grads)
+            st["dec"] = reduce(lo, n if "dec_hi" not in st else hi)
 
         self.allreduce_kl(eng)
         if hi is not None:
@@ -350,8 +369,18 @@ class DataParallel:
             eng.backward(after_decoder=after_decoder)
         if "dec" not in st:
             after_decoder()
-        st["head"] = self._reduce_region(flat, 0, lo, bf16_grads) if lo > 0 else ([], [])
+        st["head"] = reduce(0, lo) if lo > 0 else ([], [])
         self._st = st
+
+    def abandon_exchange(self):
+        """Drop a sharded exchange no optimizer step will complete (an accumulated group discarded or started over
+        unstepped): its collectives are waited for - they read the gradient buffer the next backward rewrites - and
+        their results are not used."""
+        st, self._st = self._st, None
+        for key in ("dec_hi", "dec", "head"):
+            for w in (st or {}).get(key, ([], []))[0]:
+                w.wait()
+        self._guard_wait()
 
     def _clip_norm_sharded(self, eng, regions, max_grad_norm: float, grad_scale: float):
         """The clip coefficient of a sharded step, once every region is reduced: the sum of squares of this rank's shards

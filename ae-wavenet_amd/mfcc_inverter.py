@@ -6,8 +6,9 @@ from .surface import HipModelBase
 
 
 class MfccInverter(HipModelBase):
-    def __init__(self, hps, take_compat: bool = False):
-        super().__init__(hps, "mfcc_inverter", take_compat=take_compat, n_mel=hps.n_lc_in)
+    def __init__(self, hps, take_compat: bool = False, accumulate=1):
+        """accumulate: micro-batches per optimizer step, an integer >= 1 (HipModelBase.accumulate)."""
+        super().__init__(hps, "mfcc_inverter", take_compat=take_compat, n_mel=hps.n_lc_in, accumulate=accumulate)
         try:
             import mfcc as _mfcc                # the reference's librosa front-end (mfcc.py:39-76)
             self.mfcc = _mfcc.ProcessWav(sample_rate=hps.sample_rate, win_sz=hps.mfcc_win_sz,

@@ -481,6 +481,11 @@ class TrainEngine:
         self.act_epoch = 0                # bumped by everything that overwrites the activations a backward reads
         self.eval_a = self.eval_b = self.eval_fin = None      # the forward plans minus EVAL_DROP (+ loss, accumulate); finalize
         self.eval_acc = self.eval_hist = self.eval_out = self.eval_loss = None
+        # ===== gradient accumulation (aew_accum_t): the running sums of a group of micro-batches and the op that folds
+        # into them exist from the first micro-step of an engine used with accumulate > 1 (accum_grads / accum_stats)
+        self.acc_grads = None             # flat like ps.grads: the sum of the open group's gradients
+        self.acc_stats = None             # vqvae-ema: z_sum | n_sum of the open group, laid out like bn.zn_sum
+        self.accum = Plan("accum")        # one op, re-addressed per call like `opt` (the mode is a scalar of the op)
         # ===== the encode / conditioning sub-plans (encode(), conditioning()) and the chained launches' host-side watch
         self._encode_plan = self._cond_plan = self._cond_plan_a = None
         self._chain_flag_views = self._chain_host = None
@@ -689,8 +694,43 @@ class TrainEngine:
             self._chain_host["pending"].clear()
             self._chain_host["buf"].zero_()
 
-    def forward(self, ema_allreduce=None, timing=False, before_decoder=None):
+    def _accum_run(self, acc: torch.Tensor, g: torch.Tensor, n: int, mode: int):
+        """One launch of the accumulate op: fold g[0:n] into acc[0:n] (FIRST / ADD) or acc into g (LAST)."""
+        if mode not in (L.ACCUM_FIRST, L.ACCUM_ADD, L.ACCUM_LAST):
+            raise ValueError(f"Invalid accumulation mode: {mode!r} (0 FIRST, 1 ADD, 2 LAST)")
+        if not self.accum.ops:
+            self.accum.add(L.OP_ACCUM, L.Accum(), "accumulate", TAG_ADAM)
+        a = self.accum.array()[0].u.accum
+        a.acc, a.g, a.n, a.mode = acc.data_ptr(), g.data_ptr(), int(n), int(mode)
+        self.accum.run(self._stream())
+
+    def accum_grads(self, mode: int, lo: int = 0, hi: Optional[int] = None):
+        """Gradient accumulation, one launch (AEW_OP_ACCUM) over the element range [lo, hi) (multiples of 4, like
+        adam_step) of the flat gradient buffer and the running sum `acc_grads`: FIRST acc = g, ADD acc = acc + g, LAST
+        g = acc + g (acc is left alone) - one fp32 addition per element, so a group's sum is ((g1 + g2) + g3) + ... in
+        that order.  A data-parallel caller folds a region in as soon as it is final.  No host synchronisation."""
+        hi = self.ps.numel if hi is None else hi
+        assert lo % 4 == 0 and (hi % 4 == 0 or hi == self.ps.numel) and 0 <= lo <= hi <= self.ps.numel
+        if self.acc_grads is None:
+            self.acc_grads = self.ws.alloc("accum.grads", self.ps.numel, torch.float32)
+        self._accum_run(self.acc_grads[lo:], self.ps.grads[lo:], hi - lo, mode)
+
+    def accum_stats(self, mode: int):
+        """The same fold over the EMA statistics of the batch (z_sum | n_sum; vqvae-ema only): after LAST they hold the
+        sums over the group - n_sum exactly, its terms are integer counts."""
+        if self.ema_plan is None:
+            raise L.AewError(f"accum_stats() needs the vqvae-ema bottleneck (this engine: {self.bn_type})")
+        n = self.zn_sum.numel()
+        if self.acc_stats is None:
+            self.acc_stats = self.ws.alloc("accum.stats", n, torch.float32)
+        self._accum_run(self.acc_stats, self.zn_sum, n, mode)
+
+    def forward(self, ema_allreduce=None, timing=False, before_decoder=None, accum: Optional[int] = None):
         """timing=True forces eager launches (the per-op event timing needs them).
+        accum: None, or the fold (0 FIRST, 1 ADD, 2 LAST) of this micro-batch in a group of accumulated ones.  FIRST /
+        ADD: the batch's EMA statistics go into the group's sums (accum_stats) and NO EMA is applied (fwd_b_noema), no
+        statistics collective is issued.  LAST: z_sum / n_sum become the group's sums and the forward goes on as without
+        accumulation - the cross-rank sum, then the EMA, once for the group.  Engines without EMA statistics: ignored.
         before_decoder(): called between the two forward plans - the first point at which a decoder parameter is read
         (pack_dec_late); a data-parallel caller waits there for the all-gather of the decoder's parameter shards.
         ema_allreduce(z_sum, n_sum): cross-rank sum of the EMA statistics.  If it returns a work handle
@@ -702,6 +742,13 @@ class TrainEngine:
         self.lin_live = True
         if before_decoder is not None:
             before_decoder()
+        if accum is not None and self.ema_plan is not None:
+            self.accum_stats(accum)
+            if accum != L.ACCUM_LAST:                          # inside a group: no collective, no EMA
+                self._run(self.fwd_b_noema, timing)
+                if not timing:
+                    self._chain_watch("fwd")
+                return self.loss_buf[0]
         if ema_allreduce is not None and self.ema_plan is not None:
             work = ema_allreduce(self.z_sum, self.n_sum)
             if work is not None:
@@ -757,8 +804,10 @@ class TrainEngine:
         else:
             self.gmul[:1].fill_(float(g))
 
-    def backward(self, timing=False, after_decoder=None, after_decoder_hi=None):
-        """after_decoder: optional callback invoked between the decoder part of the backward (all
+    def backward(self, timing=False, after_decoder=None, after_decoder_hi=None, refresh_codebook: bool = True):
+        """refresh_codebook=False: the backward of a micro-batch inside a group of accumulated ones - no EMA ran in its
+        forward, so the codebook that follows the EMA statistics is not refreshed either (update_codebook_every_step).
+        after_decoder: optional callback invoked between the decoder part of the backward (all
         decoder gradients final in ps.grads[dec_grad_offset:]) and the bottleneck / encoder part.
         after_decoder_hi: optional callback invoked as soon as ps.grads[dec_hi_offset:] is final (engines built with two
         grouped weight-gradient launches only: dec_hi_offset is not None)."""
@@ -780,7 +829,7 @@ class TrainEngine:
         if not timing and self.nt_chain_bwd_used >= 2:
             self._chain_watch("bwd")
         self.finish_ema(timing)
-        if self.update_codebook_every_step and self.ema_plan is not None:     # (the codebook that follows the EMA statistics)
+        if self.update_codebook_every_step and self.ema_plan is not None and refresh_codebook:     # (the codebook that follows the EMA statistics)
             self._run(self.cb, timing)
 
     def update_codebook(self):

@@ -80,7 +80,13 @@ class FusedAdam(torch.optim.Optimizer):
     without.  The average starts from the parameters in front of the first averaged step; a step the device skips leaves
     it alone.  Parameters and moments are bit for bit those of a step without it.  `averaged_weights()` puts the average
     in the parameters' place for sampling / evaluation.  A number in (0, 1), or None = off.  The values live in
-    `param_groups[0]["ema_decay"]` / `["ema_warmup"]`."""
+    `param_groups[0]["ema_decay"]` / `["ema_warmup"]`.
+
+    Gradient accumulation (`accumulate=k` on the model): inside a group - until the model's k-th backward - step() is a
+    no-op: no launch, step count, moments, average and update-ratio record keep their bits.  Behind the k-th backward the
+    gradient buffer holds the group's SUM and the step runs with grad_scale / k: the optimizer, the clip norm, the update
+    ratios and the averaged weights see the MEAN of the micro-batch gradients - do not also divide the loss by k.  The
+    state_dict gains no key."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None,
                  track_update_ratio=False, ema_decay=None, ema_warmup=True):
@@ -102,16 +108,24 @@ class FusedAdam(torch.optim.Optimizer):
         d = _check_ema_decay(g.get("ema_decay"))
         if eng.averaged_in:
             raise L.AewError("FusedAdam.step() inside averaged_weights(): the averaged weights sit in the parameters' place")
+        k = getattr(self.model, "accumulate", 1)
+        scale = self.grad_scale
+        if k > 1:
+            # gradient accumulation: a step inside a group is a no-op (no launch, no counter moves); the step behind the
+            # group's k-th backward sees the SUM in the gradient buffer and takes the mean through the scale
+            if not self.model.group_ready:
+                return
+            scale = self.grad_scale / k                          # (in double; rounded to fp32 where grad_scale is)
+            self.model._group_ready = False
         kw = {}
         if d is not None:                                        # (off: the calls below are the ones of an optimizer without it)
             kw["avg_rate"] = ema_rate_at(d, eng.avg_steps, bool(g.get("ema_warmup", True)))
         dp = getattr(self.model, "_dp", None)
         if dp is not None and dp.sharded and not dp._solo():
             # data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather
-            dp.optimizer_step(eng, g["lr"], self.grad_scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track,
-                              **kw)
+            dp.optimizer_step(eng, g["lr"], scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track, **kw)
         else:
-            eng.adam_step(g["lr"], self.grad_scale, g["betas"], g["eps"], max_grad_norm=c, track=track, **kw)
+            eng.adam_step(g["lr"], scale, g["betas"], g["eps"], max_grad_norm=c, track=track, **kw)
 
     # ---- the averaged weights -------------------------------------------------------------------------------------
     @contextlib.contextmanager

@@ -72,6 +72,17 @@ def _check_codebook_restart(opt):
     return out
 
 
+def _check_accumulate(k):
+    """The `accumulate` option: a whole number >= 1 (Python and numpy integers; no bool, no fraction, no string)."""
+    try:
+        i = None if isinstance(k, bool) else operator.index(k)
+    except TypeError:
+        i = None
+    if i is None or not 1 <= i <= 2 ** 31 - 1:
+        raise ValueError(f"Invalid accumulate: {k!r} (micro-batches per optimizer step: an integer >= 1)")
+    return i
+
+
 class _StepFn(torch.autograd.Function):
     """loss = f(parameters, batch) with a hand-written backward (the bwd plan)."""
 
@@ -79,12 +90,40 @@ class _StepFn(torch.autograd.Function):
     def forward(ctx, anchor, owner):
         ctx.owner = owner
         dp = owner._dp
+        ctx.fold = fold = owner._begin_micro_step()          # None without accumulation; else (mode, micro-step)
+        kw = {} if fold is None else {"accum": fold[0]}
         if dp is not None and dp.sharded and not dp._solo():
-            loss = dp.forward(owner._engine)                 # the decoder's parameter all-gather stays in flight under the encoder
+            loss = dp.forward(owner._engine, **kw)           # the decoder's parameter all-gather stays in flight under the encoder
         else:
-            loss = owner._engine.forward(owner._ema_allreduce)
+            loss = owner._engine.forward(owner._ema_allreduce, **kw)
         ctx.act = (owner._engine.serial, owner._engine.act_epoch)    # whose activations, and which, the backward reads
         return loss.clone()
+
+    @staticmethod
+    def _backward_accumulated(owner, fold, g):
+        """Micro-step j of k > 1: the backward plan writes the micro-batch's gradient, AEW_OP_ACCUM folds it into the
+        group's running sum (FIRST, ADD ..., and LAST, which leaves the SUM in .grad).  Collectives, the codebook upkeep
+        and the restart belong to the group: they run with the last micro-step only."""
+        mode, j = fold
+        eng, dp = owner._engine, owner._dp
+        if j != owner._micro:
+            raise L.AewError(f"loss.backward() out of order: this loss belongs to micro-step {j + 1} of the accumulated "
+                             f"group, the group stands at micro-step {owner._micro + 1} (one backward() per run(), in "
+                             "order; model.reset_accumulation() discards the open group).  No gradient was written")
+        last = mode == L.ACCUM_LAST
+        owner._grads_cleared = False
+        if last and dp is not None and dp.sharded and not dp._solo():
+            dp.backward_exchange(eng, dp.bf16_grads, accum_last=True)    # each region: LAST fold, then its reduce-scatter
+        else:
+            if dp is not None:
+                dp.allreduce_kl(eng)                         # (belongs to the micro-batch's own backward)
+            eng.backward(refresh_codebook=last)
+            eng.accum_grads(mode)
+        if last:
+            owner._auto_restart()
+        owner._after_backward(g, reduce=last)
+        owner._micro = 0 if last else j + 1
+        owner._group_ready = last
 
     @staticmethod
     def backward(ctx, g):
@@ -102,15 +141,19 @@ class _StepFn(torch.autograd.Function):
                              "batch.  Call backward() before evaluating, or run() the batch again.  No gradient was written")
         owner._engine.set_upstream_grad(g)
         dp = owner._dp
-        prev = owner._grads_carried()
-        if dp is not None and dp.sharded and not dp._solo():
-            dp.backward_exchange(owner._engine, dp.bf16_grads)   # reduce-scatter issued under the encoder backward
+        if ctx.fold is not None:                             # accumulate > 1: the accumulator carries the group
+            _StepFn._backward_accumulated(owner, ctx.fold, g)
+            prev = None
         else:
-            if dp is not None:
-                dp.allreduce_kl(owner._engine)               # VAE: the clamp's gate sees the global KL
-            owner._engine.backward()
-        owner._auto_restart()                                # (the deferred EMA and the codebook refresh are done by here)
-        owner._after_backward(g)
+            prev = owner._grads_carried()
+            if dp is not None and dp.sharded and not dp._solo():
+                dp.backward_exchange(owner._engine, dp.bf16_grads)   # reduce-scatter issued under the encoder backward
+            else:
+                if dp is not None:
+                    dp.allreduce_kl(owner._engine)               # VAE: the clamp's gate sees the global KL
+                owner._engine.backward()
+            owner._auto_restart()                                # (the deferred EMA and the codebook refresh are done by here)
+            owner._after_backward(g)
         if prev is not None:
             eng = owner._engine
             eng.ps.grads[:eng.ps.numel].add_(prev)
@@ -214,9 +257,10 @@ class HipModelBase(nn.Module):
     """Common implementation; subclasses set `kind` and the parameter prefix layout."""
 
     def __init__(self, hps, kind: str, loss_mode: str = "intended", take_compat: bool = False,
-                 update_codebook_every_step: bool = True, n_mel: Optional[int] = None, codebook_restart=None):
+                 update_codebook_every_step: bool = True, n_mel: Optional[int] = None, codebook_restart=None, accumulate=1):
         super().__init__()
         codebook_restart = _check_codebook_restart(codebook_restart)
+        accumulate = _check_accumulate(accumulate)
         if hps.global_model != kind:
             hps = type(hps)(hps)
             hps["global_model"] = kind
@@ -234,6 +278,10 @@ class HipModelBase(nn.Module):
         self._engines: Dict[int, TrainEngine] = {}      # engines by batch size (train B, sampling B = 1, ...)
         self._opt_carry: Optional[OptState] = None       # the optimizer state while no engine holds it
         self._grads_cleared = True                       # no backward yet / FusedAdam.zero_grad() since the last one
+        self._accumulate = accumulate                    # micro-batches per optimizer step (1: no accumulation)
+        self._micro = 0                                  # micro-batches folded into the open group, 0 .. accumulate - 1
+        self._group_ready = False                        # .grad holds a whole group's sum that no step() has consumed
+        self._fold_open = False                          # a run() of a group has folded its statistics, its backward is due
         self._weights_epoch = 0                          # bumped whenever parameter values change behind torch's back
         self._device = torch.device("cpu")
         self._pending_state: Optional[Dict[str, torch.Tensor]] = None
@@ -270,11 +318,73 @@ class HipModelBase(nn.Module):
         """wav samples per window (wavenet.py:287-294 via checkpoint.py:40)."""
         return G.input_size(self.hps, self.kind == "autoencoder", output_size)
 
+    # ---- gradient accumulation: k micro-batches per optimizer step ----------------------------
+    @property
+    def accumulate(self) -> int:
+        """Micro-batches per optimizer step (the constructor's `accumulate`, set_accumulate()).  With k > 1 the k-th
+        loss.backward() of a group leaves the SUM of the group's gradients in .grad (the earlier ones leave their own
+        micro-batch's), FusedAdam.step() is a no-op until then and applies grad_scale / k - the optimizer sees the MEAN
+        of the micro-batch gradients, so do not also divide the loss by k - and the EMA statistics, the codebook
+        refresh, the code restart and every data-parallel exchange happen once per group."""
+        return self._accumulate
+
+    @property
+    def micro_step(self) -> int:
+        """Micro-batches folded into the open group so far: 0 .. accumulate - 1."""
+        return self._micro
+
+    @property
+    def group_ready(self) -> bool:
+        """True from the k-th backward of a group until FusedAdam.step() consumes it (or the next group begins)."""
+        return self._group_ready
+
+    def set_accumulate(self, k):
+        """Change the accumulation count; only between groups."""
+        k = _check_accumulate(k)
+        if self._micro != 0 or self._group_ready or self._fold_open:
+            raise L.AewError("set_accumulate() inside an accumulated group (micro-steps pending, or a finished group no "
+                             "step() has consumed): step the optimizer first, or discard the group with "
+                             "model.reset_accumulation()")
+        self._accumulate = k
+
+    def reset_accumulation(self):
+        """Discard the open group: the next run() starts a fresh one.  Nothing is launched; the partial sums are simply
+        overwritten by the next group's first micro-step."""
+        if self._group_ready and self._dp is not None and self._dp.sharded and not self._dp._solo():
+            self._dp.abandon_exchange()
+        self._micro, self._group_ready, self._fold_open = 0, False, False
+
+    def _begin_micro_step(self):
+        """The fold of the coming forward / backward pair: None without accumulation, else (AEW_OP_ACCUM mode, micro-step
+        index).  Beginning a group while the last one is still unstepped drops that sum, as torch drops an unstepped
+        gradient."""
+        k = self._accumulate
+        if k == 1:
+            return None
+        if self._group_ready:
+            self.reset_accumulation()
+        j = self._micro
+        if self._fold_open and j > 0:
+            raise L.AewError(f"run() at micro-step {j + 1} of {k} while the previous run() of the group has had no "
+                             "backward(): its EMA statistics are already folded into the group and would be counted "
+                             "twice.  Call loss.backward() after every run() of a group (model.evaluate() computes a "
+                             "loss without a training step), or discard the group with model.reset_accumulation()")
+        self._fold_open = True
+        return (L.ACCUM_LAST if j == k - 1 else L.ACCUM_FIRST if j == 0 else L.ACCUM_ADD), j
+
+    def _refuse_mid_group(self, what):
+        """The group's running sums live in the engine: it must not be replaced or dropped before the group is stepped."""
+        if self._micro != 0 or self._group_ready:
+            raise L.AewError(f"{what} inside an accumulated group (micro-step {self._micro} of {self._accumulate}"
+                             f"{', group ready' if self._group_ready else ''}): the engine holds the group's running sums.  "
+                             "Step the optimizer first, or discard the group with model.reset_accumulation()")
+
     def override(self, n_win_batch=None):
         """mfcc_inverter.py:30-35 (checkpoint.py:46)."""
         if n_win_batch is not None and n_win_batch != self.window_batch_size:
             if self._engine is not None:
                 self._refuse_while_averaged_in("override()")         # (before anything is changed)
+                self._refuse_mid_group("override()")
             self.window_batch_size = n_win_batch
             self._set_geometry(n_win_batch)
             self._drop_engine()
@@ -368,6 +478,7 @@ class HipModelBase(nn.Module):
         # lazily on the next run() and the values (and the Adam moments) are copied back in.
         if self._engine is not None:
             self._refuse_while_averaged_in("model.to() / a dtype change")
+            self._refuse_mid_group("model.to() / a dtype change")
             self._dp_finish()
             self._sync_buffers_from_engine()
             self._save_opt_carry()
@@ -465,6 +576,8 @@ class HipModelBase(nn.Module):
         eng = self._engine
         if eng is not None and eng.B == B:
             return eng
+        if eng is not None:                                      # (before anything is changed)
+            self._refuse_mid_group(f"a batch of {B} windows (the group's engine has {eng.B}; sample() uses 1)")
         if self._device.type != "cuda":
             raise L.AewError("this model executes only through the HIP library on an MI355X; "
                              "move it to a cuda device first (no CPU execution path exists)")
@@ -636,12 +749,14 @@ class HipModelBase(nn.Module):
             if t % opt["every"] == 0:
                 self._restart_codes(self._engine, opt["min_usage"], t)
 
-    def _after_backward(self, g):
+    def _after_backward(self, g, reduce=True):
+        """reduce=False: a micro-batch inside an accumulated group - its gradient is not exchanged."""
         eng = self._engine
+        self._fold_open = False
         # re-attach .grad views (optim.zero_grad(set_to_none=True) detaches them)
         for name, pname in self._pnames:
             self._parameters[pname].grad = eng.ps.view(name, grad=True)
-        if self._dp is not None and not self._dp.sharded:
+        if self._dp is not None and not self._dp.sharded and reduce:
             self._dp.allreduce_grads(eng)
         # gradient statistics: AEW_OP_MOMENTS ops on a side lane of the backward plan (views, no kernels here)
         m = self.objective.metrics

@@ -644,6 +644,23 @@ typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.op
  * AEW_E_ARG: n < 0, a NULL pointer with n > 0, buffers that overlap; AEW_E_ALIGN: a or b not 16-byte aligned. */
 typedef struct { float* a; float* b; int64_t n; } aew_swap_t;
 
+/* Gradient accumulation (appended to ABI 28; aew_sizeof 25 - index 24 stays unused, it answers -1): fold the buffer a backward just wrote into a running sum, k micro-batches per optimizer
+ * step.  One pass, float4 loads and stores with a scalar tail, a grid that depends on n only; plain vector loads and stores,
+ * no atomics.  Every element gets ONE round-to-nearest fp32 addition that is never contracted with anything: a numpy fp32
+ * `acc + g` gives the same bits, and the sum of a group is ((g1 + g2) + g3) + ... + gk whatever the launch geometry.
+ * n = 0 is a no-op.  AEW_E_ARG: n < 0, a NULL pointer with n > 0, a mode outside 0..2, buffers that overlap;
+ * AEW_E_ALIGN: acc or g not 16-byte aligned.  A refused call writes nothing. */
+enum { AEW_ACCUM_FIRST = 0, AEW_ACCUM_ADD = 1, AEW_ACCUM_LAST = 2 };
+typedef struct {
+    float* acc;                  /* running sum [n], 16-byte aligned */
+    float* g;                    /* the buffer a backward just wrote [n], 16-byte aligned */
+    int64_t n;
+    int32_t mode;                /* 0 FIRST: acc[i] = g[i]
+                                    1 ADD  : acc[i] = __fadd_rn(acc[i], g[i])
+                                    2 LAST : g[i]   = __fadd_rn(acc[i], g[i])   (acc is not written) */
+    int32_t pad_;
+} aew_accum_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -962,7 +979,8 @@ enum {
     AEW_OP_SPK_BWD, AEW_OP_BASE_GATHER, AEW_OP_SOFTMAX_NLL, AEW_OP_COLSUM, AEW_OP_REDUCE,
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
-    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT
+    AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
+    AEW_OP_ACCUM
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -989,14 +1007,14 @@ typedef struct {
         aew_vae_t vae; aew_ae_norm_t aen; aew_jitter_t jit; aew_vq_diag_t diag; aew_mfcc_t mfcc;
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
         aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
-        aew_grad_welford_t gwel; aew_seg_select_t ssel;
+        aew_grad_welford_t gwel; aew_seg_select_t ssel; aew_accum_t accum;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum (24 is unused: -1) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
