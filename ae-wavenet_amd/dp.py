@@ -7,6 +7,11 @@ windows (sampler rule data.py:100-106); per step the ranks exchange
   * the VQ-EMA statistics z_sum / n_sum (SUM) before the EMA update, so that all replicas keep
     an identical codebook (north-star requirement; the reference lets replicas drift).
 
+A step through the module surface (model.run, loss.backward, FusedAdam.step) runs under ONE schedule object - LocalSchedule
+(nothing attached, or one rank without force_collectives), AllReduceSchedule (dp.attach(model)) or ShardedSchedule
+(dp.attach(model, sharded=True)) - picked by DataParallel.schedule() at every use (HipModelBase._schedule).  Its interface is
+all that surface.py, optim.py and grad_analysis.py know of a schedule; the table of who does what is in DESIGN.md §6.
+
 Two schedules for the gradient exchange (same result up to fp32 summation order):
   train_step          all-reduce of the decoder tail under the encoder backward, all-reduce of the head under the
                       decoder's Adam range (round 1);
@@ -58,6 +63,8 @@ from typing import List
 import torch
 import torch.distributed as dist
 
+from . import _lib as L
+
 
 def shard_indices(n: int, rank: int, world: int, epoch: int) -> List[int]:
     """Replica-sharded looping sampler order of the reference (data.py:100-106)."""
@@ -66,6 +73,84 @@ def shard_indices(n: int, rank: int, world: int, epoch: int) -> List[int]:
     vals = list(range(rank, n, world))
     perm = torch.randperm(len(vals), generator=g).tolist()
     return [vals[i] for i in perm]
+
+
+class LocalSchedule:
+    """A step that exchanges nothing.  The interface of all three schedules; fold: None, or the AEW_OP_ACCUM mode of this
+    micro-batch in a group of accumulated ones (collectives and codebook upkeep run with a group's LAST one only)."""
+    shards = False                          # True: .grad holds reduced values for this rank's shards only
+
+    def _nothing(self, *args):
+        pass
+
+    wait_params = _nothing                  # (): in front of a run() - the parameters its forward reads are complete
+    wait_all = _nothing                     # (): in front of every other reader of the parameters - no all-gather in flight
+    reduce_grads = _nothing                 # (eng): behind the backward AND the code restart of a step / a group's last fold
+    abandon = _nothing                      # (): an exchange no optimizer step will complete (a finished group dropped)
+
+    def forward(self, eng, ema_allreduce, fold=None):
+        return eng.forward(ema_allreduce, **({} if fold is None else {"accum": fold}))
+
+    def backward(self, eng, fold=None):     # the ONE backward path: the plan writes the micro-batch's gradient, then the fold
+        eng.backward(**({} if fold is None else {"refresh_codebook": fold == L.ACCUM_LAST}))
+        if fold is not None:
+            eng.accum_grads(fold)           # (FIRST, ADD ..., and LAST, which leaves the group's SUM in .grad)
+
+    def step(self, eng, lr, grad_scale, **adam_kw):
+        eng.adam_step(lr, grad_scale, **adam_kw)
+
+    def restart_codes(self, eng, min_usage, call, **kw):
+        eng.restart_codes(min_usage, call, **kw)
+
+    def eval_finish(self, eng):
+        return eng.eval_finish()
+
+
+class AllReduceSchedule(LocalSchedule):
+    """The backward leaves the fully reduced gradient in every .grad, every rank runs the whole Adam step.  The
+    DataParallel's methods are looked up when they are called (tests and tools wrap them on the instance)."""
+
+    def __init__(self, dp):
+        self.dp = dp
+
+    def wait_all(self):
+        self.dp.finish()
+
+    wait_params = wait_all                  # (the parameter all-gathers of a preceding sharded step)
+
+    def backward(self, eng, fold=None):
+        self.dp.allreduce_kl(eng)           # VAE: the clamp's gate sees the global KL (every micro-batch's own)
+        super().backward(eng, fold)
+
+    def reduce_grads(self, eng):
+        self.dp.allreduce_grads(eng)
+
+    def restart_codes(self, eng, min_usage, call, **kw):
+        self.dp.restart_codes(eng, min_usage, call, **kw)
+
+    def eval_finish(self, eng):
+        return self.dp.eval_finish(eng)
+
+
+class ShardedSchedule(AllReduceSchedule):
+    """Reduce-scatter under the backward, sharded Adam, all-gather (forward / backward_exchange / optimizer_step below)."""
+    shards = True
+    wait_params = reduce_grads = LocalSchedule._nothing      # (forward() waits for the parameters region by region)
+
+    def forward(self, eng, ema_allreduce, fold=None):       # (the statistics go through dp.allreduce_ema_async)
+        return self.dp.forward(eng, **({} if fold is None else {"accum": fold}))
+
+    def backward(self, eng, fold=None):
+        if fold in (L.ACCUM_FIRST, L.ACCUM_ADD):             # inside a group nothing is exchanged
+            return super().backward(eng, fold)
+        # reduce-scatter issued under the encoder backward; a group's last micro-batch: each region's LAST fold in front of it
+        self.dp.backward_exchange(eng, self.dp.bf16_grads, **({} if fold is None else {"accum_last": True}))
+
+    def step(self, eng, lr, grad_scale, **adam_kw):
+        self.dp.optimizer_step(eng, lr, grad_scale, **adam_kw)
+
+    def abandon(self):
+        self.dp.abandon_exchange()
 
 
 class DataParallel:
@@ -90,6 +175,10 @@ class DataParallel:
     def _solo(self) -> bool:
         """One rank and no request to run the collectives anyway: every exchange is skipped."""
         return self.world == 1 and not self.force_collectives
+
+    def schedule(self):
+        """The exchange schedule of a step through the module surface, for the state this object is in NOW."""
+        return LocalSchedule() if self._solo() else ShardedSchedule(self) if self.sharded else AllReduceSchedule(self)
 
     # ---- measurement: how long the compute stream actually stalls on collectives ---------------------------------
     def _wait(self, work, what: str):
@@ -350,7 +439,7 @@ class DataParallel:
 
         def reduce(a, b):
             if accum_last and b > a:
-                eng.accum_grads(2, a, b)                 # (AEW_ACCUM_LAST)
+                eng.accum_grads(L.ACCUM_LAST, a, b)
             return self._reduce_region(flat, a, b, bf16_grads)
 
         def after_decoder_hi():

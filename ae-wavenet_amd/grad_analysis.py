@@ -146,8 +146,7 @@ class GradStats:
     def add(self):
         """Fold the gradients of the last backward in (AEW_OP_GRAD_WELFORD; the chunk sums sums() / noise_scale() read come
         out of the same launch)."""
-        dp = getattr(self.model, "_dp", None)
-        if dp is not None and dp.sharded and not dp._solo():
+        if getattr(getattr(self.model, "_schedule", None), "shards", False):      # (any nn.Module: no schedule, no shards)
             raise L.AewError("GradStats.add() is not supported under the sharded data-parallel schedule: each rank holds the "
                              "reduced gradient of its own shards only")
         with torch.no_grad():

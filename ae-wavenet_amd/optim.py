@@ -120,12 +120,8 @@ class FusedAdam(torch.optim.Optimizer):
         kw = {}
         if d is not None:                                        # (off: the calls below are the ones of an optimizer without it)
             kw["avg_rate"] = ema_rate_at(d, eng.avg_steps, bool(g.get("ema_warmup", True)))
-        dp = getattr(self.model, "_dp", None)
-        if dp is not None and dp.sharded and not dp._solo():
-            # data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather
-            dp.optimizer_step(eng, g["lr"], scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track, **kw)
-        else:
-            eng.adam_step(g["lr"], scale, g["betas"], g["eps"], max_grad_norm=c, track=track, **kw)
+        # (data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather)
+        self.model._schedule.step(eng, g["lr"], scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track, **kw)
 
     # ---- the averaged weights -------------------------------------------------------------------------------------
     @contextlib.contextmanager

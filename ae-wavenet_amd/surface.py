@@ -25,6 +25,7 @@ from torch import nn
 
 from . import _lib as L
 from . import geometry as G
+from .dp import LocalSchedule
 from .model import OptState, TrainEngine
 
 
@@ -89,41 +90,10 @@ class _StepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, owner):
         ctx.owner = owner
-        dp = owner._dp
         ctx.fold = fold = owner._begin_micro_step()          # None without accumulation; else (mode, micro-step)
-        kw = {} if fold is None else {"accum": fold[0]}
-        if dp is not None and dp.sharded and not dp._solo():
-            loss = dp.forward(owner._engine, **kw)           # the decoder's parameter all-gather stays in flight under the encoder
-        else:
-            loss = owner._engine.forward(owner._ema_allreduce, **kw)
+        loss = owner._schedule.forward(owner._engine, owner._ema_allreduce, None if fold is None else fold[0])
         ctx.act = (owner._engine.serial, owner._engine.act_epoch)    # whose activations, and which, the backward reads
         return loss.clone()
-
-    @staticmethod
-    def _backward_accumulated(owner, fold, g):
-        """Micro-step j of k > 1: the backward plan writes the micro-batch's gradient, AEW_OP_ACCUM folds it into the
-        group's running sum (FIRST, ADD ..., and LAST, which leaves the SUM in .grad).  Collectives, the codebook upkeep
-        and the restart belong to the group: they run with the last micro-step only."""
-        mode, j = fold
-        eng, dp = owner._engine, owner._dp
-        if j != owner._micro:
-            raise L.AewError(f"loss.backward() out of order: this loss belongs to micro-step {j + 1} of the accumulated "
-                             f"group, the group stands at micro-step {owner._micro + 1} (one backward() per run(), in "
-                             "order; model.reset_accumulation() discards the open group).  No gradient was written")
-        last = mode == L.ACCUM_LAST
-        owner._grads_cleared = False
-        if last and dp is not None and dp.sharded and not dp._solo():
-            dp.backward_exchange(eng, dp.bf16_grads, accum_last=True)    # each region: LAST fold, then its reduce-scatter
-        else:
-            if dp is not None:
-                dp.allreduce_kl(eng)                         # (belongs to the micro-batch's own backward)
-            eng.backward(refresh_codebook=last)
-            eng.accum_grads(mode)
-        if last:
-            owner._auto_restart()
-        owner._after_backward(g, reduce=last)
-        owner._micro = 0 if last else j + 1
-        owner._group_ready = last
 
     @staticmethod
     def backward(ctx, g):
@@ -139,23 +109,25 @@ class _StepFn(torch.autograd.Function):
             raise L.AewError("loss.backward() after model.evaluate(): the evaluation overwrote the activations (and code "
                              "indices, logits) this loss was computed from, so its gradients would be those of another "
                              "batch.  Call backward() before evaluating, or run() the batch again.  No gradient was written")
-        owner._engine.set_upstream_grad(g)
-        dp = owner._dp
-        if ctx.fold is not None:                             # accumulate > 1: the accumulator carries the group
-            _StepFn._backward_accumulated(owner, ctx.fold, g)
-            prev = None
-        else:
+        eng.set_upstream_grad(g)
+        mode, j = ctx.fold or (None, 0)
+        if mode is None:
             prev = owner._grads_carried()
-            if dp is not None and dp.sharded and not dp._solo():
-                dp.backward_exchange(owner._engine, dp.bf16_grads)   # reduce-scatter issued under the encoder backward
-            else:
-                if dp is not None:
-                    dp.allreduce_kl(owner._engine)               # VAE: the clamp's gate sees the global KL
-                owner._engine.backward()
-            owner._auto_restart()                                # (the deferred EMA and the codebook refresh are done by here)
-            owner._after_backward(g)
+        else:                                                # accumulate > 1: the accumulator carries the group
+            if j != owner._micro:
+                raise L.AewError(f"loss.backward() out of order: this loss belongs to micro-step {j + 1} of the accumulated "
+                                 f"group, the group stands at micro-step {owner._micro + 1} (one backward() per run(), in "
+                                 "order; model.reset_accumulation() discards the open group).  No gradient was written")
+            prev, owner._grads_cleared = None, False
+        # collectives, the codebook upkeep and the restart belong to the group: they run with its last micro-step only
+        last = mode in (None, L.ACCUM_LAST)
+        owner._schedule.backward(eng, mode)
+        if last:
+            owner._auto_restart()                            # (the deferred EMA and the codebook refresh are done by here)
+        owner._after_backward(g, reduce=last)
+        if mode is not None:
+            owner._micro, owner._group_ready = (0 if last else j + 1), last
         if prev is not None:
-            eng = owner._engine
             eng.ps.grads[:eng.ps.numel].add_(prev)
         # (the anchor's "gradient": a cached zero, not a fill kernel per step)
         z = getattr(owner, "_anchor_zero", None)
@@ -181,9 +153,8 @@ class Evaluator:
         eng = m._engine
         if eng is None:
             raise L.AewError("Evaluator.result(): no engine - nothing has been evaluated on this device yet")
-        dp = m._dp
         with torch.no_grad():
-            out = (dp.eval_finish(eng) if dp is not None and not dp._solo() else eng.eval_finish()).clone()
+            out = m._schedule.eval_finish(eng).clone()
         return {name: out[i] for i, name in enumerate(L.EVAL_OUT_NAMES)}
 
 
@@ -350,8 +321,8 @@ class HipModelBase(nn.Module):
     def reset_accumulation(self):
         """Discard the open group: the next run() starts a fresh one.  Nothing is launched; the partial sums are simply
         overwritten by the next group's first micro-step."""
-        if self._group_ready and self._dp is not None and self._dp.sharded and not self._dp._solo():
-            self._dp.abandon_exchange()
+        if self._group_ready:
+            self._schedule.abandon()
         self._micro, self._group_ready, self._fold_open = 0, False, False
 
     def _begin_micro_step(self):
@@ -434,11 +405,16 @@ class HipModelBase(nn.Module):
     _BUF_NAMES = {"bn_emb": "bottleneck.emb", "bn_ema_numer": "bottleneck.ema_numer",
                   "bn_ema_denom": "bottleneck.ema_denom", "bn_ind_hist": "bottleneck.ind_hist"}
 
+    @property
+    def _schedule(self):
+        """The exchange schedule of a step (dp.LocalSchedule / AllReduceSchedule / ShardedSchedule), asked for at every use:
+        tests and tools change the DataParallel's mode, model._dp and model._ema_allreduce after attach()."""
+        return LocalSchedule() if self._dp is None else self._dp.schedule()
+
     def _dp_finish(self):
         """Data parallel, sharded schedule: the parameter all-gathers of the last optimizer step may still be in
         flight on the collective stream - everything that reads the parameters outside run() waits for them first."""
-        if self._dp is not None:
-            self._dp.finish()
+        self._schedule.wait_all()
 
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
         self._dp_finish()
@@ -630,8 +606,7 @@ class HipModelBase(nn.Module):
         (B, w-1), loss scalar with a grad_fn whose backward fills every parameter's .grad."""
         B = wav.shape[0]
         eng = self._ensure_engine(B)
-        if self._dp is not None and not (self._dp.sharded and not self._dp._solo()):
-            self._dp.finish()                                # (sharded: _StepFn.forward waits region by region)
+        self._schedule.wait_params()
         eng.set_inputs(wav, mel, voice, jitter, eps=eps)
         loss = _StepFn.apply(self._anchor, self)
         w, g = eng.n_win, eng.geom
@@ -718,7 +693,7 @@ class HipModelBase(nn.Module):
         grads = [(name, self._parameters[pname].grad) for name, pname in self._pnames]
         if all(gr is None for _, gr in grads):
             return None
-        if self._dp is not None and self._dp.sharded and not self._dp._solo():
+        if self._schedule.shards:
             raise L.AewError("backward() onto existing gradients (no zero_grad() since the last backward) is not supported "
                              "under the sharded data-parallel schedule: each rank holds the reduced gradient of its own "
                              "shards only")
@@ -735,10 +710,7 @@ class HipModelBase(nn.Module):
     def _restart_codes(self, eng, min_usage: float, call: int):
         """One restart launch with the model's settings; through the data-parallel path where ranks have to agree."""
         kw = {k: (self._restart or _RESTART_DEFAULTS)[k] for k in _RESTART_DEFAULTS}
-        if self._dp is not None and not self._dp._solo():
-            self._dp.restart_codes(eng, min_usage, call, **kw)
-        else:
-            eng.restart_codes(min_usage, call, **kw)
+        self._schedule.restart_codes(eng, min_usage, call, **kw)
 
     def _auto_restart(self):
         """codebook_restart: the backward of step t = step_count + 1 restarts dead codes when t % every == 0, with call = t
@@ -756,8 +728,8 @@ class HipModelBase(nn.Module):
         # re-attach .grad views (optim.zero_grad(set_to_none=True) detaches them)
         for name, pname in self._pnames:
             self._parameters[pname].grad = eng.ps.view(name, grad=True)
-        if self._dp is not None and not self._dp.sharded and reduce:
-            self._dp.allreduce_grads(eng)
+        if reduce:
+            self._schedule.reduce_grads(eng)
         # gradient statistics: AEW_OP_MOMENTS ops on a side lane of the backward plan (views, no kernels here)
         m = self.objective.metrics
         gs = eng.gstat
