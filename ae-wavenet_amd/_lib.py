@@ -24,7 +24,7 @@ EF_OUT2_COPY = 1 << 10
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
- OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM) = range(1, 35)
+ OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS) = range(1, 37)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -203,6 +203,16 @@ class Accum(C.Structure):
     _fields_ = [("acc", vp), ("g", vp), ("n", i64), ("mode", i32), ("pad_", i32)]
 
 
+class CodeLookup(C.Structure):
+    """aew_code_lookup_t: zq[q] = emb[ind[q]] (pad channels zero); an index outside [0, K) gives a zero row and counts in *bad."""
+    _fields_ = [("ind", vp), ("emb", vp), ("zq", vp), ("bad", vp), ("Q", i32), ("K", i32), ("d", i32), ("d_pitch", i32)]
+
+
+class CodeRuns(C.Structure):
+    """aew_code_runs_t: run-length collapse of code rows: units (-1 behind the last run), lengths (0 behind it), n_runs."""
+    _fields_ = [("ind", vp), ("ind_pitch", i64), ("units", vp), ("lengths", vp), ("n_runs", vp), ("B", i32), ("N", i32)]
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -325,7 +335,7 @@ class _OpU(C.Union):
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
-                ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum)]
+                ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns)]
 
 
 class Op(C.Structure):
@@ -339,7 +349,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_ADAM: "adam", OP_ZERO: "zero", OP_VAE: "vae", OP_AE_NORM: "aen", OP_JITTER: "jit",
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
-            OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum"}
+            OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
+            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun"}
 
 
 
@@ -453,7 +464,7 @@ def load():
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
-                       (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum)):
+                       (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

@@ -1,0 +1,82 @@
+"""Code sequences as data: the functional forms of the two device ops that go with the discrete codes of a VQ-VAE
+(csrc/aew_codes.hip), and the mu-law companding that turns an amplitude into the decoder's sample values.
+
+    zq = lookup(emb, codes)                       # AEW_OP_CODE_LOOKUP: codebook rows of a code tensor
+    units, lengths, n_runs = code_runs(codes)     # AEW_OP_CODE_RUNS: frames -> units (run-length collapse)
+
+Both run as one-op plans on torch's current stream, take any device tensor (rows of any length: the concatenated codes
+of an utterance) and never synchronise with the host.  `model.encode()` / `model.decode()` / `model.convert()`
+(surface.py) are the calls that produce and consume the codes.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib as L
+
+
+def _run(kind: int, rec, what: str, dev: torch.device):
+    if dev.type != "cuda":
+        raise L.AewError(f"{what} runs on the GPU only (tensor on '{dev}'); there is no CPU path")
+    op = L.Op()
+    op.kind = kind
+    setattr(op.u, L.OP_FIELD[kind], rec)
+    fail = C.c_int(-1)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.load().aew_run_plan(C.byref(op), 1, C.c_void_p(st), C.byref(fail)), what)
+
+
+def lookup(emb: torch.Tensor, codes: torch.Tensor, d_pitch: Optional[int] = None,
+           bad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """emb fp32 (K, d), codes int64 of any shape -> fp32 codes.shape + (d_pitch,), d_pitch = d by default: emb[codes] bit
+    for bit, channels d..d_pitch zero.  A code outside [0, K) is not followed: its row is zeros and, with `bad` (an int32
+    device tensor; element 0 is the counter, zero it first), counted there."""
+    if emb.dim() != 2 or emb.dtype != torch.float32 or codes.dtype != torch.int64:
+        raise L.AewError("lookup(): emb fp32 (K, d) and int64 codes expected")
+    K, d = emb.shape
+    dp = d if d_pitch is None else int(d_pitch)
+    emb, flat = emb.contiguous(), codes.to(emb.device).reshape(-1).contiguous()
+    zq = torch.empty(flat.numel(), dp, dtype=torch.float32, device=emb.device)
+    if flat.numel():
+        lk = L.CodeLookup()
+        lk.ind, lk.emb, lk.zq, lk.bad = flat.data_ptr(), emb.data_ptr(), zq.data_ptr(), (bad.data_ptr() if bad is not None else None)
+        lk.Q, lk.K, lk.d, lk.d_pitch = flat.numel(), K, d, dp
+        _run(L.OP_CODE_LOOKUP, lk, "code lookup", emb.device)
+    return zq.view(*codes.shape, dp)
+
+
+def code_runs(codes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """codes int64 (B, N) or (N,) (any row stride) -> (units int64 (B, N), lengths int32 (B, N), n_runs int32 (B,)):
+    position t starts a run iff t == 0 or codes[b, t] != codes[b, t - 1]; units[b, r] / lengths[b, r] are the code and the
+    length of run r, -1 / 0 behind the last run.  Fixed output sizes - the host is never told a size, so the call can be
+    captured in a graph; `units[b, :n_runs[b]]` is the caller's (synchronising) cut."""
+    if codes.dtype != torch.int64 or codes.dim() not in (1, 2):
+        raise L.AewError("code_runs(): int64 codes (B, N) or (N,) expected")
+    one = codes.dim() == 1
+    c = codes.unsqueeze(0) if one else codes
+    B, N = c.shape
+    if c.stride(1) != 1 or (B > 1 and c.stride(0) < N):
+        c = c.contiguous()
+    units = torch.empty(B, N, dtype=torch.int64, device=c.device)
+    lengths = torch.empty(B, N, dtype=torch.int32, device=c.device)
+    n_runs = torch.empty(B, dtype=torch.int32, device=c.device)
+    cr = L.CodeRuns()
+    cr.ind, cr.ind_pitch = c.data_ptr(), (c.stride(0) if B > 1 else N)
+    cr.units, cr.lengths, cr.n_runs, cr.B, cr.N = units.data_ptr(), lengths.data_ptr(), n_runs.data_ptr(), B, N
+    _run(L.OP_CODE_RUNS, cr, "code runs", c.device)
+    return (units[0], lengths[0], n_runs[0]) if one else (units, lengths, n_runs)
+
+
+# ---- mu-law companding of the decoder's samples (amplitudes in [-1, 1] -> n_quant integer values) ---------------------
+def mu_encode(x: torch.Tensor, n_quant: int = 256) -> torch.Tensor:
+    """Amplitudes in [-1, 1] -> int64 mu-law values in [0, n_quant): with mu = n_quant - 1, the compressed amplitude
+    sign(x) ln(1 + mu |x|) / ln(1 + mu) is mapped affinely onto [0, mu] and rounded to the nearest integer (halves up)."""
+    mu = float(n_quant - 1)
+    y = torch.sign(x) * torch.log1p(mu * x.abs()) / math.log1p(mu)
+    return torch.floor((y + 1.0) * (0.5 * mu) + 0.5).to(torch.int64).clamp_(0, n_quant - 1)
+

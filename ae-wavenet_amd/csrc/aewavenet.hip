@@ -7,6 +7,7 @@
 #include "aew_sampler.hip"
 #include "aew_corpus.hip"
 #include "aew_gradstats.hip"
+#include "aew_codes.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -63,6 +64,8 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_GRAD_WELFORD: return launch_grad_welford(op.u.gwel, st);
         case AEW_OP_SEG_SELECT: return launch_seg_select(op.u.ssel, st);
         case AEW_OP_ACCUM: return launch_accum(op.u.accum, st);
+        case AEW_OP_CODE_LOOKUP: return launch_code_lookup(op.u.clk, st);
+        case AEW_OP_CODE_RUNS: return launch_code_runs(op.u.crun, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -97,6 +100,8 @@ extern "C" int aew_sizeof(int which) {
         case 22: return (int)sizeof(aew_grad_welford_t);
         case 23: return (int)sizeof(aew_seg_select_t);
         case 25: return (int)sizeof(aew_accum_t);      // (24 is left unused: it answers -1)
+        case 27: return (int)sizeof(aew_code_lookup_t);      // (26 is left unused like 24)
+        case 28: return (int)sizeof(aew_code_runs_t);
         default: return -1;
     }
 }

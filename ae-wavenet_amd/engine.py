@@ -1323,6 +1323,14 @@ class VqBottleneck(BottleneckPlan):
         assert self.dp == self.nlin_p
         fa.add(L.OP_VQ_NEAREST, vq, "vq.nearest", TAG_VQ)
 
+    def lookup_op(self, bad: torch.Tensor) -> "L.CodeLookup":
+        """The inverse of vq.nearest on its zq output: bn.zq from the codes in bn.ind (aew_code_lookup_t), same layouts;
+        `bad` takes the number of codes outside [0, K)."""
+        lk = L.CodeLookup()
+        lk.ind, lk.emb, lk.zq, lk.bad = self.ind.data_ptr(), self.emb.data_ptr(), self.code.ptr, bad.data_ptr()
+        lk.Q, lk.K, lk.d, lk.d_pitch = self.Q, self.K, self.d, self.nlin_p
+        return lk
+
     def _diag_op(self, w: int, scratch: torch.Tensor, out: torch.Tensor) -> "L.VqDiag":
         dv = L.VqDiag()
         dv.ze, dv.Q, dv.d, dv.d_pitch = self.lin.ptr, self.Q, self.d, self.lin.pitch

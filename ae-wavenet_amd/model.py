@@ -488,6 +488,10 @@ class TrainEngine:
         self.accum = Plan("accum")        # one op, re-addressed per call like `opt` (the mode is a scalar of the op)
         # ===== the encode / conditioning sub-plans (encode(), conditioning()) and the chained launches' host-side watch
         self._encode_plan = self._cond_plan = self._cond_plan_a = None
+        # ===== codes as an interface (encode_codes() / codes_to_conditioning()): the lookup op in front of the
+        # conditioning plan and the word that counts codes outside the codebook exist from the first decode on
+        self._decode_plan = None          # [code.lookup] + the ops of _cond_plan
+        self.codes_bad = None             # int32 [1] (a uint32 count): codes outside [0, K) in the last decode
         self._chain_flag_views = self._chain_host = None
 
     # ops of the training forward that an evaluation leaves out: they write what the next training step (or the caller,
@@ -596,11 +600,9 @@ class TrainEngine:
         self._run(self._encode_plan, False)
         self.lin_live = True
 
-    def conditioning(self):
-        """Encoder / bottleneck and the conditioning half of the decoder forward only (jitter gather, lc_conv,
-        upsampler, speaker bias): what the autoregressive sampler needs (wavenet.py:379-391).  No EMA statistics
-        or update, no index histogram update (vq.stats is skipped), no loss.
-        Returns (cond bf16 [B][T][Cp], gated bias fp32 [B][NL][2*Dp])."""
+    def _cond_plans(self):
+        """The two halves of conditioning(), built once: _cond_plan_a = fwd_a without vq.stats (encoder, bn.linear, nearest
+        code), _cond_plan = the prefix of fwd_b in front of the first gated layer, without vq.ema and the chained launches."""
         if self._cond_plan is None:
             fb = self.fwd_b
             stop = fb.labels.index("G1.0") if "G1.0" in fb.labels else next(
@@ -608,10 +610,73 @@ class TrainEngine:
             self._cond_plan = self._sub_plan("conditioning", fb, lambda i, lab: i < stop and lab != "vq.ema" and
                                              not lab.startswith("chain["))
             self._cond_plan_a = self._sub_plan("conditioning_a", self.fwd_a, lambda i, lab: lab != "vq.stats")
-        self._run(self._cond_plan_a, False)
-        self._run(self._cond_plan, False)
+
+    def _cond_out(self):
         d = self.dec
         return d.cond.tensor(), d.bias_bl[:self.B * d.NL * 2 * d.Dp].view(self.B, d.NL, 2 * d.Dp)
+
+    def _need_codes(self, what: str):
+        if not hasattr(self.bn, "lookup_op"):
+            raise L.AewError(f"{what} needs a VQ bottleneck (vqvae or vqvae-ema): the bottleneck of this engine is "
+                             f"'{self.bn_type}', which has no discrete codes")
+
+    def encode_codes(self):
+        """Encoder -> bn.linear -> nearest code for the batch in the inputs (_cond_plan_a: the training forward's first half
+        without vq.stats): the codes are left in `ind` [Q = B * embed_len], their distances in `min_dist`.  Writes no
+        EMA statistic, histogram, loss or metric word; overwrites the encoder activations (act_epoch).  No host
+        synchronisation.  Returns (ind, min_dist) as views of the workspace buffers."""
+        self._need_codes("encode_codes()")
+        self._cond_plans()
+        self.act_epoch += 1
+        self._run(self._cond_plan_a, False)
+        self.lin_live = True
+        return self.ind[:self.Q], self.min_dist[:self.Q]
+
+    DECODE_DROP = ("diagnostics (codebook)",)
+
+    def decode_plan(self) -> Plan:
+        """[code.lookup] + the ops of _cond_plan (the same records), built at the first use with the `codes_bad` word.
+        One op of _cond_plan is left out: "diagnostics (codebook)" sits in front of the first gated layer on a side lane
+        of fwd_b, reduces the ENCODER outputs bn.lin - which a decode never computed - and writes `diag`, the record
+        behind objective.metrics.  Nothing the conditioning needs depends on it."""
+        self._need_codes("codes_to_conditioning()")
+        if self._decode_plan is None:
+            self._cond_plans()
+            self.codes_bad = self.ws.alloc("codes.bad", 1, torch.int32)
+            head = Plan("lookup")
+            head.add(L.OP_CODE_LOOKUP, self.bn.lookup_op(self.codes_bad), "code.lookup", TAG_VQ)
+            dp = self._sub_plan("codes_to_conditioning", self._cond_plan, lambda i, lab: lab not in self.DECODE_DROP)
+            dp.splice(0, head)
+            self._decode_plan = dp
+        return self._decode_plan
+
+    def codes_to_conditioning(self, codes: torch.Tensor):
+        """The decoder's conditioning from GIVEN codes (int64, B * embed_len of them, row-major) instead of the encoder's:
+        the codes go to `ind`, one AEW_OP_CODE_LOOKUP writes bn.zq = emb[ind] and the conditioning plan runs unchanged.
+        `voice` and `jitter` are read from the inputs (set_inputs / the in_voice, in_jitter buffers).  A code outside
+        [0, K) is not followed: its row of zq is zero and `codes_bad[0]` counts it - the caller decides (reading the word
+        synchronises).  Writes none of emb, the EMA accumulators and statistics, ind_hist, loss_buf, met_buf, diag, the
+        parameters, gradients, moments or the average; overwrites activations (act_epoch).
+        Returns (cond, bias) exactly as conditioning() does."""
+        dp = self.decode_plan()
+        if codes.dtype != torch.int64 or codes.numel() != self.Q:
+            raise L.AewError(f"codes_to_conditioning(): {self.Q} int64 codes expected (B = {self.B} rows of "
+                             f"{self.geom.embed_len}), got {tuple(codes.shape)} {codes.dtype}")
+        self.act_epoch += 1
+        self.ind[:self.Q].copy_(codes.reshape(-1))
+        self.codes_bad.zero_()
+        self._run(dp, False)
+        return self._cond_out()
+
+    def conditioning(self):
+        """Encoder / bottleneck and the conditioning half of the decoder forward only (jitter gather, lc_conv,
+        upsampler, speaker bias): what the autoregressive sampler needs (wavenet.py:379-391).  No EMA statistics
+        or update, no index histogram update (vq.stats is skipped), no loss.
+        Returns (cond bf16 [B][T][Cp], gated bias fp32 [B][NL][2*Dp])."""
+        self._cond_plans()
+        self._run(self._cond_plan_a, False)
+        self._run(self._cond_plan, False)
+        return self._cond_out()
 
     # ---- chained launches: a hand-off wait that gave up must not pass silently --------------------------------------
     def _chain_flags(self):

@@ -106,9 +106,9 @@ class _StepFn(torch.autograd.Function):
         owner = ctx.owner
         eng = owner._engine
         if eng is None or (eng.serial, eng.act_epoch) != ctx.act:
-            raise L.AewError("loss.backward() after model.evaluate(): the evaluation overwrote the activations (and code "
-                             "indices, logits) this loss was computed from, so its gradients would be those of another "
-                             "batch.  Call backward() before evaluating, or run() the batch again.  No gradient was written")
+            raise L.AewError("loss.backward() after model.evaluate() / encode() / decode(): that call overwrote the activations "
+                             "(and code indices, logits) this loss was computed from, so its gradients would be those of another "
+                             "batch.  Call backward() first, or run() the batch again.  No gradient was written")
         eng.set_upstream_grad(g)
         mode, j = ctx.fold or (None, 0)
         if mode is None:
@@ -655,7 +655,6 @@ class HipModelBase(nn.Module):
         the decoder window are fed from `wav` (default: receptive field + 1, like the reference, which starts
         drawing at base_global_rf, wavenet.py:423-431); the rest are drawn.  One input window (B = 1); replicas are
         parallel streams (wavenet.py:378-381)."""
-        from . import sampler as S
         if wav.shape[0] != 1:
             raise L.AewError("sampling takes one window; replicas come from set_n_replicas()")
         R = max(1, int(self.n_replicas))
@@ -664,12 +663,7 @@ class HipModelBase(nn.Module):
             eng = self._ensure_engine(1)
             eng.set_inputs(wav, mel, voice, jitter)
             cond, bias = eng.conditioning()
-            # the sampler keeps its own packed copy of the weights: re-pack whenever they may have changed.  FusedAdam
-            # updates parameters by raw pointer (no tensor _version bump), hence the explicit counters
-            stamp = (eng.serial, eng.ps.params._version, eng.weights_version, self._weights_epoch)
-            if self._sampler is None or self._sampler[0] != stamp:
-                self._sampler = (stamp, S.from_engine(eng))
-            smp = self._sampler[1]
+            smp = self._engine_sampler(eng)
             g = eng.geom
             T, rf = g.dec_in_len, smp.g.rf()
             n16 = (R + 15) // 16 * 16
@@ -681,6 +675,106 @@ class HipModelBase(nn.Module):
             out, _ = smp.generate(cond.expand(n16, -1, -1).contiguous(), bias.expand(n16, -1, -1).contiguous(),
                                   forced.contiguous(), seed=seed)
             return torch.cat([given, out[:R]], 0).float()
+
+    def _engine_sampler(self, eng):
+        """The cached sampler over the live engine's decoder.  It keeps its own packed copy of the weights: re-packed
+        whenever they may have changed.  FusedAdam updates parameters by raw pointer (no tensor _version bump), hence
+        the explicit counters."""
+        from . import sampler as S
+        stamp = (eng.serial, eng.ps.params._version, eng.weights_version, self._weights_epoch)
+        if self._sampler is None or self._sampler[0] != stamp:
+            self._sampler = (stamp, S.from_engine(eng))
+        return self._sampler[1]
+
+    # ---- the codes between encoder and decoder as an interface ------------------------------------------------------
+    def _need_codes(self, what: str):
+        if self.bn_type not in ("vqvae", "vqvae-ema"):
+            raise L.AewError(f"{what} needs a model with discrete codes (bn_type vqvae or vqvae-ema); the bottleneck of "
+                             f"this model is '{self.bn_type}'")
+
+    def encode(self, mel, return_dist: bool = False):
+        """mel (B, n_mel, frames) -> codes int64 (B, embed_len), a fresh tensor: the index of the nearest codebook entry
+        per encoder frame (the training forward's encoder, bottleneck linear and nearest-code search; no EMA statistics,
+        no histogram, no loss word is written).  return_dist=True: (codes, dist) with the (B, embed_len) distances to the
+        chosen entries.  Inside `FusedAdam.averaged_weights()` it uses the averaged weights.  It overwrites the encoder
+        activations: a pending `loss.backward()` of an earlier run() raises afterwards.  No host synchronisation."""
+        self._need_codes("encode()")
+        B = mel.shape[0]
+        with torch.no_grad():
+            eng = self._ensure_engine(B)
+            self._dp_finish()
+            eng.in_mel.copy_(mel)                                    # (the only input the plan reads)
+            ind, dist = eng.encode_codes()
+            codes = ind.view(B, self.embed_len).clone()
+            return (codes, dist.view(B, self.embed_len).clone()) if return_dist else codes
+
+    def zero_amplitude_code(self) -> int:
+        """The mu-law value a sample of amplitude 0 encodes to (codes.mu_encode with this model's n_quant)."""
+        from . import codes as CD
+        return int(CD.mu_encode(torch.zeros(1), self.n_quant)[0])
+
+    def decode(self, codes, voice, prime=None, n_prime: Optional[int] = None, seed: Optional[int] = None, jitter=None):
+        """codes (B, embed_len) int64, voice (B,) -> (B, dec_in_len) float32 mu-law values: the decoder conditioned on the
+        GIVEN codes in the given voices, one sampler stream per row (padded to a multiple of 16 streams by repeating row
+        0; the pad streams are dropped).  The first n_prime positions (default: receptive field + 1, as in sample())
+        are forced to prime[:, :n_prime] - mu-law values (B, >= n_prime) - or, without `prime`, to the value silence
+        encodes to (zero_amplitude_code()); the rest are drawn.  jitter (B, >= embed_len): the conditioning gather's
+        index, default the identity (no jitter at inference).  seed as in sample().  A code outside [0, K) raises
+        AewError with the count before the sampler starts (the lookup never follows it)."""
+        self._need_codes("decode()")
+        E = self.embed_len
+        if codes.dim() != 2 or codes.shape[1] != E or codes.dtype != torch.int64:
+            raise L.AewError(f"decode(): codes (B, {E}) int64 expected, got {tuple(codes.shape)} {codes.dtype}")
+        B = codes.shape[0]
+        if tuple(voice.shape) != (B,):
+            raise L.AewError(f"decode(): voice ({B},) expected (one per row of codes), got {tuple(voice.shape)}")
+        if jitter is not None and (jitter.dim() != 2 or jitter.shape[0] != B or jitter.shape[1] < E):
+            raise L.AewError(f"decode(): jitter ({B}, >= {E}) expected, got {tuple(jitter.shape)}")
+        with torch.no_grad():
+            eng = self._ensure_engine(B)
+            self._dp_finish()
+            dev = eng.device
+            eng.in_voice.copy_(voice)
+            eng.in_jitter.copy_(torch.arange(E, device=dev).expand(B, -1) if jitter is None else jitter[:, :E])
+            cond, bias = eng.codes_to_conditioning(codes.to(dev))
+            bad = int(eng.codes_bad[0].item()) & 0xFFFFFFFF          # (generation synchronises anyway)
+            if bad:
+                raise L.AewError(f"decode(): {bad} of the {B * E} codes lie outside the codebook [0, {eng.K}); nothing was "
+                                 "generated")
+            smp = self._engine_sampler(eng)
+            T, rf = eng.geom.dec_in_len, smp.g.rf()
+            n_forced = min(T, rf + 1 if n_prime is None else max(1, n_prime))
+            n16 = (B + 15) // 16 * 16
+            forced = torch.full((n16, T), -1, dtype=torch.int32, device=dev)
+            if prime is None:
+                forced[:, :n_forced] = self.zero_amplitude_code()
+            else:
+                if prime.dim() != 2 or prime.shape[0] != B or prime.shape[1] < n_forced:
+                    raise L.AewError(f"decode(): prime ({B}, >= {n_forced}) expected, got {tuple(prime.shape)}")
+                forced[:B, :n_forced] = prime[:, :n_forced].to(device=dev, dtype=torch.int32)
+                forced[B:] = forced[0]
+            rows = torch.arange(n16, device=dev)
+            rows[B:] = 0                                             # pad streams repeat row 0
+            if seed is None:
+                seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
+            out, _ = smp.generate(cond[rows].contiguous(), bias[rows].contiguous(), forced, seed=seed)
+            return out[:B].float()
+
+    def convert(self, wav, mel, voice_to, n_prime: Optional[int] = None, seed: Optional[int] = None, jitter=None):
+        """Voice conversion: decode(encode(mel), voice_to, prime=<the decoder window of wav>).  wav (B, enc_in_len), mel
+        (B, n_mel, frames), voice_to (B,) - or (V,) with B = 1: that one window is decoded in V voices at once, as V
+        streams.  Returns (B or V, dec_in_len) float32 mu-law values whose first n_prime columns are the window's."""
+        self._need_codes("convert()")
+        B, T, o = wav.shape[0], self.dec_in_len, int(self.trim_dec_in[0])
+        V = voice_to.shape[0] if voice_to.dim() == 1 else -1
+        if V != B and not (B == 1 and V >= 1):
+            raise L.AewError(f"convert(): voice_to ({B},) expected, or (V,) with one window; got {tuple(voice_to.shape)} "
+                             f"for {B} windows")
+        codes = self.encode(mel)
+        given = wav[:, o:o + T]
+        if V != B:
+            codes, given = codes.expand(V, -1).contiguous(), given.expand(V, -1)
+        return self.decode(codes, voice_to, prime=given, n_prime=n_prime, seed=seed, jitter=jitter)
 
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared

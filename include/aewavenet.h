@@ -661,6 +661,43 @@ typedef struct {
     int32_t pad_;
 } aew_accum_t;
 
+/* Code sequences as data (appended to ABI 28; aew_sizeof 27 / 28 - index 26 stays unused, it answers -1).
+ *
+ * AEW_OP_CODE_LOOKUP: the inverse of AEW_OP_VQ_NEAREST on its zq output, same layouts -
+ *     zq[q][j] = emb[ind[q]][j] for j < d,   zq[q][j] = 0 for d <= j < d_pitch,   q < Q.
+ * It moves bytes only: the result equals numpy's emb[ind] bit for bit.  An index outside [0, K) is never followed - the
+ * test comes before any load from emb: that row of zq is written as zeros and, with bad != NULL, the thread that owns the
+ * row adds 1 to *bad (integer atomicAdd; the caller zeroes the word).  16-byte loads and stores where d, d_pitch are
+ * multiples of 4 and emb, zq are 16-byte aligned, 4-byte ones otherwise.
+ * AEW_E_ARG: Q, K or d < 1, d_pitch < d, a NULL ind / emb / zq; AEW_E_ALIGN: ind not 8-byte aligned, emb / zq / bad not
+ * 4-byte aligned.  Both before any launch. */
+typedef struct {
+    const int64_t* ind;          /* [Q]                                                        */
+    const float* emb;            /* [K][d]                                                     */
+    float* zq;                   /* [Q][d_pitch]                                               */
+    uint32_t* bad;               /* optional: += number of q with ind[q] outside [0, K)        */
+    int32_t Q, K, d, d_pitch;
+} aew_code_lookup_t;
+
+/* AEW_OP_CODE_RUNS: run-length collapse of code rows (frames -> units).  Position t of row b starts a run iff t == 0 or
+ * ind[b][t] != ind[b][t - 1].  With n = the number of runs of the row:
+ *     units[b][r]   = the code of run r for r < n, -1 for n <= r < N
+ *     lengths[b][r] = the length of run r for r < n, 0 for n <= r < N          n_runs[b] = n
+ * One workgroup of 256 threads per row walks it in chunks of 1024 positions (four per thread) and carries the run count and
+ * the position of the last start from chunk to chunk; inside a chunk a start's rank comes from its wave's ballot (popcount
+ * of the lanes below) and the waves' counts meet in LDS.  Integer work only, no atomics, every output element is written exactly once:
+ * the result is a pure function of the input.  Output sizes are fixed, so the op can sit in a captured graph.
+ * AEW_E_ARG: B or N < 1, ind_pitch < N, a NULL pointer; AEW_E_ALIGN: ind / units not 8-byte aligned, lengths / n_runs not
+ * 4-byte aligned.  Both before any launch. */
+typedef struct {
+    const int64_t* ind;          /* [B][ind_pitch], N codes per row                            */
+    int64_t ind_pitch;           /* elements between rows (>= N)                               */
+    int64_t* units;              /* [B][N]                                                     */
+    int32_t* lengths;            /* [B][N]                                                     */
+    int32_t* n_runs;             /* [B]                                                        */
+    int32_t B, N;
+} aew_code_runs_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -980,7 +1017,7 @@ enum {
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
-    AEW_OP_ACCUM
+    AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1008,13 +1045,14 @@ typedef struct {
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
         aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
         aew_grad_welford_t gwel; aew_seg_select_t ssel; aew_accum_t accum;
+        aew_code_lookup_t clk; aew_code_runs_t crun;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum (24 is unused: -1) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs (24 and 26 are unused: -1) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
