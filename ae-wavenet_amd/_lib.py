@@ -24,7 +24,7 @@ EF_OUT2_COPY = 1 << 10
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
- OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS) = range(1, 37)
+ OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS) = range(1, 38)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -190,6 +190,22 @@ class Adam(C.Structure):
                 ("avg", vp), ("avg_rate", f32), ("pad2_", i32)]
 
 
+class AdamTensor(C.Structure):
+    """aew_adam_tensor_t: one tensor's record of a grouped Adam launch (decay = fp32(1 - lr * weight_decay), in double)."""
+    _fields_ = [("lr", f32), ("decay", f32), ("frozen", i32), ("pad_", i32)]
+
+
+class AdamGroups(C.Structure):
+    """aew_adam_groups_t: the HOST record AdamGrouped.groups points at (keep it alive while a plan holds its address)."""
+    _fields_ = [("chunks", vp), ("chunks_host", vp), ("n_chunks", i64), ("tensors", vp), ("n_tensors", i32), ("pad_", i32),
+                ("base", i64)]
+
+
+class AdamGrouped(C.Structure):
+    """aew_adam_grouped_t (AEW_OP_ADAM_GROUPS): the Adam descriptor and the record of its parameter groups."""
+    _fields_ = [("adam", Adam), ("groups", vp)]
+
+
 class Swap(C.Structure):
     """aew_swap_t: exchange two flat fp32 buffers in place (the parameters and their average, Adam.avg)."""
     _fields_ = [("a", vp), ("b", vp), ("n", i64)]
@@ -335,7 +351,8 @@ class _OpU(C.Union):
                 ("zero", Zero), ("vae", Vae), ("aen", AeNorm), ("jit", Jitter), ("diag", VqDiag), ("mfcc", Mfcc),
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
-                ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns)]
+                ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
+                ("adamg", AdamGrouped)]
 
 
 class Op(C.Structure):
@@ -350,7 +367,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
-            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun"}
+            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg"}
 
 
 
@@ -365,6 +382,22 @@ def uw_chunks(offs, lens):
     chunks = (UwChunk * max(nc.value, 1))()
     check(lib.aew_uw_chunks(o, ln, P, C.cast(chunks, C.c_void_p), nc.value, C.byref(nc), first), "aew_uw_chunks")
     return chunks, list(first)
+
+
+def adam_tensor_records(groups, n_tensors: int) -> bytes:
+    """The bytes of n_tensors aew_adam_tensor_t records for groups = [(lr, weight_decay, frozen)]: lr rounded to fp32,
+    decay = 1 - lr * weight_decay computed in double and rounded to fp32 once (include/aewavenet.h)."""
+    import numpy as np
+    if len(groups) != n_tensors:
+        raise ValueError(f"groups has {len(groups)} records, the flat buffer {n_tensors} tensors")
+    lr = np.array([g[0] for g in groups], np.float64)
+    wd = np.array([g[1] for g in groups], np.float64)
+    if not (np.isfinite(lr).all() and np.isfinite(wd).all() and (lr >= 0).all() and (wd >= 0).all()):
+        raise ValueError("groups: lr and weight_decay must be finite and not negative")
+    rec = np.zeros(n_tensors, np.dtype([("lr", "<f4"), ("decay", "<f4"), ("frozen", "<i4"), ("pad_", "<i4")]))
+    rec["lr"], rec["decay"] = lr, 1.0 - lr * wd
+    rec["frozen"] = [1 if g[2] else 0 for g in groups]
+    return rec.tobytes()
 
 
 def select_key(bits: int) -> int:
@@ -464,7 +497,8 @@ def load():
     for which, cls in ((0, Op), (1, GemmNT), (2, GemmTN), (3, Seg), (4, View), (5, CopyRec), (6, Actor), (7, Sampler), (8, Tuning),
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
-                       (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns)):
+                       (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
+                       (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

@@ -1576,12 +1576,20 @@ __global__ __launch_bounds__(256) void k_grad_norm(const aew_grad_norm_t p) {
 }
 
 // =============================================================================================
-// update / weight ratios (aew_uw_track_t, aew_update_ratio_t; chassis.py:162-185): the Adam launch with one block per
-// chunk of the host's chunk table, fp64 sums of (p_old - p_new)^2 and p_old^2 per chunk, then one block per tensor
+// The chunked Adam launch: one block per chunk of the host's chunk table (no chunk crosses a tensor boundary), ONE body
+// with compile-time switches.
+//   TRACK  (aew_uw_track_t, aew_update_ratio_t; chassis.py:162-185): fp64 sums of (p_old - p_new)^2 and p_old^2 per chunk,
+//          then one block per tensor (k_update_ratio).
+//   GROUPS (aew_adam_groups_t): the block reads its tensor's record {lr, decay, frozen} once - uniform values, scalar
+//          registers.  A frozen chunk loads and stores nothing (with TRACK: it reads p for the weight norm); the others
+//          take the decoupled decay p * decay (one __fmul_rn, none where decay == 1) in front of adam_elem with
+//          step = lr_t / bc1.
+// TRACK without GROUPS is the tracked launch as it always was, bit for bit.
 // =============================================================================================
-template <bool CLIP, bool AVG>
+template <bool CLIP, bool AVG, bool TRACK, bool GROUPS>
 __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_uw_chunk_t* __restrict__ chunks, double* part,
-                                                 const int64_t base, const int chunk0) {
+                                                 const aew_adam_tensor_t* __restrict__ tensors, const int64_t base,
+                                                 const int chunk0) {
     constexpr int IT = AEW_UW_CHUNK / 1024;            // float4 rounds of the block over a whole chunk
     __shared__ double sh[4];
     const int tid = threadIdx.x;
@@ -1599,8 +1607,15 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
         skip = skip || a.clip[1] != 0.f;
         gs = a.clip[0];
     }
+    float lr = a.lr, decay = 1.0f;
+    if (GROUPS) {                                      // the tensor's record: the same words for every thread of the block
+        const aew_adam_tensor_t rec = tensors[c.tensor];
+        lr = rec.lr; decay = rec.decay;
+        skip = skip || rec.frozen != 0;                // frozen: like a skipped step, for this tensor alone
+    }
+    if (!TRACK && skip) return;                        // nothing to sum: no load, no store
     const float inv_sqrt_bc2 = rsqrtf(a.bc2);
-    const float step = a.lr / a.bc1;
+    const float step = lr / a.bc1;
     double sd = 0.0, sw = 0.0;                         // one chain per sum and thread, elements ascending
     float4 p[IT], g[IT], m[IT], v[IT], sa[IT];
 #pragma unroll
@@ -1620,10 +1635,14 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
     for (int it = 0; it < IT; ++it) {
         const int64_t i4 = s + (int64_t)(it * 256 + tid) * 4;
         if (i4 + 4 <= e_adam) {
-            const float4 old = p[it];
+            const float4 old = p[it];                  // (with GROUPS: the value in front of the decay)
             const float* op = &old.x;
             float* pp = &p[it].x; float* gp = &g[it].x; float* mp = &m[it].x; float* vp = &v[it].x;
             if (!skip) {
+                if (GROUPS && decay != 1.0f) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pp[r] = __fmul_rn(pp[r], decay);
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pp[r], gp[r], mp[r], vp[r]);
                 *reinterpret_cast<float4*>(a.p + i4) = p[it];
@@ -1636,13 +1655,15 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
                     *reinterpret_cast<float4*>(a.avg + i4) = sa[it];
                 }
             }
+            if (TRACK) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (i4 + r < e_sum) {
-                    const float d = op[r] - pp[r];     // fp32, as the reference's `c - p`
-                    sd += (double)d * (double)d;
-                    sw += (double)op[r] * (double)op[r];
-                }
+                for (int r = 0; r < 4; ++r)
+                    if (i4 + r < e_sum) {
+                        const float d = op[r] - pp[r];     // fp32, as the reference's `c - p`
+                        sd += (double)d * (double)d;
+                        sw += (double)op[r] * (double)op[r];
+                    }
+            }
         }
     }
     if (tid == 0 && (e_adam & 3)) {                    // a.n % 4 elements at the very end of the buffer, behind thread 0's chain
@@ -1651,18 +1672,20 @@ __global__ __launch_bounds__(256) void k_adam_uw(const aew_adam_t a, const aew_u
             float pn = old;
             if (!skip) {
                 float mm = a.m[i], vv = a.v[i];
+                if (GROUPS && decay != 1.0f) pn = __fmul_rn(pn, decay);
                 adam_elem<CLIP>(a, gs, step, inv_sqrt_bc2, pn, a.g[i], mm, vv);
                 a.m[i] = mm; a.v[i] = vv;
                 a.p[i] = pn;
                 if (AVG) a.avg[i] = avg_elem(a.avg[i], a.avg_rate, pn);
             }
-            if (i < e_sum) {
+            if (TRACK && i < e_sum) {
                 const float d = old - pn;
                 sd += (double)d * (double)d;
                 sw += (double)old * (double)old;
             }
         }
     }
+    if (!TRACK) return;
     sd = gn_block_sum(sd, sh);
     sw = gn_block_sum(sw, sh);
     if (tid == 0) {                                    // the chunk's only writer in this launch; earlier launches of the step are
@@ -2442,33 +2465,50 @@ extern "C" int aew_uw_chunks(const int64_t* off, const int64_t* len, int32_t n_t
     *n_chunks = nc;
     return 0;
 }
-static int launch_adam_tracked(const aew_adam_t& p, hipStream_t st) {
-    const aew_uw_track_t& t = *p.track;
-    if (!t.chunks || !t.chunks_host || !t.part || t.n_chunks < 1 || t.n_chunks > 0x7fffffff || t.base < 0 || p.n < 1) return AEW_E_ARG;
-    if ((t.base & 3) || ((uintptr_t)t.part & 15)) return AEW_E_ALIGN;
-    const aew_uw_chunk_t* ch = t.chunks_host;
+// The chunked launch (AEW_OP_ADAM with track, AEW_OP_ADAM_GROUPS with or without it): both records speak of a chunk table and of `base`; where both are set
+// they must name the same table and base - the launch has one grid.
+template <bool CLIP, bool AVG>
+static auto adam_uw_kernel(bool track, bool groups) -> decltype(&k_adam_uw<CLIP, AVG, true, false>) {
+    return track ? (groups ? k_adam_uw<CLIP, AVG, true, true> : k_adam_uw<CLIP, AVG, true, false>)
+                 : k_adam_uw<CLIP, AVG, false, true>;
+}
+static int launch_adam_chunked(const aew_adam_t& p, const aew_adam_groups_t* gr, hipStream_t st) {
+    const aew_uw_track_t* t = p.track;
+    if (t && (!t->chunks || !t->chunks_host || !t->part || t->n_chunks < 1 || t->n_chunks > 0x7fffffff || t->base < 0 || p.n < 1)) return AEW_E_ARG;
+    if (gr && (!gr->chunks || !gr->chunks_host || !gr->tensors || gr->n_tensors < 1 || gr->n_chunks < 1 || gr->n_chunks > 0x7fffffff ||
+               gr->base < 0 || p.n < 1)) return AEW_E_ARG;
+    if (t && gr && (t->chunks != gr->chunks || t->chunks_host != gr->chunks_host || t->n_chunks != gr->n_chunks || t->base != gr->base))
+        return AEW_E_ARG;
+    if (t && ((t->base & 3) || ((uintptr_t)t->part & 15))) return AEW_E_ALIGN;
+    if (gr && ((gr->base & 3) || ((uintptr_t)gr->tensors & 15))) return AEW_E_ALIGN;
+    const aew_uw_chunk_t* ch = t ? t->chunks_host : gr->chunks_host;
+    const aew_uw_chunk_t* ch_dev = t ? t->chunks : gr->chunks;
+    const int64_t n_chunks = t ? t->n_chunks : gr->n_chunks, base = t ? t->base : gr->base;
     auto pad_end = [&](int64_t c) { return ch[c].off + ((ch[c].len + 3) & ~3); };
     // c0: the first chunk that ends (pad elements included) behind base; c1: the last one that starts in front of base + n
-    int64_t lo = 0, hi = t.n_chunks;
-    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (pad_end(mid) > t.base) hi = mid; else lo = mid + 1; }
+    int64_t lo = 0, hi = n_chunks;
+    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (pad_end(mid) > base) hi = mid; else lo = mid + 1; }
     const int64_t c0 = lo;
-    lo = c0, hi = t.n_chunks;
-    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (ch[mid].off < t.base + p.n) lo = mid + 1; else hi = mid; }
+    lo = c0, hi = n_chunks;
+    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (ch[mid].off < base + p.n) lo = mid + 1; else hi = mid; }
     const int64_t c1 = lo - 1;
     // the chunks (+ pads) must cover the range without a gap: an element outside every chunk would miss its update
-    if (c0 >= t.n_chunks || c1 < c0 || ch[c0].off > t.base || pad_end(c1) < t.base + p.n) return AEW_E_ARG;
+    if (c0 >= n_chunks || c1 < c0 || ch[c0].off > base || pad_end(c1) < base + p.n) return AEW_E_ARG;
     for (int64_t c = c0; c < c1; ++c)
         if (ch[c].len < 1 || ch[c].len > AEW_UW_CHUNK || pad_end(c) != ch[c + 1].off) return AEW_E_ARG;
     if (ch[c1].len < 1 || ch[c1].len > AEW_UW_CHUNK) return AEW_E_ARG;
-    if (t.zero) {
+    if (gr)                                            // every record the launch reads lies inside the device table
+        for (int64_t c = c0; c <= c1; ++c)
+            if (ch[c].tensor < 0 || ch[c].tensor >= gr->n_tensors) return AEW_E_ARG;
+    if (t && t->zero) {
         aew_zero_t z;
-        z.ptr = t.part; z.bytes = t.n_chunks * 16;
+        z.ptr = t->part; z.bytes = t->n_chunks * 16;
         if (int rc = launch_zero(z, st)) return rc;
     }
     const dim3 grid((unsigned)(c1 - c0 + 1));
-    auto k = p.clip ? (p.avg ? k_adam_uw<true, true> : k_adam_uw<true, false>)
-                    : (p.avg ? k_adam_uw<false, true> : k_adam_uw<false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, p, t.chunks, t.part, t.base, (int)c0);
+    auto k = p.clip ? (p.avg ? adam_uw_kernel<true, true>(t, gr) : adam_uw_kernel<true, false>(t, gr))
+                    : (p.avg ? adam_uw_kernel<false, true>(t, gr) : adam_uw_kernel<false, false>(t, gr));
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, p, ch_dev, t ? t->part : (double*)nullptr, gr ? gr->tensors : nullptr, base, (int)c0);
     return (int)hipGetLastError();
 }
 static int launch_update_ratio(const aew_update_ratio_t& p, hipStream_t st) {
@@ -2479,16 +2519,25 @@ static int launch_update_ratio(const aew_update_ratio_t& p, hipStream_t st) {
     hipLaunchKernelGGL(k_update_ratio, dim3((unsigned)p.n_tensors), dim3(256), 0, st, p);
     return (int)hipGetLastError();
 }
-static int launch_adam(const aew_adam_t& p, hipStream_t st) {
+static int adam_check(const aew_adam_t& p) {
     if (((uintptr_t)p.p | (uintptr_t)p.g | (uintptr_t)p.m | (uintptr_t)p.v) & 15) return AEW_E_ALIGN;
     if (p.avg) {
         if ((uintptr_t)p.avg & 15) return AEW_E_ALIGN;
         if (!(p.avg_rate >= 0.f && p.avg_rate <= 1.f)) return AEW_E_ARG;
     }
-    if (p.track) return launch_adam_tracked(p, st);
+    return 0;
+}
+static int launch_adam(const aew_adam_t& p, hipStream_t st) {
+    if (int rc = adam_check(p)) return rc;
+    if (p.track) return launch_adam_chunked(p, nullptr, st);
     auto k = p.clip ? (p.avg ? k_adam<true, true> : k_adam<true, false>) : (p.avg ? k_adam<false, true> : k_adam<false, false>);
     hipLaunchKernelGGL(k, dim3(cdiv64((p.n + 3) / 4, 256)), dim3(256), 0, st, p);
     return (int)hipGetLastError();
+}
+static int launch_adam_groups(const aew_adam_grouped_t& p, hipStream_t st) {
+    if (!p.groups || !p.adam.p || !p.adam.g || !p.adam.m || !p.adam.v) return AEW_E_ARG;
+    if (int rc = adam_check(p.adam)) return rc;
+    return launch_adam_chunked(p.adam, p.groups, st);
 }
 static int launch_swap(const aew_swap_t& p, hipStream_t st) {
     if (p.n < 0 || (p.n > 0 && (!p.a || !p.b))) return AEW_E_ARG;

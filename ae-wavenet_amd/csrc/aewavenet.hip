@@ -66,6 +66,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_ACCUM: return launch_accum(op.u.accum, st);
         case AEW_OP_CODE_LOOKUP: return launch_code_lookup(op.u.clk, st);
         case AEW_OP_CODE_RUNS: return launch_code_runs(op.u.crun, st);
+        case AEW_OP_ADAM_GROUPS: return launch_adam_groups(op.u.adamg, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -102,6 +103,9 @@ extern "C" int aew_sizeof(int which) {
         case 25: return (int)sizeof(aew_accum_t);      // (24 is left unused: it answers -1)
         case 27: return (int)sizeof(aew_code_lookup_t);      // (26 is left unused like 24)
         case 28: return (int)sizeof(aew_code_runs_t);
+        case 29: return (int)sizeof(aew_adam_tensor_t);
+        case 30: return (int)sizeof(aew_adam_groups_t);
+        case 31: return (int)sizeof(aew_adam_grouped_t);
         default: return -1;
     }
 }

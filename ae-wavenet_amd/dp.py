@@ -55,6 +55,13 @@ All-reduce schedule: allreduce_grads behind the fold that leaves the sum in the 
 backward_exchange(accum_last=True) folds each region in front of its reduce-scatter, so the overlap with the encoder
 backward is kept.  The statistics all-reduce (sync or async, finish_ema unchanged) runs on the group's z_sum / n_sum; the
 parameter all-gathers follow real optimizer steps only.
+
+Parameter groups (groups in the Adam keywords; aew_adam_groups_t): every range / shard / remainder call of a step carries
+the per-tensor records, so a tensor is stepped with its own rate and decay, or left alone, wherever a shard cut falls.  The
+clip norm covers the trainable tensors only.  All-reduce schedule: the first range call takes it over their element
+ranges, no collective.  Sharded schedule: a rank's shards and the replicated remainders are cut to those ranges
+(TrainEngine.trainable_ranges; more than 8: chained launches) - the ONE fp64 word and the second launch are unchanged.
+The gradients of frozen tensors are still exchanged: the backward plan does not know about them.
 """
 from __future__ import annotations
 
@@ -471,16 +478,20 @@ class DataParallel:
                 w.wait()
         self._guard_wait()
 
-    def _clip_norm_sharded(self, eng, regions, max_grad_norm: float, grad_scale: float):
+    def _clip_norm_sharded(self, eng, regions, max_grad_norm: float, grad_scale: float, groups=None):
         """The clip coefficient of a sharded step, once every region is reduced: the sum of squares of this rank's shards
         (one launch), all-reduced over the ranks as ONE fp64 word, then a finalizing launch that adds the replicated
         remainders (the same values on every rank: counted once; empty ranges where a region has none).  Every rank sums
-        the same words in the same order, so all hold the same coefficient bit for bit."""
+        the same words in the same order, so all hold the same coefficient bit for bit.
+        groups (an Adam keyword: parameter groups): the norm covers the trainable tensors only - the shards and the
+        remainders are cut to their element ranges (TrainEngine.trainable_ranges; more than 8: chained launches)."""
         shards, rems = [], []
         for a, b in regions:                             # the regions this step's backward_exchange reduced
             s, rem = self._split(a, b)
             shards.append((a + self.rank * s, a + (self.rank + 1) * s))
             rems.append((rem, b))
+        if groups is not None:
+            shards, rems = eng.trainable_ranges(groups, shards), eng.trainable_ranges(groups, rems)
         eng.grad_norm_step(shards, max_grad_norm, grad_scale, finalize=False)
         dist.all_reduce(eng.clip_sumsq[1:2], op=dist.ReduceOp.SUM, group=self.group)
         eng.grad_norm_step(rems, max_grad_norm, grad_scale, finalize=True, add_partial=True)
@@ -515,7 +526,7 @@ class DataParallel:
                 if key in st:
                     reduced(key, what)
             regions = ([(st["hi"], n), (lo, st["hi"])] if "dec_hi" in st else [(lo, n)]) + [(0, lo)]
-            self._clip_norm_sharded(eng, regions, clip, grad_scale)
+            self._clip_norm_sharded(eng, regions, clip, grad_scale, adam_kw.get("groups"))
             adam_kw = dict(adam_kw, norm_done=True)
         if "dec_hi" in st:                               # the upper layers' region: reduced under the rest of the chain
             reduced("dec_hi", "grads.decoder_hi")

@@ -453,6 +453,11 @@ class TrainEngine:
         tr.chunks, tr.chunks_host, tr.n_chunks = self.uw_chunks.data_ptr(), C.addressof(chunks), nch
         tr.part = self.uw_part.data_ptr()
         self._uw_zero, self._uw_stale = True, False
+        # ===== parameter groups (aew_adam_groups_t: runs only when adam_step() is given groups): the same chunk table;
+        # the device table of P tensor records exists from the first grouped step on (_groups_table)
+        gr = self.adam_groups = L.AdamGroups()                                # host record; the grouped Adam op holds its address
+        gr.chunks, gr.chunks_host, gr.n_chunks, gr.n_tensors = self.uw_chunks.data_ptr(), C.addressof(chunks), nch, P
+        self._tensor_span = [(ps.off[n], ps.off[n] + ru(ps.numel_of(n), 4)) for n in names]   # pad elements included
         self.ratio = Plan("ratio")
         ur = L.UpdateRatio()
         ur.part, ur.first, ur.n_tensors, ur.finalize = self.uw_part.data_ptr(), self.uw_first.data_ptr(), P, 1
@@ -470,6 +475,11 @@ class TrainEngine:
         self.avg_live = False             # adam_avg holds an average (started by a step, or restored by load_opt_state)
         self.averaged_in = False          # the average sits in ps.params, the raw parameters in adam_avg
         self.swap = Plan("swap")          # one op over ps.params / adam_avg, added with the buffer
+        # ===== parameter groups: the device table of tensor records, what it holds and the pinned ring it is sent through
+        self.adam_groups_tbl = None       # int32 [P][4] (aew_adam_tensor_t); allocated by the first grouped step
+        self.opt_groups = Plan("adam groups")   # one AEW_OP_ADAM_GROUPS op, added with the table
+        self._groups_sent = None          # the bytes the table holds (an upload happens only when they change)
+        self._groups_ring = None
         # ===== restart of dead codes (aew_vq_restart_t, vqvae-ema only): like the average, the counters, the pair list
         # and the op exist from the first restart_codes() on
         self.restart = Plan("restart")    # one op over bn.lin / emb / ema_numer / ema_denom, added with its buffers
@@ -953,12 +963,22 @@ class TrainEngine:
         multiple of 4, hi >= lo; empty ranges allowed, at most 8).  finalize=True: the total goes to clip_sumsq[0] and
         norm / coefficient / flag / skip count to clip_out (what adam_step(max_grad_norm=...) reads).  finalize=False:
         the sum goes to clip_sumsq[1] only - a sharded caller all-reduces that word and passes add_partial=True to the
-        finalizing launch, which adds it in.  No host synchronisation."""
+        finalizing launch, which adds it in.  No host synchronisation.
+        More than 8 ranges (the trainable tensors of a step with frozen ones, trainable_ranges): a chain of launches in
+        stream order, each over up to 8 ranges - all but the last leave their running sum in clip_sumsq[1]
+        (finalize = 0), the next adds it in (add_in)."""
         if not (max_grad_norm > 0):
             raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
+        K = L.GRAD_NORM_MAX_RANGES
+        if len(ranges) > K:
+            for i in range(0, len(ranges), K):
+                last = i + K >= len(ranges)
+                self.grad_norm_step(ranges[i:i + K], max_grad_norm, grad_scale, finalize=finalize and last,
+                                    add_partial=add_partial or i > 0)
+            return
         g = self.clip.array()[0].u.gnorm
-        if not 1 <= len(ranges) <= L.GRAD_NORM_MAX_RANGES:
-            raise ValueError("1..8 ranges")
+        if not 1 <= len(ranges):
+            raise ValueError("at least one range")
         for i in range(L.GRAD_NORM_MAX_RANGES):
             lo, hi = ranges[i] if i < len(ranges) else (0, 0)
             assert lo % 4 == 0 and 0 <= lo <= hi <= self.ps.numel
@@ -999,7 +1019,7 @@ class TrainEngine:
 
     def adam_step(self, lr: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                   lo: int = 0, hi: Optional[int] = None, count: bool = True, max_grad_norm: Optional[float] = None,
-                  norm_done: bool = False, track: bool = False, avg_rate: Optional[float] = None):
+                  norm_done: bool = False, track: bool = False, avg_rate: Optional[float] = None, groups=None):
         """One Adam step over the flat buffer, or over its element range [lo, hi) (multiples of 4): a
         data-parallel caller updates the decoder tail while the encoder gradients are still being
         reduced (`count=False` on all but the first range of a step).
@@ -1014,7 +1034,11 @@ class TrainEngine:
         avg_rate: the launch also moves the averaged weights (adam_avg, aew_adam_t.avg) of the elements it updates towards
         their new values, avg += avg_rate * (p_new - avg), avg_rate = 1 - decay of this step; the first averaged call of
         an engine without an average starts it from the parameters in front of that step.  A step the device skips leaves
-        the average alone; avg_steps advances with count like step_count.  None: the op carries no average."""
+        the average alone; avg_steps advances with count like step_count.  None: the op carries no average.
+        groups: one (lr, weight_decay, frozen) per parameter tensor in ps.names() order (aew_adam_groups_t): every tensor
+        is stepped with its own rate and decoupled decay, a frozen one is left alone, and the clip norm of the step covers
+        the trainable tensors only (trainable_ranges).  `lr` is then not read.  None: the op carries no record - the
+        launch of an engine without groups, grid and bits."""
         if self.averaged_in:
             raise L.AewError("adam_step() while the averaged weights are swapped in: the step would update the average "
                              "in the parameters' place (leave FusedAdam.averaged_weights() / call swap_averaged() first)")
@@ -1022,6 +1046,8 @@ class TrainEngine:
             raise ValueError(f"Invalid avg_rate: {avg_rate} (1 - decay, within [0, 1])")
         hi = self.ps.numel if hi is None else hi
         assert lo % 4 == 0 and (hi % 4 == 0 or hi == self.ps.numel) and 0 <= lo < hi <= self.ps.numel
+        if groups is not None:
+            self._groups_table(groups)                   # (refuses a malformed list; uploads the records when they changed)
         # every argument is checked by here: a refused call leaves the counters and the average as they were
         if avg_rate is not None:
             if not self.avg_live:
@@ -1035,8 +1061,10 @@ class TrainEngine:
             self._uw_zero = True
         self.weights_version += 1
         if max_grad_norm is not None and count and not norm_done:
-            self.grad_norm_step([(0, self.ps.numel)], max_grad_norm, grad_scale)
-        a = self.opt.array()[0].u.adam
+            self.grad_norm_step(self.trainable_ranges(groups), max_grad_norm, grad_scale)
+        # (with groups: the op of its own that carries the descriptor and the group record - the `opt` plan is untouched)
+        plan = self.opt if groups is None else self.opt_groups
+        a = plan.array()[0].u.adam if groups is None else plan.array()[0].u.adamg.adam
         a.p, a.g = self.ps.params.data_ptr() + 4 * lo, self.ps.grads.data_ptr() + 4 * lo
         a.m, a.v = self.adam_m.data_ptr() + 4 * lo, self.adam_v.data_ptr() + 4 * lo
         a.n = hi - lo
@@ -1051,12 +1079,72 @@ class TrainEngine:
             self.uw_track.base, self.uw_track.zero = lo, int(self._uw_zero)
             a.track = C.addressof(self.uw_track)
             self._uw_zero = False
-        self.opt.run(self._stream())
+        if groups is not None:
+            self.adam_groups.base = lo
+        plan.run(self._stream())
         if track:
             if lo == 0 and hi == self.ps.numel:
                 self.ratio_step()
             else:
                 self._uw_stale = True
+
+    # ---- parameter groups: the device table of tensor records and the element ranges of the trainable tensors
+    GROUPS_RING_SLOTS = 4
+
+    def _groups_table(self, groups):
+        """The device table of P aew_adam_tensor_t records for `groups` = [(lr, weight_decay, frozen)] in ps.names()
+        order.  Allocated at its first use; uploaded only when a record differs from what the table holds, in stream
+        order and without a host-device synchronisation: the bytes go through a ring of GROUPS_RING_SLOTS pinned slots,
+        and a slot is rewritten only when the copy that last read it is complete (in practice long ago: four changes of
+        the table back)."""
+        raw = L.adam_tensor_records(groups, self.uw_n)
+        P = self.uw_n
+        if self.adam_groups_tbl is None:
+            self.adam_groups_tbl = self.ws.alloc("adam.groups", 4 * P, torch.int32)
+            self.adam_groups.tensors = self.adam_groups_tbl.data_ptr()
+            ag = L.AdamGrouped()                         # the op: `opt`'s descriptor (re-addressed per call) + the record
+            ag.adam = self.opt.array()[0].u.adam          # (a copy: the guard word and the buffers)
+            ag.groups = C.addressof(self.adam_groups)
+            self.opt_groups.add(L.OP_ADAM_GROUPS, ag, "adam (groups)", TAG_ADAM)
+        if raw == self._groups_sent:
+            return
+        src = torch.frombuffer(bytearray(raw), dtype=torch.int32)
+        if self.device.type == "cuda":
+            ring = self._groups_ring
+            if ring is None:
+                n = self.GROUPS_RING_SLOTS
+                ring = self._groups_ring = {"buf": torch.zeros(n, 4 * P, dtype=torch.int32).pin_memory(),
+                                            "ev": [torch.cuda.Event() for _ in range(n)], "next": 0}
+            slot = ring["next"]
+            ring["next"] = (slot + 1) % self.GROUPS_RING_SLOTS
+            ring["ev"][slot].synchronize()               # (returns at once for an event that was never recorded)
+            ring["buf"][slot].copy_(src)
+            self.adam_groups_tbl[:4 * P].copy_(ring["buf"][slot], non_blocking=True)
+            ring["ev"][slot].record()
+        else:
+            self.adam_groups_tbl[:4 * P].copy_(src)
+        self._groups_sent = raw
+
+    def trainable_ranges(self, groups, within=None):
+        """Element ranges [(lo, hi)] of the flat buffer, ascending and merged, that the tensors `groups` does not freeze
+        cover (their pad elements included; None: the whole buffer) - what the clip norm of a grouped step is taken over.
+        within: [(a, b)] - the ranges are cut to these (a sharded caller's shards and remainders), in their order.  Never
+        empty: (0, 0) stands for "nothing"."""
+        if groups is None:
+            merged = [(0, self.ps.numel)]
+        else:
+            assert len(groups) == self.uw_n
+            merged = []
+            for (lo, hi), g in zip(self._tensor_span, groups):
+                if g[2] or hi == lo:
+                    continue
+                if merged and merged[-1][1] == lo:
+                    merged[-1] = (merged[-1][0], hi)
+                else:
+                    merged.append((lo, hi))
+        if within is not None:
+            merged = [(max(lo, a), min(hi, b)) for a, b in within for lo, hi in merged if max(lo, a) < min(hi, b)]
+        return merged or [(0, 0)]
 
     def _avg_buffer(self) -> torch.Tensor:
         """adam_avg, allocated (and the swap plan completed) at its first use; avg_live becomes True only behind a call."""

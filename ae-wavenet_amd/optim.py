@@ -6,6 +6,8 @@ Drop-in for the harness: `ss.optim = FusedAdam(model, lr)` in place of `t.optim.
 from __future__ import annotations
 
 import contextlib
+import fnmatch
+import math
 
 import numpy as np
 import torch
@@ -38,6 +40,64 @@ def _check_flag(name, b):
     if not isinstance(b, (bool, int)) or b not in (0, 1):
         raise ValueError(f"Invalid {name}: {b!r} (True or False)")
     return bool(b)
+
+
+def _check_rate(name, x):
+    try:                                                     # whatever float() takes, like max_grad_norm
+        f = float(x)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if isinstance(x, bool) or not (math.isfinite(f) and f >= 0.0):
+        raise ValueError(f"Invalid {name}: {x!r} (a finite number, not negative)")
+    return f
+
+
+def _check_frozen(b):
+    if not isinstance(b, bool):
+        raise ValueError(f"Invalid frozen: {b!r} (True or False)")
+    return b
+
+
+GROUP_KEYS = ("params", "lr", "weight_decay", "frozen")
+
+
+def match_groups(names, groups):
+    """groups = [dict(params=name | fnmatch pattern | list of them, lr=, weight_decay=, frozen=)] over the dotted parameter
+    names -> [(indices into names, options)] per entry, in order: the first entry that matches a tensor takes it; the
+    tensors no entry matches come last, with no options (the constructor's).  ValueError: an unknown key, no `params`, a
+    pattern that matches no name at all, a rejected value."""
+    taken, out = {}, []
+    for k, entry in enumerate(groups):
+        if not isinstance(entry, dict) or "params" not in entry:
+            raise ValueError(f"groups[{k}]: a dict with a `params` key, got {entry!r}")
+        for key in entry:
+            if key not in GROUP_KEYS:
+                raise ValueError(f"groups[{k}]: unknown key {key!r} (one of {GROUP_KEYS})")
+        pats = entry["params"]
+        pats = [pats] if isinstance(pats, str) else list(pats) if isinstance(pats, (list, tuple)) else []
+        if not pats or not all(isinstance(p, str) for p in pats):
+            raise ValueError(f"groups[{k}]: params must be a name, a pattern or a list of them, got {entry['params']!r}")
+        opts = {}
+        if "lr" in entry:
+            opts["lr"] = _check_rate("lr", entry["lr"])
+        if "weight_decay" in entry:
+            opts["weight_decay"] = _check_rate("weight_decay", entry["weight_decay"])
+        if "frozen" in entry:
+            opts["frozen"] = _check_frozen(entry["frozen"])
+        mine = []
+        for pat in pats:
+            hit = [i for i, n in enumerate(names) if fnmatch.fnmatchcase(n, pat)]
+            if not hit:
+                raise ValueError(f"groups[{k}]: pattern {pat!r} matches no parameter")
+            for i in hit:
+                if i not in taken:
+                    taken[i] = k
+                    mine.append(i)
+        out.append((sorted(mine), opts))
+    rest = [i for i in range(len(names)) if i not in taken]
+    if rest:
+        out.append((rest, {}))
+    return out
 
 
 def ema_decay_at(ema_decay: float, t: int, warmup: bool = True) -> float:
@@ -86,16 +146,69 @@ class FusedAdam(torch.optim.Optimizer):
     no-op: no launch, step count, moments, average and update-ratio record keep their bits.  Behind the k-th backward the
     gradient buffer holds the group's SUM and the step runs with grad_scale / k: the optimizer, the clip norm, the update
     ratios and the averaged weights see the MEAN of the micro-batch gradients - do not also divide the loss by k.  The
-    state_dict gains no key."""
+    state_dict gains no key.
+
+    Parameter groups (`groups`, `weight_decay`, `requires_grad`): per-tensor learning rate, decoupled weight decay
+    (torch.optim.AdamW: p *= 1 - lr * weight_decay in front of the Adam update) and frozen tensors, inside the same
+    launch (aew_adam_groups_t) - so clipping, the update ratios, the averaged weights, accumulation and both data-parallel
+    schedules go on working.  groups = [dict(params=name | fnmatch pattern | list of them, lr=, weight_decay=, frozen=)]
+    over `model.named_parameters()`: the first entry that matches a tensor takes it, the tensors no entry matches form a
+    last group with the constructor's lr / weight_decay.  `param_groups` is the torch list of these groups; step() reads
+    every group's lr / weight_decay / frozen at each call, so torch.optim.lr_scheduler.* and hand-written schedules work
+    per group.  `p.requires_grad_(False)` freezes a tensor too, with or without groups; it is read at each step().  A
+    frozen tensor, its moments and its average keep their bits; the clip norm covers the trainable tensors only
+    (clip_grad_norm_ over them).  betas, eps, max_grad_norm, track_update_ratio, ema_decay and ema_warmup stay optimizer-
+    wide and are read from param_groups[0].  DEVIATIONS from torch: ONE step count for all tensors (a tensor unfrozen later
+    continues with the global step and its old moments, where torch keeps a step per parameter and no state for a frozen
+    one), and the backward still computes the gradients of frozen tensors (`.grad` shows them).  With no groups,
+    weight_decay = 0 and nothing frozen the step is the launch of an optimizer without any of this, grid and bits, and
+    state_dict() its dictionary key for key."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_grad_norm=None,
-                 track_update_ratio=False, ema_decay=None, ema_warmup=True):
+                 track_update_ratio=False, ema_decay=None, ema_warmup=True, weight_decay=0.0, groups=None):
         defaults = dict(lr=lr, betas=betas, eps=eps, max_grad_norm=_check_max_grad_norm(max_grad_norm),
                         track_update_ratio=_check_flag("track_update_ratio", track_update_ratio),
-                        ema_decay=_check_ema_decay(ema_decay), ema_warmup=_check_flag("ema_warmup", ema_warmup))
+                        ema_decay=_check_ema_decay(ema_decay), ema_warmup=_check_flag("ema_warmup", ema_warmup),
+                        weight_decay=_check_rate("weight_decay", weight_decay), frozen=False)
         self.model = model
-        super().__init__(list(model.parameters()), defaults)
+        named = list(model.named_parameters())
+        self._index = {id(p): i for i, (_, p) in enumerate(named)}        # position in named_parameters() = ps.names() order
+        if groups is None:
+            super().__init__([p for _, p in named], defaults)
+        else:
+            _check_rate("lr", lr)
+            super().__init__([dict(opts, params=[named[i][1] for i in idx])
+                              for idx, opts in match_groups([n for n, _ in named], groups)], defaults)
         self.grad_scale = grad_scale
+
+    def _tensor_records(self):
+        """[(lr, weight_decay, frozen)] per tensor in named_parameters() order as the groups say NOW, or None where they
+        say nothing a plain step does not do: one lr, no decay, nothing frozen."""
+        plain, lr0 = True, self.param_groups[0]["lr"]
+        if all(g["lr"] == lr0 and g.get("weight_decay", 0.0) == 0 and not g.get("frozen", False) for g in self.param_groups) \
+                and all(p.requires_grad for g in self.param_groups for p in g["params"]):
+            return None                                          # (the common case, kept short: it runs at every step)
+        rec = [None] * len(self._index)
+        for g in self.param_groups:
+            lr, wd, fr = g["lr"], g.get("weight_decay", 0.0), g.get("frozen", False)
+            for p in g["params"]:
+                f = bool(fr) or not p.requires_grad
+                rec[self._index[id(p)]] = (lr, wd, f)
+                plain = plain and not f
+            plain = plain and wd == 0 and lr == lr0
+        if plain:
+            return None
+        for g in self.param_groups:                              # (a schedule may have put anything there)
+            _check_rate("lr", g["lr"]); _check_rate("weight_decay", g.get("weight_decay", 0.0))
+            _check_frozen(g.get("frozen", False))
+        if any(r is None for r in rec):
+            raise ValueError("param_groups no longer hold every parameter of the model")
+        return [(float(lr), float(wd), f) for lr, wd, f in rec]
+
+    def _grouped(self):
+        """Does the state dictionary need more than one plain group?"""
+        return len(self.param_groups) > 1 or any(g.get("weight_decay", 0.0) != 0 or g.get("frozen", False)
+                                                 for g in self.param_groups)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -120,6 +233,9 @@ class FusedAdam(torch.optim.Optimizer):
         kw = {}
         if d is not None:                                        # (off: the calls below are the ones of an optimizer without it)
             kw["avg_rate"] = ema_rate_at(d, eng.avg_steps, bool(g.get("ema_warmup", True)))
+        rec = self._tensor_records()
+        if rec is not None:                                      # (plain: the calls below are the ones of an optimizer without groups)
+            kw["groups"] = rec
         # (data parallel, sharded: Adam on this rank's shards of the reduce-scattered gradient, then all-gather)
         self.model._schedule.step(eng, g["lr"], scale, betas=g["betas"], eps=g["eps"], max_grad_norm=c, track=track, **kw)
 
@@ -231,7 +347,24 @@ class FusedAdam(torch.optim.Optimizer):
                 a = av.avg.detach().cpu()
                 for i, (n, o, k, shp) in enumerate(lay):
                     state[i]["param_avg"] = a[o:o + k].reshape(shp).clone()
-        return {"state": state, "param_groups": [group]}
+        if not self._grouped():
+            return {"state": state, "param_groups": [group]}
+        # several groups: torch's format - `params` holds the tensors' positions in model.parameters() order (what a
+        # one-group file numbers them by), every group its lr / weight_decay, `frozen` where set; the optimizer-wide
+        # extras stay in group 0.  A stock torch.optim.AdamW built with the same grouping loads it.
+        decays = any(gg.get("weight_decay", 0.0) != 0 for gg in self.param_groups)
+        out = []
+        for k, gg in enumerate(self.param_groups):
+            one = dict(group) if k == 0 else {key: group[key] for key in ("betas", "eps", "amsgrad", "maximize", "foreach",
+                                                                           "capturable", "differentiable", "fused")}
+            one["lr"], one["weight_decay"] = gg["lr"], gg.get("weight_decay", 0.0)
+            one["params"] = [self._index[id(p)] for p in gg["params"]]
+            if gg.get("frozen", False):
+                one["frozen"] = True
+            if decays:
+                one["decoupled_weight_decay"] = True
+            out.append(one)
+        return {"state": state, "param_groups": out}
 
     def load_state_dict(self, state_dict):
         if self.model._engine is not None and self.model._engine.averaged_in:
@@ -242,8 +375,29 @@ class FusedAdam(torch.optim.Optimizer):
         if len(order) != len(lay):
             raise ValueError(f"optimizer state has {len(order)} parameters, the model {len(lay)}")
         g0 = groups[0]
-        # the group's options; one that is absent (a torch.optim.Adam checkpoint) keeps the constructor's
-        opts = {k: tuple(g0[k]) if k == "betas" else g0[k] for k in ("lr", "betas", "eps") if k in g0}
+        # per-group options: a file with one group leaves them as the constructor set them (its lr is taken where this
+        # optimizer has one group too); a file with several must cut the parameters the way this optimizer does
+        mine = [[self._index[id(p)] for p in g["params"]] for g in self.param_groups]
+        per_group = []
+        if len(groups) > 1:
+            if sorted(order) != list(range(len(lay))):
+                raise ValueError(f"optimizer state with {len(groups)} groups must number the parameters 0..{len(lay) - 1} once each")
+            by_set = {frozenset(idx): k for k, idx in enumerate(mine)}
+            for k, g in enumerate(groups):
+                hit = by_set.get(frozenset(g["params"]))
+                if hit is None or len(groups) != len(mine):
+                    names = [lay[i][0] for i in g["params"][:3]]
+                    raise ValueError(f"optimizer state: group {k} of the file ({len(g['params'])} parameters: {names} ...) is "
+                                     f"no group of this optimizer ({len(mine)} groups, the file {len(groups)})")
+                o = {"frozen": _check_frozen(bool(g.get("frozen", False)))}
+                if "lr" in g:
+                    o["lr"] = _check_rate("lr", g["lr"])
+                if "weight_decay" in g:
+                    o["weight_decay"] = _check_rate("weight_decay", g["weight_decay"])
+                per_group.append((hit, o))
+        # the optimizer-wide options; one that is absent (a torch.optim.Adam checkpoint) keeps the constructor's
+        opts = {k: tuple(g0[k]) if k == "betas" else g0[k] for k in (("lr", "betas", "eps") if len(mine) == 1 else ("betas", "eps"))
+                if k in g0}
         if g0.get("max_grad_norm") is not None:
             opts["max_grad_norm"] = g0["max_grad_norm"]
         if g0.get("track_update_ratio") is not None:
@@ -258,7 +412,7 @@ class FusedAdam(torch.optim.Optimizer):
             s = st.get(idx, st.get(str(idx)))
             if s is None:
                 continue
-            n, o, k, shp = lay[pos]
+            n, o, k, shp = lay[idx if len(groups) > 1 else pos]
             if tuple(s["exp_avg"].shape) != shp:
                 raise ValueError(f"exp_avg of parameter {n} has shape {tuple(s['exp_avg'].shape)}, expected {shp}")
             m[o:o + k] = s["exp_avg"].detach().float().cpu().reshape(-1)
@@ -273,6 +427,8 @@ class FusedAdam(torch.optim.Optimizer):
         if n_avg not in (0, len(order)):
             raise ValueError(f"optimizer state has param_avg for {n_avg} of {len(order)} parameters")
         self.param_groups[0].update(opts)                        # every check has passed by here
+        for hit, o in per_group:
+            self.param_groups[hit].update(o)
         if not found:
             return
         # the averaged weights: restored with their step count; a state without them (torch.optim.Adam's own, or written

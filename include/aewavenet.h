@@ -601,6 +601,46 @@ typedef struct {                 /* HOST record aew_adam_t.track points at (read
     int32_t pad_;
 } aew_uw_track_t;
 
+/* ---------------------------------------------------------------------------------------
+ * Parameter groups (appended to ABI 28; AEW_OP_ADAM_GROUPS, aew_adam_grouped_t below; aew_sizeof 29 / 30 / 31): per-tensor learning rate, decoupled weight decay and frozen
+ * tensors inside the Adam launch - what torch.optim.AdamW with param groups and requires_grad_(False) do on the host.
+ * Tensor t of the chunk table (aew_uw_chunk_t.tensor) carries a record (lr_t, decay_t, frozen_t).  The host computes
+ * decay_t = 1 - lr_t * weight_decay_t in double and rounds it to fp32 ONCE.  For every element of tensor t, the pad
+ * elements behind it up to the next multiple of 4 included:
+ *   frozen_t != 0 : p, m, v and avg are not written; g, m, v and avg are not read.  With aew_adam_t.track the launch reads
+ *                   p: the chunk adds p^2 to its weight sum and 0 to its update sum (update norm 0, the true weight norm,
+ *                   ratio 0).  Without it a frozen chunk issues no memory access at all.
+ *   else          : p1 = (decay_t == 1.0f) ? p : __fmul_rn(p, decay_t)         - decoupled decay FIRST (one rounding)
+ *                   then the element update of every Adam launch on (p1, g, m, v) with step = lr_t / bc1 in place of
+ *                   lr / bc1: torch.optim.AdamW.  bc1 / bc2 are those of the optimizer's ONE step count.
+ *                   DEVIATION from torch, which keeps a step per parameter and no state for a frozen one: a tensor that
+ *                   is unfrozen later continues with the global step and the moments it had when it was frozen.
+ *   tracking      : the tracked p_old is the value in front of the decay (the update norm includes the decay's part).
+ *   average       : avg moves towards p_new as in every launch; a frozen tensor's average keeps its bits.
+ *   skipped steps : guard non-zero / clip[1] != 0 leave everything alone, as in every launch.
+ * Clipping: the norm behind clip[0] is the caller's - it runs aew_grad_norm_t over the element ranges of the non-frozen
+ * tensors only (torch.nn.utils.clip_grad_norm_ over the trainable parameters), in chained launches (finalize = 0 /
+ * add_in) where there are more than AEW_GRAD_NORM_MAX_RANGES ranges.
+ * Launch: one block per chunk that overlaps [base, base + n), the shape of the tracked launch; the block reads its tensor's
+ * record once (uniform: scalar registers).  A range may begin or end inside a chunk at a multiple of 4; the n % 4 elements
+ * at the very end of the buffer follow the tracked launch's rule.  aew_adam_t.lr is not read.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    float lr;                    /* lr_t                                                                                   */
+    float decay;                 /* (float)(1.0 - (double)lr_t * (double)weight_decay_t); 1.0f = no decay, no multiply      */
+    int32_t frozen;              /* != 0: the tensor is left alone                                                          */
+    int32_t pad_;
+} aew_adam_tensor_t;
+typedef struct {                 /* HOST record aew_adam_grouped_t.groups points at (read at launch time only)             */
+    const aew_uw_chunk_t* chunks;        /* device copy of the chunk table (aew_uw_chunks)                                 */
+    const aew_uw_chunk_t* chunks_host;   /* host copy: the launcher finds the chunks that overlap [base, base + n) in it    */
+    int64_t n_chunks;
+    const aew_adam_tensor_t* tensors;    /* device [n_tensors], 16-byte aligned; read when the kernel runs                  */
+    int32_t n_tensors;           /* every chunk's `tensor` the launch covers must lie in [0, n_tensors): AEW_E_ARG           */
+    int32_t pad_;
+    int64_t base;                /* flat offset of aew_adam_t.p[0] (a multiple of 4)                                        */
+} aew_adam_groups_t;
+
 typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.optim.Adam defaults,
                                     checkpoint.py:49-50)                                      */
     float* p; const float* g; float* m; float* v;
@@ -643,6 +683,19 @@ typedef struct {                 /* fused Adam over a flat fp32 buffer (torch.op
  * their average (aew_adam_t.avg) around sampling / evaluation.  n = 0 is a no-op.
  * AEW_E_ARG: n < 0, a NULL pointer with n > 0, buffers that overlap; AEW_E_ALIGN: a or b not 16-byte aligned. */
 typedef struct { float* a; float* b; int64_t n; } aew_swap_t;
+
+/* The Adam launch with parameter groups (appended to ABI 28; AEW_OP_ADAM_GROUPS, aew_sizeof 31): `adam` is the descriptor
+ * of AEW_OP_ADAM, every field with its meaning there (clip, track, avg included; `lr` is not read), `groups` the HOST
+ * record of aew_adam_groups_t above: per-tensor lr / decay / frozen, one block per chunk like a launch with `track`.
+ * aew_adam_t itself is unchanged, so a plan built from AEW_OP_ADAM ops is byte for byte what it was.
+ * Refused before any launch under the conditions of `track`: AEW_E_ARG for a NULL `groups`, chunks that do not cover
+ * [base, base + n), a NULL table / tensors, base < 0, a chunk whose tensor lies outside the table, and - with adam.track
+ * also set - a track record that names another table or base; AEW_E_ALIGN for base % 4 or tensors % 16, and whatever
+ * AEW_OP_ADAM refuses.  A refused call writes nothing. */
+typedef struct {
+    aew_adam_t adam;
+    const aew_adam_groups_t* groups;
+} aew_adam_grouped_t;
 
 /* Gradient accumulation (appended to ABI 28; aew_sizeof 25 - index 24 stays unused, it answers -1): fold the buffer a backward just wrote into a running sum, k micro-batches per optimizer
  * step.  One pass, float4 loads and stores with a scalar tail, a grid that depends on n only; plain vector loads and stores,
@@ -1017,7 +1070,7 @@ enum {
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
-    AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS
+    AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1045,14 +1098,14 @@ typedef struct {
         aew_moments_t mom; aew_gemm_tn_group_t tng; aew_nt_chain_t chain; aew_grad_norm_t gnorm; aew_update_ratio_t ratio;
         aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
         aew_grad_welford_t gwel; aew_seg_select_t ssel; aew_accum_t accum;
-        aew_code_lookup_t clk; aew_code_runs_t crun;
+        aew_code_lookup_t clk; aew_code_runs_t crun; aew_adam_grouped_t adamg;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs (24 and 26 are unused: -1) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped (24 and 26 are unused: -1) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
