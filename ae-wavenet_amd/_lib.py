@@ -24,7 +24,7 @@ EF_OUT2_COPY = 1 << 10
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
- OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS) = range(1, 38)
+ OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS) = range(1, 39)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -252,6 +252,23 @@ class EvalAcc(C.Structure):
                 ("Q", i32), ("K", i32), ("loss", vp), ("acc", vp), ("hist", vp), ("finalize", i32), ("pad_", i32), ("out", vp)]
 
 
+EVAL_GACC_N, EVAL_GOUT_N, EVAL_TOUT_N = 8, 12, 16
+# finalize's gout[g][i] / tout[i] by name (aew_eval_groups_t; Evaluator.by_group() / information() hand them out under these)
+EVAL_GOUT_NAMES = ("windows", "positions", "nll", "bits_per_sample", "top1", "tprb", "dist", "queries", "code_entropy",
+                   "code_perplexity", "codes_used")
+EVAL_TOUT_NAMES = ("n", "code_entropy", "group_entropy", "cond_entropy", "mutual_information", "mutual_information_mm",
+                   "mi_over_group_entropy", "mi_over_code_entropy", "cells", "groups_used", "codes_used", "dropped_windows",
+                   "batches")
+
+
+class EvalGroups(C.Structure):
+    """aew_eval_groups_t: fold one evaluated batch into the per-group record and the (group, code) table / finalize them."""
+    _fields_ = [("nll", vp), ("ptgt", vp), ("wav", vp), ("wav_pitch", i32), ("tgt_off", i32), ("B", i32), ("w", i32),
+                ("amax", vp), ("logits", vp), ("bs", i64), ("pitch", i32), ("n_quant", i32), ("ind", vp), ("dist", vp),
+                ("Qw", i32), ("K", i32), ("group", vp), ("G", i32), ("finalize", i32), ("gacc", vp), ("ghist", vp),
+                ("gtot", vp), ("win", vp), ("gout", vp), ("tout", vp), ("scratch", vp)]
+
+
 class WindowGather(C.Structure):
     """aew_window_gather_t: cut the next batch's windows out of the device-resident corpus (corpus.DeviceCorpus)."""
     _fields_ = [("snd", vp), ("n_snd", i64), ("snd_bytes", i32), ("B", i32), ("starts", vp), ("voices", vp), ("N", i64),
@@ -352,7 +369,7 @@ class _OpU(C.Union):
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
-                ("adamg", AdamGrouped)]
+                ("adamg", AdamGrouped), ("evg", EvalGroups)]
 
 
 class Op(C.Structure):
@@ -367,7 +384,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
-            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg"}
+            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg"}
 
 
 
@@ -498,7 +515,7 @@ def load():
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
-                       (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped)):
+                       (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

@@ -3,6 +3,7 @@
 
     zq = lookup(emb, codes)                       # AEW_OP_CODE_LOOKUP: codebook rows of a code tensor
     units, lengths, n_runs = code_runs(codes)     # AEW_OP_CODE_RUNS: frames -> units (run-length collapse)
+    info = voice_information(codes, voice, K, n_voices)   # AEW_OP_EVAL_GROUPS, codes-only: I(code; voice) of given codes
 
 Both run as one-op plans on torch's current stream, take any device tensor (rows of any length: the concatenated codes
 of an utterance) and never synchronise with the host.  `model.encode()` / `model.decode()` / `model.convert()`
@@ -12,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -70,6 +71,44 @@ def code_runs(codes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Te
     cr.units, cr.lengths, cr.n_runs, cr.B, cr.N = units.data_ptr(), lengths.data_ptr(), n_runs.data_ptr(), B, N
     _run(L.OP_CODE_RUNS, cr, "code runs", c.device)
     return (units[0], lengths[0], n_runs[0]) if one else (units, lengths, n_runs)
+
+
+def voice_information(codes: torch.Tensor, voice: torch.Tensor, K: int, n_voices: int) -> Dict[str, torch.Tensor]:
+    """How much of the voice the codes carry, for codes that come from `model.encode()` or from disk: codes int64
+    (B, E) with voice (B,) - one voice per row - or flat (N,) with voice (N,) - one per code; K codebook entries,
+    n_voices voices.  One codes-only accumulate (AEW_OP_EVAL_GROUPS) into a fresh record plus one finalize; returns what
+    `Evaluator.information()` returns - 0-d float32 device tensors n, code_entropy, group_entropy, cond_entropy,
+    mutual_information, mutual_information_mm (Miller-Madow corrected, not clamped), mi_over_group_entropy,
+    mi_over_code_entropy, cells, groups_used, codes_used, dropped_windows, batches - plus `counts`, the exact (n_voices, K)
+    int64 table.  A code outside [0, K) is not counted; a row whose voice lies outside [0, n_voices) is dropped (and
+    counted in dropped_windows).  One workgroup serves one row, so the (B, E) form is the one to use for long
+    sequences.  No host synchronisation."""
+    if codes.dtype != torch.int64 or codes.dim() not in (1, 2) or codes.numel() < 1:
+        raise L.AewError("voice_information(): int64 codes (B, E) or (N,) expected")
+    c = codes.unsqueeze(1) if codes.dim() == 1 else codes
+    B, E = c.shape
+    if tuple(voice.shape) != (B,):
+        raise L.AewError(f"voice_information(): voice ({B},) expected (one per row of codes), got {tuple(voice.shape)}")
+    K, G = int(K), int(n_voices)
+    if K < 1 or G < 1:
+        raise L.AewError("voice_information(): K and n_voices must be at least 1")
+    dev = c.device
+    c, v = c.contiguous(), voice.to(device=dev, dtype=torch.int64).contiguous()
+    rec = torch.zeros(G * L.EVAL_GACC_N + 4 + 4 * B + K + 4 * G, dtype=torch.float64, device=dev)   # gacc | gtot | win | scratch
+    ghist = torch.zeros(G, K, dtype=torch.int32, device=dev)                                        # (uint32 counts)
+    out = torch.empty(G * L.EVAL_GOUT_N + L.EVAL_TOUT_N, dtype=torch.float32, device=dev)
+    ev = L.EvalGroups()
+    ev.B, ev.ind, ev.Qw, ev.K, ev.group, ev.G = B, c.data_ptr(), E, K, v.data_ptr(), G
+    ev.gacc, ev.gtot = rec.data_ptr(), rec.data_ptr() + 8 * G * L.EVAL_GACC_N
+    ev.win, ev.scratch = ev.gtot + 8 * 4, ev.gtot + 8 * (4 + 4 * B)
+    ev.ghist, ev.gout, ev.tout = ghist.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * G * L.EVAL_GOUT_N
+    _run(L.OP_EVAL_GROUPS, ev, "voice information (accumulate)", dev)
+    ev.finalize = 1
+    _run(L.OP_EVAL_GROUPS, ev, "voice information (finalize)", dev)
+    tout = out[G * L.EVAL_GOUT_N:]
+    info = {name: tout[i] for i, name in enumerate(L.EVAL_TOUT_NAMES)}
+    info["counts"] = ghist.to(torch.int64) & 0xffffffff
+    return info
 
 
 # ---- mu-law companding of the decoder's samples (amplitudes in [-1, 1] -> n_quant integer values) ---------------------

@@ -8,6 +8,7 @@
 #include "aew_corpus.hip"
 #include "aew_gradstats.hip"
 #include "aew_codes.hip"
+#include "aew_evalgroups.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -67,6 +68,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_CODE_LOOKUP: return launch_code_lookup(op.u.clk, st);
         case AEW_OP_CODE_RUNS: return launch_code_runs(op.u.crun, st);
         case AEW_OP_ADAM_GROUPS: return launch_adam_groups(op.u.adamg, st);
+        case AEW_OP_EVAL_GROUPS: return launch_eval_groups(op.u.evg, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -106,6 +108,7 @@ extern "C" int aew_sizeof(int which) {
         case 29: return (int)sizeof(aew_adam_tensor_t);
         case 30: return (int)sizeof(aew_adam_groups_t);
         case 31: return (int)sizeof(aew_adam_grouped_t);
+        case 32: return (int)sizeof(aew_eval_groups_t);
         default: return -1;
     }
 }

@@ -65,7 +65,7 @@ The gradients of frozen tensors are still exchanged: the backward plan does not 
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.distributed as dist
@@ -112,6 +112,10 @@ class LocalSchedule:
     def eval_finish(self, eng):
         return eng.eval_finish()
 
+    def eval_group_finish(self, eng):
+        gout, tout = eng.eval_group_finish()
+        return gout.clone(), tout.clone()
+
 
 class AllReduceSchedule(LocalSchedule):
     """The backward leaves the fully reduced gradient in every .grad, every rank runs the whole Adam step.  The
@@ -137,6 +141,9 @@ class AllReduceSchedule(LocalSchedule):
 
     def eval_finish(self, eng):
         return self.dp.eval_finish(eng)
+
+    def eval_group_finish(self, eng):
+        return self.dp.eval_group_finish(eng)
 
 
 class ShardedSchedule(AllReduceSchedule):
@@ -686,6 +693,42 @@ class DataParallel:
         out = eng.eval_finish().clone()
         eng.eval_acc.copy_(own[0])
         eng.eval_hist.copy_(own[1])
+        return out
+
+    def sum_eval_group_record(self, gacc: torch.Tensor, gtot: torch.Tensor, ghist: Optional[torch.Tensor]):
+        """The ranks' grouped evaluation records (aew_eval_groups_t: gacc float64 [G][8], gtot float64 [4], ghist uint32
+        counts held as int32 [G][K], or None without a codebook) summed in ONE all-reduce.  COLLECTIVE.  Like
+        sum_eval_record: the counts are widened to int64 and travel in the float64 buffer of the sums, where integers
+        under 2^53 are exact.  Returns (gacc, gtot, ghist int64 or None); the arguments are left alone."""
+        na, nt = gacc.numel(), gtot.numel()
+        nh = ghist.numel() if ghist is not None else 0
+        buf = self._buf("eval_groups", 0, na + nt + nh, torch.float64, gacc.device)
+        buf[:na].copy_(gacc.reshape(-1))
+        buf[na:na + nt].copy_(gtot)
+        if nh:
+            buf[na + nt:].copy_(ghist.reshape(-1).to(torch.int64) & 0xffffffff)
+        if not self._solo():
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
+        return (buf[:na].clone().view_as(gacc), buf[na:na + nt].clone(),
+                buf[na + nt:].to(torch.int64).view_as(ghist) if nh else None)
+
+    def eval_group_finish(self, eng):
+        """TrainEngine.eval_group_finish over the sum of every rank's grouped record.  COLLECTIVE: like eval_finish, the
+        summed record takes the place of this rank's own for the finalize launch and the rank's own is put back behind
+        it.  Counts saturate at 2^32 - 1.  Returns copies of (gout, tout)."""
+        own = eng.eval_gacc.clone(), eng.eval_gtot.clone(), (eng.eval_ghist.clone() if eng.eval_ghist is not None else None)
+        gacc, gtot, ghist = self.sum_eval_group_record(*own)
+        eng.eval_gacc.copy_(gacc)
+        eng.eval_gtot.copy_(gtot)
+        if ghist is not None:
+            ghist = ghist.clamp_(max=0xffffffff)
+            eng.eval_ghist.copy_(torch.where(ghist >= 2 ** 31, ghist - 2 ** 32, ghist))      # back to unsigned words in int32
+        gout, tout = eng.eval_group_finish()
+        out = gout.clone(), tout.clone()
+        eng.eval_gacc.copy_(own[0])
+        eng.eval_gtot.copy_(own[1])
+        if ghist is not None:
+            eng.eval_ghist.copy_(own[2])
         return out
 
     def attach(self, model, sharded: bool = False, bf16_grads: bool = False):

@@ -491,6 +491,13 @@ class TrainEngine:
         self.act_epoch = 0                # bumped by everything that overwrites the activations a backward reads
         self.eval_a = self.eval_b = self.eval_fin = None      # the forward plans minus EVAL_DROP (+ loss, accumulate); finalize
         self.eval_acc = self.eval_hist = self.eval_out = self.eval_loss = None
+        # ===== evaluation by group (aew_eval_groups_t): the per-group record, the (group, code) table and the two plans
+        # exist from the first grouped evaluation on (eval_group_plans()); an engine that never groups holds none of them
+        self.eval_G = 0                   # number of groups the record was built for
+        self.eval_grouping = False        # evaluate() also folds the batch into the grouped record (in.group)
+        self.eval_g = self.eval_gfin = None
+        self.eval_gacc = self.eval_ghist = self.eval_gtot = self.eval_win = self.eval_gout = self.eval_tout = None
+        self.in_group = None              # int64 [B]: the group id per window of the batch evaluate() folds
         # ===== gradient accumulation (aew_accum_t): the running sums of a group of micro-batches and the op that folds
         # into them exist from the first micro-step of an engine used with accumulate > 1 (accum_grads / accum_stats)
         self.acc_grads = None             # flat like ps.grads: the sum of the open group's gradients
@@ -546,6 +553,56 @@ class TrainEngine:
         self.eval_fin = Plan("eval_fin")
         self.eval_fin.add(L.OP_EVAL_ACC, fin, "eval.finalize", TAG_LOSS)
         return self.eval_a, self.eval_b, self.eval_fin
+
+    def eval_group_plans(self, G: int):
+        """Evaluation by group, built once at its first use: the record of aew_eval_groups_t for G groups - eval_gacc
+        (float64 [G][8]), eval_ghist (uint32 [G][K] held as int32; absent without a codebook), eval_gtot (float64 [4]),
+        eval_win (float64 [B][4]) -, the outputs eval_gout (float [G][12]) / eval_tout (float [16]), the group ids
+        in_group (int64 [B]) and two one-op plans: eval_g folds the batch evaluate() just ran (its pointers are those of
+        the softmax_nll op, as eval.accumulate's), eval_gfin turns the record into the outputs.  The plain evaluation
+        plans are not touched.  Returns (eval_g, eval_gfin)."""
+        G = int(G)
+        if self.eval_gfin is not None and G == self.eval_G:
+            return self.eval_g, self.eval_gfin
+        if G < 1:
+            raise L.AewError(f"evaluation by group needs at least one group, got {G}")
+        if self.eval_gfin is not None:             # another number of groups: the record and its two plans are built anew
+            for name in ("eval.gacc", "eval.ghist", "eval.gscratch", "eval.gtot", "eval.win", "eval.gout", "eval.tout", "in.group"):
+                self.ws.bufs.pop(name, None)
+            self.eval_ghist = None
+        self.eval_plans()
+        ws, fb, B = self.ws, self.fwd_b, self.B
+        K = self.bn.K if self.bn is not None else 0
+        self.eval_gacc = ws.alloc("eval.gacc", G * L.EVAL_GACC_N, torch.float64)[:G * L.EVAL_GACC_N].view(G, L.EVAL_GACC_N)
+        if K:
+            self.eval_ghist = ws.alloc("eval.ghist", G * K, torch.int32)[:G * K].view(G, K)     # (uint32 counts)
+            scratch = ws.alloc("eval.gscratch", K + 4 * G, torch.float64)
+        self.eval_gtot = ws.alloc("eval.gtot", 4, torch.float64)[:4]
+        self.eval_win = ws.alloc("eval.win", B * 4, torch.float64)[:B * 4].view(B, 4)
+        self.eval_gout = ws.alloc("eval.gout", G * L.EVAL_GOUT_N, torch.float32)[:G * L.EVAL_GOUT_N].view(G, L.EVAL_GOUT_N)
+        self.eval_tout = ws.alloc("eval.tout", L.EVAL_TOUT_N, torch.float32)[:L.EVAL_TOUT_N]
+        self.in_group = ws.alloc("in.group", B, torch.int64)[:B]
+        sm = fb.ops[fb.labels.index("softmax_nll")].u.sm
+        ev = L.EvalGroups()
+        ev.nll, ev.ptgt, ev.wav, ev.wav_pitch, ev.tgt_off, ev.B, ev.w = sm.nll, sm.ptgt, sm.wav, sm.wav_pitch, sm.tgt_off, sm.B, sm.w
+        if sm.amax:
+            ev.amax = sm.amax
+        else:
+            ev.logits, ev.bs, ev.pitch, ev.n_quant = sm.logits, sm.bs, sm.pitch, sm.Q
+        if K:
+            ev.ind, ev.dist, ev.Qw, ev.K = self.ind.data_ptr(), self.min_dist.data_ptr(), self.Q // B, K
+            ev.ghist, ev.scratch = self.eval_ghist.data_ptr(), scratch.data_ptr()
+        ev.group, ev.G = self.in_group.data_ptr(), G
+        ev.gacc, ev.gtot, ev.win = self.eval_gacc.data_ptr(), self.eval_gtot.data_ptr(), self.eval_win.data_ptr()
+        ev.gout, ev.tout = self.eval_gout.data_ptr(), self.eval_tout.data_ptr()
+        self.eval_g = Plan("eval_g")
+        self.eval_g.add(L.OP_EVAL_GROUPS, ev, "eval.group_accumulate", TAG_LOSS)
+        fin = L.EvalGroups.from_buffer_copy(ev)
+        fin.finalize = 1
+        self.eval_gfin = Plan("eval_gfin")
+        self.eval_gfin.add(L.OP_EVAL_GROUPS, fin, "eval.group_finalize", TAG_LOSS)
+        self.eval_G = G
+        return self.eval_g, self.eval_gfin
 
     # --------------------------------------------------------------------------------------
     # execution
@@ -850,6 +907,8 @@ class TrainEngine:
         self.act_epoch += 1
         self._run(ea, False)
         self._run(eb, False)
+        if self.eval_grouping:                     # the batch once more, per window, into the record of in_group's ids
+            self._run(self.eval_g, False)
         self._chain_watch("fwd")
         return self.eval_loss[0]
 
@@ -864,6 +923,27 @@ class TrainEngine:
         is left as it is, so more batches may follow.  Reading the view is the caller's synchronisation."""
         self._run(self.eval_plans()[2], False)
         return self.eval_out
+
+    def eval_group_reset(self, G: Optional[int] = None):
+        """Start a new grouped record (zeroes eval_gacc / eval_ghist / eval_gtot / eval_win on the device) for G groups
+        - default: as many as the record has - and switch grouping on: every evaluate() from here on also folds its
+        batch by the ids in in_group."""
+        if G is None and self.eval_gfin is None:
+            raise L.AewError("eval_group_reset(): no grouped evaluation record yet; give the number of groups")
+        self.eval_group_plans(self.eval_G if G is None else G)
+        for t in (self.eval_gacc, self.eval_ghist, self.eval_gtot, self.eval_win):
+            if t is not None:
+                t.zero_()
+        self.eval_grouping = True
+
+    def eval_group_finish(self):
+        """Finalize launch of the grouped record -> (eval_gout float [G][12], eval_tout float [16]) device views
+        (_lib.EVAL_GOUT_NAMES / EVAL_TOUT_NAMES); the record is left as it is.  Reading a view is the caller's
+        synchronisation."""
+        if self.eval_gfin is None:
+            raise L.AewError("eval_group_finish(): no grouped evaluation record (eval_group_reset() starts one)")
+        self._run(self.eval_gfin, False)
+        return self.eval_gout, self.eval_tout
 
     def finish_ema(self, timing=False):
         """Deferred vq.ema (see forward): wait for the statistics' all-reduce, then accumulate."""

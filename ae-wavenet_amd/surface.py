@@ -139,8 +139,10 @@ class _StepFn(torch.autograd.Function):
 class Evaluator:
     """What `model.evaluation()` yields: the running record of the model.evaluate() calls made inside the block."""
 
-    def __init__(self, model):
+    def __init__(self, model, group=None):
         self._model = model
+        self._group = group                # a grouping block: ("voice" | "group", G)
+        self._started = False              # ... whose grouped record an evaluate() of the block has started
 
     def result(self) -> Dict[str, torch.Tensor]:
         """The record so far as 0-d device tensors (one finalize launch, no host synchronisation; reading a value is the
@@ -156,6 +158,61 @@ class Evaluator:
         with torch.no_grad():
             out = m._schedule.eval_finish(eng).clone()
         return {name: out[i] for i, name in enumerate(L.EVAL_OUT_NAMES)}
+
+    def _grouped_engine(self, what: str):
+        eng = self._model._engine
+        if self._group is None:
+            raise L.AewError(f"Evaluator.{what}: this block does not group - use model.evaluation(by='voice') or "
+                             "model.evaluation(groups=G)")
+        if eng is None or eng.eval_gfin is None or not self._started:
+            raise L.AewError(f"Evaluator.{what}: nothing has been evaluated inside this block yet")
+        return eng
+
+    def by_group(self) -> Dict[str, torch.Tensor]:
+        """The record so far, split over the groups: a dict of (G,) float32 device tensors - windows, positions, nll
+        (nats per position), bits_per_sample, top1, tprb, dist, queries, code_entropy (bits, of the group's own code
+        distribution), code_perplexity, codes_used.  A group that saw no window reads 0 throughout.  One finalize
+        launch, no host synchronisation; under data parallel the ranks' grouped records are summed first (ONE
+        all-reduce; COLLECTIVE).  Without a codebook the three code entries are 0.  Counts above 2^24 are rounded by
+        fp32; counts() has the exact table."""
+        eng = self._grouped_engine("by_group()")
+        with torch.no_grad():
+            gout, _ = self._model._schedule.eval_group_finish(eng)
+        return {name: gout[:, i] for i, name in enumerate(L.EVAL_GOUT_NAMES)}
+
+    def information(self) -> Dict[str, torch.Tensor]:
+        """What the codes tell about the group, from the (group, code) table of the record so far, as 0-d float32
+        device tensors (entropies in bits): n (counted queries), code_entropy H(C), group_entropy H(G), cond_entropy
+        H(C|G), mutual_information I(C;G), mutual_information_mm (Miller-Madow corrected: I - (cells - groups_used -
+        codes_used + 1) / (2 n ln 2); NOT clamped, slightly negative values occur when the codes are independent of the
+        group), mi_over_group_entropy, mi_over_code_entropy, cells (non-zero table entries), groups_used, codes_used,
+        dropped_windows (group id outside [0, G)), batches.  The plug-in value I overestimates when the queries are few
+        against G * K cells; the corrected value is the one to compare across runs then.  One finalize launch, no host
+        synchronisation; ONE all-reduce under data parallel (COLLECTIVE).  fp32 rounds counts above 2^24: counts()
+        is exact.  Raises AewError for a model without discrete codes."""
+        self._model._need_codes("Evaluator.information()")
+        eng = self._grouped_engine("information()")
+        with torch.no_grad():
+            _, tout = self._model._schedule.eval_group_finish(eng)
+        return {name: tout[i] for i, name in enumerate(L.EVAL_TOUT_NAMES)}
+
+    def counts(self) -> torch.Tensor:
+        """A (G, K) int64 copy of THIS rank's (group, code) table: the exact counts (the fp32 outputs of by_group() /
+        information() round above 2^24).  No collective, no host synchronisation."""
+        self._model._need_codes("Evaluator.counts()")
+        eng = self._grouped_engine("counts()")
+        return eng.eval_ghist.to(torch.int64) & 0xffffffff
+
+    def windows(self) -> Dict[str, torch.Tensor]:
+        """Per-window means of the LAST evaluated batch, as (B,) float32 device tensors: nll (nats per position), top1,
+        tprb, dist (0 without a codebook) - per-utterance scoring without a second pass.  Also filled for a window
+        whose group id was dropped.  No launch of the library, no host synchronisation."""
+        eng = self._grouped_engine("windows()")
+        win = eng.eval_win
+        n_pos = float(eng.n_win - 1)
+        out = {"nll": win[:, 0] / n_pos, "top1": win[:, 2] / n_pos, "tprb": win[:, 1] / n_pos}
+        out["dist"] = win[:, 3] / float(eng.Q // eng.B) if eng.eval_ghist is not None else torch.zeros_like(win[:, 3])
+        return {k: v.to(torch.float32) for k, v in out.items()}
 
 
 class Objective:
@@ -258,6 +315,7 @@ class HipModelBase(nn.Module):
         self._pending_state: Optional[Dict[str, torch.Tensor]] = None
         self._ema_allreduce = None
         self._dp = None
+        self._eval_ev = None                             # inside a grouping evaluation() block: its Evaluator
         self.objective = Objective(self)
         # inference surface (chassis.py:296, 313: model.wavenet.set_n_replicas / .n_quant; `model.wavenet` of the
         # MFCC inverter is the model itself here)
@@ -573,6 +631,11 @@ class HipModelBase(nn.Module):
             new.eval_plans()
             new.eval_acc.copy_(eng.eval_acc)
             new.eval_hist.copy_(eng.eval_hist)
+        if eng is not None and self._eval_ev is not None and self._eval_ev._started:
+            new.eval_group_reset(eng.eval_G)                     # ... and so does the grouped one (eval_win is per batch)
+            for dst, src in ((new.eval_gacc, eng.eval_gacc), (new.eval_ghist, eng.eval_ghist), (new.eval_gtot, eng.eval_gtot)):
+                if src is not None:
+                    dst.copy_(src)
         return self._adopt_engine(new)
 
     def _adopt_engine(self, eng):
@@ -615,28 +678,71 @@ class HipModelBase(nn.Module):
         self._fill_forward_metrics(eng)
         return pred, target, loss
 
-    def evaluate(self, wav, mel, voice, jitter, eps=None):
+    def evaluate(self, wav, mel, voice, jitter, eps=None, group=None):
         """The loss of a held-out batch, computed without a training step: nothing the next run() / backward() / step()
         reads is written - not the EMA statistics, the code histogram, the diagnostics behind `objective.metrics`, the
         loss word, parameters, gradients or optimizer state (TrainEngine.evaluate).  Inside
         `FusedAdam.averaged_weights()` it uses the averaged weights.  It does overwrite the activations: a pending
         `loss.backward()` of an earlier run() raises afterwards.  Every call also folds the batch into the running record
         `model.evaluation()` reads; outside such a block that record is simply never read.  No collectives, no host
-        synchronisation.  Returns the 0-d device loss."""
+        synchronisation.  Returns the 0-d device loss.  Inside `model.evaluation(by="voice")` the batch is also folded
+        per window into the grouped record by its `voice` ids; inside `model.evaluation(groups=G)` by `group`, an int64
+        (B,) tensor of ids in [0, G) (a window with an id outside is dropped from the grouped record and counted as
+        dropped) - one more small op, still no host synchronisation."""
+        ev = self._eval_ev
+        grp = ev._group if ev is not None else None
+        if group is not None and (grp is None or grp[0] != "group"):
+            raise L.AewError("evaluate(group=...) needs an enclosing `with model.evaluation(groups=G)` block")
+        if grp is not None and grp[0] == "group":
+            if group is None:
+                raise L.AewError("evaluate() inside model.evaluation(groups=G) needs group=ids, one id per window")
+            if tuple(group.shape) != (wav.shape[0],):
+                raise L.AewError(f"evaluate(): group ({wav.shape[0]},) expected (one id per window), got {tuple(group.shape)}")
         with torch.no_grad():
             eng = self._ensure_engine(wav.shape[0])
             self._dp_finish()
             eng.set_inputs(wav, mel, voice, jitter, eps=eps)
+            eng.eval_grouping = grp is not None
+            if grp is not None:
+                if not ev._started:                                  # the block's first batch starts the grouped record
+                    eng.eval_group_reset(grp[1])
+                    ev._started = True
+                eng.in_group.copy_(voice if grp[0] == "voice" else group)
             return eng.evaluate().clone()
 
     @contextlib.contextmanager
-    def evaluation(self):
+    def evaluation(self, by: Optional[str] = None, groups: Optional[int] = None):
         """`with model.evaluation() as ev:` - the record starts at zero, every model.evaluate() inside adds its batch,
         `ev.result()` returns the means (Evaluator.result).  The record follows the model when another batch size makes
-        another engine the live one."""
+        another engine the live one.
+
+        `model.evaluation(by="voice")` also keeps the record per voice (G = hps.n_speakers groups, the ids are the
+        `voice` argument of each evaluate()); `model.evaluation(groups=G)` keeps it per caller-supplied id
+        (`evaluate(..., group=ids)`: gender, utterance, dataset).  Then `ev.by_group()`, `ev.information()`,
+        `ev.counts()` and `ev.windows()` read it (Evaluator); `ev.result()` is what it is without grouping, bit for
+        bit.  With no arguments nothing of this exists or runs."""
+        if by is not None and groups is not None:
+            raise L.AewError("evaluation(): give by='voice' or groups=G, not both")
+        if by is not None and by != "voice":
+            raise L.AewError(f"evaluation(by={by!r}): only by='voice' is known; use groups=G with evaluate(group=ids) "
+                             "for any other labelling")
+        if groups is not None and int(groups) < 1:
+            raise L.AewError(f"evaluation(groups={groups}): at least one group")
+        if self._eval_ev is not None:
+            raise L.AewError("evaluation(): a grouping evaluation block is already open")
         if self._engine is not None and self._engine.eval_acc is not None:     # (else: the record is allocated as zeros)
             self._engine.eval_reset()
-        yield Evaluator(self)
+        if by is None and groups is None:
+            yield Evaluator(self)
+            return
+        # (the grouped record is started by the block's first evaluate(): the engine may not exist yet)
+        self._eval_ev = Evaluator(self, ("voice", int(self.hps.n_speakers)) if by is not None else ("group", int(groups)))
+        try:
+            yield self._eval_ev
+        finally:
+            self._eval_ev = None
+            if self._engine is not None:
+                self._engine.eval_grouping = False
 
     def forward(self, wav, mel, voice, jitter):
         """train(): logits (B, Q, w) for the batch (teacher-forced).  eval(): the reference's inference call

@@ -46,7 +46,8 @@ extern "C" {
  * append-only - two op kinds behind the existing ones, two descriptors that fit the union's size, aew_sizeof indices 22
  * and 23, two host functions; no existing record, op number or function changed - so a caller built against 28 runs
  * unchanged.  A binding that wants the additions finds them through aew_sizeof(22) / aew_sizeof(23) (-1 in a library
- * without them). */
+ * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 32,
+ * aew_eval_groups_t / AEW_OP_EVAL_GROUPS). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -553,6 +554,74 @@ typedef struct {
     int32_t finalize; int32_t pad_;
     float* out;                                             /* [AEW_EVAL_OUT_N], written by finalize only              */
 } aew_eval_acc_t;
+
+/* ---------------------------------------------------------------------------------------
+ * Evaluation by group (appended to ABI 28; AEW_OP_EVAL_GROUPS, aew_sizeof 32): the sums of aew_eval_acc_t taken PER
+ * WINDOW and folded into a record indexed by a per-window group id (the voice, or any labelling the caller has), and the
+ * (group, code) contingency table from which the mutual information I(code; group) is read off - how much of the
+ * grouping (speaker identity) the discrete codes carry.  It writes nothing a training step reads.
+ *
+ * finalize == 0 (accumulate).  nll, ptgt, wav / wav_pitch / tgt_off, B, w, amax or logits / bs / pitch / n_quant are those
+ * of aew_eval_acc_t.  ind int64 [B * Qw] / dist [B * Qw] (optional): query q belongs to window q / Qw (b-major).  group
+ * int64 [B].  nll == NULL selects CODES-ONLY mode: no position sums are taken (w, ptgt, wav, amax, logits are ignored),
+ * only the queries are counted; ind is required.
+ * The record (device memory, zeroed by the caller before the first batch):
+ *   gacc  double [G][8]   per group: 0 windows, 1 positions (w - 1 per window; codes-only: none), 2 S(nll), 3 S(ptgt),
+ *                         4 top-1 hits, 5 queries (Qw per window, with ind), 6 S(dist) (with ind and dist), 7 never written
+ *   ghist uint32 [G][K]   the contingency table: ghist[group[b]][ind[q]] += 1 (integer atomics: exact in any order; a
+ *                         query whose code lies outside [0, K) is not counted anywhere)
+ *   gtot  double [4]      0: windows dropped because group[b] lies outside [0, G) - such a window is counted nowhere,
+ *                         neither in its positions nor in its queries; 1: batches; 2, 3 never written
+ *   win   double [B][4]   OVERWRITTEN by every accumulate launch: S(nll), S(ptgt), hits, S(dist) of window b alone (also
+ *                         for a dropped window; codes-only: 0, 0, 0, S(dist))
+ * Order of the floating sums (no floating atomics; two runs are bit-equal).  Per window: ONE workgroup of 1024 threads
+ * owns window b; thread t adds the window's elements u = t, t + 1024, ... ascending, u < w - 1 (for dist: its queries
+ * j < Qw ascending), each converted to double first, to a double that starts at 0.0; the 1024 partial sums are folded by
+ * the halving tree  for (o = 512; o > 0; o >>= 1) s[t] += s[t + o] for t < o  - THE order and THE tree of aew_eval_acc_t -
+ * and s[0] goes to win[b].  Per group: a second kernel, one thread per group, walks b = 0 .. B - 1 ascending and adds the
+ * window sums of its group to gacc[g], one double addition per entry; counts are added as doubles (exact below 2^53).
+ * So for B == 1, gacc[g][2..4] and [6] carry the bits aew_eval_acc_t adds to acc[2], acc[3], acc[4], acc[6].
+ *
+ * finalize != 0: nothing is accumulated; gout and tout are written from the record.  With n_gk = ghist[g][k],
+ * n_g = sum_k n_gk, n_k = sum_g n_gk, N = sum n_gk (all integer); every quotient taken in double and rounded to fp32
+ * once; x / 0 = 0; terms with n_gk == 0 are skipped:
+ *   gout float [G][12]  per group: 0 windows, 1 positions, 2 nll per position gacc[2] / gacc[1], 3 bits per sample
+ *                       ([2] / ln 2, in double), 4 top-1 gacc[4] / gacc[1], 5 mean target probability gacc[3] / gacc[1],
+ *                       6 mean dist gacc[6] / gacc[5], 7 queries gacc[5], 8 E_g = -sum_k (n_gk / n_g) log2(n_gk / n_g),
+ *                       9 2^E_g (0 if n_g == 0), 10 number of k with n_gk > 0, 11 0
+ *   tout float [16]     0 N, 1 H(C) = -sum_k (n_k / N) log2(n_k / N), 2 H(G) = -sum_g (n_g / N) log2(n_g / N),
+ *                       3 H(C|G) = sum_g (n_g / N) E_g, 4 I = (sum_g J_g) / N with
+ *                       J_g = sum_k n_gk log2(((double)n_gk * N) / ((double)n_g * n_k)) - computed this way a table with
+ *                       independent rows and columns gives 0 exactly -, 5 the Miller-Madow corrected value
+ *                       I - (cells - rows - cols + 1) / (2 N ln 2) (cells, rows, cols: the numbers of non-zero n_gk, n_g,
+ *                       n_k; NOT clamped, it may be slightly negative), 6 I / H(G), 7 I / H(C), 8 cells, 9 rows, 10 cols,
+ *                       11 gtot[0] dropped windows, 12 gtot[1] batches, 13..15 0
+ * Every sum over k (E_g, J_g, H(C)) follows THE order - thread t takes k = t, t + 1024, ... ascending - and THE tree; the
+ * sums over g (H(G), H(C|G), sum J_g, cells) are taken ascending g by one thread, rows with n_g == 0 skipped.  With
+ * ghist == NULL gout[.][8..10] are 0 and tout is zero except [11] and [12].
+ * scratch (finalize with ghist only): 8-byte words [K + 4 * G], written by finalize - the column sums n_k as uint64 [K],
+ * then per group n_g, E_g, J_g, cells_g as doubles.
+ *
+ * Before any launch - accumulate: AEW_E_ARG for B < 1, G < 1, a NULL group / gacc / gtot / win, ind with K < 1, Qw < 1
+ * or a NULL ghist, codes-only without ind; unless codes-only: w < 2, a NULL ptgt / wav, neither amax nor logits (or
+ * logits with n_quant < 1).  finalize: AEW_E_ARG for G < 1, a NULL gacc / gtot / gout / tout, ghist with K < 1 or a NULL
+ * scratch.  AEW_E_ALIGN (both): gacc, gtot, win, ind, group or scratch not 8-byte aligned, any other pointer not 4-byte
+ * aligned. */
+#define AEW_EVAL_GACC_N 8
+#define AEW_EVAL_GOUT_N 12
+#define AEW_EVAL_TOUT_N 16
+typedef struct {
+    const float* nll; const float* ptgt;                    /* [B][w] (nll NULL: codes-only)                           */
+    const float* wav; int32_t wav_pitch; int32_t tgt_off;
+    int32_t B, w;
+    const int32_t* amax;
+    const float* logits; int64_t bs; int32_t pitch; int32_t n_quant;
+    const int64_t* ind; const float* dist; int32_t Qw, K;   /* optional: [B * Qw], b-major                             */
+    const int64_t* group; int32_t G; int32_t finalize;      /* [B] group id per window                                 */
+    double* gacc; uint32_t* ghist; double* gtot; double* win;
+    float* gout; float* tout;                               /* written by finalize only                                */
+    void* scratch;                                          /* finalize with ghist: [K + 4 * G] 8-byte words           */
+} aew_eval_groups_t;
 
 /* ---------------------------------------------------------------------------------------
  * Per-parameter update / weight ratios (ABI 22): what the reference's training loop computes around optim.step()
@@ -1070,7 +1139,8 @@ enum {
     AEW_OP_ADAM, AEW_OP_ZERO, AEW_OP_VAE, AEW_OP_AE_NORM, AEW_OP_JITTER, AEW_OP_VQ_DIAG, AEW_OP_MFCC,
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
-    AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS
+    AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
+    AEW_OP_EVAL_GROUPS
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1099,13 +1169,14 @@ typedef struct {
         aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
         aew_grad_welford_t gwel; aew_seg_select_t ssel; aew_accum_t accum;
         aew_code_lookup_t clk; aew_code_runs_t crun; aew_adam_grouped_t adamg;
+        aew_eval_groups_t evg;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped (24 and 26 are unused: -1) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups (24 and 26 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
