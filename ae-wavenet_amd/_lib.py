@@ -24,7 +24,8 @@ EF_OUT2_COPY = 1 << 10
  OP_LC_GATHER, OP_LC_SCATTER, OP_SPK_BIAS, OP_SPK_BWD, OP_BASE_GATHER, OP_SOFTMAX_NLL, OP_COLSUM,
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
- OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS) = range(1, 39)
+ OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
+ OP_MEL_TILE, OP_CODE_STITCH) = range(1, 41)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -229,6 +230,27 @@ class CodeRuns(C.Structure):
     _fields_ = [("ind", vp), ("ind_pitch", i64), ("units", vp), ("lengths", vp), ("n_runs", vp), ("B", i32), ("N", i32)]
 
 
+class UttRow(C.Structure):
+    """aew_utt_row_t: one batch row of a whole-utterance encode - where its window starts in the ragged mel buffer, how many
+    frames exist there, where its codes go and how many of them are stored.  UTT_ROW_DTYPE is the same record for numpy."""
+    _fields_ = [("src", i64), ("dst", i64), ("pitch", i32), ("avail", i32), ("n_valid", i32), ("pad_", i32)]
+
+
+UTT_ROW_DTYPE = [("src", "<i8"), ("dst", "<i8"), ("pitch", "<i4"), ("avail", "<i4"), ("n_valid", "<i4"), ("pad_", "<i4")]
+
+
+class MelTile(C.Structure):
+    """aew_mel_tile_t: in_mel[b] = the window of table[first_row + b] cut out of the ragged mel buffer, zeros behind it."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("mel", vp), ("n_src", i64),
+                ("in_mel", vp), ("n_mel", i32), ("mel_len", i32)]
+
+
+class CodeStitch(C.Structure):
+    """aew_code_stitch_t: the first n_valid codes (and distances) of each batch row to their place in the ragged outputs."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("ind", vp), ("min_dist", vp),
+                ("codes", vp), ("dist", vp), ("n_dst", i64), ("E", i32), ("pad_", i32)]
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -369,7 +391,7 @@ class _OpU(C.Union):
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
-                ("adamg", AdamGrouped), ("evg", EvalGroups)]
+                ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch)]
 
 
 class Op(C.Structure):
@@ -384,7 +406,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_VQ_DIAG: "diag", OP_MFCC: "mfcc", OP_MOMENTS: "mom", OP_GEMM_TN_GROUP: "tng", OP_NT_CHAIN: "chain",
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
-            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg"}
+            OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
+            OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch"}
 
 
 
@@ -507,6 +530,8 @@ def load():
     lib.aew_grad_norm_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.aew_corpus_locate.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.aew_utterance_locate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.aew_seg_select_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.aew_select_key.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
     lib.aew_uw_chunks.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64,
@@ -515,7 +540,8 @@ def load():
                        (9, NtStage), (10, NtChain), (11, Adam), (12, GradNorm), (13, UwChunk), (14, UwTrack),
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
-                       (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups)):
+                       (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
+                       (36, CodeStitch)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
@@ -569,4 +595,4 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
            "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles",
-           "aew_corpus_locate", "aew_seg_select_size", "aew_select_key")
+           "aew_corpus_locate", "aew_seg_select_size", "aew_select_key", "aew_utterance_locate")

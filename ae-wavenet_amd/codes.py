@@ -7,14 +7,18 @@
 
 Both run as one-op plans on torch's current stream, take any device tensor (rows of any length: the concatenated codes
 of an utterance) and never synchronise with the host.  `model.encode()` / `model.decode()` / `model.convert()`
-(surface.py) are the calls that produce and consume the codes.
+(surface.py) are the calls that produce and consume the codes of one window; `model.encode_utterances()` /
+`encode_wavs()` / `encode_corpus()` produce those of whole utterances as an `UtteranceCodes`, from the work list
+`tile_plan()` states (csrc/aew_utterance.hip).
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -109,6 +113,143 @@ def voice_information(codes: torch.Tensor, voice: torch.Tensor, K: int, n_voices
     info = {name: tout[i] for i, name in enumerate(L.EVAL_TOUT_NAMES)}
     info["counts"] = ghist.to(torch.int64) & 0xffffffff
     return info
+
+
+# ---- whole utterances: the work list of model.encode_utterances() and the codes it returns ------------------------------
+@dataclass
+class TilePlan:
+    """tile_plan()'s result: per utterance the code offsets, per batch row (n_batches * B of them, the idle rows that
+    fill the last batch included) the utterance (-1: idle), its window, the window's first frame, the frames that exist
+    there, the codes stored and where the first of them goes in the flat outputs.  Host arrays only."""
+    E: int
+    s: int
+    rf: int
+    mel_len: int
+    B: int
+    frames: np.ndarray          # int64 [U]
+    offsets: np.ndarray         # int64 [U + 1]: utterance u owns codes [offsets[u], offsets[u + 1])
+    utt: np.ndarray             # int32 [R]
+    window: np.ndarray          # int32 [R]
+    start: np.ndarray           # int64 [R]
+    avail: np.ndarray           # int32 [R]
+    n_valid: np.ndarray         # int32 [R]
+    dst: np.ndarray             # int64 [R]
+    n_rows: int                 # rows that are not idle
+
+    @property
+    def n_batches(self) -> int:
+        return len(self.utt) // self.B
+
+    @property
+    def n_codes(self) -> int:
+        return int(self.offsets[-1])
+
+    def table(self, bases) -> np.ndarray:
+        """The aew_utt_row_t records (a structured array, _lib.UTT_ROW_DTYPE) for utterances whose (n_mel, F_u) arrays start
+        at the element offsets `bases` [U] of the ragged mel buffer."""
+        rec = np.zeros(len(self.utt), np.dtype(L.UTT_ROW_DTYPE))
+        live = self.utt >= 0
+        u = self.utt[live]
+        rec["src"][live] = np.asarray(bases, np.int64)[u] + self.start[live]
+        rec["pitch"][live] = self.frames[u]
+        rec["dst"], rec["avail"], rec["n_valid"] = self.dst, self.avail, self.n_valid
+        return rec
+
+
+def tile_plan(frames: Sequence[int], E: int, s: int, rf: int, B: int) -> TilePlan:
+    """The work list of a whole-utterance encode, a pure function of the frame counts (it never reads the device): an
+    utterance of F frames has N = 0 codes if F < rf, else (F - rf) // s + 1, in ceil(N / E) windows of mel_len =
+    s * (E - 1) + rf frames; window w starts at frame w * s * E, finds min(mel_len, F - w * s * E) frames there (the
+    rest are zeros) and stores the codes [w * E, min(N, w * E + E)) - those whose receptive field lies inside the real
+    frames.  The windows of all utterances, in order, fill batches of B rows; the last batch is padded with idle rows."""
+    E, s, rf, B = int(E), int(s), int(rf), int(B)
+    if E < 1 or s < 1 or rf < 1 or B < 1:
+        raise ValueError("tile_plan(): E, s, rf and B must be at least 1")
+    F = np.asarray(list(frames), np.int64).reshape(-1)
+    if (F < 0).any():
+        raise ValueError("tile_plan(): negative frame count")
+    mel_len = s * (E - 1) + rf
+    N = np.where(F < rf, 0, (F - rf) // s + 1)
+    offsets = np.concatenate([[0], np.cumsum(N)]).astype(np.int64)
+    nw = -(-N // E)
+    n_rows = int(nw.sum())
+    R = -(-n_rows // B) * B
+    first = np.concatenate([[0], np.cumsum(nw)])[:-1]
+    utt = np.full(R, -1, np.int32)
+    window, start, avail = np.zeros(R, np.int32), np.zeros(R, np.int64), np.zeros(R, np.int32)
+    n_valid, dst = np.zeros(R, np.int32), np.zeros(R, np.int64)
+    u = np.repeat(np.arange(len(F)), nw)
+    w = np.arange(n_rows) - np.repeat(first, nw)
+    utt[:n_rows], window[:n_rows] = u, w
+    start[:n_rows] = w * (s * E)
+    avail[:n_rows] = np.minimum(mel_len, F[u] - w * (s * E))
+    n_valid[:n_rows] = np.minimum(E, N[u] - w * E)
+    dst[:n_rows] = offsets[u] + w * E
+    return TilePlan(E, s, rf, mel_len, B, F, offsets, utt, window, start, avail, n_valid, dst, n_rows)
+
+
+class UtteranceCodes:
+    """The codes of U whole utterances: `codes` int64, flat, on the device; `offsets` int64 (U + 1,) on the host -
+    utterance u owns codes[offsets[u]:offsets[u + 1]] (they follow from the frame counts alone, so reading them never
+    waits for the device); optional `dist` float32 like codes, `voice` int64 (U,), `names` (U strings)."""
+
+    def __init__(self, codes: torch.Tensor, offsets: torch.Tensor, dist: Optional[torch.Tensor] = None,
+                 voice: Optional[torch.Tensor] = None, names: Optional[Sequence[str]] = None):
+        offsets = torch.as_tensor(offsets, dtype=torch.int64).cpu()
+        U = offsets.numel() - 1
+        if codes.dtype != torch.int64 or codes.dim() != 1 or U < 0 or int(offsets[-1]) != codes.numel() or int(offsets[0]) != 0:
+            raise L.AewError("UtteranceCodes: flat int64 codes and offsets (U + 1,) from 0 to len(codes) expected")
+        if dist is not None and dist.shape != codes.shape:
+            raise L.AewError("UtteranceCodes: dist must have one value per code")
+        if voice is not None and tuple(voice.shape) != (U,):
+            raise L.AewError(f"UtteranceCodes: voice ({U},) expected, got {tuple(voice.shape)}")
+        if names is not None and len(names) != U:
+            raise L.AewError(f"UtteranceCodes: {U} names expected, got {len(names)}")
+        self.codes, self.offsets, self.dist, self.voice = codes, offsets, dist, voice
+        self.names = None if names is None else [str(n) for n in names]
+        self._off = offsets.tolist()
+
+    def __len__(self) -> int:
+        return len(self._off) - 1
+
+    def row(self, u: int) -> torch.Tensor:
+        """The codes of utterance u (a view)."""
+        u = range(len(self))[u]
+        return self.codes[self._off[u]:self._off[u + 1]]
+
+    def units(self, u: int):
+        """codes.code_runs of row u: (units, lengths, n_runs)."""
+        return code_runs(self.row(u))
+
+    def padded(self, fill: int = -1) -> torch.Tensor:
+        """(U, longest row) int64, row u = its codes followed by `fill`."""
+        lens = torch.tensor([b - a for a, b in zip(self._off[:-1], self._off[1:])], dtype=torch.int64)
+        width = int(lens.max()) if len(self) else 0
+        out = torch.full((len(self), width), int(fill), dtype=torch.int64, device=self.codes.device)
+        if self.codes.numel():
+            mask = (torch.arange(width)[None, :] < lens[:, None]).to(self.codes.device)
+            out.masked_scatter_(mask, self.codes)
+        return out
+
+    def save(self, path):
+        """One .npz: codes, offsets and - where present - voice, names, dist."""
+        arrays = {"codes": self.codes.cpu().numpy(), "offsets": self.offsets.numpy()}
+        if self.voice is not None:
+            arrays["voice"] = self.voice.cpu().numpy()
+        if self.names is not None:
+            arrays["names"] = np.asarray(self.names, dtype=np.str_)
+        if self.dist is not None:
+            arrays["dist"] = self.dist.cpu().numpy()
+        with open(path, "wb") as fh:
+            np.savez(fh, **arrays)
+
+    @classmethod
+    def load(cls, path, device=None) -> "UtteranceCodes":
+        with np.load(path, allow_pickle=False) as z:
+            put = lambda k: torch.from_numpy(z[k]).to(device) if device is not None else torch.from_numpy(z[k])
+            return cls(put("codes"), torch.from_numpy(z["offsets"]), dist=put("dist") if "dist" in z else None,
+                       voice=put("voice") if "voice" in z else None,
+                       names=[str(n) for n in z["names"]] if "names" in z else None)
 
 
 # ---- mu-law companding of the decoder's samples (amplitudes in [-1, 1] -> n_quant integer values) ---------------------

@@ -9,6 +9,7 @@
 #include "aew_gradstats.hip"
 #include "aew_codes.hip"
 #include "aew_evalgroups.hip"
+#include "aew_utterance.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -69,6 +70,8 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_CODE_RUNS: return launch_code_runs(op.u.crun, st);
         case AEW_OP_ADAM_GROUPS: return launch_adam_groups(op.u.adamg, st);
         case AEW_OP_EVAL_GROUPS: return launch_eval_groups(op.u.evg, st);
+        case AEW_OP_MEL_TILE: return launch_mel_tile(op.u.mtile, st);
+        case AEW_OP_CODE_STITCH: return launch_code_stitch(op.u.cstitch, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -109,6 +112,9 @@ extern "C" int aew_sizeof(int which) {
         case 30: return (int)sizeof(aew_adam_groups_t);
         case 31: return (int)sizeof(aew_adam_grouped_t);
         case 32: return (int)sizeof(aew_eval_groups_t);
+        case 34: return (int)sizeof(aew_utt_row_t);      // (33 is left unused like 24 and 26)
+        case 35: return (int)sizeof(aew_mel_tile_t);
+        case 36: return (int)sizeof(aew_code_stitch_t);
         default: return -1;
     }
 }

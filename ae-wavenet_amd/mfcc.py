@@ -80,6 +80,7 @@ class DeviceMfcc:
         self.dct = f32(d)
         self.sg = f32(np.stack([_savgol_rows(1), _savgol_rows(2)]))
         self._plans = {}
+        self._ragged_scratch = None                                 # ragged(): one buffer, sized for the longest utterance seen
         L.load()
 
     def n_frames(self, n: int) -> int:
@@ -117,6 +118,51 @@ class DeviceMfcc:
         buf[:B * n].view(B, n).copy_(wav)
         p.run(torch.cuda.current_stream(self.dev).cuda_stream)
         return out[:B * self.n_out * Ft].view(B, self.n_out, Ft).clone()
+
+
+    MIN_FRAMES = 9                                                  # the delta filters' window (AEW_OP_MFCC refuses fewer)
+
+    def ragged(self, wavs):
+        """Whole utterances: wavs, 1-D device tensors of mu-law values of any lengths -> (flat, frames, bases): `flat` the
+        float32 ragged buffer that holds utterance u's (3 * n_mfcc, frames[u]) array at element bases[u].  One AEW_OP_MFCC
+        record per utterance, so the dB floor and the delta edges are the utterance's own - what the reference's ProcessWav
+        gives when its loader hands over an entire file (data.py WavFileDataset).  An utterance too short for MIN_FRAMES
+        frames has none.  The records run one behind the other on the stream and share one scratch buffer sized for the
+        longest utterance this object has seen: memory does not grow with the number of distinct lengths, and
+        __call__'s per-shape workspaces are not involved.  No host synchronisation."""
+        frames, wavs = [], list(wavs)
+        for w in wavs:
+            if w.dim() != 1 or w.device != self.dev:
+                raise L.AewError("DeviceMfcc.ragged: 1-D tensors on the device expected")
+            n = int(w.numel())
+            Ft = self.n_frames(n) if self.left_pad + n > self.win // 2 else 0
+            frames.append(Ft if Ft >= self.MIN_FRAMES else 0)
+        bases = [0]
+        for Ft in frames:
+            bases.append(bases[-1] + self.n_out * Ft)
+        flat = torch.empty(bases[-1], dtype=torch.float32, device=self.dev)
+        nf_max = max([Ft + self.trim_left + self.trim_right for Ft in frames if Ft] or [0])
+        need = nf_max * (self.n_mels + 1 + self.n_mfcc)
+        if need > (0 if self._ragged_scratch is None else self._ragged_scratch.numel()):
+            self._ragged_scratch = torch.empty(need, dtype=torch.float32, device=self.dev)
+        p, keep = Plan("mfcc.ragged"), []
+        for w, Ft, base in zip(wavs, frames, bases):
+            if not Ft:
+                continue
+            x = w.to(torch.float32).contiguous()
+            keep.append(x)
+            n = int(x.numel())
+            m = L.Mfcc()
+            m.wav, m.wav_bs, m.n, m.B = x.data_ptr(), n, n, 1
+            m.win, m.hop, m.n_bins, m.n_mels, m.n_mfcc = self.win, self.hop, self.win // 2 + 1, self.n_mels, self.n_mfcc
+            m.left_pad, m.trim_left, m.trim_right = self.left_pad, self.trim_left, self.trim_right
+            m.n_frames = Ft + self.trim_left + self.trim_right
+            m.window, m.twiddle, m.melw = self.window.data_ptr(), self.twiddle.data_ptr(), self.melw.data_ptr()
+            m.dct, m.sg, m.scratch = self.dct.data_ptr(), self.sg.data_ptr(), self._ragged_scratch.data_ptr()
+            m.out, m.out_bs, m.out_pitch = flat.data_ptr() + 4 * base, self.n_out * Ft, Ft
+            p.add(L.OP_MFCC, m, "mfcc")
+        p.run(torch.cuda.current_stream(self.dev).cuda_stream)
+        return flat, frames, bases[:-1]
 
 
 class ProcessWav:

@@ -13,6 +13,7 @@ import os
 import math
 from typing import Dict, NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -509,6 +510,9 @@ class TrainEngine:
         # conditioning plan and the word that counts codes outside the codebook exist from the first decode on
         self._decode_plan = None          # [code.lookup] + the ops of _cond_plan
         self.codes_bad = None             # int32 [1] (a uint32 count): codes outside [0, K) in the last decode
+        # ===== whole utterances (encode_tiles(): aew_mel_tile_t / aew_code_stitch_t): one op each in front of and behind
+        # _cond_plan_a, re-addressed per batch like `opt`; they exist from the first whole-utterance encode on
+        self.utt_tile, self.utt_stitch = Plan("utt.tile"), Plan("utt.stitch")
         self._chain_flag_views = self._chain_host = None
 
     # ops of the training forward that an evaluation leaves out: they write what the next training step (or the caller,
@@ -698,6 +702,78 @@ class TrainEngine:
         self._run(self._cond_plan_a, False)
         self.lin_live = True
         return self.ind[:self.Q], self.min_dist[:self.Q]
+
+    def utterance_ops(self):
+        """The records of the two ops around _cond_plan_a in a whole-utterance encode, built at the first use:
+        (aew_mel_tile_t writing in_mel, aew_code_stitch_t reading ind / min_dist).  The caller fills in the table, its
+        first row, the ragged buffers and their sizes."""
+        self._need_codes("encode_tiles()")
+        if not self.utt_tile.ops:
+            g = self.geom
+            E, _, _, mel_len = G.utterance_geometry(g)
+            mt = L.MelTile()
+            mt.in_mel, mt.B, mt.n_mel, mt.mel_len = self.in_mel.data_ptr(), self.B, self.n_mel, mel_len
+            self.utt_tile.add(L.OP_MEL_TILE, mt, "utt.tile", TAG_VQ)
+            cs = L.CodeStitch()
+            cs.ind, cs.min_dist, cs.B, cs.E = self.ind.data_ptr(), self.min_dist.data_ptr(), self.B, E
+            self.utt_stitch.add(L.OP_CODE_STITCH, cs, "utt.stitch", TAG_VQ)
+        return self.utt_tile.array()[0].u.mtile, self.utt_stitch.array()[0].u.cstitch
+
+    def utterance_batch_plan(self, mel: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor, first_row: int,
+                             codes: torch.Tensor, dist: Optional[torch.Tensor] = None) -> Plan:
+        """One batch of a whole-utterance encode as a plan of its own (for a caller's captured graph): [utt.tile] + the
+        ops of _cond_plan_a (the same records) + [utt.stitch] over the rows [first_row, first_row + B) of `table` (uint8
+        device bytes of aew_utt_row_t records; table_host: the same bytes in pinned host memory, read at capture).  The
+        caller keeps the tensors alive."""
+        mt0, cs0 = self.utterance_ops()
+        self._cond_plans()
+        mt, cs = L.MelTile.from_buffer_copy(mt0), L.CodeStitch.from_buffer_copy(cs0)
+        mt.table, mt.table_host, mt.first_row = table.data_ptr(), table_host.data_ptr(), int(first_row)
+        mt.mel, mt.n_src = mel.data_ptr(), mel.numel()
+        cs.table, cs.table_host, cs.first_row = mt.table, mt.table_host, mt.first_row
+        cs.codes, cs.n_dst, cs.dist = codes.data_ptr(), codes.numel(), (dist.data_ptr() if dist is not None else None)
+        p = Plan("utt.batch")
+        p.add(L.OP_MEL_TILE, mt, "utt.tile", TAG_VQ)
+        p.splice(1, self._sub_plan("conditioning_a", self._cond_plan_a, lambda i, lab: True))
+        p.add(L.OP_CODE_STITCH, cs, "utt.stitch", TAG_VQ)
+        return p
+
+    def encode_tiles(self, mel: torch.Tensor, table, codes: torch.Tensor, dist: Optional[torch.Tensor] = None):
+        """Whole utterances through the fixed-geometry encoder: `mel` flat fp32, the ragged buffer of the utterances'
+        (n_mel, F_u) arrays; `table` a numpy array of aew_utt_row_t records (_lib.UTT_ROW_DTYPE), a multiple of B rows
+        (codes.TilePlan.table); `codes` int64 - and `dist` fp32 - flat outputs.  The table goes to the device once (pinned,
+        non-blocking); per batch of B rows one AEW_OP_MEL_TILE fills in_mel, _cond_plan_a runs unchanged and one
+        AEW_OP_CODE_STITCH moves the codes whose receptive field lies inside real frames.  Writes what encode_codes()
+        writes and nothing else of the engine; no host synchronisation."""
+        mt, cs = self.utterance_ops()
+        self._cond_plans()
+        n = len(table)
+        if n % self.B or table.dtype.itemsize != C.sizeof(L.UttRow):
+            raise L.AewError(f"encode_tiles(): a multiple of B = {self.B} aew_utt_row_t records expected, got {n}")
+        if mel.dtype != torch.float32 or codes.dtype != torch.int64 or not mel.is_contiguous() or not codes.is_contiguous() \
+                or (dist is not None and (dist.dtype != torch.float32 or dist.numel() != codes.numel())):
+            raise L.AewError("encode_tiles(): flat fp32 mel, int64 codes and fp32 dist (one per code) expected")
+        if n == 0:
+            return
+        host = torch.empty(n * table.dtype.itemsize, dtype=torch.uint8, pin_memory=True)
+        host.numpy()[:] = table.view(np.uint8).reshape(-1)
+        dev = torch.empty_like(host, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        mt.table = cs.table = dev.data_ptr()
+        mt.table_host = cs.table_host = host.data_ptr()
+        mt.mel, mt.n_src = mel.data_ptr(), mel.numel()
+        cs.codes, cs.n_dst, cs.dist = codes.data_ptr(), codes.numel(), (dist.data_ptr() if dist is not None else None)
+        self.act_epoch += 1
+        st = self._stream()
+        for first in range(0, n, self.B):
+            mt.first_row = cs.first_row = first
+            self.utt_tile.run(st)
+            self._run(self._cond_plan_a, False)
+            self.utt_stitch.run(st)
+        self.lin_live = True
+        # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
+        # keep no address of them
+        mt.table = cs.table = mt.table_host = cs.table_host = mt.mel = cs.codes = cs.dist = None
 
     DECODE_DROP = ("diagnostics (codebook)",)
 

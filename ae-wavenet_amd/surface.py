@@ -322,6 +322,7 @@ class HipModelBase(nn.Module):
         self.n_quant, self.n_replicas = hps.n_quant, 1
         self.sample_seed = 0
         self._sampler = None
+        self._utt_mfcc = None                            # encode_wavs() / encode_corpus(): the whole-utterance front-end
         self._anchor = torch.zeros((), requires_grad=True)
         # geometry attributes of the reference classes (autoencoder_model.py:119-146,
         # mfcc_inverter.py:38-65)
@@ -813,6 +814,114 @@ class HipModelBase(nn.Module):
             ind, dist = eng.encode_codes()
             codes = ind.view(B, self.embed_len).clone()
             return (codes, dist.view(B, self.embed_len).clone()) if return_dist else codes
+
+    # ---- whole utterances: codes for any length and for a corpus ----------------------------------------------------
+    def _encode_ragged(self, what, flat, frames, bases, voice, batch, return_dist, names):
+        """flat: the ragged fp32 buffer of the utterances' (n_mel, frames[u]) arrays at the element offsets `bases`."""
+        from . import codes as CD
+        if batch is not None and int(batch) < 1:
+            raise L.AewError(f"{what}: batch must be at least 1, got {batch}")
+        B = int(batch) if batch is not None else (self._engine.B if self._engine is not None else int(self.hps.n_batch))
+        U = len(frames)
+        if voice is not None:
+            voice = torch.as_tensor(voice, dtype=torch.int64)
+            if tuple(voice.shape) != (U,):
+                raise L.AewError(f"{what}: voice ({U},) expected (one per utterance), got {tuple(voice.shape)}")
+        with torch.no_grad():
+            eng = self._ensure_engine(B)
+            self._dp_finish()
+            E, s, rf, _ = G.utterance_geometry(eng.geom)
+            plan = CD.tile_plan(frames, E, s, rf, B)
+            codes = torch.empty(plan.n_codes, dtype=torch.int64, device=eng.device)
+            dist = torch.empty(plan.n_codes, dtype=torch.float32, device=eng.device) if return_dist else None
+            eng.encode_tiles(flat, plan.table(bases), codes, dist)
+        return CD.UtteranceCodes(codes, torch.from_numpy(plan.offsets), dist=dist, voice=voice, names=names)
+
+    def encode_utterances(self, mels, voice=None, batch=None, return_dist: bool = False, names=None):
+        """mels: a list of (n_mel, F_u) device tensors of ANY frame counts -> `codes.UtteranceCodes`: the codes of each
+        whole utterance, flat (int64 `codes`, `offsets` of size U + 1; `dist` with return_dist=True; `voice` / `names`
+        carried along).  An utterance of F frames has 0 codes below the encoder's receptive field rf, else
+        (F - rf) // s + 1 (geometry.utterance_geometry).  The encoder is a chain of valid convolutions, so the utterance
+        is cut into overlapping windows of the engine's fixed geometry at hop s * embed_len, zero-padded behind its last
+        frame, and only codes whose receptive field lies inside real frames are kept: frame for frame the bits one run
+        over the whole utterance gives.  The windows of all utterances are packed into batches of `batch` rows (default:
+        the live engine's B); the last batch is padded with idle rows.  The work list is `codes.tile_plan` of the frame
+        counts - the device is never asked for a size.  Otherwise the rules of encode(): VQ bottlenecks only; no
+        codebook, EMA statistic, histogram, loss or metric word is written; inside `FusedAdam.averaged_weights()` the
+        averaged weights are used; a pending `loss.backward()` raises afterwards; no host synchronisation and no
+        collective (under data parallel each rank encodes what it is given)."""
+        self._need_codes("encode_utterances()")
+        mels = list(mels)
+        n_mel = self._opts["n_mel"] or 3 * self.hps.n_mfcc
+        for m in mels:
+            if m.dim() != 2 or m.shape[0] != n_mel or m.device.type != "cuda":
+                raise L.AewError(f"encode_utterances(): ({n_mel}, frames) device tensors expected, got {tuple(m.shape)} on "
+                                 f"'{m.device}'")
+        frames = [int(m.shape[1]) for m in mels]
+        bases, at = [], 0
+        for F in frames:
+            bases.append(at)
+            at += n_mel * F
+        flat = torch.cat([m.to(torch.float32).reshape(-1) for m in mels]) if at else \
+            torch.empty(0, dtype=torch.float32, device=self._device)
+        return self._encode_ragged("encode_utterances()", flat, frames, bases, voice, batch, return_dist, names)
+
+    def _utterance_mfcc(self):
+        from .mfcc import DeviceMfcc
+        h = self.hps
+        if self._utt_mfcc is None or self._utt_mfcc.dev != self._device:
+            self._utt_mfcc = DeviceMfcc(self._device, h.sample_rate, h.mfcc_win_sz, h.mfcc_hop_sz, h.n_mels, h.n_mfcc)
+        if self._utt_mfcc.n_out != (self._opts["n_mel"] or 3 * h.n_mfcc):
+            raise L.AewError(f"encode_wavs(): the MFCC front-end yields {self._utt_mfcc.n_out} channels, the encoder takes "
+                             f"{self._opts['n_mel']}")
+        return self._utt_mfcc
+
+    def encode_wavs(self, wavs, voice=None, batch=None, return_dist: bool = False, names=None):
+        """wavs: a list of 1-D device tensors of mu-law values, whole utterances of any lengths -> `codes.UtteranceCodes`.
+        The MFCC of each WHOLE utterance is computed on the device (one AEW_OP_MFCC record per utterance,
+        DeviceMfcc.ragged: the dB floor and the delta edges are the utterance's, the reference's definition when its
+        loader hands over entire files) straight into the ragged buffer encode_utterances() tiles."""
+        self._need_codes("encode_wavs()")
+        if self._device.type != "cuda":
+            raise L.AewError("encode_wavs() runs on an MI355X only; move the model to a cuda device first")
+        flat, frames, bases = self._utterance_mfcc().ragged(wavs)
+        return self._encode_ragged("encode_wavs()", flat, frames, bases, voice, batch, return_dist, names)
+
+    def encode_corpus(self, corpus, batch=None, max_frames_per_chunk: int = 1 << 16, return_dist: bool = False):
+        """Tokenise a `corpus.DeviceCorpus`: every utterance of `corpus.samples`, in that order, straight from the
+        resident sound bytes, as encode_wavs() does -> `codes.UtteranceCodes` with `voice` = the samples' voice_index and
+        `names` = their file_path (where the records carry one).  The utterances are taken in chunks of at most
+        max_frames_per_chunk mel frames (one utterance at least), which bounds the memory held besides the result;
+        every utterance is encoded on its own, so the chunking does not change a bit."""
+        from . import codes as CD
+        self._need_codes("encode_corpus()")
+        if corpus.snd is None:
+            corpus._need_device()
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[corpus.snd_bytes]
+        snd = corpus.snd[:corpus.n_snd * corpus.snd_bytes].view(dt)
+        mf = self._utterance_mfcc()
+        chunks, cur, held = [], [], 0
+        for sam in corpus.samples:
+            F = max(0, mf.n_frames(int(sam[2]) - int(sam[1])))
+            if cur and held + F > int(max_frames_per_chunk):
+                chunks.append(cur)
+                cur, held = [], 0
+            cur.append(sam)
+            held += F
+        if cur:
+            chunks.append(cur)
+        parts = [self.encode_wavs([snd[int(s[1]):int(s[2])] for s in ch], batch=batch, return_dist=return_dist) for ch in chunks]
+        dev = self._device
+        codes = torch.cat([p.codes for p in parts]) if parts else torch.empty(0, dtype=torch.int64, device=dev)
+        dist = (torch.cat([p.dist for p in parts]) if parts else torch.empty(0, dtype=torch.float32, device=dev)) \
+            if return_dist else None
+        offsets, at = [0], 0
+        for p in parts:
+            offsets += [at + o for o in p._off[1:]]
+            at = offsets[-1]
+        voice = torch.tensor([int(s[0]) for s in corpus.samples], dtype=torch.int64)
+        names = [str(s[3]) for s in corpus.samples] if all(len(s) > 3 for s in corpus.samples) else None
+        return CD.UtteranceCodes(codes, torch.tensor(offsets, dtype=torch.int64), dist=dist, voice=voice, names=names)
 
     def zero_amplitude_code(self) -> int:
         """The mu-law value a sample of amplitude 0 encodes to (codes.mu_encode with this model's n_quant)."""

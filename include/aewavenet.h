@@ -46,8 +46,8 @@ extern "C" {
  * append-only - two op kinds behind the existing ones, two descriptors that fit the union's size, aew_sizeof indices 22
  * and 23, two host functions; no existing record, op number or function changed - so a caller built against 28 runs
  * unchanged.  A binding that wants the additions finds them through aew_sizeof(22) / aew_sizeof(23) (-1 in a library
- * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 32,
- * aew_eval_groups_t / AEW_OP_EVAL_GROUPS). */
+ * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 34 .. 36,
+ * aew_utt_row_t, aew_mel_tile_t / AEW_OP_MEL_TILE, aew_code_stitch_t / AEW_OP_CODE_STITCH). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -820,6 +820,76 @@ typedef struct {
     int32_t B, N;
 } aew_code_runs_t;
 
+/* Whole utterances through the fixed-geometry encoder (appended to ABI 28; AEW_OP_MEL_TILE / AEW_OP_CODE_STITCH,
+ * aew_sizeof 34 / 35 / 36 - index 33 stays unused, it answers -1).  The encoder is a chain of valid convolutions of
+ * stride s and receptive field rf mel frames, mel_len = s * (E - 1) + rf for E = embed_len codes per window.  An utterance of F frames has N = 0 codes if F < rf, else
+ * (F - rf) / s + 1; its window w starts at frame w * s * E and holds the codes [w E, min(N, w E + E)).  The frames a window
+ * lacks are zeros, and a code is stored only if its receptive field lies inside the real frames - so the codes of the
+ * windows, put side by side, are those of one run over the whole utterance, bit for bit (the exact fp32 chain sums every
+ * output frame in an order that depends on the K axis and not on the position).
+ *
+ * Both ops read one table of records in DEVICE memory, one record per batch row: the launch is given the table and the
+ * first row of its batch, so a caller uploads the table of a whole call once and no launch waits for the host.  The
+ * launchers check the rows [first_row, first_row + B) on `table_host`, a host copy of the same records (the pinned buffer
+ * the upload was made from); the kernels repeat the check on the device copy and treat a record that fails it as idle
+ * (zeros / nothing stored), so a captured graph whose table is rewritten between replays stays inside its buffers.
+ * Plain loads and stores, no atomics, every loop bounded by the record.
+ *
+ * The ragged mel buffer holds the utterances' (n_mel, F_u) arrays one behind the other: channel c, frame t of a window
+ * is element src + c * pitch + t. */
+typedef struct {
+    int64_t src;                 /* element offset of the window's first frame (channel 0) in the ragged mel buffer */
+    int64_t dst;                 /* element offset of the window's first code in the ragged outputs                 */
+    int32_t pitch;               /* elements between channels: the utterance's frame count                         */
+    int32_t avail;               /* frames that exist from src on, 0 .. mel_len; 0: an idle row (src, pitch unused) */
+    int32_t n_valid;             /* codes of the row that are stored, 0 .. E; 0: nothing (dst unused)               */
+    int32_t pad_;
+} aew_utt_row_t;
+
+/* AEW_OP_MEL_TILE: for b < B, with r = table[first_row + b], in_mel[b][c][t] = mel[r.src + c * r.pitch + t] for
+ * t < r.avail and +0.0f for r.avail <= t < mel_len; every element of in_mel[0 .. B) is written exactly once, nothing
+ * else is.  16-byte stores where in_mel is 16-byte aligned and n_mel * mel_len a multiple of 4 (4-byte ones otherwise);
+ * a window's first frame is only 4-byte aligned, so the loads are 16, 8 or 4 bytes wide as each address allows.
+ * AEW_E_ARG: a NULL table / table_host / mel / in_mel, B < 1 or > 65535, first_row < 0, n_mel or mel_len < 1, n_src < 0,
+ * a row with avail outside [0, mel_len] or - avail > 0 - src < 0, pitch < avail or a last element
+ * src + (n_mel - 1) * pitch + avail - 1 outside [0, n_src); AEW_E_ALIGN: the tables not 8-byte, mel / in_mel not 4-byte
+ * aligned.  All before any launch: a refused call writes nothing. */
+typedef struct {
+    const aew_utt_row_t* table;       /* device memory                                         */
+    const aew_utt_row_t* table_host;  /* the same records in host memory (read by the launcher) */
+    int32_t first_row, B;
+    const float* mel;            /* the ragged mel buffer, n_src elements                      */
+    int64_t n_src;
+    float* in_mel;               /* [B][n_mel][mel_len]                                        */
+    int32_t n_mel, mel_len;
+} aew_mel_tile_t;
+
+/* AEW_OP_CODE_STITCH: for b < B, with r = table[first_row + b], codes[r.dst + j] = ind[b][j] and - dist != NULL -
+ * dist[r.dst + j] = min_dist[b][j] for j < r.n_valid; it writes nothing else.  One wave per row, 8-byte (codes) and 4-byte
+ * (distances) accesses: the widest a destination offset of any element count allows.
+ * AEW_E_ARG: a NULL table / table_host / ind / codes, dist without min_dist, B < 1 or > 65535, first_row < 0, E < 1,
+ * n_dst < 0, a row with n_valid outside [0, E] or - n_valid > 0 - [dst, dst + n_valid) outside [0, n_dst); AEW_E_ALIGN:
+ * the tables / ind / codes not 8-byte, min_dist / dist not 4-byte aligned.  All before any launch. */
+typedef struct {
+    const aew_utt_row_t* table;       /* device memory                                         */
+    const aew_utt_row_t* table_host;  /* the same records in host memory (read by the launcher) */
+    int32_t first_row, B;
+    const int64_t* ind;          /* [B][E]: AEW_OP_VQ_NEAREST's indices of the batch           */
+    const float* min_dist;       /* [B][E]: its distances (needed with dist only)              */
+    int64_t* codes;              /* ragged output, n_dst elements                              */
+    float* dist;                 /* optional ragged output, n_dst elements                     */
+    int64_t n_dst;
+    int32_t E, pad_;
+} aew_code_stitch_t;
+
+/* The index arithmetic of the two ops for one record, as the kernels and the launchers compute it (one __host__ __device__
+ * definition; host-only export for tests): *avail / *n_valid = the frames AEW_OP_MEL_TILE copies / the codes
+ * AEW_OP_CODE_STITCH stores, *src = the element of the ragged mel buffer that in_mel[b]'s flat element i (row-major
+ * (n_mel, mel_len)) is copied from, -1 where it becomes zero.  AEW_E_ARG: a NULL pointer, n_mel / mel_len / E < 1,
+ * n_src / n_dst < 0, i outside [0, n_mel * mel_len), or a record either launcher refuses. */
+int aew_utterance_locate(const aew_utt_row_t* row, int n_mel, int mel_len, int E, int64_t n_src, int64_t n_dst, int64_t i,
+                         int64_t* src, int32_t* avail, int32_t* n_valid);
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1140,7 +1210,7 @@ enum {
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
-    AEW_OP_EVAL_GROUPS
+    AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1169,14 +1239,14 @@ typedef struct {
         aew_swap_t swap; aew_vq_restart_t vqr; aew_eval_acc_t eva; aew_window_gather_t wgat;
         aew_grad_welford_t gwel; aew_seg_select_t ssel; aew_accum_t accum;
         aew_code_lookup_t clk; aew_code_runs_t crun; aew_adam_grouped_t adamg;
-        aew_eval_groups_t evg;
+        aew_eval_groups_t evg; aew_mel_tile_t mtile; aew_code_stitch_t cstitch;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups (24 and 26 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch (24, 26 and 33 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
