@@ -25,7 +25,7 @@ EF_OUT2_COPY = 1 << 10
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
- OP_MEL_TILE, OP_CODE_STITCH) = range(1, 41)
+ OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH) = range(1, 43)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -251,6 +251,32 @@ class CodeStitch(C.Structure):
                 ("codes", vp), ("dist", vp), ("n_dst", i64), ("E", i32), ("pad_", i32)]
 
 
+class CondRow(C.Structure):
+    """aew_cond_row_t: one batch row of a whole-utterance conditioning - where its window starts in the flat code buffer
+    and which of its codes exist, which rows of its cond it owns and where they go, its voice, whether it is the first
+    window of its utterance.  COND_ROW_DTYPE is the same record for numpy."""
+    _fields_ = [("code0", i64), ("utt", i32), ("stream", i32), ("lo", i32), ("hi", i32), ("src_row", i32), ("n_rows", i32),
+                ("dst_row", i32), ("pitch", i32), ("voice", i32), ("first", i32)]
+
+
+COND_ROW_DTYPE = [("code0", "<i8"), ("utt", "<i4"), ("stream", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("src_row", "<i4"),
+                  ("n_rows", "<i4"), ("dst_row", "<i4"), ("pitch", "<i4"), ("voice", "<i4"), ("first", "<i4")]
+
+
+class CodeTile(C.Structure):
+    """aew_code_tile_t: ind[b] / in_voice[b] = the window of table[first_row + b] cut out of the flat code buffer, code 0
+    where the utterance has none; codes outside [0, K) become 0 and are counted in *bad."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("codes", vp), ("n_codes", i64),
+                ("ind", vp), ("in_voice", vp), ("bad", vp), ("E", i32), ("K", i32), ("n_voice", i32), ("pad_", i32)]
+
+
+class CondStitch(C.Structure):
+    """aew_cond_stitch_t: the cond rows each batch row owns (and its gated bias, for a first window) to their stream."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("cond", vp), ("cond_bs", i64),
+                ("cond_pitch", i32), ("T", i32), ("cond_utt", vp), ("n_dst", i64), ("bias", vp), ("bias_utt", vp),
+                ("Cp", i32), ("bias_n", i32), ("n_streams", i32), ("pad_", i32)]
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -391,7 +417,8 @@ class _OpU(C.Union):
                 ("mom", Moments), ("tng", GemmTNGroup), ("chain", NtChain), ("gnorm", GradNorm),
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
-                ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch)]
+                ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
+                ("ctile", CodeTile), ("cndst", CondStitch)]
 
 
 class Op(C.Structure):
@@ -407,7 +434,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
             OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
-            OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch"}
+            OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst"}
 
 
 
@@ -541,7 +568,7 @@ def load():
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
-                       (36, CodeStitch)):
+                       (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

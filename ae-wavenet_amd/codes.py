@@ -9,7 +9,9 @@ Both run as one-op plans on torch's current stream, take any device tensor (rows
 of an utterance) and never synchronise with the host.  `model.encode()` / `model.decode()` / `model.convert()`
 (surface.py) are the calls that produce and consume the codes of one window; `model.encode_utterances()` /
 `encode_wavs()` / `encode_corpus()` produce those of whole utterances as an `UtteranceCodes`, from the work list
-`tile_plan()` states (csrc/aew_utterance.hip).
+`tile_plan()` states (csrc/aew_utterance.hip); `model.utterance_conditioning()` / `decode_utterances()` /
+`convert_utterances()` consume them again at the utterance's length, from the work list `cond_tile_plan()` and the stream
+assignment `stream_groups()` (csrc/aew_cond_utterance.hip).
 """
 from __future__ import annotations
 
@@ -250,6 +252,119 @@ class UtteranceCodes:
             return cls(put("codes"), torch.from_numpy(z["offsets"]), dist=put("dist") if "dist" in z else None,
                        voice=put("voice") if "voice" in z else None,
                        names=[str(n) for n in z["names"]] if "names" in z else None)
+
+
+# ---- whole utterances, the other way: the work list of model.utterance_conditioning() / decode_utterances() ------------
+@dataclass
+class CondTilePlan:
+    """cond_tile_plan()'s result: per utterance its conditioning length L(N_u) and its stream; per batch row
+    (n_batches * B of them, the idle rows that fill the last batch included) the utterance (-1: idle), its window, the
+    window's first code relative to the utterance's (negative in front of it), the window codes [lo, hi) that exist, the
+    cond rows [src_row, src_row + n_rows) it owns, the conditioning position dst_row of the first of them and whether it
+    is the utterance's first window.  Utterance u is stream u of a [U][pitch][Cp] buffer, pitch = the longest L(N_u)
+    (at least 1) unless given; one with L(N_u) = 0 has no row.  Host arrays only."""
+    E: int
+    S: int
+    T: int
+    trim0: int
+    p: int
+    h: int
+    B: int
+    n_codes: np.ndarray         # int64 [U]
+    lengths: np.ndarray         # int64 [U]: L(N_u)
+    pitch: int                  # rows per stream
+    utt: np.ndarray             # int32 [R]
+    window: np.ndarray          # int32 [R]
+    start: np.ndarray           # int64 [R]
+    lo: np.ndarray              # int32 [R]
+    hi: np.ndarray              # int32 [R]
+    src_row: np.ndarray         # int32 [R]
+    owned: np.ndarray           # int32 [R]: rows the window owns
+    dst_row: np.ndarray         # int32 [R]
+    first: np.ndarray           # int32 [R]
+    n_rows: int                 # rows that are not idle
+
+    @property
+    def n_batches(self) -> int:
+        return len(self.utt) // self.B
+
+    def offsets(self, Cp: int) -> np.ndarray:
+        """Element offset of each utterance's conditioning in the stitched [U][pitch][Cp] buffer."""
+        return np.arange(len(self.n_codes), dtype=np.int64) * (self.pitch * int(Cp))
+
+    def table(self, bases, voices) -> np.ndarray:
+        """The aew_cond_row_t records (a structured array, _lib.COND_ROW_DTYPE) for utterances whose codes start at the
+        indices `bases` [U] of the flat code buffer and whose voices are `voices` [U]."""
+        rec = np.zeros(len(self.utt), np.dtype(L.COND_ROW_DTYPE))
+        rec["utt"] = -1
+        live = self.utt >= 0
+        u = self.utt[live]
+        rec["utt"][live] = rec["stream"][live] = u
+        rec["code0"][live] = np.asarray(bases, np.int64).reshape(-1)[u] + self.start[live]
+        rec["voice"][live] = np.asarray(voices, np.int64).reshape(-1)[u]
+        rec["pitch"][live] = self.pitch
+        for name, arr in (("lo", self.lo), ("hi", self.hi), ("src_row", self.src_row), ("n_rows", self.owned),
+                          ("dst_row", self.dst_row), ("first", self.first)):
+            rec[name][live] = arr[live]
+        return rec
+
+
+def cond_tile_plan(n_codes: Sequence[int], E: int, S: int, T: int, trim0: int, B: int, L_of, pitch: Optional[int] = None) -> CondTilePlan:
+    """The work list of a whole-utterance conditioning, a pure function of the code counts (it never reads the device).
+    (E, S, T, trim0) and L_of = n -> L(n) are geometry.conditioning_geometry's: with p = ceil(trim0 / S) pad codes and the
+    hop h = (T - (p S - trim0)) // S, an utterance of N codes has ceil(L(N) / (h S)) windows; window w holds the codes
+    [w h - p, w h - p + E) - those inside [0, N) exist, the others are code 0 - and owns the conditioning positions
+    [w h S, min((w + 1) h S, L(N))): its cond rows from p S - trim0 on.  The windows of all utterances, in order, fill
+    batches of B rows; the last batch is padded with idle rows."""
+    E, S, T, trim0, B = int(E), int(S), int(T), int(trim0), int(B)
+    if E < 1 or S < 1 or T < 1 or trim0 < 0 or B < 1:
+        raise ValueError("cond_tile_plan(): E, S, T and B must be at least 1, trim0 at least 0")
+    p = -(-trim0 // S)
+    lead = p * S - trim0
+    h = (T - lead) // S
+    if h < 1:
+        raise ValueError(f"cond_tile_plan(): T = {T} rows hold no hop of S = {S} behind row {lead}")
+    N = np.asarray(list(n_codes), np.int64).reshape(-1)
+    if (N < 0).any():
+        raise ValueError("cond_tile_plan(): negative code count")
+    Ln = np.asarray([int(L_of(int(n))) for n in N], np.int64).reshape(-1)
+    if (Ln < 0).any() or (Ln > np.maximum(N, 0) * S).any():
+        raise ValueError("cond_tile_plan(): L(n) must lie in [0, n * S]")
+    hop = h * S
+    nw = -(-Ln // hop)
+    n_rows = int(nw.sum())
+    R = -(-n_rows // B) * B
+    t_max = max(int(Ln.max()) if len(Ln) else 0, 1)
+    if pitch is None:
+        pitch = t_max
+    elif int(pitch) < t_max:
+        raise ValueError(f"cond_tile_plan(): pitch {pitch} is shorter than the longest conditioning, {t_max} rows")
+    firstw = np.concatenate([[0], np.cumsum(nw)])[:-1]
+    utt = np.full(R, -1, np.int32)
+    window, start = np.zeros(R, np.int32), np.zeros(R, np.int64)
+    lo, hi, src_row = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
+    rows, dst_row, first = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
+    u = np.repeat(np.arange(len(N)), nw)
+    w = np.arange(n_rows) - np.repeat(firstw, nw)
+    c0 = w * h - p
+    utt[:n_rows], window[:n_rows], start[:n_rows] = u, w, c0
+    lo[:n_rows] = np.clip(-c0, 0, E)
+    hi[:n_rows] = np.maximum(np.clip(N[u] - c0, 0, E), lo[:n_rows])
+    src_row[:n_rows] = lead
+    dst_row[:n_rows] = w * hop
+    rows[:n_rows] = np.minimum(hop, Ln[u] - w * hop)
+    first[:n_rows] = w == 0
+    return CondTilePlan(E, S, T, trim0, p, h, B, N, Ln, int(pitch), utt, window, start, lo, hi, src_row, rows, dst_row,
+                        first, n_rows)
+
+
+def stream_groups(lengths: Sequence[int], seed: int, width: int = 16):
+    """Which sampler call generates which utterance, a pure function of (lengths, seed): the utterances with a length
+    above 0, ordered longest first (stable: equal lengths keep their input order), are cut into groups of `width`;
+    returns [(seed + g, [utterance indices of group g])] - the k-th index of a group is stream slot k of that group's
+    one Sampler.generate call, whose seed is seed + g and whose step count is the length of its first member."""
+    order = sorted((u for u, n in enumerate(lengths) if int(n) > 0), key=lambda u: -int(lengths[u]))
+    return [(int(seed) + g, order[at:at + width]) for g, at in enumerate(range(0, len(order), width))]
 
 
 # ---- mu-law companding of the decoder's samples (amplitudes in [-1, 1] -> n_quant integer values) ---------------------

@@ -10,6 +10,7 @@
 #include "aew_codes.hip"
 #include "aew_evalgroups.hip"
 #include "aew_utterance.hip"
+#include "aew_cond_utterance.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -72,6 +73,8 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_EVAL_GROUPS: return launch_eval_groups(op.u.evg, st);
         case AEW_OP_MEL_TILE: return launch_mel_tile(op.u.mtile, st);
         case AEW_OP_CODE_STITCH: return launch_code_stitch(op.u.cstitch, st);
+        case AEW_OP_CODE_TILE: return launch_code_tile(op.u.ctile, st);
+        case AEW_OP_COND_STITCH: return launch_cond_stitch(op.u.cndst, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -115,6 +118,9 @@ extern "C" int aew_sizeof(int which) {
         case 34: return (int)sizeof(aew_utt_row_t);      // (33 is left unused like 24 and 26)
         case 35: return (int)sizeof(aew_mel_tile_t);
         case 36: return (int)sizeof(aew_code_stitch_t);
+        case 37: return (int)sizeof(aew_cond_row_t);
+        case 38: return (int)sizeof(aew_code_tile_t);
+        case 39: return (int)sizeof(aew_cond_stitch_t);
         default: return -1;
     }
 }

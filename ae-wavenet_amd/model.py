@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from . import geometry as G
-from .engine import (F3, BottleneckPlan, DecoderPlan, EncoderPlan, Packer, ParamStore, TAG_ADAM, TAG_LOSS, TAG_PACK, TAG_VQ,
+from .engine import (F3, BottleneckPlan, DecoderPlan, EncoderPlan, Packer, ParamStore, TAG_ADAM, TAG_LOSS, TAG_PACK, TAG_UPS, TAG_VQ,
                      bottleneck_param_specs, decoder_param_specs, encoder_param_specs, reduce_op)
 from .plan import CopyTableBuilder, Mat, Plan, Workspace, insert_nt_chains, ru, split_small_nt
 
@@ -513,6 +513,10 @@ class TrainEngine:
         # ===== whole utterances (encode_tiles(): aew_mel_tile_t / aew_code_stitch_t): one op each in front of and behind
         # _cond_plan_a, re-addressed per batch like `opt`; they exist from the first whole-utterance encode on
         self.utt_tile, self.utt_stitch = Plan("utt.tile"), Plan("utt.stitch")
+        # ===== whole utterances, the decoder's side (conditioning_tiles(): aew_code_tile_t / aew_cond_stitch_t): one op each
+        # in front of and behind the decode plan, re-addressed per batch in the same way
+        self.cond_tile, self.cond_stitch = Plan("code.tile"), Plan("cond.stitch")
+        self._dec_pack_plan = None        # decoder_pack_plan(): the decoder's weight layouts alone
         self._chain_flag_views = self._chain_host = None
 
     # ops of the training forward that an evaluation leaves out: they write what the next training step (or the caller,
@@ -810,6 +814,128 @@ class TrainEngine:
         self.codes_bad.zero_()
         self._run(dp, False)
         return self._cond_out()
+
+    def conditioning_ops(self):
+        """The records of the two ops around the decode plan in a whole-utterance conditioning, built at the first use:
+        (aew_code_tile_t writing ind / in_voice and counting into codes_bad, aew_cond_stitch_t reading dec.cond and the
+        gated bias).  The caller fills in the table, its first row, the flat codes and the per-stream outputs."""
+        self.decode_plan()
+        if self.take_compat:
+            raise L.AewError("conditioning_tiles(): this engine was built with take_compat=True, whose conditioning gather "
+                             "is not the identity the tiling of whole utterances rests on")
+        if not self.cond_tile.ops:
+            d = self.dec
+            G.conditioning_geometry(self.geom)                       # (raises for a window shorter than one hop)
+            ct = L.CodeTile()
+            ct.ind, ct.in_voice, ct.bad = self.ind.data_ptr(), self.in_voice.data_ptr(), self.codes_bad.data_ptr()
+            ct.B, ct.E, ct.K, ct.n_voice = self.B, self.geom.embed_len, self.K, int(self.hps.n_speakers)
+            self.cond_tile.add(L.OP_CODE_TILE, ct, "code.tile", TAG_VQ)
+            cs = L.CondStitch()
+            cs.cond, cs.cond_bs, cs.cond_pitch, cs.T, cs.Cp = d.cond.ptr, d.cond.bs, d.cond.pitch, d.T, d.Cp
+            cs.bias, cs.bias_n, cs.B = d.bias_bl.data_ptr(), d.NL * 2 * d.Dp, self.B
+            self.cond_stitch.add(L.OP_COND_STITCH, cs, "cond.stitch", TAG_UPS)
+        return self.cond_tile.array()[0].u.ctile, self.cond_stitch.array()[0].u.cndst
+
+    def decoder_pack_plan(self) -> Plan:
+        """The pack of the decoder's weight layouts as a plan of its own, built at the first use.  The conditioning GEMMs
+        read packed copies of the parameters that the training forward refreshes at its head; decode_plan() holds that
+        pack only where it sits in fwd_b (separate packs, placed late).  A whole-utterance conditioning may be the first
+        thing a process runs - codes from disk, weights from a checkpoint - so it packs for itself: the same op record
+        where one exists, else a table of the decoder's records alone (the merged table packs every layout of the step)."""
+        if self._dec_pack_plan is None:
+            lab = "pack weights (decoder)"
+            if lab in self.decode_plan().labels:
+                self._dec_pack_plan = Plan("pack_dec")               # (already part of the decode plan: nothing to add)
+            elif lab in self.fwd_a.labels:
+                op = L.Op.from_buffer_copy(self.fwd_a.ops[self.fwd_a.labels.index(lab)])
+                op.lane = op.join = 0                                # (a side-lane op there; alone it is the main lane)
+                self._dec_pack_plan = Plan("pack_dec")
+                self._dec_pack_plan.ops.append(op)
+                self._dec_pack_plan.labels.append(lab)
+            else:
+                tb = CopyTableBuilder(self.ws, "tbl.pack_dec_alone")
+                tb.recs.extend(L.CopyRec.from_buffer_copy(r) for r in self.pack_dec.recs)
+                self._dec_pack_plan = Plan("pack_dec")
+                tb.emit(self._dec_pack_plan, lab)
+        return self._dec_pack_plan
+
+    def _cond_utt_check(self, what: str, codes_flat, cond_utt, bias_utt):
+        d = self.dec
+        if codes_flat.dtype != torch.int64 or codes_flat.dim() != 1 or not codes_flat.is_contiguous():
+            raise L.AewError(f"{what}: flat contiguous int64 codes expected, got {tuple(codes_flat.shape)} {codes_flat.dtype}")
+        if cond_utt.dtype != torch.bfloat16 or cond_utt.dim() != 3 or cond_utt.shape[2] != d.Cp or not cond_utt.is_contiguous():
+            raise L.AewError(f"{what}: cond_utt bf16 (streams, rows, {d.Cp}) contiguous expected, got {tuple(cond_utt.shape)} "
+                             f"{cond_utt.dtype}")
+        if bias_utt.dtype != torch.float32 or tuple(bias_utt.shape) != (cond_utt.shape[0], d.NL, 2 * d.Dp) \
+                or not bias_utt.is_contiguous():
+            raise L.AewError(f"{what}: bias_utt fp32 ({cond_utt.shape[0]}, {d.NL}, {2 * d.Dp}) contiguous expected, got "
+                             f"{tuple(bias_utt.shape)} {bias_utt.dtype}")
+
+    def conditioning_batch_plan(self, codes_flat: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor, first_row: int,
+                                cond_utt: torch.Tensor, bias_utt: torch.Tensor) -> Plan:
+        """One batch of a whole-utterance conditioning as a plan of its own (for a caller's captured graph): [code.tile] +
+        the ops of decode_plan() (the same records) + [cond.stitch] over the rows [first_row, first_row + B) of `table`
+        (uint8 device bytes of aew_cond_row_t records; table_host: the same bytes in pinned host memory, read at
+        capture).  in_jitter is set to the identity and the decoder's weight layouts are packed here, once (after a change
+        of the weights the caller runs decoder_pack_plan() again); the caller zeroes codes_bad and cond_utt and keeps the
+        tensors alive."""
+        ct0, cs0 = self.conditioning_ops()
+        self._cond_utt_check("conditioning_batch_plan()", codes_flat, cond_utt, bias_utt)
+        ct, cs = L.CodeTile.from_buffer_copy(ct0), L.CondStitch.from_buffer_copy(cs0)
+        ct.table, ct.table_host, ct.first_row = table.data_ptr(), table_host.data_ptr(), int(first_row)
+        ct.codes, ct.n_codes = codes_flat.data_ptr(), codes_flat.numel()
+        cs.table, cs.table_host, cs.first_row = ct.table, ct.table_host, ct.first_row
+        cs.cond_utt, cs.n_dst, cs.bias_utt, cs.n_streams = cond_utt.data_ptr(), cond_utt.numel(), bias_utt.data_ptr(), cond_utt.shape[0]
+        self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
+        self.decoder_pack_plan().run(self._stream())
+        p = Plan("cond.batch")
+        p.add(L.OP_CODE_TILE, ct, "code.tile", TAG_VQ)
+        p.splice(1, self._sub_plan("codes_to_conditioning", self.decode_plan(), lambda i, lab: True))
+        p.add(L.OP_COND_STITCH, cs, "cond.stitch", TAG_UPS)
+        return p
+
+    def conditioning_tiles(self, codes_flat: torch.Tensor, table, cond_utt: torch.Tensor, bias_utt: torch.Tensor):
+        """The conditioning of whole utterances through the fixed-geometry chain: `codes_flat` int64, the flat code
+        buffer; `table` a numpy array of aew_cond_row_t records (_lib.COND_ROW_DTYPE), a multiple of B rows
+        (codes.CondTilePlan.table); `cond_utt` bf16 (streams, rows per stream, Cp) and `bias_utt` fp32 (streams, NL,
+        2 * Dp), contiguous - the caller zero-fills cond_utt once, rows behind an utterance's length are not written.  The
+        table goes to the device once (pinned, non-blocking); per batch of B rows one AEW_OP_CODE_TILE fills ind and
+        in_voice, decode_plan() runs unchanged with in_jitter the identity, and one AEW_OP_COND_STITCH moves the rows each
+        window owns and the gated bias of first windows.  Codes outside [0, K) become code 0 and count in `codes_bad[0]`
+        (zeroed here; non-zero: the caller decides - reading the word synchronises).  Writes what codes_to_conditioning()
+        writes, the packed layouts of the decoder's weights (decoder_pack_plan(), once per call: what the head of a
+        training forward writes) and nothing else of the engine; no host synchronisation."""
+        ct, cs = self.conditioning_ops()
+        dp = self.decode_plan()
+        n = len(table)
+        if n % self.B or table.dtype.itemsize != C.sizeof(L.CondRow):
+            raise L.AewError(f"conditioning_tiles(): a multiple of B = {self.B} aew_cond_row_t records expected, got {n}")
+        self._cond_utt_check("conditioning_tiles()", codes_flat, cond_utt, bias_utt)
+        self.codes_bad.zero_()
+        if n == 0:
+            return
+        host = torch.empty(n * table.dtype.itemsize, dtype=torch.uint8, pin_memory=True)
+        host.numpy()[:] = table.view(np.uint8).reshape(-1)
+        dev = torch.empty_like(host, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        ct.table = cs.table = dev.data_ptr()
+        ct.table_host = cs.table_host = host.data_ptr()
+        ct.codes, ct.n_codes = codes_flat.data_ptr(), codes_flat.numel()
+        cs.cond_utt, cs.n_dst, cs.bias_utt, cs.n_streams = cond_utt.data_ptr(), cond_utt.numel(), bias_utt.data_ptr(), cond_utt.shape[0]
+        self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
+        self.act_epoch += 1
+        st = self._stream()
+        self.decoder_pack_plan().run(st)
+        try:
+            for first in range(0, n, self.B):
+                ct.first_row = cs.first_row = first
+                self.cond_tile.run(st)
+                self._run(dp, False)
+                self.cond_stitch.run(st)
+        finally:
+            # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
+            # keep no address of them
+            ct.table = cs.table = ct.table_host = cs.table_host = ct.codes = cs.cond_utt = cs.bias_utt = None
 
     def conditioning(self):
         """Encoder / bottleneck and the conditioning half of the decoder forward only (jitter gather, lc_conv,

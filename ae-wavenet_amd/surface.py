@@ -20,6 +20,7 @@ import math
 import operator
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -990,6 +991,182 @@ class HipModelBase(nn.Module):
         if V != B:
             codes, given = codes.expand(V, -1).contiguous(), given.expand(V, -1)
         return self.decode(codes, voice_to, prime=given, n_prime=n_prime, seed=seed, jitter=jitter)
+
+    # ---- whole utterances, the decoder's side: conditioning of any length from codes, generation, conversion ----------
+    def _utterance_rows(self, what, codes, voice):
+        """(rows: list of 1-D int64 device tensors, voices: list of ints) from an UtteranceCodes or a list of tensors."""
+        from . import codes as CD
+        if isinstance(codes, CD.UtteranceCodes):
+            rows = [codes.row(u) for u in range(len(codes))]
+            if voice is None:
+                voice = codes.voice
+        else:
+            rows = list(codes)
+        U = len(rows)
+        for r in rows:
+            if not torch.is_tensor(r) or r.dim() != 1 or r.dtype != torch.int64:
+                raise L.AewError(f"{what}: an UtteranceCodes or a list of 1-D int64 tensors expected")
+        if voice is None:
+            raise L.AewError(f"{what}: voice ({U},) expected (the codes carry none)")
+        voice = torch.as_tensor(voice, dtype=torch.int64).cpu().reshape(-1)
+        if voice.numel() != U:
+            raise L.AewError(f"{what}: voice ({U},) expected (one per utterance), got {tuple(voice.shape)}")
+        voices = voice.tolist()
+        nv = int(self.hps.n_speakers)
+        if any(v < 0 or v >= nv for v in voices):
+            raise L.AewError(f"{what}: voices must lie in [0, {nv}), got {voices}")
+        return rows, voices
+
+    def _utterance_engine(self, what, batch):
+        from . import codes as CD
+        self._need_codes(what)
+        if self._opts.get("take_compat"):
+            raise L.AewError(f"{what}: this model was built with take_compat=True, whose conditioning gather is not the "
+                             "identity the tiling of whole utterances rests on")
+        if batch is not None and int(batch) < 1:
+            raise L.AewError(f"{what}: batch must be at least 1, got {batch}")
+        if self._device.type != "cuda":
+            raise L.AewError(f"{what} runs on an MI355X only; move the model to a cuda device first")
+        cg = G.conditioning_geometry(self.geom)                      # (raises where the window cannot tile)
+        B = int(batch) if batch is not None else (self._engine.B if self._engine is not None else int(self.hps.n_batch))
+        eng = self._ensure_engine(B)
+        self._dp_finish()
+        return eng, cg
+
+    def _check_codes(self, what, rows, K):
+        """Raises for a code outside [0, K) anywhere in `rows` - before anything is generated (one read of the device)."""
+        flat = [r for r in rows if r.numel()]
+        if flat:
+            flat = torch.cat([r.to(self._device) for r in flat])
+            bad = int(((flat < 0) | (flat >= K)).sum())
+            if bad:
+                raise L.AewError(f"{what}: {bad} of the {flat.numel()} codes lie outside the codebook [0, {K}); nothing was "
+                                 "generated")
+
+    def _conditioning_of(self, eng, cg, rows, voices, n_streams):
+        """cond (n_streams, T_max, Cp) bf16 / bias (n_streams, NL, 2 * Dp) fp32 / lengths for the utterances `rows`, stream
+        u = utterance u; the streams behind them stay zero."""
+        from . import codes as CD
+        plan = CD.cond_tile_plan([r.numel() for r in rows], cg.E, cg.S, cg.T, cg.trim0, eng.B, cg.L)
+        d, dev = eng.dec, eng.device
+        cond = torch.zeros(n_streams, plan.pitch, d.Cp, dtype=torch.bfloat16, device=dev)
+        bias = torch.zeros(n_streams, d.NL, 2 * d.Dp, dtype=torch.float32, device=dev)
+        bases = np.concatenate([[0], np.cumsum(plan.n_codes)])[:-1]
+        if plan.n_rows:
+            flat = torch.cat([r.to(dev) for r in rows])
+            eng.conditioning_tiles(flat, plan.table(bases, voices), cond, bias)
+        return cond, bias, plan.lengths
+
+    def utterance_conditioning(self, codes, voice=None, batch=None):
+        """The decoder's conditioning of WHOLE utterances from their codes: `codes` a `codes.UtteranceCodes` (its `voice`
+        is the default) or a list of 1-D int64 tensors of any lengths, `voice` (U,) -> (cond bf16 (U16, T_max, Cp), bias
+        fp32 (U16, NL, 2 * Dp), lengths int64 (U,) on the host): stream u holds the L(N_u) = lengths[u] conditioning rows
+        of utterance u - 320 N - 2172 at the reference strides, 0 below 7 codes - and zeros behind them; U16 is U rounded
+        up to a multiple of 16 (the sampler's stream count), T_max the longest length.  The conditioning chain (codebook
+        row, identity gather, LC conv, transposed-conv upsamplers) is shift-invariant and valid, so each utterance is cut
+        into overlapping windows of the engine's fixed geometry (geometry.conditioning_geometry; work list:
+        codes.cond_tile_plan), run through the unchanged conditioning plan `batch` windows at a time, and the rows each
+        window owns are stitched: row for row the bits a run over the whole code sequence gives.  Row q of stream u
+        belongs to sample o + q of the utterance's waveform, o = conditioning_geometry(...).o.  The result takes
+        U16 * T_max * Cp * 2 bytes.  The rules of decode() hold; a code outside [0, K) raises AewError."""
+        what = "utterance_conditioning()"
+        eng, cg = self._utterance_engine(what, batch)
+        rows, voices = self._utterance_rows(what, codes, voice)
+        with torch.no_grad():
+            self._check_codes(what, rows, eng.K)
+            cond, bias, lengths = self._conditioning_of(eng, cg, rows, voices, max(16, -(-len(rows) // 16) * 16))
+        return cond, bias, torch.from_numpy(lengths.copy())
+
+    def decode_utterances(self, codes, voice=None, prime=None, n_prime: Optional[int] = None, seed: Optional[int] = None,
+                          batch=None):
+        """Generate whole utterances from their codes: `codes` / `voice` / `batch` as in utterance_conditioning() -> a
+        list of U float32 tensors of mu-law values, the u-th of L(N_u) samples (empty where L(N_u) = 0: under 7 codes at
+        the reference strides; such an utterance takes no stream).  Element q is sample o + q of the waveform the codes
+        were encoded from.  `prime`: a list of per-utterance mu-law tensors aligned to conditioning position 0 (that is
+        wav[o:]); the first n_prime positions (default: receptive field + 1, as in decode(); clipped to L_u) are forced to
+        it - without `prime`, to zero_amplitude_code() - and the rest are drawn.
+
+        Streams.  codes.stream_groups(lengths, seed) states, as a pure function, what runs where: the utterances with
+        L > 0 are ordered longest first (stable: equal lengths keep their input order), group g takes the 16 from
+        position 16 g on, utterance k of a group is stream slot k of ONE Sampler.generate call with seed `seed + g` over
+        T_max = the group's longest length.  Shorter streams are padded with zero conditioning and their tails dropped;
+        slots a group leaves empty repeat its first utterance and are dropped.  Results come back in input order, and two
+        calls with the same seed agree bit for bit.  seed=None takes sample_seed and advances it by the group count.
+
+        Memory: the conditioning of one group is 16 * T_max * Cp * 2 bytes - about 0.65 GB for ten-second utterances
+        (160 000 samples) at Cp = 128.
+
+        The rules of decode() hold: VQ bottlenecks only; a code outside [0, K) raises AewError with nothing generated; no
+        codebook, EMA statistic, histogram, loss or metric word is written; inside `FusedAdam.averaged_weights()` the
+        averaged weights are used; a pending `loss.backward()` raises afterwards; no collective under data parallel.  A
+        model built with take_compat=True is refused."""
+        from . import codes as CD
+        what = "decode_utterances()"
+        eng, cg = self._utterance_engine(what, batch)
+        rows, voices = self._utterance_rows(what, codes, voice)
+        U = len(rows)
+        if prime is not None and len(prime) != U:
+            raise L.AewError(f"{what}: prime must hold one tensor per utterance ({U}), got {len(prime)}")
+        lengths = [cg.L(r.numel()) for r in rows]
+        with torch.no_grad():
+            dev = eng.device
+            self._check_codes(what, rows, eng.K)
+            smp = self._engine_sampler(eng)
+            rf = smp.g.rf()
+            n_forced = [min(n, rf + 1 if n_prime is None else max(1, int(n_prime))) for n in lengths]
+            for u in range(U) if prime is not None else ():
+                if lengths[u] and (prime[u].dim() != 1 or prime[u].numel() < n_forced[u]):
+                    raise L.AewError(f"{what}: prime[{u}] must be 1-D with at least {n_forced[u]} values, got "
+                                     f"{tuple(prime[u].shape)}")
+            if seed is None:
+                seed = self.sample_seed
+                self.sample_seed += len(CD.stream_groups(lengths, 0))
+            out = [torch.empty(0, dtype=torch.float32, device=dev) for _ in range(U)]
+            zero = self.zero_amplitude_code()
+            for g_seed, members in CD.stream_groups(lengths, seed):
+                n = len(members)
+                cond, bias, got = self._conditioning_of(eng, cg, [rows[u] for u in members], [voices[u] for u in members], 16)
+                assert got.tolist() == [lengths[u] for u in members]
+                bad = int(eng.codes_bad[0].item()) & 0xFFFFFFFF          # (generation synchronises anyway)
+                if bad:
+                    raise L.AewError(f"{what}: codes outside the codebook [0, {eng.K}) were met ({bad} counted over the "
+                                     "overlapping windows)")
+                T_max = cond.shape[1]
+                forced = torch.full((16, T_max), -1, dtype=torch.int32, device=dev)
+                for k, u in enumerate(members):
+                    if prime is None:
+                        forced[k, :n_forced[u]] = zero
+                    else:
+                        forced[k, :n_forced[u]] = prime[u][:n_forced[u]].to(device=dev, dtype=torch.int32)
+                if n < 16:                                               # empty slots repeat the group's first utterance
+                    cond[n:], bias[n:], forced[n:] = cond[0], bias[0], forced[0]
+                wav, _ = smp.generate(cond, bias, forced, seed=g_seed)
+                for k, u in enumerate(members):
+                    out[u] = wav[k, :lengths[u]].float()
+            return out
+
+    def convert_utterances(self, wavs, voice_to, n_prime: Optional[int] = None, seed: Optional[int] = None, batch=None):
+        """Voice conversion of whole utterances: decode_utterances(encode_wavs(wavs), voice_to, prime=[w[o:] for w in
+        wavs]) with o = geometry.conditioning_geometry(model.geom).o (2235 at the reference geometry, whatever
+        n_win_batch).  wavs: a list of 1-D device tensors of mu-law values; voice_to: one voice per utterance - or, with
+        ONE utterance, (V,): that utterance is decoded in V voices at once, as V streams.  Returns a list of float32
+        tensors; element q of an output is aligned to sample o + q of its input, and its first n_prime values are the
+        input's."""
+        what = "convert_utterances()"
+        self._need_codes(what)
+        wavs = list(wavs)
+        voice_to = torch.as_tensor(voice_to, dtype=torch.int64).cpu().reshape(-1)
+        U, V = len(wavs), voice_to.numel()
+        if V != U and not (U == 1 and V >= 1):
+            raise L.AewError(f"{what}: voice_to ({U},) expected, or (V,) with one utterance; got {tuple(voice_to.shape)} for "
+                             f"{U} utterances")
+        o = G.conditioning_geometry(self.geom).o
+        uc = self.encode_wavs(wavs, batch=batch)
+        rows = [uc.row(u) for u in range(U)]
+        prime = [w[o:] for w in wavs]
+        if V != U:
+            rows, prime = rows * V, prime * V
+        return self.decode_utterances(rows, voice_to, prime=prime, n_prime=n_prime, seed=seed, batch=batch)
 
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared

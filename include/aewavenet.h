@@ -46,8 +46,8 @@ extern "C" {
  * append-only - two op kinds behind the existing ones, two descriptors that fit the union's size, aew_sizeof indices 22
  * and 23, two host functions; no existing record, op number or function changed - so a caller built against 28 runs
  * unchanged.  A binding that wants the additions finds them through aew_sizeof(22) / aew_sizeof(23) (-1 in a library
- * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 34 .. 36,
- * aew_utt_row_t, aew_mel_tile_t / AEW_OP_MEL_TILE, aew_code_stitch_t / AEW_OP_CODE_STITCH). */
+ * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 37 .. 39,
+ * aew_cond_row_t, aew_code_tile_t / AEW_OP_CODE_TILE, aew_cond_stitch_t / AEW_OP_COND_STITCH). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -890,6 +890,80 @@ typedef struct {
 int aew_utterance_locate(const aew_utt_row_t* row, int n_mel, int mel_len, int E, int64_t n_src, int64_t n_dst, int64_t i,
                          int64_t* src, int32_t* avail, int32_t* n_valid);
 
+/* Whole utterances through the fixed-geometry conditioning chain (appended to ABI 28; AEW_OP_CODE_TILE /
+ * AEW_OP_COND_STITCH, aew_sizeof 37 / 38 / 39).  The chain codes -> codebook rows -> identity gather -> LC conv (k = 3,
+ * valid) -> transposed-conv upsamplers (padding f - s) is shift-invariant and valid: a shift of one code moves the last
+ * upsampler's output by S = prod(strides) rows, and no output row reads outside its inputs.  For n codes that output has
+ * L(n) rows ("conditioning positions"); an engine of E = embed_len codes keeps T = dec_in_len of its L(E) rows from row
+ * trim0 on.  With p = ceil(trim0 / S) and the hop h = (T - (p S - trim0)) / S codes, window w of an utterance of N codes
+ * holds the codes [w h - p, w h - p + E) - code 0 where the utterance has none - and owns the conditioning positions
+ * [w h S, min((w + 1) h S, L(N))): its cond rows from p S - trim0 on.  Row for row these are the bits of one run over
+ * the whole code sequence (a row's sums depend on the K axis of its GEMMs, not on its position).
+ *
+ * Both ops read one table of records in DEVICE memory, one per batch row, as the whole-utterance encode's ops do: the
+ * launchers check the rows [first_row, first_row + B) on `table_host` (the pinned buffer the upload was made from), the
+ * kernels repeat the check on the device copy and treat a record that fails it as idle, so a captured graph whose table
+ * is rewritten between replays stays inside its buffers. */
+typedef struct {
+    int64_t code0;               /* index in the flat code buffer of the window's code 0 (in front of the buffer or behind it
+                                    where lo / hi keep the reads inside): window code j is codes[code0 + j]             */
+    int32_t utt;                 /* the utterance, < 0: an idle row (nothing else of the record is used)                */
+    int32_t stream;              /* its stream: cond_utt[stream], bias_utt[stream]                                      */
+    int32_t lo, hi;              /* the window's codes [lo, hi) exist, 0 <= lo <= hi <= E; the others are code 0        */
+    int32_t src_row;             /* first owned row of the window's cond, [src_row, src_row + n_rows) inside [0, T)     */
+    int32_t n_rows;              /* owned rows                                                                          */
+    int32_t dst_row;             /* conditioning position of the first owned row: its row in the stream's buffer        */
+    int32_t pitch;               /* rows per stream of cond_utt; [dst_row, dst_row + n_rows) lies inside [0, pitch)     */
+    int32_t voice;               /* the utterance's voice, [0, n_voice)                                                 */
+    int32_t first;               /* != 0: the first window of its utterance (AEW_OP_COND_STITCH stores its bias)        */
+} aew_cond_row_t;
+
+/* AEW_OP_CODE_TILE: for b < B, with r = table[first_row + b]: ind[b][j] = codes[r.code0 + j] for r.lo <= j < r.hi, 0 for
+ * the other j < E; in_voice[b] = r.voice; an idle row gets code 0 and voice 0.  A code outside [0, K) is written as 0 -
+ * the lookup behind it never follows it - and counted in *bad (uint32, atomicAdd; windows overlap, so one bad code may
+ * count more than once: test the word for non-zero).  One wave per row, 8-byte accesses.
+ * AEW_E_ARG: a NULL table / table_host / codes / ind / in_voice / bad, B < 1 or > 65535, first_row < 0, E, K or n_voice
+ * < 1, n_codes < 0, a live row with lo / hi outside 0 <= lo <= hi <= E, a read [code0 + lo, code0 + hi) outside
+ * [0, n_codes) or a voice outside [0, n_voice); AEW_E_ALIGN: a pointer that is not 16-byte aligned (bad: 4-byte).  All
+ * before any launch: a refused call writes nothing. */
+typedef struct {
+    const aew_cond_row_t* table;       /* device memory                                         */
+    const aew_cond_row_t* table_host;  /* the same records in host memory (read by the launcher) */
+    int32_t first_row, B;
+    const int64_t* codes;        /* the flat code buffer, n_codes elements                     */
+    int64_t n_codes;
+    int64_t* ind;                /* [B][E]: what AEW_OP_CODE_LOOKUP reads                      */
+    int64_t* in_voice;           /* [B]                                                        */
+    uint32_t* bad;               /* one device word, added to                                  */
+    int32_t E, K;
+    int32_t n_voice, pad_;
+} aew_code_tile_t;
+
+/* AEW_OP_COND_STITCH: for b < B, with r = table[first_row + b], the rows [r.src_row, r.src_row + r.n_rows) of cond[b]
+ * (bf16, Cp channels, cond_pitch elements between rows, cond_bs between batch rows) go to the rows
+ * r.stream * r.pitch + r.dst_row ... of cond_utt ([streams][r.pitch][Cp], contiguous); where r.first, bias[b][0:bias_n)
+ * (fp32) goes to bias_utt[r.stream].  Nothing else is written: not an idle row's, not the rows of a stream behind its
+ * last window (the caller zero-fills cond_utt once).  One launch for the B windows, 16-byte loads and stores.
+ * AEW_E_ARG: a NULL table / table_host / cond / cond_utt / bias / bias_utt, B < 1 or > 65535, first_row < 0, T < 1,
+ * Cp < 8 or no multiple of 8, cond_pitch < Cp or cond_pitch / cond_bs no multiple of 8, bias_n < 4 or no multiple of 4,
+ * n_streams < 1, n_dst < 0, a live row with a source range outside [0, T), stream outside [0, n_streams), pitch < 1,
+ * a destination range outside [0, pitch) or a stream buffer that ends behind n_dst elements; AEW_E_ALIGN: a pointer that is
+ * not 16-byte aligned.  All before any launch. */
+typedef struct {
+    const aew_cond_row_t* table;
+    const aew_cond_row_t* table_host;
+    int32_t first_row, B;
+    const uint16_t* cond;        /* dec.cond: [B] rows of T x Cp bf16                          */
+    int64_t cond_bs;             /* elements between its batch rows                            */
+    int32_t cond_pitch, T;       /* elements between its rows; rows per window                 */
+    uint16_t* cond_utt;          /* n_dst elements                                             */
+    int64_t n_dst;
+    const float* bias;           /* [B][bias_n]: the gated bias of the batch (spk_bias)        */
+    float* bias_utt;             /* [n_streams][bias_n]                                        */
+    int32_t Cp, bias_n;
+    int32_t n_streams, pad_;
+} aew_cond_stitch_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1210,7 +1284,7 @@ enum {
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
-    AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH
+    AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1240,13 +1314,14 @@ typedef struct {
         aew_grad_welford_t gwel; aew_seg_select_t ssel; aew_accum_t accum;
         aew_code_lookup_t clk; aew_code_runs_t crun; aew_adam_grouped_t adamg;
         aew_eval_groups_t evg; aew_mel_tile_t mtile; aew_code_stitch_t cstitch;
+        aew_code_tile_t ctile; aew_cond_stitch_t cndst;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch (24, 26 and 33 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch (24, 26 and 33 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
