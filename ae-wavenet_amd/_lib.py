@@ -496,7 +496,14 @@ class Actor(C.Structure):
 class Sampler(C.Structure):
     _fields_ = [("actors", vp), ("n_slots", i32), ("n_batches", i32), ("n_steps", i32), ("flag_stride", i32),
                 ("kr_max", i32), ("spin_max", i32), ("flags", vp), ("status", vp), ("forced", vp),
-                ("wav_out", vp), ("seed", C.c_uint64), ("nap_eighths", i32), ("pad", i32), ("prof", vp)]
+                ("wav_out", vp), ("seed", C.c_uint64), ("nap_eighths", i32), ("pad", i32), ("prof", vp), ("draw", vp)]
+
+
+class DrawRec(C.Structure):                                # aew_draw_t: the draw controls of one stream
+    _fields_ = [("inv_temp", C.c_float), ("top_k", i32), ("top_p", C.c_float), ("flags", i32)]
+
+
+DRAW_GREEDY = 1                                            # aew_draw_t.flags bit 0
 
 
 LIB_PATH = os.environ.get("AEW_LIB_PATH") or \
@@ -568,7 +575,7 @@ def load():
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
-                       (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch)):
+                       (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

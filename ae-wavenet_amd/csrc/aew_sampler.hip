@@ -378,13 +378,139 @@ __device__ void smp_dense(const aew_actor_t& a, const SmpEnv& e, int T) {
 // SAMPLE actor `index` serves streams [4*index, 4*index+4) of every batch: 16 lanes per stream, Q/16 logits per
 // lane.  Draw = first k with cumsum(exp(l - max))[k] > u * total  (inverse CDF; u from the counter RNG), which
 // replaces softmax + torch.multinomial(probs, 1) (wavenet.py:463-464).
-__device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const aew_sampler_t& s) {
-    const int T = s.n_steps, sub = e.lane >> 4, l16 = e.lane & 15;
+//
+// DRAW = true (aew_sampler_t.draw set) applies the stream's aew_draw_t record between the logit loads and the draw: the
+// rule in include/aewavenet.h.  Selection needs no sort: with the order-preserving 32-bit key of a logit, the K-set is
+// {key > tau} plus the first ties at tau in index order, tau = the top_k-th largest key, built bit by bit from the top (32
+// rounds: 16 compares per lane and a 16-lane count); the P-set is the same with the weight sum of {key >= cand} against
+// top_p * (K-set sum) in place of the count, and a tie at tau is kept while the mass before it is under the target.  One
+// wave serves four streams whose records may differ and every cross-lane step must run with the whole wave, so a pass
+// is taken when ANY of the four streams needs it (wave-uniform branch) and a stream that does not need it ignores its
+// result.  Greedy and top_p <= 0 are top_k = 1: one kept value, which the draw then returns whatever u is.
+// DRAW = false is the code of before, token for token.
+__device__ __forceinline__ int smp_row_sum(int x) {                   // sum over the 16 lanes of a DPP row, in every lane
+    x += __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, false);  // row_ror:8, 4, 2, 1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x124, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x122, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x121, 0xf, 0xf, false);
+    return x;
+}
+// (each level adds the same two partial sums in every lane that shares them, only swapped, and a + b == b + a in fp32:
+// the 16 lanes of a stream hold the same bits and take the same decisions)
+__device__ __forceinline__ float smp_row_sumf(float x) {
+    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, false));
+    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xf, 0xf, false));
+    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x122, 0xf, 0xf, false));
+    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121, 0xf, 0xf, false));
+    return x;
+}
+__device__ __forceinline__ int smp_row_excl(int x, int l16) {         // sum of x over the lower lanes of the stream
+    int incl = x;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        const int up = __shfl_up(incl, o, 16);
+        if (l16 >= o) incl += up;
+    }
+    return incl - x;
+}
+
+// Applies `rec` to one stream's logits: on entry v[k] = logit of value l16 * per + k (k < per), mx = the stream's maximum;
+// on exit v[k] = the weight of that value, zero outside the P-set.  Returns the kept mask of this lane (bit k).  Called by
+// the whole wave.
+__device__ __forceinline__ unsigned smp_draw_select(float (&v)[16], float mx, const aew_draw_t& rec, int per, int Q, int l16) {
+    const bool one = (rec.flags & 1) || !(rec.top_p > 0.f);
+    const int kk = one ? 1 : ((rec.top_k <= 0 || rec.top_k >= Q) ? Q : rec.top_k);
+    const bool k_on = kk < Q, p_on = !one && rec.top_p < 1.f;
+    unsigned key[16];                                                // invalid slots: key 0 (no candidate threshold is 0), weight 0
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (k < per) {
+            const unsigned bits = __float_as_uint(v[k] + 0.f);      // (-0 orders as +0)
+            key[k] = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
+            v[k] = __expf((v[k] - mx) * rec.inv_temp);
+        } else {
+            key[k] = 0u;
+            v[k] = 0.f;
+        }
+    }
+    unsigned keep = per >= 16 ? 0xffffu : (1u << per) - 1u;
+    if (__any(k_on)) {
+        unsigned tau = 0u;                                           // the largest threshold that at least kk keys reach
+#pragma nounroll
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = tau | (1u << bit);
+            int c = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) c += key[k] >= cand ? 1 : 0;
+            if (smp_row_sum(c) >= kk) tau = cand;
+        }
+        int gt = 0, tie = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            gt += key[k] > tau ? 1 : 0;
+            tie += (k < per && key[k] == tau) ? 1 : 0;
+        }
+        const int grant = kk - smp_row_sum(gt);                      // ties at tau that still fit, granted in index order
+        int rank = smp_row_excl(tie, l16);
+        unsigned in = 0u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < per) {
+                if (key[k] > tau) in |= 1u << k;
+                else if (key[k] == tau) { if (rank < grant) in |= 1u << k; ++rank; }
+            }
+        if (k_on) keep = in;
+    }
+    if (__any(p_on)) {
+        float wk[16];
+        float part = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { wk[k] = ((keep >> k) & 1u) ? v[k] : 0.f; part += wk[k]; }
+        const float target = rec.top_p * smp_row_sumf(part);
+        unsigned tau = 0u;                                           // the largest threshold whose {key >= tau} reaches the target
+#pragma nounroll
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = tau | (1u << bit);
+            float sge = 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) sge += key[k] >= cand ? wk[k] : 0.f;
+            if (smp_row_sumf(sge) >= target) tau = cand;
+        }
+        float sgt = 0.f;
+        int tie = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            sgt += key[k] > tau ? wk[k] : 0.f;
+            tie += (((keep >> k) & 1u) && key[k] == tau) ? 1 : 0;
+        }
+        sgt = smp_row_sumf(sgt);                                     // mass before the ties (under the target by the choice of tau)
+        int rank = smp_row_excl(tie, l16);
+        unsigned in = 0u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if ((keep >> k) & 1u) {
+                if (key[k] > tau) in |= 1u << k;
+                else if (key[k] == tau) { if (sgt + (float)rank * v[k] < target) in |= 1u << k; ++rank; }
+            }
+        if (p_on) keep = in;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (!((keep >> k) & 1u)) v[k] = 0.f;
+    return keep;
+}
+
+// The fields of aew_sampler_t it needs come by value: taking the descriptor by address would put the kernel's copy of it
+// on the stack wherever this role is left a called function.
+template <bool DRAW>
+__device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const int T, const int32_t* const forced_in,
+                           int32_t* const wav_out, const uint64_t seed, const aew_draw_t* const draw) {
+    const int sub = e.lane >> 4, l16 = e.lane & 15;
     const int per = a.n_quant >> 4;                                  // <= 16
     const int chunks = a.row_bytes >> 4;                             // 16-byte chunks of an h_0 row
     auto feed = [&](int b, int t, int value) {                       // publish position t: wav_out + h_0(t)
         const int stream = b * 16 + a.index * 4 + sub;
-        if (l16 == 0) s.wav_out[(int64_t)stream * T + t] = value;
+        if (l16 == 0) wav_out[(int64_t)stream * T + t] = value;
         const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.w) + (int64_t)value * a.row_bytes);
         char* dst = sbuf_at(a.out, b, t) + (a.index * 4 + sub) * 64;           // layout 1: [group][stream][32 ch]
         for (int c = l16; c < chunks; c += 16)
@@ -392,7 +518,7 @@ __device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const aew_samp
     };
     for (int b = 0; b < e.nb; ++b) {                                 // position 0 is given
         const int stream = b * 16 + a.index * 4 + sub;
-        int v = s.forced[(int64_t)stream * T];
+        int v = forced_in[(int64_t)stream * T];
         v = v < 0 ? 0 : (v >= a.n_quant ? a.n_quant - 1 : v);
         feed(b, 0, v);
     }
@@ -402,7 +528,9 @@ __device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const aew_samp
             if (!smp_wait(a, e, t, b)) return;
             if (t + 1 < T) {
                 const int stream = b * 16 + a.index * 4 + sub;
-                int value = s.forced[(int64_t)stream * T + t + 1];
+                int value = forced_in[(int64_t)stream * T + t + 1];
+                [[maybe_unused]] aew_draw_t rec;                     // DRAW: in flight with the logit loads, not a trip of its own
+                if constexpr (DRAW) rec = draw[stream];
                 const float* lp = reinterpret_cast<const float*>(sbuf_at(a.in0, b, t) + (a.index * 4 + sub) * a.in0.pitch) + l16 * per;
                 float v[16];
                 float mx = -3.0e38f;
@@ -436,9 +564,17 @@ __device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const aew_samp
 #pragma unroll
                 for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
                 float part = 0.f;
+                unsigned keep = 0u;
+                if constexpr (DRAW) {
+                    keep = smp_draw_select(v, mx, rec, per, a.n_quant, l16);
+#pragma unroll
+                    for (int k = 0; k < 16; ++k)
+                        if (k < per) part += v[k];
+                } else {
 #pragma unroll
                 for (int k = 0; k < 16; ++k)
                     if (k < per) { v[k] = __expf(v[k] - mx); part += v[k]; }
+                }
                 float incl = part;                                   // inclusive scan over the 16 lanes of the stream
 #pragma unroll
                 for (int o = 1; o < 16; o <<= 1) {
@@ -446,22 +582,30 @@ __device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const aew_samp
                     if (l16 >= o) incl += up;
                 }
                 const float total = __shfl(incl, 15, 16);
-                const float u = (float)aew_jitter_u(s.seed, 0x53414d50ull, stream, t + 1);
+                const float u = (float)aew_jitter_u(seed, 0x53414d50ull, stream, t + 1);
                 const float target = u * total;
                 // owner = first lane whose inclusive sum exceeds target (last lane if rounding leaves none)
-                const bool mine = incl > target;
+                // (DRAW: a lane that keeps nothing adds zero, but the scan groups its sums differently per lane, so its
+                // inclusive sum can sit an ulp above its predecessor's: only a lane that keeps something may own the draw)
+                const bool mine = incl > target && (!DRAW || keep != 0u);
                 const unsigned long long m = __ballot(mine) >> (e.lane & 48);
-                const int owner = (m & 0xffffull) ? __ffsll((long long)(m & 0xffffull)) - 1 : 15;
+                int owner = (m & 0xffffull) ? __ffsll((long long)(m & 0xffffull)) - 1 : 15;
                 int pick = per - 1;
+                if constexpr (DRAW) {                                // the fall-backs are the LAST KEPT value: of the lane, of the stream
+                    if (keep) pick = 31 - __clz((int)keep);
+                    const unsigned hk = (unsigned)((__ballot(keep != 0u) >> (e.lane & 48)) & 0xffffull);
+                    if (!(m & 0xffffull) && hk) owner = 31 - __clz((int)hk);
+                }
                 float run = incl - part;
                 bool found = false;
 #pragma unroll
                 for (int k = 0; k < 16; ++k)
                     if (k < per) {
                         run += v[k];
-                        if (!found && run > target) { pick = k; found = true; }
+                        if (!found && run > target && (!DRAW || ((keep >> k) & 1u))) { pick = k; found = true; }
                     }
-                const int drawn = __shfl(l16 * per + pick, owner, 16);
+                int drawn = __shfl(l16 * per + pick, owner, 16);
+                if constexpr (DRAW) drawn = drawn < 0 ? 0 : drawn;   // (in [0, Q) whatever the record holds; the upper clamp follows)
                 if (value < 0) value = drawn;
                 value = value >= a.n_quant ? a.n_quant - 1 : value;
                 feed(b, t + 1, value);
@@ -471,7 +615,7 @@ __device__ void smp_sample(const aew_actor_t& a, const SmpEnv& e, const aew_samp
 }
 
 // two actors per SIMD must fit (a DEEP decoder has 1684): at most 256 registers per wavefront
-template <int KR>
+template <int KR, bool DRAW>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_sampler(const aew_sampler_t s) {
     const int slot = blockIdx.x;
     const aew_actor_t a = s.actors[slot];               // by value: wave-uniform, lives in SGPRs
@@ -486,16 +630,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     e.prof = s.prof ? s.prof + (int64_t)slot * 4 : nullptr;
     e.acc_wait = e.acc_work = e.acc_pub = e.items = 0;
     e.t_mark = s.prof ? __builtin_amdgcn_s_memtime() : 0ull;
+    // DRAW at KR = 12: every role is inlined by force.  The longer SAMPLE body takes the inliner's budget, and a role left
+    // as a called function takes `a` and `e` by address, which moves them from SGPRs to scratch for every role of the
+    // instantiation.  NOT at KR = 16: fully inlined that instantiation needs more than 256 VGPRs and spills, and a spill
+    // between an smp_issue16 and its smp_landed would save a register whose load is still in flight (the compiler does
+    // not see those loads).  There SAMPLE stays a called function, as it is in k_sampler<16, false>.
+#define SMP_ROLE(call) if constexpr (DRAW && KR == 12) { [[clang::always_inline]] call; } else call
     switch (role) {
-        case AEW_ACT_EARLY: smp_early<KR>(a, e, s.n_steps); break;
-        case AEW_ACT_LATE: smp_late<KR>(a, e, s.n_steps); break;
-        case AEW_ACT_RES: smp_dense<AEW_ACT_RES>(a, e, s.n_steps); break;
-        case AEW_ACT_SKIP: smp_dense<AEW_ACT_SKIP>(a, e, s.n_steps); break;
-        case AEW_ACT_POST1: smp_dense<AEW_ACT_POST1>(a, e, s.n_steps); break;
-        case AEW_ACT_POST2: smp_dense<AEW_ACT_POST2>(a, e, s.n_steps); break;
-        case AEW_ACT_SAMPLE: smp_sample(a, e, s); break;
+        case AEW_ACT_EARLY: SMP_ROLE(smp_early<KR>(a, e, s.n_steps)); break;
+        case AEW_ACT_LATE: SMP_ROLE(smp_late<KR>(a, e, s.n_steps)); break;
+        case AEW_ACT_RES: SMP_ROLE(smp_dense<AEW_ACT_RES>(a, e, s.n_steps)); break;
+        case AEW_ACT_SKIP: SMP_ROLE(smp_dense<AEW_ACT_SKIP>(a, e, s.n_steps)); break;
+        case AEW_ACT_POST1: SMP_ROLE(smp_dense<AEW_ACT_POST1>(a, e, s.n_steps)); break;
+        case AEW_ACT_POST2: SMP_ROLE(smp_dense<AEW_ACT_POST2>(a, e, s.n_steps)); break;
+        case AEW_ACT_SAMPLE: SMP_ROLE(smp_sample<DRAW>(a, e, s.n_steps, s.forced, s.wav_out, s.seed, s.draw)); break;
         default: break;
     }
+#undef SMP_ROLE
     e.dump();
 }
 
@@ -504,7 +655,10 @@ static int launch_sampler(const aew_sampler_t& s, hipStream_t st) {
     if (s.n_slots < 1 || s.n_batches < 1 || s.n_steps < 1 || s.flag_stride < 1) return AEW_E_ARG;
     if (s.kr_max != 12 && s.kr_max != 16) return AEW_E_ARG;
     if ((int64_t)s.n_steps * s.n_batches >= (1ll << 31) - 2) return AEW_E_ARG;       // sequence numbers are 32-bit
-    const void* fn = s.kr_max == 12 ? reinterpret_cast<const void*>(k_sampler<12>) : reinterpret_cast<const void*>(k_sampler<16>);
+    // (s.draw == NULL: the instantiation and the launch of before; the residency check is made on the one launched)
+    void (*const kern)(const aew_sampler_t) = s.draw ? (s.kr_max == 12 ? k_sampler<12, true> : k_sampler<16, true>)
+                                                     : (s.kr_max == 12 ? k_sampler<12, false> : k_sampler<16, false>);
+    const void* fn = reinterpret_cast<const void*>(kern);
     // every actor must be resident at once: they wait on each other
     int dev = 0, per_cu = 0, cus = 0;
     hipError_t err = hipGetDevice(&dev);
@@ -518,7 +672,6 @@ static int launch_sampler(const aew_sampler_t& s, hipStream_t st) {
     if (err != hipSuccess) return (int)err;
     err = hipMemsetAsync(s.status, 0, 4 * sizeof(uint32_t), st);
     if (err != hipSuccess) return (int)err;
-    if (s.kr_max == 12) hipLaunchKernelGGL(k_sampler<12>, dim3(s.n_slots), dim3(64), 0, st, s);
-    else hipLaunchKernelGGL(k_sampler<16>, dim3(s.n_slots), dim3(64), 0, st, s);
+    hipLaunchKernelGGL(kern, dim3(s.n_slots), dim3(64), 0, st, s);
     return (int)hipGetLastError();
 }

@@ -121,6 +121,7 @@ extern "C" int aew_sizeof(int which) {
         case 37: return (int)sizeof(aew_cond_row_t);
         case 38: return (int)sizeof(aew_code_tile_t);
         case 39: return (int)sizeof(aew_cond_stitch_t);
+        case 41: return (int)sizeof(aew_draw_t);      // (40 is left unused like 24, 26 and 33)
         default: return -1;
     }
 }

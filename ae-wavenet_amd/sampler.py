@@ -17,8 +17,10 @@ the HIP kernel.  There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -34,6 +36,70 @@ def _frag_blob(W: torch.Tensor, nk: int) -> torch.Tensor:
     Wp = torch.zeros(32, nk * 32, dtype=torch.float32, device=W.device)
     Wp[:W.shape[0], :W.shape[1]] = W
     return Wp.view(2, 16, nk, 4, 8).permute(2, 0, 3, 1, 4).contiguous().view(nk, 2, 64, 8).to(torch.bfloat16)
+
+
+class Draw:
+    """Draw controls of one stream: the host form of aew_draw_t (include/aewavenet.h states the rule).
+
+    temperature divides the logits (weights exp((l - max l) / temperature)); 0 - or Draw.greedy() - always feeds the
+    most probable value (ties: the lowest).  top_k > 0 keeps the k most probable values, top_p < 1 the shortest prefix of
+    those, most probable first, that holds at least top_p of their weight.  Draw() is neutral: the draw without
+    controls, bit for bit.  Validation raises AewError here, before anything is launched."""
+    __slots__ = ("temperature", "top_k", "top_p", "is_greedy", "inv_temp")
+
+    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) \
+                or temperature < 0:
+            raise L.AewError(f"Draw: temperature must be a finite number >= 0, got {temperature!r}")
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0 or top_k >= 1 << 31:
+            raise L.AewError(f"Draw: top_k must be an int >= 0 (0 = off), got {top_k!r}")
+        if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not (0 < top_p <= 1):
+            raise L.AewError(f"Draw: top_p must lie in (0, 1] (1 = off), got {top_p!r}")
+        self.temperature, self.top_k, self.top_p = float(temperature), top_k, float(top_p)
+        with np.errstate(over="ignore", divide="ignore"):
+            inv = float(np.float32(1.0) / np.float32(temperature)) if temperature > 0 else math.inf
+        self.is_greedy = not math.isfinite(inv)              # temperature 0, or so small that 1 / T leaves fp32
+        self.inv_temp = 1.0 if self.is_greedy else inv
+
+    @classmethod
+    def greedy(cls) -> "Draw":
+        return cls(temperature=0.0)
+
+    def is_neutral(self) -> bool:
+        return not self.is_greedy and self.inv_temp == 1.0 and self.top_k == 0 and self.top_p == 1.0
+
+    def record(self) -> Tuple[float, int, float, int]:
+        """(inv_temp, top_k, top_p, flags) as aew_draw_t holds them."""
+        return self.inv_temp, self.top_k, self.top_p, L.DRAW_GREEDY if self.is_greedy else 0
+
+    def __eq__(self, other):
+        return isinstance(other, Draw) and self.record() == other.record()
+
+    def __hash__(self):
+        return hash(self.record())
+
+    def __repr__(self):
+        return "Draw.greedy()" if self.is_greedy and self.top_k == 0 and self.top_p == 1.0 else \
+            f"Draw(temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p})"
+
+
+DRAW_DTYPE = np.dtype([("inv_temp", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("flags", "<i4")])     # aew_draw_t
+
+
+def draw_table(draws, n_streams: int) -> torch.Tensor:
+    """The packed aew_draw_t records of n_streams streams: a CPU int32 tensor (n_streams, 4) whose words are inv_temp
+    (fp32 bits), top_k, top_p (fp32 bits), flags.  draws: one Draw for every stream, or a sequence with one Draw per
+    stream."""
+    if isinstance(draws, Draw):
+        draws = [draws] * n_streams
+    else:
+        draws = list(draws)
+        if len(draws) != n_streams or not all(isinstance(d, Draw) for d in draws):
+            raise L.AewError(f"draw: one Draw, or a sequence of {n_streams} Draws (one per stream) expected")
+    rec = np.zeros(n_streams, DRAW_DTYPE)
+    for i, d in enumerate(draws):
+        rec[i] = d.record()
+    return torch.from_numpy(rec.view("<i4").reshape(n_streams, 4).copy())
 
 
 class SamplerGeometry:
@@ -136,7 +202,7 @@ class Sampler:
     # ---- one generation ----------------------------------------------------------------------------------------
     def generate(self, cond: torch.Tensor, bias: torch.Tensor, forced: torch.Tensor, seed: int = 0,
                  want_logits: bool = False, spin_max: int = 0, stream: int = 0, timing: bool = False,
-                 profile: bool = False, dry_run: bool = False):
+                 profile: bool = False, dry_run: bool = False, draw=None):
         """cond   bf16 [n_streams][>= T][>= Ck] (zero-padded channels; any row / stream strides that are multiples
                   of 8 elements): the upsampled local conditioning at every position (engine: dec.cond)
         bias   fp32 [n_streams][NL][>= n_pairs*32]: per-stream gated bias, (16 filt | 16 gate) per channel tile,
@@ -146,7 +212,11 @@ class Sampler:
         distribution of position t+1 given positions <= t.  timing: HIP-event time of the kernel in self.last
         (stream must be torch's current stream, i.e. 0 = the default stream).  dry_run: build the actor table only
         (works with CPU tensors) and return a description of it - tests/test_sampler.py replays the protocol from
-        that under random schedules."""
+        that under random schedules.
+        draw   None: the draw and the kernel of before.  Otherwise the streams' draw controls - a packed table (int32
+                  [n_streams][4], see draw_table) or what draw_table accepts - and the launch is the kernel's DRAW
+                  instantiation, also when every record is neutral (which then returns the bits of draw=None).  The actor
+                  table does not depend on it."""
         g = self.g
         n_streams, T = forced.shape
         if n_streams % 16:
@@ -162,6 +232,10 @@ class Sampler:
             raise L.AewError("sampler: bias shape")
         if bool((forced[:, 0] < 0).any()):
             raise L.AewError("sampler: position 0 must be given")
+        if draw is not None and not torch.is_tensor(draw):
+            draw = draw_table(draw, n_streams)
+        if draw is not None and (draw.dtype != torch.int32 or tuple(draw.shape) != (n_streams, 4)):
+            raise L.AewError(f"sampler: draw table int32 ({n_streams}, 4) expected, got {draw.dtype} {tuple(draw.shape)}")
         dev, fs = self.dev, self.flag_stride
         z = lambda *shape, dt=torch.bfloat16: torch.zeros(*shape, dtype=dt, device=dev)
         rings = [d + 1 for d in g.dils]
@@ -335,7 +409,9 @@ class Sampler:
         sp.nap_eighths = self.nap_eighths
         prof = torch.zeros(n_slots, 4, dtype=torch.int64, device=dev) if profile else None
         sp.prof = prof.data_ptr() if profile else None
-        self.last = dict(n_slots=n_slots, n_actors=n_act, depth=depth)
+        draw = draw.to(dev).contiguous() if draw is not None else None      # (alive until status.cpu() below)
+        sp.draw = draw.data_ptr() if draw is not None else None
+        self.last = dict(n_slots=n_slots, n_actors=n_act, depth=depth, draw=draw is not None)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing else None
         if ev:
             ev[0].record()

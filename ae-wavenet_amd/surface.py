@@ -322,6 +322,7 @@ class HipModelBase(nn.Module):
         # MFCC inverter is the model itself here)
         self.n_quant, self.n_replicas = hps.n_quant, 1
         self.sample_seed = 0
+        self.draw = None                                 # default draw controls of the sampling calls (sampler.Draw; None: off)
         self._sampler = None
         self._utt_mfcc = None                            # encode_wavs() / encode_corpus(): the whole-utterance front-end
         self._anchor = torch.zeros((), requires_grad=True)
@@ -758,14 +759,33 @@ class HipModelBase(nn.Module):
         eng.forward(self._ema_allreduce)
         return eng.logits().permute(0, 2, 1)
 
-    def sample(self, wav, mel, voice, jitter, n_prime: Optional[int] = None, seed: Optional[int] = None):
+    def _draw_records(self, what, draw, n):
+        """The draw controls of n replicas / rows / utterances: None when there are none or all are neutral (no table is
+        passed: the sampler launches what it launched before), else a list of n sampler.Draw.  `draw` None: model.draw."""
+        from . import sampler as S
+        if draw is None:
+            draw = self.draw
+        if draw is None:
+            return None
+        if isinstance(draw, S.Draw):
+            draw = [draw] * n
+        else:
+            draw = list(draw)
+            if len(draw) != n or not all(isinstance(d, S.Draw) for d in draw):
+                raise L.AewError(f"{what}: draw must be one Draw or a sequence of {n} Draws, got {draw!r}")
+        return None if all(d.is_neutral() for d in draw) else draw
+
+    def sample(self, wav, mel, voice, jitter, n_prime: Optional[int] = None, seed: Optional[int] = None, draw=None):
         """Autoregressive generation on the persistent-kernel sampler (sampler.py).  The first n_prime positions of
         the decoder window are fed from `wav` (default: receptive field + 1, like the reference, which starts
         drawing at base_global_rf, wavenet.py:423-431); the rest are drawn.  One input window (B = 1); replicas are
-        parallel streams (wavenet.py:378-381)."""
+        parallel streams (wavenet.py:378-381).  draw: the draw controls (sampler.Draw: temperature, top-k, nucleus,
+        greedy) of every replica, or a sequence with one per replica; default model.draw; None or neutral: the plain
+        draw, bit for bit."""
         if wav.shape[0] != 1:
             raise L.AewError("sampling takes one window; replicas come from set_n_replicas()")
         R = max(1, int(self.n_replicas))
+        recs = self._draw_records("sample()", draw, R)
         self._dp_finish()
         with torch.no_grad():
             eng = self._ensure_engine(1)
@@ -781,7 +801,8 @@ class HipModelBase(nn.Module):
             if seed is None:
                 seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
             out, _ = smp.generate(cond.expand(n16, -1, -1).contiguous(), bias.expand(n16, -1, -1).contiguous(),
-                                  forced.contiguous(), seed=seed)
+                                  forced.contiguous(), seed=seed,
+                                  draw=None if recs is None else recs + [recs[0]] * (n16 - R))
             return torch.cat([given, out[:R]], 0).float()
 
     def _engine_sampler(self, eng):
@@ -929,13 +950,15 @@ class HipModelBase(nn.Module):
         from . import codes as CD
         return int(CD.mu_encode(torch.zeros(1), self.n_quant)[0])
 
-    def decode(self, codes, voice, prime=None, n_prime: Optional[int] = None, seed: Optional[int] = None, jitter=None):
+    def decode(self, codes, voice, prime=None, n_prime: Optional[int] = None, seed: Optional[int] = None, jitter=None,
+               draw=None):
         """codes (B, embed_len) int64, voice (B,) -> (B, dec_in_len) float32 mu-law values: the decoder conditioned on the
         GIVEN codes in the given voices, one sampler stream per row (padded to a multiple of 16 streams by repeating row
         0; the pad streams are dropped).  The first n_prime positions (default: receptive field + 1, as in sample())
         are forced to prime[:, :n_prime] - mu-law values (B, >= n_prime) - or, without `prime`, to the value silence
         encodes to (zero_amplitude_code()); the rest are drawn.  jitter (B, >= embed_len): the conditioning gather's
-        index, default the identity (no jitter at inference).  seed as in sample().  A code outside [0, K) raises
+        index, default the identity (no jitter at inference).  seed as in sample().  draw: one sampler.Draw for every
+        row or a sequence with one per row (pad streams take row 0's), default model.draw.  A code outside [0, K) raises
         AewError with the count before the sampler starts (the lookup never follows it)."""
         self._need_codes("decode()")
         E = self.embed_len
@@ -946,6 +969,7 @@ class HipModelBase(nn.Module):
             raise L.AewError(f"decode(): voice ({B},) expected (one per row of codes), got {tuple(voice.shape)}")
         if jitter is not None and (jitter.dim() != 2 or jitter.shape[0] != B or jitter.shape[1] < E):
             raise L.AewError(f"decode(): jitter ({B}, >= {E}) expected, got {tuple(jitter.shape)}")
+        recs = self._draw_records("decode()", draw, B)
         with torch.no_grad():
             eng = self._ensure_engine(B)
             self._dp_finish()
@@ -973,13 +997,16 @@ class HipModelBase(nn.Module):
             rows[B:] = 0                                             # pad streams repeat row 0
             if seed is None:
                 seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
-            out, _ = smp.generate(cond[rows].contiguous(), bias[rows].contiguous(), forced, seed=seed)
+            out, _ = smp.generate(cond[rows].contiguous(), bias[rows].contiguous(), forced, seed=seed,
+                                  draw=None if recs is None else recs + [recs[0]] * (n16 - B))
             return out[:B].float()
 
-    def convert(self, wav, mel, voice_to, n_prime: Optional[int] = None, seed: Optional[int] = None, jitter=None):
+    def convert(self, wav, mel, voice_to, n_prime: Optional[int] = None, seed: Optional[int] = None, jitter=None,
+                draw=None):
         """Voice conversion: decode(encode(mel), voice_to, prime=<the decoder window of wav>).  wav (B, enc_in_len), mel
         (B, n_mel, frames), voice_to (B,) - or (V,) with B = 1: that one window is decoded in V voices at once, as V
-        streams.  Returns (B or V, dec_in_len) float32 mu-law values whose first n_prime columns are the window's."""
+        streams.  Returns (B or V, dec_in_len) float32 mu-law values whose first n_prime columns are the window's.  draw as
+        in decode(): one Draw, or one per output row (per voice with one window)."""
         self._need_codes("convert()")
         B, T, o = wav.shape[0], self.dec_in_len, int(self.trim_dec_in[0])
         V = voice_to.shape[0] if voice_to.dim() == 1 else -1
@@ -990,7 +1017,7 @@ class HipModelBase(nn.Module):
         given = wav[:, o:o + T]
         if V != B:
             codes, given = codes.expand(V, -1).contiguous(), given.expand(V, -1)
-        return self.decode(codes, voice_to, prime=given, n_prime=n_prime, seed=seed, jitter=jitter)
+        return self.decode(codes, voice_to, prime=given, n_prime=n_prime, seed=seed, jitter=jitter, draw=draw)
 
     # ---- whole utterances, the decoder's side: conditioning of any length from codes, generation, conversion ----------
     def _utterance_rows(self, what, codes, voice):
@@ -1078,7 +1105,7 @@ class HipModelBase(nn.Module):
         return cond, bias, torch.from_numpy(lengths.copy())
 
     def decode_utterances(self, codes, voice=None, prime=None, n_prime: Optional[int] = None, seed: Optional[int] = None,
-                          batch=None):
+                          batch=None, draw=None):
         """Generate whole utterances from their codes: `codes` / `voice` / `batch` as in utterance_conditioning() -> a
         list of U float32 tensors of mu-law values, the u-th of L(N_u) samples (empty where L(N_u) = 0: under 7 codes at
         the reference strides; such an utterance takes no stream).  Element q is sample o + q of the waveform the codes
@@ -1092,6 +1119,10 @@ class HipModelBase(nn.Module):
         T_max = the group's longest length.  Shorter streams are padded with zero conditioning and their tails dropped;
         slots a group leaves empty repeat its first utterance and are dropped.  Results come back in input order, and two
         calls with the same seed agree bit for bit.  seed=None takes sample_seed and advances it by the group count.
+
+        draw: one sampler.Draw for every utterance, or a sequence with one per utterance (default model.draw).  A record
+        follows its utterance into the stream slot stream_groups assigns; an empty slot takes the record of the
+        utterance it repeats.  Groups, seeds and order do not depend on it, and neutral records change no bit.
 
         Memory: the conditioning of one group is 16 * T_max * Cp * 2 bytes - about 0.65 GB for ten-second utterances
         (160 000 samples) at Cp = 128.
@@ -1107,6 +1138,7 @@ class HipModelBase(nn.Module):
         U = len(rows)
         if prime is not None and len(prime) != U:
             raise L.AewError(f"{what}: prime must hold one tensor per utterance ({U}), got {len(prime)}")
+        recs = self._draw_records(what, draw, U)
         lengths = [cg.L(r.numel()) for r in rows]
         with torch.no_grad():
             dev = eng.device
@@ -1140,18 +1172,20 @@ class HipModelBase(nn.Module):
                         forced[k, :n_forced[u]] = prime[u][:n_forced[u]].to(device=dev, dtype=torch.int32)
                 if n < 16:                                               # empty slots repeat the group's first utterance
                     cond[n:], bias[n:], forced[n:] = cond[0], bias[0], forced[0]
-                wav, _ = smp.generate(cond, bias, forced, seed=g_seed)
+                slot_recs = None if recs is None else [recs[u] for u in members] + [recs[members[0]]] * (16 - n)
+                wav, _ = smp.generate(cond, bias, forced, seed=g_seed, draw=slot_recs)
                 for k, u in enumerate(members):
                     out[u] = wav[k, :lengths[u]].float()
             return out
 
-    def convert_utterances(self, wavs, voice_to, n_prime: Optional[int] = None, seed: Optional[int] = None, batch=None):
+    def convert_utterances(self, wavs, voice_to, n_prime: Optional[int] = None, seed: Optional[int] = None, batch=None,
+                           draw=None):
         """Voice conversion of whole utterances: decode_utterances(encode_wavs(wavs), voice_to, prime=[w[o:] for w in
         wavs]) with o = geometry.conditioning_geometry(model.geom).o (2235 at the reference geometry, whatever
         n_win_batch).  wavs: a list of 1-D device tensors of mu-law values; voice_to: one voice per utterance - or, with
         ONE utterance, (V,): that utterance is decoded in V voices at once, as V streams.  Returns a list of float32
         tensors; element q of an output is aligned to sample o + q of its input, and its first n_prime values are the
-        input's."""
+        input's.  draw as in decode_utterances(): one Draw, or one per output (per voice with one utterance)."""
         what = "convert_utterances()"
         self._need_codes(what)
         wavs = list(wavs)
@@ -1166,7 +1200,7 @@ class HipModelBase(nn.Module):
         prime = [w[o:] for w in wavs]
         if V != U:
             rows, prime = rows * V, prime * V
-        return self.decode_utterances(rows, voice_to, prime=prime, n_prime=n_prime, seed=seed, batch=batch)
+        return self.decode_utterances(rows, voice_to, prime=prime, n_prime=n_prime, seed=seed, batch=batch, draw=draw)
 
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared

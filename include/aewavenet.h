@@ -47,7 +47,8 @@ extern "C" {
  * and 23, two host functions; no existing record, op number or function changed - so a caller built against 28 runs
  * unchanged.  A binding that wants the additions finds them through aew_sizeof(22) / aew_sizeof(23) (-1 in a library
  * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 37 .. 39,
- * aew_cond_row_t, aew_code_tile_t / AEW_OP_CODE_TILE, aew_cond_stitch_t / AEW_OP_COND_STITCH). */
+ * aew_cond_row_t, aew_code_tile_t / AEW_OP_CODE_TILE, aew_cond_stitch_t / AEW_OP_COND_STITCH; 41, aew_draw_t, with the
+ * `draw` pointer appended to aew_sampler_t - index 40 stays unused, it answers -1). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -1593,6 +1594,28 @@ typedef struct {
     int32_t row_bytes;           /* SAMPLE: bytes of one base-table row (= h_0 row)                         */
 } aew_actor_t;
 
+/* Draw controls of ONE stream (appended to ABI 28; aew_sizeof 41 - index 40 stays unused, it answers -1): sampling
+ * temperature, top-k, nucleus (top-p) and greedy, applied by the SAMPLE actor between the logits POST2 wrote and the value
+ * it feeds.  THE RULE, for one stream at one step with fp32 logits l[0..Q) and the uniform u the draw already uses
+ * (aew_jitter_u(seed, 0x53414d50, stream, t + 1): the same number with controls on or off):
+ *   order    value i precedes value j when l[i] > l[j], or l[i] == l[j] and i < j (a total order, ties to the lower index)
+ *   greedy   (flags & 1): the value fed is the first in the order; u is not used
+ *   weights  w[i] = exp((l[i] - max l) * inv_temp) in fp32 (__expf of the fp32 product); inv_temp == 1.0f: today's weights
+ *   K-set    the first top_k values in the order; top_k <= 0 or top_k >= Q: all of them
+ *   P-set    the shortest prefix of the K-set, in the order, whose weight sum is at least top_p times the K-set's; never
+ *            empty; top_p >= 1: the whole K-set; top_p <= 0: exactly the first value
+ *   draw     weights outside the P-set are zero, then the draw of aew_sampler_run as it was: sums in index order (per lane
+ *            over its Q / 16 values, inclusive scan over the stream's 16 lanes), the drawn value is the first index whose
+ *            running sum exceeds u * total, or the last kept index if rounding leaves none.
+ * (1.0, 0, 1.0, 0) is neutral: the draw without controls, bit for bit.  Forced positions stay forced.  Whatever a record
+ * holds, the value fed lies in [0, Q). */
+typedef struct {
+    float   inv_temp;            /* 1 / temperature                                                         */
+    int32_t top_k;               /* <= 0 or >= Q: off                                                       */
+    float   top_p;               /* >= 1: off; <= 0: the first value alone                                  */
+    int32_t flags;               /* bit 0: greedy                                                           */
+} aew_draw_t;
+
 typedef struct {
     const aew_actor_t* actors;   /* DEVICE array [n_slots]; slot L runs as workgroup L (XCD L % 8)          */
     int32_t n_slots;
@@ -1612,6 +1635,10 @@ typedef struct {
     int32_t pad;
     uint64_t* prof;              /* optional [n_slots][4]: s_memtime cycles (100 MHz) each actor spent waiting,
                                     loading + computing, publishing; [3] = items.  NULL = off               */
+    const aew_draw_t* draw;      /* appended to ABI 28, optional DEVICE array [16 * n_batches], one record per stream,
+                                    constant during the run.  NULL = the draw and the kernel of before, bit for bit;
+                                    non-NULL launches the second instantiation of the kernel (same actors, same
+                                    protocol), whose SAMPLE actors apply the records                         */
 } aew_sampler_t;
 
 /* Enqueue one generation on `stream`.  Returns AEW_E_UNSUP if the device cannot keep n_slots
