@@ -25,7 +25,7 @@ EF_OUT2_COPY = 1 << 10
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
- OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH) = range(1, 43)
+ OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE) = range(1, 46)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -277,6 +277,49 @@ class CondStitch(C.Structure):
                 ("Cp", i32), ("bias_n", i32), ("n_streams", i32), ("pad_", i32)]
 
 
+class ScoreRow(C.Structure):
+    """aew_score_row_t: one batch row of a whole-utterance scoring - where its window starts in the flat code buffer and
+    which of its codes exist, the utterance's samples in the flat waveform buffer and the one that is the window's
+    decoder-input row 0, its voice, which outputs it owns and where they go.  SCORE_ROW_DTYPE is the same record for
+    numpy."""
+    _fields_ = [("code0", i64), ("wav_base", i64), ("wav_len", i64), ("wav0", i64), ("dst", i64), ("utt", i32), ("lo", i32),
+                ("hi", i32), ("voice", i32), ("src", i32), ("n_out", i32)]
+
+
+SCORE_ROW_DTYPE = [("code0", "<i8"), ("wav_base", "<i8"), ("wav_len", "<i8"), ("wav0", "<i8"), ("dst", "<i8"), ("utt", "<i4"),
+                   ("lo", "<i4"), ("hi", "<i4"), ("voice", "<i4"), ("src", "<i4"), ("n_out", "<i4")]
+
+
+class WavTile(C.Structure):
+    """aew_wav_tile_t: wav[b][wav_off : wav_off + T] / ind[b] / in_voice[b] = the window of table[first_row + b] cut out of
+    the flat waveform and code buffers; the zero-amplitude code / code 0 where the utterance has nothing, and for values
+    outside [0, n_quant) / [0, K), which are counted in *bad_wav / *bad_codes."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("codes", vp), ("n_codes", i64),
+                ("wavs", vp), ("n_wav", i64), ("ind", vp), ("in_voice", vp), ("wav", vp), ("bad_codes", vp), ("bad_wav", vp),
+                ("wav_pitch", i32), ("wav_off", i32), ("T", i32), ("n_quant", i32), ("E", i32), ("K", i32), ("n_voice", i32),
+                ("zero", f32)]
+
+
+class NllStitch(C.Structure):
+    """aew_nll_stitch_t: the per-position nll (and ptgt, and the top-1 hit) of the outputs each batch row owns to the flat
+    per-utterance arrays."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("nll", vp), ("ptgt", vp), ("amax", vp),
+                ("logits", vp), ("bs", i64), ("wav", vp), ("dst_nll", vp), ("dst_ptgt", vp), ("dst_hit", vp), ("n_dst", i64),
+                ("pitch", i32), ("n_quant", i32), ("wav_pitch", i32), ("tgt_off", i32), ("w", i32), ("pad_", i32)]
+
+
+class ScoreReduce(C.Structure):
+    """aew_score_reduce_t: per utterance (n, sum nll, sum ptgt, sum hit) as doubles in aew_eval_acc_t's order, and the
+    four means as fp32."""
+    _fields_ = [("offsets", vp), ("offsets_host", vp), ("nll", vp), ("ptgt", vp), ("hit", vp), ("n_src", i64), ("acc", vp),
+                ("out", vp), ("U", i32), ("pad_", i32)]
+
+
+# the columns of aew_score_reduce_t's `out` and the accessors of codes.UtteranceScores derived from them (the first is not
+# "nll": that is the flat per-sample tensor)
+SCORE_OUT_NAMES = ("nll_per_sample", "bits_per_sample", "top1", "mean_prob")
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -418,7 +461,7 @@ class _OpU(C.Union):
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
                 ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
-                ("ctile", CodeTile), ("cndst", CondStitch)]
+                ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce)]
 
 
 class Op(C.Structure):
@@ -434,7 +477,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_GRAD_NORM: "gnorm", OP_UPDATE_RATIO: "ratio", OP_SWAP: "swap", OP_VQ_RESTART: "vqr", OP_EVAL_ACC: "eva",
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
             OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
-            OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst"}
+            OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst",
+            OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred"}
 
 
 
@@ -575,7 +619,8 @@ def load():
                        (15, UpdateRatio), (16, NtPick), (17, Swap), (18, VqRestart), (19, TnPick), (20, EvalAcc),
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
-                       (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec)):
+                       (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec), (42, ScoreRow), (43, WavTile),
+                       (44, NllStitch), (45, ScoreReduce)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

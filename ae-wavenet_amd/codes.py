@@ -11,7 +11,8 @@ of an utterance) and never synchronise with the host.  `model.encode()` / `model
 `encode_wavs()` / `encode_corpus()` produce those of whole utterances as an `UtteranceCodes`, from the work list
 `tile_plan()` states (csrc/aew_utterance.hip); `model.utterance_conditioning()` / `decode_utterances()` /
 `convert_utterances()` consume them again at the utterance's length, from the work list `cond_tile_plan()` and the stream
-assignment `stream_groups()` (csrc/aew_cond_utterance.hip).
+assignment `stream_groups()` (csrc/aew_cond_utterance.hip); `model.score_utterances()` scores a waveform under them with
+the teacher-forced decoder, from the work list `score_tile_plan()`, and returns an `UtteranceScores` (csrc/aew_score.hip).
 """
 from __future__ import annotations
 
@@ -365,6 +366,187 @@ def stream_groups(lengths: Sequence[int], seed: int, width: int = 16):
     one Sampler.generate call, whose seed is seed + g and whose step count is the length of its first member."""
     order = sorted((u for u, n in enumerate(lengths) if int(n) > 0), key=lambda u: -int(lengths[u]))
     return [(int(seed) + g, order[at:at + width]) for g, at in enumerate(range(0, len(order), width))]
+
+
+# ---- whole utterances through the teacher-forced decoder: the work list and the result of model.score_utterances() ------
+@dataclass
+class ScoreTilePlan:
+    """score_tile_plan()'s result: per utterance n_u (positions that have both a conditioning row and a sample), n_scored
+    = max(n_u - rf - 1, 0) and the offsets of its scored samples in the flat outputs; per batch row (n_batches * B of
+    them, the idle rows that fill the last batch included) the utterance (-1: idle), its window, the window's first code
+    relative to the utterance's, the window codes [lo, hi) that exist, the utterance's sample that is the window's
+    decoder-input row 0, the outputs [src, src + n_out) it owns and the flat element the first of them goes to.  Host
+    arrays only."""
+    E: int
+    S: int
+    T: int
+    rf: int
+    r0: int
+    p: int
+    h_s: int
+    o: int
+    B: int
+    n_codes: np.ndarray         # int64 [U]
+    wav_lens: np.ndarray        # int64 [U]
+    n_u: np.ndarray             # int64 [U]
+    n_scored: np.ndarray        # int64 [U]
+    offsets: np.ndarray         # int64 [U + 1]: utterance u owns the flat elements [offsets[u], offsets[u + 1])
+    utt: np.ndarray             # int32 [R]
+    window: np.ndarray          # int32 [R]
+    start: np.ndarray           # int64 [R]
+    lo: np.ndarray              # int32 [R]
+    hi: np.ndarray              # int32 [R]
+    wav0: np.ndarray            # int64 [R]
+    src: np.ndarray             # int32 [R]
+    n_out: np.ndarray           # int32 [R]
+    dst: np.ndarray             # int64 [R]
+    n_rows: int                 # rows that are not idle
+
+    @property
+    def n_batches(self) -> int:
+        return len(self.utt) // self.B
+
+    @property
+    def n_total(self) -> int:
+        return int(self.offsets[-1])
+
+    def table(self, code_bases, wav_bases, voices) -> np.ndarray:
+        """The aew_score_row_t records (a structured array, _lib.SCORE_ROW_DTYPE) for utterances whose codes start at
+        the indices `code_bases` [U] of the flat code buffer, whose samples start at the elements `wav_bases` [U] of the
+        flat waveform buffer and whose voices are `voices` [U]."""
+        rec = np.zeros(len(self.utt), np.dtype(L.SCORE_ROW_DTYPE))
+        rec["utt"] = -1
+        live = self.utt >= 0
+        u = self.utt[live]
+        rec["utt"][live] = u
+        rec["code0"][live] = np.asarray(code_bases, np.int64).reshape(-1)[u] + self.start[live]
+        rec["wav_base"][live] = np.asarray(wav_bases, np.int64).reshape(-1)[u]
+        rec["wav_len"][live] = self.wav_lens[u]
+        rec["voice"][live] = np.asarray(voices, np.int64).reshape(-1)[u]
+        for name, arr in (("lo", self.lo), ("hi", self.hi), ("wav0", self.wav0), ("src", self.src), ("n_out", self.n_out),
+                          ("dst", self.dst)):
+            rec[name][live] = arr[live]
+        return rec
+
+
+def score_tile_plan(n_codes: Sequence[int], wav_lens: Sequence[int], geom_tuple, B: int) -> ScoreTilePlan:
+    """The work list of a whole-utterance scoring, a pure function of the code counts and waveform lengths (it never
+    reads the device).  geom_tuple = (E, S, T, rf, r0, p, h_s, o, L) is geometry.scoring_geometry(...).plan_args(): utterance
+    u has n_u = min(L(N_u), len(wav_u) - o) positions (0 where that is negative) and n_u - rf - 1 scored samples, the
+    positions q_t in [rf + 1, n_u); window j holds the codes [j h_s - p, j h_s - p + E) - those inside [0, N) exist, the
+    others are code 0 -, its decoder-input row 0 is the utterance's sample o + j h_s S - r0, and it owns the outputs
+    [r0, r0 + h_s S) whose target j h_s S + (u - r0) + rf + 1 lies below n_u; there are ceil((n_u - rf - 1) / (h_s S))
+    windows.  The windows of all utterances, in order, fill batches of B rows; the last batch is padded with idle rows."""
+    E, S, T, rf, r0, p, h_s, o = (int(v) for v in tuple(geom_tuple)[:8])
+    L_of, B = tuple(geom_tuple)[8], int(B)
+    if E < 1 or S < 1 or T < 1 or rf < 0 or r0 < 0 or p < 0 or o < 0 or B < 1:
+        raise ValueError("score_tile_plan(): E, S, T and B must be at least 1, rf, r0, p and o at least 0")
+    if h_s < 1 or r0 + h_s * S > T - rf - 1:
+        raise ValueError(f"score_tile_plan(): the {T} - {rf} - 1 outputs of a window that carry a loss do not hold a hop of "
+                         f"h_s = {h_s} codes of S = {S} behind output {r0}")
+    N = np.asarray(list(n_codes), np.int64).reshape(-1)
+    W = np.asarray(list(wav_lens), np.int64).reshape(-1)
+    if len(N) != len(W) or (N < 0).any() or (W < 0).any():
+        raise ValueError("score_tile_plan(): one non-negative code count and one waveform length per utterance expected")
+    Ln = np.asarray([int(L_of(int(n))) for n in N], np.int64).reshape(-1)
+    if (Ln < 0).any() or (Ln > np.maximum(N, 0) * S).any():
+        raise ValueError("score_tile_plan(): L(n) must lie in [0, n * S]")
+    n_u = np.maximum(np.minimum(Ln, W - o), 0)
+    n_sc = np.maximum(n_u - rf - 1, 0)
+    offsets = np.concatenate([[0], np.cumsum(n_sc)]).astype(np.int64)
+    hop = h_s * S
+    nw = -(-n_sc // hop)
+    n_rows = int(nw.sum())
+    R = -(-n_rows // B) * B
+    firstw = np.concatenate([[0], np.cumsum(nw)])[:-1]
+    utt = np.full(R, -1, np.int32)
+    window, start, wav0, dst = np.zeros(R, np.int32), np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64)
+    lo, hi, src, n_out = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
+    u = np.repeat(np.arange(len(N)), nw)
+    j = np.arange(n_rows) - np.repeat(firstw, nw)
+    c0 = j * h_s - p
+    utt[:n_rows], window[:n_rows], start[:n_rows] = u, j, c0
+    lo[:n_rows] = np.clip(-c0, 0, E)
+    hi[:n_rows] = np.maximum(np.clip(N[u] - c0, 0, E), lo[:n_rows])
+    wav0[:n_rows] = o + j * hop - r0
+    src[:n_rows] = r0
+    n_out[:n_rows] = np.minimum(hop, n_sc[u] - j * hop)
+    dst[:n_rows] = offsets[u] + j * hop
+    return ScoreTilePlan(E, S, T, rf, r0, p, h_s, o, B, N, W, n_u, n_sc, offsets, utt, window, start, lo, hi, wav0, src,
+                         n_out, dst, n_rows)
+
+
+class UtteranceScores:
+    """The teacher-forced likelihood of U whole utterances (model.score_utterances): `nll` float32, flat, on the device -
+    utterance u owns nll[offsets[u]:offsets[u + 1]], n_scored[u] values, and row(u)[i] is the NLL in nats of waveform
+    sample start + i of that utterance (start = o + rf + 1); `prob` (the probability given to the sample that came) and
+    `hit` (uint8: the arg-max class was the sample) alike where they were asked for; `offsets` int64 (U + 1,) and
+    `n_scored` int64 (U,) on the device (their host copies follow from the lengths alone: reading row() never waits);
+    `summary` float32 (U, 4) = (nll per sample, bits per sample, top-1, mean target probability) and `sums` float64
+    (U, 4) = (n, sum nll, sum prob, sum hit), summed in a fixed order that depends neither on the batch nor on the
+    tiling; `voice` int64 (U,) on the host.  An utterance with nothing to score has an empty row and a zero summary."""
+
+    def __init__(self, nll: torch.Tensor, offsets, summary: torch.Tensor, sums: torch.Tensor, start: int,
+                 prob: Optional[torch.Tensor] = None, hit: Optional[torch.Tensor] = None, voice=None):
+        off = torch.as_tensor(offsets, dtype=torch.int64).cpu()
+        U = off.numel() - 1
+        if nll.dim() != 1 or nll.dtype != torch.float32 or U < 0 or int(off[0]) != 0 or int(off[-1]) != nll.numel():
+            raise L.AewError("UtteranceScores: flat float32 nll and offsets (U + 1,) from 0 to len(nll) expected")
+        if tuple(summary.shape) != (U, 4) or tuple(sums.shape) != (U, 4):
+            raise L.AewError(f"UtteranceScores: summary and sums ({U}, 4) expected")
+        for name, t in (("prob", prob), ("hit", hit)):
+            if t is not None and t.shape != nll.shape:
+                raise L.AewError(f"UtteranceScores: {name} must have one value per scored sample")
+        self._off = off.tolist()
+        self.nll, self.prob, self.hit, self.summary, self.sums, self.start = nll, prob, hit, summary, sums, int(start)
+        self.offsets = off.to(nll.device)
+        self.n_scored = (off[1:] - off[:-1]).to(nll.device)
+        self.voice = None if voice is None else torch.as_tensor(voice, dtype=torch.int64).cpu().reshape(-1)
+
+    def __len__(self) -> int:
+        return len(self._off) - 1
+
+    def _cut(self, t, u):
+        u = range(len(self))[u]
+        return t[self._off[u]:self._off[u + 1]]
+
+    def row(self, u: int) -> torch.Tensor:
+        """The per-sample NLL of utterance u in nats (a view): element i belongs to waveform sample start + i."""
+        return self._cut(self.nll, u)
+
+    def prob_row(self, u: int) -> torch.Tensor:
+        return self._cut(self.prob, u)
+
+    def hit_row(self, u: int) -> torch.Tensor:
+        return self._cut(self.hit, u)
+
+    # the columns of `summary` as (U,) views, one accessor per name of _lib.SCORE_OUT_NAMES (attached behind the class)
+
+    def save(self, path):
+        """One .npz: nll, offsets, summary, sums, start and - where present - prob, hit, voice."""
+        arrays = {"nll": self.nll.cpu().numpy(), "offsets": np.asarray(self._off, np.int64), "summary": self.summary.cpu().numpy(),
+                  "sums": self.sums.cpu().numpy(), "start": np.asarray(self.start, np.int64)}
+        for name in ("prob", "hit", "voice"):
+            if getattr(self, name) is not None:
+                arrays[name] = getattr(self, name).cpu().numpy()
+        with open(path, "wb") as fh:
+            np.savez(fh, **arrays)
+
+    @classmethod
+    def load(cls, path, device=None) -> "UtteranceScores":
+        with np.load(path, allow_pickle=False) as z:
+            put = lambda k: torch.from_numpy(z[k]).to(device) if device is not None else torch.from_numpy(z[k])
+            return cls(put("nll"), torch.from_numpy(z["offsets"]), put("summary"), put("sums"), int(z["start"]),
+                       prob=put("prob") if "prob" in z else None, hit=put("hit") if "hit" in z else None,
+                       voice=torch.from_numpy(z["voice"]) if "voice" in z else None)
+
+
+def _summary_column(i: int, name: str):
+    return property(lambda self: self.summary[:, i], doc=f"`summary[:, {i}]`: {name} of every utterance, a (U,) view.")
+
+
+for _i, _name in enumerate(L.SCORE_OUT_NAMES):                            # nll_per_sample, bits_per_sample, top1, mean_prob
+    setattr(UtteranceScores, _name, _summary_column(_i, _name))
 
 
 # ---- mu-law companding of the decoder's samples (amplitudes in [-1, 1] -> n_quant integer values) ---------------------

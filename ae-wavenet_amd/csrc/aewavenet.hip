@@ -11,6 +11,7 @@
 #include "aew_evalgroups.hip"
 #include "aew_utterance.hip"
 #include "aew_cond_utterance.hip"
+#include "aew_score.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -75,6 +76,9 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_CODE_STITCH: return launch_code_stitch(op.u.cstitch, st);
         case AEW_OP_CODE_TILE: return launch_code_tile(op.u.ctile, st);
         case AEW_OP_COND_STITCH: return launch_cond_stitch(op.u.cndst, st);
+        case AEW_OP_WAV_TILE: return launch_wav_tile(op.u.wtile, st);
+        case AEW_OP_NLL_STITCH: return launch_nll_stitch(op.u.nllst, st);
+        case AEW_OP_SCORE_REDUCE: return launch_score_reduce(op.u.sred, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -122,6 +126,10 @@ extern "C" int aew_sizeof(int which) {
         case 38: return (int)sizeof(aew_code_tile_t);
         case 39: return (int)sizeof(aew_cond_stitch_t);
         case 41: return (int)sizeof(aew_draw_t);      // (40 is left unused like 24, 26 and 33)
+        case 42: return (int)sizeof(aew_score_row_t);
+        case 43: return (int)sizeof(aew_wav_tile_t);
+        case 44: return (int)sizeof(aew_nll_stitch_t);
+        case 45: return (int)sizeof(aew_score_reduce_t);
         default: return -1;
     }
 }

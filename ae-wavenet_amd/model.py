@@ -517,6 +517,11 @@ class TrainEngine:
         # in front of and behind the decode plan, re-addressed per batch in the same way
         self.cond_tile, self.cond_stitch = Plan("code.tile"), Plan("cond.stitch")
         self._dec_pack_plan = None        # decoder_pack_plan(): the decoder's weight layouts alone
+        # ===== whole utterances through the teacher-forced decoder (score_tiles(): aew_wav_tile_t / aew_nll_stitch_t /
+        # aew_score_reduce_t): one op each around score_plan(), re-addressed per call; they exist from the first scoring on
+        self.score_tile, self.score_stitch, self.score_reduce = Plan("wav.tile"), Plan("nll.stitch"), Plan("score.reduce")
+        self._score_plan = self._score_dec_plan = None    # decode_plan() + eval_b from the first gated layer through softmax_nll
+        self.score_bad = None             # int32 [1] (a uint32 count): samples outside [0, n_quant) in the last scoring
         self._chain_flag_views = self._chain_host = None
 
     # ops of the training forward that an evaluation leaves out: they write what the next training step (or the caller,
@@ -803,12 +808,14 @@ class TrainEngine:
         `voice` and `jitter` are read from the inputs (set_inputs / the in_voice, in_jitter buffers).  A code outside
         [0, K) is not followed: its row of zq is zero and `codes_bad[0]` counts it - the caller decides (reading the word
         synchronises).  Writes none of emb, the EMA accumulators and statistics, ind_hist, loss_buf, met_buf, diag, the
-        parameters, gradients, moments or the average; overwrites activations (act_epoch).
+        parameters, gradients, moments or the average; overwrites activations (act_epoch).  A deferred EMA accumulation is
+        applied first, as evaluate() does: the lookup reads the codebook behind it.
         Returns (cond, bias) exactly as conditioning() does."""
         dp = self.decode_plan()
         if codes.dtype != torch.int64 or codes.numel() != self.Q:
             raise L.AewError(f"codes_to_conditioning(): {self.Q} int64 codes expected (B = {self.B} rows of "
                              f"{self.geom.embed_len}), got {tuple(codes.shape)} {codes.dtype}")
+        self.finish_ema()
         self.act_epoch += 1
         self.ind[:self.Q].copy_(codes.reshape(-1))
         self.codes_bad.zero_()
@@ -886,6 +893,7 @@ class TrainEngine:
         ct.codes, ct.n_codes = codes_flat.data_ptr(), codes_flat.numel()
         cs.table, cs.table_host, cs.first_row = ct.table, ct.table_host, ct.first_row
         cs.cond_utt, cs.n_dst, cs.bias_utt, cs.n_streams = cond_utt.data_ptr(), cond_utt.numel(), bias_utt.data_ptr(), cond_utt.shape[0]
+        self.finish_ema()                                            # (a deferred EMA accumulation first, as evaluate())
         self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
         self.decoder_pack_plan().run(self._stream())
         p = Plan("cond.batch")
@@ -922,6 +930,7 @@ class TrainEngine:
         ct.table_host = cs.table_host = host.data_ptr()
         ct.codes, ct.n_codes = codes_flat.data_ptr(), codes_flat.numel()
         cs.cond_utt, cs.n_dst, cs.bias_utt, cs.n_streams = cond_utt.data_ptr(), cond_utt.numel(), bias_utt.data_ptr(), cond_utt.shape[0]
+        self.finish_ema()                                            # (a deferred EMA accumulation first, as evaluate())
         self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
         self.act_epoch += 1
         st = self._stream()
@@ -936,6 +945,174 @@ class TrainEngine:
             # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
             # keep no address of them
             ct.table = cs.table = ct.table_host = cs.table_host = ct.codes = cs.cond_utt = cs.bias_utt = None
+
+    # ---- whole utterances through the teacher-forced decoder: the likelihood of a waveform given codes and a voice ---------
+    def score_decoder_plan(self) -> Plan:
+        """The decoder half of score_plan(), built once: the ops of eval_b from the first gated layer (its chained launch
+        included) through softmax_nll - the same records, order, lanes and chained launches; eval.loss, eval.accumulate
+        and everything in EVAL_DROP are left out."""
+        if self._score_dec_plan is None:
+            eb = self.eval_plans()[1]
+            first = next(i for i, lab in enumerate(eb.labels) if lab.startswith(("G1.0", "chain[G1.0")))
+            last = eb.labels.index("softmax_nll")
+            self._score_dec_plan = self._sub_plan("score_decoder", eb, lambda i, lab: first <= i <= last)
+        return self._score_dec_plan
+
+    def score_plan(self) -> Plan:
+        """decode_plan() (code lookup + the conditioning prefix with the base gather, the same records) followed by
+        score_decoder_plan(), built once at the first use: codes, voices and decoder-input samples in, per-position nll /
+        ptgt (and arg-max, where the softmax writes one) out."""
+        if self._score_plan is None:
+            sp = self._sub_plan("score", self.decode_plan(), lambda i, lab: True)
+            sp.splice(len(sp.ops), self._sub_plan("score_decoder", self.score_decoder_plan(), lambda i, lab: True))
+            self._score_plan = sp
+        return self._score_plan
+
+    def scoring_ops(self):
+        """The records of the three ops around the score plan, built at the first use: (aew_wav_tile_t writing in_wav /
+        ind / in_voice and counting into codes_bad / score_bad, aew_nll_stitch_t reading what softmax_nll wrote,
+        aew_score_reduce_t).  The caller fills in the table, its first row, the flat buffers and the outputs."""
+        self.score_plan()
+        if self.take_compat:
+            raise L.AewError("score_tiles(): this engine was built with take_compat=True, whose conditioning gather is not "
+                             "the identity the tiling of whole utterances rests on")
+        if not self.score_tile.ops:
+            g = self.geom
+            G.scoring_geometry(g)                                        # (raises for a window shorter than one hop)
+            self.score_bad = self.ws.alloc("score.bad", 1, torch.int32)
+            sm = self.fwd_b.ops[self.fwd_b.labels.index("softmax_nll")].u.sm
+            wt = L.WavTile()
+            wt.ind, wt.in_voice, wt.wav = self.ind.data_ptr(), self.in_voice.data_ptr(), self.in_wav.data_ptr()
+            wt.bad_codes, wt.bad_wav = self.codes_bad.data_ptr(), self.score_bad.data_ptr()
+            wt.wav_pitch, wt.wav_off, wt.T, wt.n_quant = self.in_wav.shape[1], g.trim_dec_in[0], g.dec_in_len, int(self.hps.n_quant)
+            wt.B, wt.E, wt.K, wt.n_voice = self.B, g.embed_len, self.K, int(self.hps.n_speakers)
+            from .codes import mu_encode
+            wt.zero = float(mu_encode(torch.zeros(1), int(self.hps.n_quant))[0])
+            self.score_tile.add(L.OP_WAV_TILE, wt, "wav.tile", TAG_VQ)
+            ns = L.NllStitch()
+            ns.nll, ns.ptgt, ns.wav, ns.wav_pitch, ns.tgt_off, ns.B, ns.w = sm.nll, sm.ptgt, sm.wav, sm.wav_pitch, sm.tgt_off, sm.B, sm.w
+            if sm.amax:
+                ns.amax = sm.amax
+            else:
+                ns.logits, ns.bs, ns.pitch, ns.n_quant = sm.logits, sm.bs, sm.pitch, sm.Q
+            self.score_stitch.add(L.OP_NLL_STITCH, ns, "nll.stitch", TAG_LOSS)
+            self.score_reduce.add(L.OP_SCORE_REDUCE, L.ScoreReduce(), "score.reduce", TAG_LOSS)
+        return self.score_tile.array()[0].u.wtile, self.score_stitch.array()[0].u.nllst, self.score_reduce.array()[0].u.sred
+
+    def _score_check(self, what: str, codes_flat, wav_flat, nll, ptgt, hit):
+        if codes_flat.dtype != torch.int64 or codes_flat.dim() != 1 or not codes_flat.is_contiguous():
+            raise L.AewError(f"{what}: flat contiguous int64 codes expected, got {tuple(codes_flat.shape)} {codes_flat.dtype}")
+        if wav_flat.dtype != torch.float32 or wav_flat.dim() != 1 or not wav_flat.is_contiguous():
+            raise L.AewError(f"{what}: a flat contiguous float32 waveform buffer expected, got {tuple(wav_flat.shape)} "
+                             f"{wav_flat.dtype}")
+        if nll.dtype != torch.float32 or nll.dim() != 1 or not nll.is_contiguous():
+            raise L.AewError(f"{what}: flat contiguous float32 nll expected, got {tuple(nll.shape)} {nll.dtype}")
+        for name, t, dt in (("ptgt", ptgt, torch.float32), ("hit", hit, torch.uint8)):
+            if t is not None and (t.dtype != dt or t.shape != nll.shape or not t.is_contiguous()):
+                raise L.AewError(f"{what}: {name} must be {dt}, contiguous, one value per nll element")
+
+    def _score_fill(self, wt, ns, table_ptr, host_ptr, codes_flat, wav_flat, nll, ptgt, hit):
+        wt.table = ns.table = table_ptr
+        wt.table_host = ns.table_host = host_ptr
+        wt.codes, wt.n_codes, wt.wavs, wt.n_wav = codes_flat.data_ptr(), codes_flat.numel(), wav_flat.data_ptr(), wav_flat.numel()
+        ns.dst_nll, ns.n_dst = nll.data_ptr(), nll.numel()
+        ns.dst_ptgt = ptgt.data_ptr() if ptgt is not None else None
+        ns.dst_hit = hit.data_ptr() if hit is not None else None
+
+    def score_batch_plan(self, codes_flat: torch.Tensor, wav_flat: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor,
+                         first_row: int, nll: torch.Tensor, ptgt: Optional[torch.Tensor] = None,
+                         hit: Optional[torch.Tensor] = None) -> Plan:
+        """One batch of a whole-utterance scoring as a plan of its own (for a caller's captured graph): [wav.tile] + the ops
+        of score_plan() (the same records) + [nll.stitch] over the rows [first_row, first_row + B) of `table` (uint8 device
+        bytes of aew_score_row_t records; table_host: the same bytes in pinned host memory, read at capture).  in_jitter is
+        set to the identity and the decoder's weight layouts are packed here, once (after a change of the weights the
+        caller runs decoder_pack_plan() again); the caller zeroes codes_bad / score_bad and keeps the tensors alive.  A
+        deferred EMA accumulation is applied here, once, as evaluate() does at its head."""
+        wt0, ns0, _ = self.scoring_ops()
+        self._score_check("score_batch_plan()", codes_flat, wav_flat, nll, ptgt, hit)
+        wt, ns = L.WavTile.from_buffer_copy(wt0), L.NllStitch.from_buffer_copy(ns0)
+        self._score_fill(wt, ns, table.data_ptr(), table_host.data_ptr(), codes_flat, wav_flat, nll, ptgt, hit)
+        wt.first_row = ns.first_row = int(first_row)
+        self.finish_ema()
+        self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
+        self.decoder_pack_plan().run(self._stream())
+        p = Plan("score.batch")
+        p.add(L.OP_WAV_TILE, wt, "wav.tile", TAG_VQ)
+        p.splice(1, self._sub_plan("score", self.score_plan(), lambda i, lab: True))
+        p.add(L.OP_NLL_STITCH, ns, "nll.stitch", TAG_LOSS, join=True)
+        return p
+
+    def score_tiles(self, codes_flat: torch.Tensor, wav_flat: torch.Tensor, table, nll: torch.Tensor,
+                    ptgt: Optional[torch.Tensor] = None, hit: Optional[torch.Tensor] = None, *, offsets, acc: torch.Tensor,
+                    out: torch.Tensor):
+        """The teacher-forced likelihood of whole utterances through the fixed-geometry decoder: `codes_flat` int64 and
+        `wav_flat` float32 (float-encoded mu-law values), the flat ragged buffers; `table` a numpy array of
+        aew_score_row_t records (_lib.SCORE_ROW_DTYPE), a multiple of B rows (codes.ScoreTilePlan.table); `nll` - and
+        `ptgt` float32, `hit` uint8 - the flat per-utterance outputs, utterance u owning [offsets[u], offsets[u + 1])
+        (`offsets`: U + 1 host integers); `acc` float64 (U, 4) and `out` float32 (U, 4), what AEW_OP_SCORE_REDUCE writes.
+        The table and the offsets go to the device once (one pinned buffer, non-blocking); per batch of B rows one
+        AEW_OP_WAV_TILE fills in_wav / ind / in_voice, score_plan() runs with in_jitter the identity, and one
+        AEW_OP_NLL_STITCH moves the outputs each window owns; then one AEW_OP_SCORE_REDUCE.  Codes outside [0, K) become
+        code 0 and count in `codes_bad[0]`, samples outside [0, n_quant) become the zero-amplitude code and count in
+        `score_bad[0]` (both zeroed here; reading them synchronises).  Writes what codes_to_conditioning() writes, the
+        decoder's activations and logits (act_epoch), the packed layouts of the decoder's weights (decoder_pack_plan(),
+        once per call) and nothing else of the engine: none of emb, the EMA accumulators and statistics, ind_hist,
+        loss_buf, met_buf, diag, eval_acc / eval_hist, the parameters, gradients, moments or the average.  A deferred EMA
+        accumulation (forward() with an asynchronous statistics collective and no backward since) is applied first, as
+        evaluate() does: the codebook read is the one behind that update.  No host synchronisation otherwise."""
+        wt, ns, sr = self.scoring_ops()
+        sp = self.score_plan()
+        n = len(table)
+        if n % self.B or table.dtype.itemsize != C.sizeof(L.ScoreRow):
+            raise L.AewError(f"score_tiles(): a multiple of B = {self.B} aew_score_row_t records expected, got {n}")
+        self._score_check("score_tiles()", codes_flat, wav_flat, nll, ptgt, hit)
+        off = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
+        U = len(off) - 1
+        if U < 0 or acc.dtype != torch.float64 or tuple(acc.shape) != (U, 4) or not acc.is_contiguous() or \
+                out.dtype != torch.float32 or tuple(out.shape) != (U, 4) or not out.is_contiguous():
+            raise L.AewError(f"score_tiles(): offsets (U + 1,), acc float64 (U, 4) and out float32 (U, 4) expected")
+        if U and (off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != nll.numel()):
+            raise L.AewError("score_tiles(): offsets must ascend from 0 to len(nll)")
+        self.codes_bad.zero_()
+        self.score_bad.zero_()
+        if U == 0 or nll.numel() == 0:                                    # nothing to score anywhere: empty rows, zero summaries
+            acc.zero_()
+            out.zero_()
+            return
+        self._chain_watch("check")
+        self.finish_ema()
+        n_tbl = n * table.dtype.itemsize                                  # (a multiple of 64: the offsets behind it stay aligned)
+        host = torch.empty(n_tbl + off.nbytes, dtype=torch.uint8, pin_memory=True)
+        host.numpy()[:n_tbl] = table.view(np.uint8).reshape(-1)
+        host.numpy()[n_tbl:] = off.view(np.uint8)
+        dev = torch.empty_like(host, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        self._score_fill(wt, ns, dev.data_ptr(), host.data_ptr(), codes_flat, wav_flat, nll, ptgt, hit)
+        sr.offsets, sr.offsets_host, sr.U = dev.data_ptr() + n_tbl, host.data_ptr() + n_tbl, U
+        sr.nll, sr.n_src = nll.data_ptr(), nll.numel()
+        sr.ptgt = ptgt.data_ptr() if ptgt is not None else None
+        sr.hit = hit.data_ptr() if hit is not None else None
+        sr.acc, sr.out = acc.data_ptr(), out.data_ptr()
+        self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
+        st = self._stream()
+        try:
+            if n:
+                self.act_epoch += 1
+                self.decoder_pack_plan().run(st)
+            for first in range(0, n, self.B):
+                wt.first_row = ns.first_row = first
+                self.score_tile.run(st)
+                self._run(sp, False)
+                self.score_stitch.run(st)
+            self.score_reduce.run(st)
+            if n:
+                self._chain_watch("fwd")
+        finally:
+            # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
+            # keep no address of them
+            wt.table = ns.table = wt.table_host = ns.table_host = wt.codes = wt.wavs = None
+            ns.dst_nll = ns.dst_ptgt = ns.dst_hit = None
+            sr.offsets = sr.offsets_host = sr.nll = sr.ptgt = sr.hit = sr.acc = sr.out = None
 
     def conditioning(self):
         """Encoder / bottleneck and the conditioning half of the decoder forward only (jitter gather, lc_conv,

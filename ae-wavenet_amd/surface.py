@@ -1202,6 +1202,97 @@ class HipModelBase(nn.Module):
             rows, prime = rows * V, prime * V
         return self.decode_utterances(rows, voice_to, prime=prime, n_prime=n_prime, seed=seed, batch=batch, draw=draw)
 
+    # ---- whole utterances through the teacher-forced decoder: how well the decoder explains a waveform ------------------
+    def score_utterances(self, wavs, voice=None, codes=None, batch=None, return_prob: bool = False, return_hit: bool = False):
+        """The teacher-forced likelihood of WHOLE utterances: `wavs` a list of 1-D device tensors of mu-law values, `codes`
+        a `codes.UtteranceCodes` or a list of 1-D int64 tensors (default: self.encode_wavs(wavs, batch=batch), the
+        utterances' own codes), `voice` one per utterance (default: the UtteranceCodes' own) -> `codes.UtteranceScores`.
+        With ONE utterance and `voice` of shape (V,), that utterance is scored under V voices at once, as V rows - speaker
+        attribution in one call (the rule of convert_utterances).
+
+        Conditioning position q of an utterance of N codes belongs to waveform sample o + q (geometry.scoring_geometry);
+        the scored samples are the positions [rf + 1, n_u), n_u = min(L(N), len(wav) - o): the first rf + 1 positions are
+        context only, as they are primed in decode_utterances().  `row(u)[i]` of the result is the NLL in nats of waveform
+        sample `start + i`, start = o + rf + 1; `summary` holds (nll per sample, bits per sample, top-1, mean target
+        probability) per utterance, `sums` the float64 record they are quotients of.  return_prob / return_hit add the
+        per-sample probability of the sample that came / whether it was the arg-max class.  The utterance is cut into
+        overlapping windows of the engine's geometry (work list: codes.score_tile_plan), `batch` windows at a time run
+        through the unchanged conditioning and decoder plans, and the outputs each window owns are stitched: sample for
+        sample the bits of any other packing of the windows into batches - and of any other batch size for which the GEMM
+        launcher picks the same kernels (keep `batch` fixed where results are compared bit for bit).
+
+        Refused with AewError before anything runs on the device: a model without discrete codes or built with
+        take_compat=True, a window that holds no hop, a code outside [0, K), a waveform value outside [0, n_quant), a
+        voice outside [0, n_speakers).  The rules of decode() hold: no codebook, EMA statistic, histogram, loss, metric
+        or evaluation word is written; inside `FusedAdam.averaged_weights()` the averaged weights are used; a pending
+        `loss.backward()` raises afterwards; no collective under data parallel."""
+        from . import codes as CD
+        what = "score_utterances()"
+        eng, _ = self._utterance_engine(what, batch)
+        sg = G.scoring_geometry(self.geom)                                 # (raises where the window cannot tile)
+        wavs = list(wavs)
+        for w in wavs:
+            if not torch.is_tensor(w) or w.dim() != 1:
+                raise L.AewError(f"{what}: wavs must be a list of 1-D tensors of mu-law values")
+        nq, dev = int(self.n_quant), eng.device
+        uniq, wav_bases, at = {}, [], 0                                     # (one utterance under V voices is stored once)
+        for w in wavs:
+            if id(w) not in uniq:
+                uniq[id(w)] = (at, w)
+                at += w.numel()
+            wav_bases.append(uniq[id(w)][0])
+        wav_flat = torch.cat([w.to(device=dev, dtype=torch.float32) for _, w in uniq.values()]) if at else \
+            torch.empty(0, dtype=torch.float32, device=dev)
+        if at:
+            bad = int((~((wav_flat >= 0) & (wav_flat < nq))).sum())
+            if bad:
+                raise L.AewError(f"{what}: {bad} of the {at} waveform values lie outside [0, {nq}); nothing was scored")
+        if codes is None:
+            nv = int(self.hps.n_speakers)                                   # (the voices once here: the encoder runs next)
+            given = [] if voice is None else torch.as_tensor(voice, dtype=torch.int64).reshape(-1).tolist()
+            if not given or any(v < 0 or v >= nv for v in given):
+                raise L.AewError(f"{what}: voices in [0, {nv}) expected (codes encoded here carry none), got {given}")
+            if len(given) != len(wavs) and len(wavs) != 1:
+                raise L.AewError(f"{what}: voice ({len(wavs)},) expected (one per utterance), or (V,) with one utterance; "
+                                 f"got {len(given)} voices for {len(wavs)} utterances")
+            codes = self.encode_wavs(wavs, batch=batch)
+        U = len(wavs)
+        n_given = len(codes)
+        if n_given != U:
+            raise L.AewError(f"{what}: {U} waveforms but the codes of {n_given} utterances")
+        if U == 1 and voice is not None and torch.as_tensor(voice).numel() > 1:
+            V = torch.as_tensor(voice).numel()
+            rows1, _ = self._utterance_rows(what, codes, [0])
+            rows, voices = self._utterance_rows(what, rows1 * V, voice)
+            wavs, wav_bases = wavs * V, wav_bases * V
+        else:
+            rows, voices = self._utterance_rows(what, codes, voice)
+        with torch.no_grad():
+            self._check_codes(what, rows, eng.K)
+            cuniq, code_bases, cat = {}, [], 0
+            for r in rows:
+                key = (r.data_ptr(), r.numel()) if r.numel() else ("empty", 0)
+                if key not in cuniq:
+                    cuniq[key] = (cat, r)
+                    cat += r.numel()
+                code_bases.append(cuniq[key][0])
+            codes_flat = torch.cat([r.to(dev) for _, r in cuniq.values()]) if cat else torch.empty(0, dtype=torch.int64, device=dev)
+            plan = CD.score_tile_plan([r.numel() for r in rows], [w.numel() for w in wavs], sg.plan_args(), eng.B)
+            n_rows = len(rows)
+            nll = torch.zeros(plan.n_total, dtype=torch.float32, device=dev)
+            prob = torch.zeros(plan.n_total, dtype=torch.float32, device=dev) if return_prob else None
+            hit = torch.zeros(plan.n_total, dtype=torch.uint8, device=dev) if return_hit else None
+            # the summary's top-1 and mean probability need the two arrays whether the caller wants them or not
+            prob_w = prob if prob is not None else torch.zeros(plan.n_total, dtype=torch.float32, device=dev)
+            hit_w = hit if hit is not None else torch.zeros(plan.n_total, dtype=torch.uint8, device=dev)
+            acc = torch.zeros(n_rows, 4, dtype=torch.float64, device=dev)
+            out = torch.zeros(n_rows, 4, dtype=torch.float32, device=dev)
+            if n_rows:
+                eng.score_tiles(codes_flat, wav_flat, plan.table(code_bases, wav_bases, voices), nll, prob_w, hit_w,
+                                offsets=plan.offsets, acc=acc, out=out)
+        return CD.UtteranceScores(nll, torch.from_numpy(plan.offsets.copy()), out, acc, sg.o + sg.rf + 1, prob=prob, hit=hit,
+                                  voice=torch.tensor(voices, dtype=torch.int64))
+
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared
         (FusedAdam.zero_grad(), or every .grad is None as zero_grad(set_to_none=True) leaves them), else a copy of the

@@ -48,7 +48,8 @@ extern "C" {
  * unchanged.  A binding that wants the additions finds them through aew_sizeof(22) / aew_sizeof(23) (-1 in a library
  * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 37 .. 39,
  * aew_cond_row_t, aew_code_tile_t / AEW_OP_CODE_TILE, aew_cond_stitch_t / AEW_OP_COND_STITCH; 41, aew_draw_t, with the
- * `draw` pointer appended to aew_sampler_t - index 40 stays unused, it answers -1). */
+ * `draw` pointer appended to aew_sampler_t - index 40 stays unused, it answers -1; 42 .. 45, aew_score_row_t,
+ * aew_wav_tile_t / AEW_OP_WAV_TILE, aew_nll_stitch_t / AEW_OP_NLL_STITCH, aew_score_reduce_t / AEW_OP_SCORE_REDUCE). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -965,6 +966,116 @@ typedef struct {
     int32_t n_streams, pad_;
 } aew_cond_stitch_t;
 
+/* Whole utterances through the teacher-forced decoder: the likelihood of a waveform given codes and a voice (appended to
+ * ABI 28; AEW_OP_WAV_TILE / AEW_OP_NLL_STITCH / AEW_OP_SCORE_REDUCE, aew_sizeof 42 .. 45).  With rf = the sum of the
+ * dilations and T = dec_in_len = w + rf, output position u of a window reads decoder-input rows [u, u + rf] and cond rows
+ * [u, u + rf]; its target is decoder-input sample u + rf + 1, and u = w - 1 carries no loss.  In the coordinates of the
+ * whole-utterance conditioning (position q of an utterance of N codes is waveform sample o + q, 0 <= q < L(N)) the scored
+ * samples are q_t in [rf + 1, n_u), n_u = min(L(N), len(wav) - o).  With r0 = p S - trim0 and the hop
+ * h_s = (w - 1 - r0) / S codes, window j holds the codes [j h_s - p, j h_s - p + E), its cond row 0 is position
+ * a_j = j h_s S - r0, and it OWNS the outputs u in [r0, r0 + h_s S) whose target a_j + u + rf + 1 lies below n_u: every
+ * row an owned output reads is a real row of the utterance.
+ *
+ * AEW_OP_WAV_TILE and AEW_OP_NLL_STITCH read one table of records in DEVICE memory, one per batch row, under the rules of
+ * the conditioning ops above: the launchers check the rows [first_row, first_row + B) on `table_host`, the kernels repeat
+ * the check on the device copy and treat a record that fails it as idle. */
+typedef struct {
+    int64_t code0;               /* index in the flat code buffer of the window's code 0: window code j is codes[code0 + j]  */
+    int64_t wav_base;            /* element of the flat waveform buffer that holds the utterance's sample 0                 */
+    int64_t wav_len;             /* samples of the utterance; [wav_base, wav_base + wav_len) lies inside [0, n_wav)         */
+    int64_t wav0;                /* the utterance's sample that is the window's decoder-input row 0 (o + a_j; it may lie in
+                                    front of the utterance, and wav0 + T behind it: those rows get the zero code)            */
+    int64_t dst;                 /* element of the flat outputs the first owned output goes to                              */
+    int32_t utt;                 /* the utterance, < 0: an idle row (nothing else of the record is used)                    */
+    int32_t lo, hi;              /* the window's codes [lo, hi) exist, 0 <= lo <= hi <= E; the others are code 0            */
+    int32_t voice;               /* the row's voice, [0, n_voice)                                                           */
+    int32_t src;                 /* first owned output position u; [src, src + n_out) lies inside [0, w - 1)                */
+    int32_t n_out;               /* owned outputs                                                                           */
+} aew_score_row_t;
+
+/* AEW_OP_WAV_TILE: for b < B, with r = table[first_row + b]: wav[b][wav_off + t] = wavs[r.wav_base + r.wav0 + t] for the
+ * t < T with 0 <= r.wav0 + t < r.wav_len, `zero` (the zero-amplitude code) for the others and for an idle row; ind[b] and
+ * in_voice[b] as AEW_OP_CODE_TILE writes them.  A sample outside [0, n_quant) (a NaN included) is written as `zero` - the
+ * base gather indexes a table with it - and counted in *bad_wav; a code outside [0, K) is written as 0 and counted in
+ * *bad_codes (uint32, integer atomicAdd; windows overlap, so one value may count more than once).  Nothing else of `wav`
+ * is written.
+ * AEW_E_ARG: a NULL pointer, B < 1 or > 65535, first_row < 0, E, K, n_voice, n_quant or T < 1, wav_off < 0,
+ * wav_off + T > wav_pitch, n_codes or n_wav < 0, `zero` outside [0, n_quant), a live row with lo / hi outside
+ * 0 <= lo <= hi <= E, a code read outside [0, n_codes), a voice outside [0, n_voice), wav_len < 0 or
+ * [wav_base, wav_base + wav_len) outside [0, n_wav), |wav0| >= 2^40; AEW_E_ALIGN: a pointer off 16 bytes (bad_*: 4).  All
+ * before any launch: a refused call writes nothing. */
+typedef struct {
+    const aew_score_row_t* table;       /* device memory                                         */
+    const aew_score_row_t* table_host;  /* the same records in host memory (read by the launcher) */
+    int32_t first_row, B;
+    const int64_t* codes;        /* the flat code buffer, n_codes elements                     */
+    int64_t n_codes;
+    const float* wavs;           /* the flat ragged waveform buffer (float-encoded mu-law values), n_wav elements */
+    int64_t n_wav;
+    int64_t* ind;                /* [B][E]                                                     */
+    int64_t* in_voice;           /* [B]                                                        */
+    float* wav;                  /* the engine's waveform input, [B][wav_pitch]                */
+    uint32_t* bad_codes;         /* one device word each, added to                             */
+    uint32_t* bad_wav;
+    int32_t wav_pitch, wav_off;  /* elements between batch rows; first decoder-input sample (trim_dec_in[0]) */
+    int32_t T, n_quant;
+    int32_t E, K;
+    int32_t n_voice;
+    float zero;                  /* the zero-amplitude code                                    */
+} aew_wav_tile_t;
+
+/* AEW_OP_NLL_STITCH: for b < B, with r = table[first_row + b] and i < r.n_out, u = r.src + i:
+ *   dst_nll[r.dst + i] = nll[b * w + u];   dst_ptgt[r.dst + i] = ptgt[b * w + u] (where dst_ptgt is given);
+ *   dst_hit[r.dst + i] = 1 if the arg-max class of position (b, u) equals its target (int)wav[b][tgt_off + u + 1], else 0
+ *   (where dst_hit is given).  The arg-max is amax[b * w + u] where the softmax op wrote one, else the scan of
+ *   logits[b * bs + u * pitch + 0 .. n_quant) in which the lowest class keeps a tie - the rule of aew_eval_acc_t.
+ * Nothing outside the owned ranges is written.
+ * AEW_E_ARG: a NULL table / table_host / nll / dst_nll, dst_ptgt without ptgt, dst_hit without wav or without both amax
+ * and logits (n_quant >= 1, pitch >= n_quant, bs >= 0), B < 1 or > 65535, first_row < 0, w < 2, tgt_off < 0,
+ * tgt_off + w > wav_pitch, n_dst < 0, a live row with [src, src + n_out) outside [0, w - 1) or [dst, dst + n_out) outside
+ * [0, n_dst); AEW_E_ALIGN: table / table_host off 16 bytes, a float / int32 pointer off 4.  All before any launch. */
+typedef struct {
+    const aew_score_row_t* table;
+    const aew_score_row_t* table_host;
+    int32_t first_row, B;
+    const float* nll;            /* [B][w]: what AEW_OP_SOFTMAX_NLL wrote                      */
+    const float* ptgt;           /* [B][w] (optional)                                          */
+    const int32_t* amax;         /* [B][w] (optional)                                          */
+    const float* logits;         /* (optional; read where amax is NULL)                        */
+    int64_t bs;                  /* elements between the batch rows of logits                  */
+    const float* wav;            /* the engine's waveform input, [B][wav_pitch]                */
+    float* dst_nll;              /* n_dst elements                                             */
+    float* dst_ptgt;             /* n_dst elements (optional)                                  */
+    uint8_t* dst_hit;            /* n_dst elements (optional)                                  */
+    int64_t n_dst;
+    int32_t pitch, n_quant;      /* elements between the rows of logits; classes               */
+    int32_t wav_pitch, tgt_off;
+    int32_t w, pad_;
+} aew_nll_stitch_t;
+
+/* AEW_OP_SCORE_REDUCE: one workgroup of 1024 threads per utterance u < U over the stitched flat arrays, elements
+ * [offsets[u], offsets[u + 1]) = n of them:
+ *   acc[u] = (n, sum nll, sum ptgt, sum hit) as doubles - THE order and THE tree of aew_eval_acc_t: thread t adds its
+ *            elements t, t + 1024, ... ascending into a double, then for (o = 512; o > 0; o >>= 1) s[t] += s[t + o] for
+ *            t < o.  No floating atomics.  ptgt / hit may be NULL: their sums are 0.
+ *   out[u] = (nll per sample, bits per sample = that / ln 2, top-1 = sum hit / n, mean target probability): quotients in
+ *            double, rounded to fp32 once; all 0 where n = 0.
+ * The sums run over the flat arrays, so they depend neither on the batch size nor on the tiling that filled them.
+ * AEW_E_ARG: a NULL offsets / offsets_host / nll / acc / out, U < 1 or > 2^20, n_src < 0, offsets_host[0] < 0, a
+ * decreasing pair or offsets_host[U] > n_src; AEW_E_ALIGN: offsets / acc off 8 bytes, nll / ptgt / out off 4.  The kernel
+ * repeats the range check on the device copy and treats a failing utterance as empty. */
+typedef struct {
+    const int64_t* offsets;      /* device memory, [U + 1]                                     */
+    const int64_t* offsets_host; /* the same numbers in host memory (read by the launcher)     */
+    const float* nll;            /* n_src elements                                             */
+    const float* ptgt;           /* (optional)                                                 */
+    const uint8_t* hit;          /* (optional)                                                 */
+    int64_t n_src;
+    double* acc;                 /* [U][4]                                                     */
+    float* out;                  /* [U][4]                                                     */
+    int32_t U, pad_;
+} aew_score_reduce_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1285,7 +1396,8 @@ enum {
     AEW_OP_MOMENTS, AEW_OP_GEMM_TN_GROUP, AEW_OP_NT_CHAIN, AEW_OP_GRAD_NORM, AEW_OP_UPDATE_RATIO,
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
-    AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH
+    AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH,
+    AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1316,13 +1428,14 @@ typedef struct {
         aew_code_lookup_t clk; aew_code_runs_t crun; aew_adam_grouped_t adamg;
         aew_eval_groups_t evg; aew_mel_tile_t mtile; aew_code_stitch_t cstitch;
         aew_code_tile_t ctile; aew_cond_stitch_t cndst;
+        aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch (24, 26 and 33 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce (24, 26, 33 and 40 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
