@@ -11,6 +11,7 @@ Package layout:
   optim.py              fused Adam on the flat parameter buffer
   dp.py                 data-parallel helpers (RCCL via torch.distributed)
   corpus.py             the training corpus in device memory, batches cut on the device (DeviceCorpus, DeviceBatches)
+  align.py              comparing utterances: batched DTW and code edit distance on the device (dtw, edit_distance, abx)
 """
 __version__ = "0.1.0"
 

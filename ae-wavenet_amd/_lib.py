@@ -25,7 +25,7 @@ EF_OUT2_COPY = 1 << 10
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
- OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE) = range(1, 46)
+ OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE, OP_SEQ_ALIGN) = range(1, 47)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -320,6 +320,38 @@ class ScoreReduce(C.Structure):
 SCORE_OUT_NAMES = ("nll_per_sample", "bits_per_sample", "top1", "mean_prob")
 
 
+ALIGN_DTW, ALIGN_EDIT = 0, 1
+ALIGN_EUCLID, ALIGN_SQEUCLID = 0, 1
+ALIGN_MAX_D, ALIGN_MAX_LEN = 256, 1 << 20
+
+
+class AlignSeq(C.Structure):
+    """aew_align_seq_t: one sequence inside a side's buffer - element (i, k) is feat[base + i * frame_stride + k * chan_stride].
+    ALIGN_SEQ_DTYPE is the same record for numpy."""
+    _fields_ = [("base", i64), ("frame_stride", i64), ("chan_stride", i64), ("len", i32), ("pad_", i32)]
+
+
+ALIGN_SEQ_DTYPE = [("base", "<i8"), ("frame_stride", "<i8"), ("chan_stride", "<i8"), ("len", "<i4"), ("pad_", "<i4")]
+
+
+class AlignPair(C.Structure):
+    """aew_align_pair_t: which A-side and B-side sequences a pair compares, where its n * m back-pointer bytes and its
+    n + m - 1 path entries start.  ALIGN_PAIR_DTYPE is the same record for numpy."""
+    _fields_ = [("a", i32), ("b", i32), ("back_base", i64), ("path_base", i64)]
+
+
+ALIGN_PAIR_DTYPE = [("a", "<i4"), ("b", "<i4"), ("back_base", "<i8"), ("path_base", "<i8")]
+
+
+class SeqAlign(C.Structure):
+    """aew_seq_align_t: DTW (cost, steps, optional back-pointers and path) or the edit distance of n_pairs pairs of
+    sequences, one wavefront per pair; the tables as device and host copies."""
+    _fields_ = [("mode", i32), ("metric", i32), ("D", i32), ("n_pairs", i32), ("seq_a", vp), ("seq_a_host", vp),
+                ("seq_b", vp), ("seq_b_host", vp), ("pairs", vp), ("pairs_host", vp), ("n_a", i32), ("n_b", i32),
+                ("feat_a", vp), ("feat_b", vp), ("n_feat_a", i64), ("n_feat_b", i64), ("cost", vp), ("steps", vp), ("bad", vp),
+                ("ws", vp), ("ws_bytes", i64), ("back", vp), ("n_back", i64), ("path", vp), ("n_path", i64)]
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -461,7 +493,8 @@ class _OpU(C.Union):
                 ("ratio", UpdateRatio), ("swap", Swap), ("vqr", VqRestart), ("eva", EvalAcc), ("wgat", WindowGather),
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
                 ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
-                ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce)]
+                ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce),
+                ("align", SeqAlign)]
 
 
 class Op(C.Structure):
@@ -478,7 +511,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
             OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
             OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst",
-            OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred"}
+            OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred", OP_SEQ_ALIGN: "align"}
 
 
 
@@ -620,7 +653,7 @@ def load():
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
                        (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec), (42, ScoreRow), (43, WavTile),
-                       (44, NllStitch), (45, ScoreReduce)):
+                       (44, NllStitch), (45, ScoreReduce), (47, AlignSeq), (48, AlignPair), (49, SeqAlign)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

@@ -1,0 +1,311 @@
+"""Comparing utterances on the device: dynamic time warping over sequences of feature frames and the edit distance of
+code strings, thousands of independent pairs per launch (AEW_OP_SEQ_ALIGN, csrc/aew_align.hip; include/aewavenet.h
+states the rule bit for bit).
+
+    al = dtw(a, b)                          # a, b: Ragged views or lists of (n_u, D) fp32 device tensors; pair u = (a[u], b[u])
+    al.cost, al.steps, al.mean              # device tensors (P,): summed local distance, path length, cost / steps
+    al = dtw(a, pairs=[(0, 1), (0, 2)], return_path=True);  al.path(0)      # (steps, 2) int32 cells - the ONE call that waits
+    ed = edit_distance(codes_a, codes_b, collapse=True);    ed.distance, ed.rate
+    err = abx(d_ax, d_bx)                   # ABX error of paired distances, a device scalar
+
+`model.code_distance()` and `model.cepstral_distance()` (surface.py) are these calls over the codebook rows of code
+sequences and over the model's own MFCC front-end.  Everything runs as one-op plans on torch's current stream; nothing
+but `Alignment.path()` (and `edit_distance(collapse=True)`, which has to learn the number of units) synchronises with
+the host.  There is no CPU path: a tensor that is not on the GPU is refused.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+METRICS = {"euclid": L.ALIGN_EUCLID, "sqeuclid": L.ALIGN_SQEUCLID}
+STRIP = 64                                   # A frames a wave holds at a time: longer A sides carry a boundary row in the workspace
+
+
+class Ragged:
+    """Sequences inside ONE device buffer, read in place: element (i, k) of sequence u is
+    flat[base[u] + i * frame_stride[u] + k * chan_stride[u]], i < length[u], k < D.  frame_stride / chan_stride: one int
+    for all sequences or one per sequence.  Frame-major (n, D) rows are (frame_stride, chan_stride) = (D, 1); the
+    channel-major (channels, frames) arrays of `DeviceMfcc.ragged` are (1, frames) - with `base` moved by c0 * frames
+    and a smaller D the view takes channels c0 .. c0 + D - 1 only."""
+
+    def __init__(self, flat: torch.Tensor, base: Sequence[int], length: Sequence[int], frame_stride, chan_stride, D: int):
+        U = len(base)
+        one = lambda v: [int(v)] * U if np.isscalar(v) else [int(x) for x in v]
+        self.flat, self.D = flat, int(D)
+        self.base, self.length = [int(x) for x in base], [int(x) for x in length]
+        self.frame_stride, self.chan_stride = one(frame_stride), one(chan_stride)
+        if not torch.is_tensor(flat) or flat.dim() != 1 or not flat.is_contiguous():
+            raise L.AewError("Ragged: a flat contiguous tensor expected")
+        if not (len(self.length) == len(self.frame_stride) == len(self.chan_stride) == U):
+            raise L.AewError("Ragged: base, length and the strides must have one entry per sequence")
+        n = flat.numel()
+        for u in range(U):
+            ln, fs, cs, b = self.length[u], self.frame_stride[u], self.chan_stride[u], self.base[u]
+            if ln < 0 or ln > L.ALIGN_MAX_LEN or fs < 0 or cs < 0:
+                raise L.AewError(f"Ragged: sequence {u}: length in [0, {L.ALIGN_MAX_LEN}] and strides >= 0 expected")
+            if ln and (b < 0 or b + (ln - 1) * fs + (self.D - 1) * cs >= n):
+                raise L.AewError(f"Ragged: sequence {u} reaches outside its buffer of {n} elements")
+
+    def __len__(self) -> int:
+        return len(self.base)
+
+    def table(self) -> np.ndarray:
+        """The aew_align_seq_t records."""
+        t = np.zeros(len(self), dtype=L.ALIGN_SEQ_DTYPE)
+        t["base"], t["len"] = self.base, self.length
+        t["frame_stride"], t["chan_stride"] = self.frame_stride, self.chan_stride
+        return t
+
+
+def _ragged(x, what: str, dtype) -> Ragged:
+    """A Ragged as it is; a list of (n_u, D) tensors (dtype fp32) or 1-D tensors (int64) concatenated once."""
+    if isinstance(x, Ragged):
+        if x.flat.dtype != dtype:
+            raise L.AewError(f"{what}: a {dtype} buffer expected, got {x.flat.dtype}")
+        return x
+    rows = list(x)
+    want = 2 if dtype == torch.float32 else 1
+    for r in rows:
+        if not torch.is_tensor(r) or r.dim() != want or r.dtype != dtype:
+            raise L.AewError(f"{what}: a Ragged or a list of {'(n, D) float32' if want == 2 else '1-D int64'} tensors expected")
+    if not rows:
+        raise L.AewError(f"{what}: at least one sequence expected")
+    if len({r.device for r in rows}) != 1:
+        raise L.AewError(f"{what}: the sequences lie on different devices")
+    D = int(rows[0].shape[1]) if want == 2 else 1
+    if want == 2 and any(int(r.shape[1]) != D for r in rows):
+        raise L.AewError(f"{what}: every sequence must have the same number of channels")
+    lens = [int(r.shape[0]) for r in rows]
+    base = [0]
+    for ln in lens:
+        base.append(base[-1] + ln * D)
+    flat = torch.cat([r.reshape(-1) for r in rows])
+    return Ragged(flat, base[:-1], lens, D, 1, D)
+
+
+def default_pairs(n_a: int, n_b: Optional[int], pairs) -> np.ndarray:
+    """(P, 2) int64: `pairs` as given, else (u, u) for every u - zip(a, b), which needs as many b as a."""
+    if pairs is None:
+        if n_b is not None and n_b != n_a:
+            raise L.AewError(f"without pairs= the two sides are zipped: {n_a} and {n_b} sequences do not match")
+        u = np.arange(n_a, dtype=np.int64)
+        return np.stack([u, u], 1)
+    pr = np.asarray(pairs.cpu() if torch.is_tensor(pairs) else pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2 or pr.shape[0] < 1 or not np.issubdtype(pr.dtype, np.integer):
+        raise L.AewError("pairs: a (P, 2) integer array with P >= 1 expected")
+    pr = pr.astype(np.int64)
+    nb = n_a if n_b is None else n_b
+    if (pr < 0).any() or (pr[:, 0] >= n_a).any() or (pr[:, 1] >= nb).any():
+        raise L.AewError(f"pairs: an index outside the {n_a} / {nb} sequences")
+    return pr
+
+
+def pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, max_back_bytes: Optional[int]):
+    """(records, chunks, n_back, n_path, wstride).  records: aew_align_pair_t with path_base = the prefix sum of
+    n + m - 1 over ALL pairs and back_base = the prefix sum of n * m inside the pair's chunk; chunks: [(lo, hi)] runs of
+    consecutive pairs whose back matrices fit max_back_bytes together (one run with max_back_bytes None; a pair larger
+    than the limit gets a run of its own); n_back: bytes the largest chunk needs; n_path: path entries of all pairs;
+    wstride: per chunk, the longest B side among its pairs of more than STRIP A frames (the workspace is
+    8 * pairs * wstride bytes).  A pair with an empty side owns neither back bytes nor path entries."""
+    P = len(pairs)
+    la, lb = np.asarray(lens_a, np.int64)[pairs[:, 0]], np.asarray(lens_b, np.int64)[pairs[:, 1]]
+    live = (la > 0) & (lb > 0)
+    cells, cap = np.where(live, la * lb, 0), np.where(live, la + lb - 1, 0)
+    t = np.zeros(P, dtype=L.ALIGN_PAIR_DTYPE)
+    t["a"], t["b"] = pairs[:, 0], pairs[:, 1]
+    t["path_base"] = np.concatenate([[0], np.cumsum(cap)[:-1]])
+    chunks, lo, held = [], 0, 0
+    for p in range(P):
+        if max_back_bytes is not None and p > lo and held + int(cells[p]) > int(max_back_bytes):
+            chunks.append((lo, p))
+            lo, held = p, 0
+        t["back_base"][p] = held
+        held += int(cells[p])
+    chunks.append((lo, P))
+    n_back = max(int(cells[a:b].sum()) for a, b in chunks)
+    wstride = [int(np.where(la[a:b] > STRIP, lb[a:b], 0).max()) for a, b in chunks]
+    return t, chunks, n_back, int(cap.sum()), wstride
+
+
+class _Launches:
+    """The op records of one call and everything they point to."""
+
+    def __init__(self, mode: int, metric: int, ra: Ragged, rb: Ragged, pairs: np.ndarray, want_path: bool,
+                 max_back_bytes: Optional[int]):
+        dev = ra.flat.device
+        if rb.flat.device != dev:
+            raise L.AewError(f"the two sides lie on different devices ('{dev}' and '{rb.flat.device}')")
+        if ra.D != rb.D:
+            raise L.AewError(f"the two sides have {ra.D} and {rb.D} channels")
+        if not 1 <= ra.D <= L.ALIGN_MAX_D:
+            raise L.AewError(f"D must lie in [1, {L.ALIGN_MAX_D}], got {ra.D}")
+        if dev.type != "cuda":
+            raise L.AewError(f"the alignment runs on the GPU only (tensor on '{dev}'); there is no CPU path")
+        self.dev, self.P, self.want_path = dev, len(pairs), want_path
+        ta, tb = ra.table(), rb.table()
+        tp, self.chunks, n_back, self.n_path, wstride = pair_table(ra.length, rb.length, pairs,
+                                                                   max_back_bytes if want_path else None)
+        self.host = (ta, tb, tp)                                     # the launcher reads these at every launch
+        up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)
+        self.tables = (up(ta), up(tb), up(tp))                       # uploaded once per call
+        P = self.P
+        self.cost = torch.empty(P, dtype=torch.float32, device=dev)
+        self.steps = torch.empty(P, dtype=torch.int32, device=dev)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws_elems = max(2 * (b - a) * w for (a, b), w in zip(self.chunks, wstride))
+        self.ws = torch.empty(ws_elems, dtype=torch.float32, device=dev) if ws_elems else None
+        self.back = torch.empty(max(n_back, 1), dtype=torch.uint8, device=dev) if want_path else None
+        self.path = torch.empty(max(self.n_path, 1), 2, dtype=torch.int32, device=dev) if want_path else None
+        self.path_base = tp["path_base"].copy()
+        self.keep = (ra.flat, rb.flat)
+        psz = C.sizeof(L.AlignPair)
+        self.recs: List[L.SeqAlign] = []
+        for lo, hi in self.chunks:
+            r = L.SeqAlign()
+            r.mode, r.metric, r.D, r.n_pairs = mode, metric, ra.D, hi - lo
+            r.seq_a, r.seq_a_host, r.n_a = self.tables[0].data_ptr(), ta.ctypes.data, len(ta)
+            r.seq_b, r.seq_b_host, r.n_b = self.tables[1].data_ptr(), tb.ctypes.data, len(tb)
+            r.pairs, r.pairs_host = self.tables[2].data_ptr() + lo * psz, tp.ctypes.data + lo * psz
+            r.feat_a, r.n_feat_a = (ra.flat.data_ptr() if ra.flat.numel() else None), ra.flat.numel()
+            r.feat_b, r.n_feat_b = (rb.flat.data_ptr() if rb.flat.numel() else None), rb.flat.numel()
+            r.cost, r.steps, r.bad = self.cost.data_ptr() + 4 * lo, self.steps.data_ptr() + 4 * lo, self.bad.data_ptr()
+            if self.ws is not None:
+                r.ws, r.ws_bytes = self.ws.data_ptr(), 4 * self.ws.numel()
+            if want_path:
+                r.back, r.n_back = self.back.data_ptr(), self.back.numel()
+                r.path, r.n_path = self.path.data_ptr(), self.path.shape[0]
+            self.recs.append(r)
+
+    def run(self, what: str):
+        fail = C.c_int(-1)
+        ops = (L.Op * len(self.recs))()
+        for op, r in zip(ops, self.recs):
+            op.kind, op.u.align = L.OP_SEQ_ALIGN, r
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream(self.dev).cuda_stream
+            L.check(L.load().aew_run_plan(C.cast(ops, C.c_void_p), len(self.recs), C.c_void_p(st), C.byref(fail)), what,
+                    fail.value if fail.value >= 0 else None)
+        return self
+
+
+class Alignment:
+    """What dtw() returns.  cost (P,) fp32: the local distances summed along the best path (+inf for a pair with an empty
+    side, NaN for one with a non-finite local distance); steps (P,) int32: the cells on that path (0 for those pairs);
+    mean = cost / steps; bad: int32 (1,), a uint32 count of the pairs that were not finite.  All on the device; reading
+    them is the caller's synchronisation."""
+
+    def __init__(self, run: _Launches):
+        self.cost, self.steps, self.bad = run.cost, run.steps, run.bad
+        self.mean = run.cost / run.steps
+        self._run = run
+
+    def __len__(self) -> int:
+        return self._run.P
+
+    def path(self, p: int) -> torch.Tensor:
+        """The warping path of pair p: (steps, 2) int32 cells (i, j) from (0, 0) to (n - 1, m - 1), on the device.  This
+        call - and no other here - waits for the device: it reads steps[p] to cut the pair's fixed-size path region."""
+        if not self._run.want_path:
+            raise L.AewError("path(): the alignment was computed without return_path=True")
+        p = range(len(self))[p]
+        n = int(self.steps[p].item())
+        lo = int(self._run.path_base[p])
+        return self._run.path[lo:lo + n]
+
+
+def dtw(a, b=None, pairs=None, metric: str = "euclid", return_path: bool = False, max_back_bytes: int = 1 << 30) -> Alignment:
+    """Dynamic time warping of pairs of sequences of D-channel fp32 frames (D <= 256).  a, b: `Ragged` views or lists of
+    (n_u, D) float32 device tensors (concatenated once); b=None compares `a` with itself.  pairs: (P, 2) integers, pair p
+    = (a[pairs[p, 0]], b[pairs[p, 1]]), default zip(a, b).  metric "euclid" or "sqeuclid": the local distance.  The step
+    pattern is the symmetric one - diagonal, up, left, each of weight 1, ties in that order - with no band.
+    return_path=True keeps one back-pointer byte per cell; when those of all pairs exceed max_back_bytes the pairs run in
+    several launches that share one buffer of bounded size (the tables are uploaded once).  -> `Alignment`."""
+    if metric not in METRICS:
+        raise L.AewError(f"dtw(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    ra = _ragged(a, "dtw(): a", torch.float32)
+    rb = ra if b is None else _ragged(b, "dtw(): b", torch.float32)
+    pr = default_pairs(len(ra), None if b is None else len(rb), pairs)
+    return Alignment(_Launches(L.ALIGN_DTW, METRICS[metric], ra, rb, pr, bool(return_path), int(max_back_bytes)).run("dtw()"))
+
+
+class EditDistances:
+    """What edit_distance() returns: distance (P,) int32 and rate (P,) fp32 = distance / max(len_a, len_b) (0 where both
+    are empty) on the device; len_a / len_b (P,) the compared lengths (host)."""
+
+    def __init__(self, distance, rate, len_a, len_b):
+        self.distance, self.rate, self.len_a, self.len_b = distance, rate, len_a, len_b
+
+    def __len__(self) -> int:
+        return int(self.distance.numel())
+
+
+def _symbol_rows(x, what: str) -> list:
+    from . import codes as CD
+    rows = [x.row(u) for u in range(len(x))] if isinstance(x, CD.UtteranceCodes) else list(x)
+    for r in rows:
+        if not torch.is_tensor(r) or r.dim() != 1 or r.dtype != torch.int64:
+            raise L.AewError(f"{what}: an UtteranceCodes or a list of 1-D int64 tensors expected")
+    if not rows:
+        raise L.AewError(f"{what}: at least one sequence expected")
+    if len({r.device for r in rows}) != 1:
+        raise L.AewError(f"{what}: the sequences lie on different devices")
+    if rows[0].device.type != "cuda":
+        raise L.AewError(f"{what}: the alignment runs on the GPU only (tensor on '{rows[0].device}'); there is no CPU path")
+    return rows
+
+
+def _units(rows: list) -> Ragged:
+    """The run-length units of every row (codes.code_runs) as one Ragged; one read of the run counts."""
+    from . import codes as CD
+    dev = rows[0].device
+    parts, counts = [], []
+    for r in rows:
+        if r.numel():
+            units, _, n_runs = CD.code_runs(r)
+            parts.append(units)
+            counts.append(n_runs.reshape(1))
+        else:
+            counts.append(torch.zeros(1, dtype=torch.int32, device=dev))
+    lens = torch.cat(counts).cpu().tolist()
+    base = [0]
+    for r in rows:
+        base.append(base[-1] + int(r.numel()))
+    flat = torch.cat(parts) if parts else torch.zeros(1, dtype=torch.int64, device=dev)
+    return Ragged(flat, base[:-1], lens, 1, 1, 1)
+
+
+def edit_distance(a, b=None, pairs=None, collapse: bool = False) -> EditDistances:
+    """Unit-cost Levenshtein distance between code strings.  a, b: `codes.UtteranceCodes` or lists of 1-D int64 device
+    tensors; b=None compares `a` with itself; pairs as in dtw().  The symbols are compared, never used as an index.
+    collapse=True compares the run-length units of every string (codes.code_runs: frames -> units) instead of its
+    frames - that reads the unit counts back once.  -> `EditDistances`."""
+    rows_a = _symbol_rows(a, "edit_distance(): a")
+    rows_b = None if b is None else _symbol_rows(b, "edit_distance(): b")
+    pr = default_pairs(len(rows_a), None if rows_b is None else len(rows_b), pairs)
+    if collapse:
+        ra = _units(rows_a)
+        rb = ra if rows_b is None else _units(rows_b)
+    else:
+        ra = _ragged(rows_a, "edit_distance(): a", torch.int64)
+        rb = ra if rows_b is None else _ragged(rows_b, "edit_distance(): b", torch.int64)
+    run = _Launches(L.ALIGN_EDIT, 0, ra, rb, pr, False, None).run("edit_distance()")
+    la, lb = np.asarray(ra.length, np.int64)[pr[:, 0]], np.asarray(rb.length, np.int64)[pr[:, 1]]
+    longest = np.maximum(la, lb)
+    denom = torch.from_numpy(np.maximum(longest, 1).astype(np.float32)).to(run.dev)       # (both empty: 0 / 1)
+    return EditDistances(run.steps, run.steps.to(torch.float32) / denom, la, lb)
+
+
+def abx(d_ax: torch.Tensor, d_bx: torch.Tensor) -> torch.Tensor:
+    """The ABX error of paired distances: X belongs with A, so a triple is wrong when d(A, X) > d(B, X) and counts one
+    half when the two are equal - the fraction with d_ax >= d_bx, ties halved, as a device scalar."""
+    if d_ax.shape != d_bx.shape or d_ax.dim() != 1 or d_ax.numel() < 1:
+        raise L.AewError(f"abx(): two (P,) tensors expected, got {tuple(d_ax.shape)} and {tuple(d_bx.shape)}")
+    if d_ax.device != d_bx.device:
+        raise L.AewError("abx(): the two tensors lie on different devices")
+    return ((d_ax > d_bx).to(torch.float32) + 0.5 * (d_ax == d_bx).to(torch.float32)).mean()

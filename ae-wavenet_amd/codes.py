@@ -557,3 +557,12 @@ def mu_encode(x: torch.Tensor, n_quant: int = 256) -> torch.Tensor:
     y = torch.sign(x) * torch.log1p(mu * x.abs()) / math.log1p(mu)
     return torch.floor((y + 1.0) * (0.5 * mu) + 0.5).to(torch.int64).clamp_(0, n_quant - 1)
 
+
+def mu_decode(x: torch.Tensor, n_quant: int = 256) -> torch.Tensor:
+    """mu-law values in [0, n_quant) (any integer or float dtype) -> float32 amplitudes in [-1, 1], the inverse of
+    mu_encode: with mu = n_quant - 1 and y = 2 x / mu - 1, sign(y) ((1 + mu)^|y| - 1) / mu.  mu_encode(mu_decode(v)) = v
+    for every value v."""
+    mu = float(n_quant - 1)
+    y = x.to(torch.float32) * (2.0 / mu) - 1.0
+    return torch.sign(y) * torch.expm1(y.abs() * math.log1p(mu)) / mu
+

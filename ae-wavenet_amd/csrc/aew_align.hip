@@ -1,0 +1,339 @@
+// aew_align.hip — AEW_OP_SEQ_ALIGN: batched dynamic time warping over fp32 frames and the Levenshtein distance of int64
+// symbol strings, one WAVEFRONT per pair (aewavenet.h states the rule and the records' checks).
+//
+// Shape.  A wave walks its pair in strips of 64 A frames: lane r owns row i0 + r.  Inside a strip it sweeps the
+// anti-diagonals along j - at step t lane r is at column j = t - r - so that C / S of the upper and the diagonal neighbour
+// are the values the lane below held one and two steps ago (one DPP move per value, the diagonal is the previous
+// step's upper value kept in a register) and the left neighbour is the lane's own last value.  The strip's bottom row goes
+// to the workspace and comes back as the next strip's top row, 64 columns per load, handed to lane 0 by a uniform-index
+// lane read.  DTW alternates two phases per 64 columns: (A) the local distances of the 64 columns for all 64 rows - lane l
+// loads B frame j0 + l into registers, column jj's frame reaches the wave by lane reads at the uniform index jj, the lane's
+// A row sits in registers for D <= 64, so the column loop touches no memory - into a per-lane ring of 128 columns in LDS
+// (ring[column & 127][lane]: a lane reads back only what it wrote itself, bank = lane, no conflict); (B) the 64 sweep
+// steps that have all their columns by then.  EDIT needs no ring: the B symbols travel up the lanes, one lane per step.
+//
+// Nothing here waits on another wave: no __syncthreads (the waves of a block share nothing), no flag, no atomic but the
+// count of pairs that are not finite.  The path kernel is a second launch behind the first on the same stream.
+// Part of the library's one translation unit (aewavenet.hip includes it behind aew_score.hip).
+#pragma once
+#include "aew_common.h"
+#include <math.h>
+
+#define AEW_ALIGN_WAVES 2          // waves (pairs) per workgroup of the DTW kernel: 2 x 32 KiB of ring = 64 KiB of LDS
+#define AEW_ALIGN_EDIT_WAVES 4     // the EDIT kernel holds no LDS
+#define AEW_ALIGN_RING 128         // columns of local distances a lane keeps: the 64 being swept + the 64 being filled
+
+// ---- the records' checks, ONE definition for the launcher (host copies) and the kernels (device copies) ---------------
+// 1 if every element (i < len, k < D) of the sequence lies inside [0, n_elems)
+__host__ __device__ __forceinline__ int align_seq_ok(const aew_align_seq_t& s, int D, int64_t n_elems) {
+    if (s.len < 0 || s.len > AEW_ALIGN_MAX_LEN) return 0;
+    if (s.len == 0) return 1;
+    const int64_t lim = (int64_t)1 << 40;
+    if (s.base < 0 || s.base >= n_elems || s.frame_stride < 0 || s.frame_stride > lim || s.chan_stride < 0 || s.chan_stride > lim)
+        return 0;
+    const int64_t last = s.base + (int64_t)(s.len - 1) * s.frame_stride + (int64_t)(D - 1) * s.chan_stride;   // < 2^50 + 2^60 + 2^48
+    return last < n_elems;
+}
+__host__ __device__ __forceinline__ int align_pair_ok(const aew_align_pair_t& p, int n_a, int n_b) {
+    return p.a >= 0 && p.a < n_a && p.b >= 0 && p.b < n_b;
+}
+// 1 if the pair's n * m back bytes and - where a path is kept - its n + m - 1 path entries lie inside their buffers
+__host__ __device__ __forceinline__ int align_room_ok(const aew_align_pair_t& p, int n, int m, int64_t n_back, bool path, int64_t n_path) {
+    if (n == 0 || m == 0) return 1;
+    const int64_t cells = (int64_t)n * m, cap = (int64_t)n + m - 1;
+    if (p.back_base < 0 || cells > n_back || p.back_base > n_back - cells) return 0;
+    if (path && (p.path_base < 0 || cap > n_path || p.path_base > n_path - cap)) return 0;
+    return 1;
+}
+
+// what a wave needs of its pair, read and checked from the device copies; ok = 0: the pair is left alone
+struct align_pair_view {
+    aew_align_pair_t pr;
+    aew_align_seq_t sa, sb;
+    int ok;
+};
+__device__ __forceinline__ align_pair_view align_load_pair(const aew_seq_align_t& p, int pi, int64_t wstride) {
+    align_pair_view v;
+    v.ok = 0;
+    v.pr = p.pairs[pi];
+    if (!align_pair_ok(v.pr, p.n_a, p.n_b)) return v;
+    v.sa = p.seq_a[v.pr.a];
+    v.sb = p.seq_b[v.pr.b];
+    if (!align_seq_ok(v.sa, p.D, p.n_feat_a) || !align_seq_ok(v.sb, p.D, p.n_feat_b)) return v;
+    if (p.back && !align_room_ok(v.pr, v.sa.len, v.sb.len, p.n_back, p.path != nullptr, p.n_path)) return v;
+    if (v.sa.len > 64 && v.sb.len > 0 && (!p.ws || v.sb.len > wstride)) return v;   // (the tables changed under a captured graph)
+    v.ok = 1;
+    return v;
+}
+
+// ---- moving a value between the lanes of the wave without the LDS crossbar -----------------------------------------------
+// the value lane l - 1 holds (lane 0: 0): one DPP move, wave_shr:1
+__device__ __forceinline__ int align_up1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ float align_up1(float v) { return __builtin_bit_cast(float, align_up1(__builtin_bit_cast(int, v))); }
+__device__ __forceinline__ int64_t align_up1(int64_t v) {
+    const uint32_t lo = (uint32_t)align_up1((int)(uint32_t)v), hi = (uint32_t)align_up1((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// the value lane l holds, l wave-uniform: v_readlane_b32
+__device__ __forceinline__ int align_lane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float align_lane(float v, int l) { return __builtin_bit_cast(float, align_lane(__builtin_bit_cast(int, v), l)); }
+__device__ __forceinline__ int64_t align_lane(int64_t v, int l) {
+    const uint32_t lo = (uint32_t)align_lane((int)(uint32_t)v, l), hi = (uint32_t)align_lane((int)(uint32_t)((uint64_t)v >> 32), l);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// ---- DTW ---------------------------------------------------------------------------------------------------------------
+// DR > 0: D <= DR, the lane's A row in DR registers (zeros behind D: t = 0 - 0, acc + 0 * 0 = acc, the same bits).
+// DR == 0: any D, the A row is read again for every column.
+template <int DR>
+__global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_align_dtw(const aew_seq_align_t p, const int64_t wstride) {
+    __shared__ float ring_all[AEW_ALIGN_WAVES][AEW_ALIGN_RING * 64];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * AEW_ALIGN_WAVES + w;
+    if (pi >= p.n_pairs) return;                                                 // wave-uniform, like every return below
+    const align_pair_view v = align_load_pair(p, pi, wstride);
+    if (!v.ok) return;
+    const int n = v.sa.len, m = v.sb.len, D = p.D;
+    if (n == 0 || m == 0) {
+        if (lane == 0) { p.cost[pi] = INFINITY; p.steps[pi] = 0; }
+        return;
+    }
+    float* ring = ring_all[w];
+    const float* A = (const float*)p.feat_a + v.sa.base;
+    const float* B = (const float*)p.feat_b + v.sb.base;
+    const int64_t afs = v.sa.frame_stride, acs = v.sa.chan_stride, bfs = v.sb.frame_stride, bcs = v.sb.chan_stride;
+    float* wsC = (float*)p.ws + (int64_t)pi * wstride;                           // (formed, not followed, where ws is NULL)
+    int* wsS = (int*)p.ws + ((int64_t)p.n_pairs + pi) * wstride;
+    uint8_t* back = p.back ? p.back + v.pr.back_base : nullptr;
+    const bool sq = p.metric == AEW_ALIGN_SQEUCLID;
+    const int nchunk = (m + 63 + 63) >> 6;                                       // sweep steps t = 0 .. m + 62
+    bool bad = false;
+    float cL = 0.f;
+    int sL = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool row_on = i < n;
+        const float* arow = A + (int64_t)(row_on ? i : n - 1) * afs;             // (idle lanes repeat the last row: reads stay inside)
+        float a[DR > 0 ? DR : 1];
+        if (DR > 0) {
+#pragma unroll
+            for (int k = 0; k < DR; ++k) a[k] = k < D ? arow[k * acs] : 0.f;
+        }
+        const bool keep_bottom = i0 + 64 < n;                                    // a strip follows: its top row is this one's bottom
+        float upPrevC = 0.f, topC = 0.f;
+        int upPrevS = 0, topS = 0;
+        cL = 0.f; sL = 0;
+        for (int c = 0; c < nchunk; ++c) {
+            const int j0 = c << 6;
+            // (A) local distances of the columns [j0, j0 + 64) that exist
+            const int jn = m - j0 < 64 ? m - j0 : 64;
+            if (DR > 0 && jn > 0) {
+                // lane l fetches frame j0 + l (the last frame again behind m); column jj's frame is then lane jj's registers,
+                // handed to the whole wave by a uniform-index lane read: no memory access inside the column loop
+                float b[DR > 0 ? DR : 1];
+                const float* bl = B + (int64_t)(j0 + lane < m ? j0 + lane : m - 1) * bfs;
+#pragma unroll
+                for (int k = 0; k < DR; ++k) b[k] = k < D ? bl[k * bcs] : 0.f;
+                for (int jj = 0; jj < jn; ++jj) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int k = 0; k < DR; ++k) {
+                        const float t = a[k] - align_lane(b[k], jj);
+                        acc = acc + t * t;
+                    }
+                    const float d = sq ? acc : sqrtf(acc);                       // sqrtf is IEEE-rounded here
+                    bad |= row_on && !isfinite(d);
+                    ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
+                }
+            }
+            for (int jj = 0; DR == 0 && jj < jn; ++jj) {
+                const float* brow = B + (int64_t)(j0 + jj) * bfs;
+                float acc = 0.f;
+                for (int k = 0; k < D; ++k) {
+                    const float t = arow[k * acs] - brow[k * bcs];
+                    acc = acc + t * t;
+                }
+                const float d = sq ? acc : sqrtf(acc);
+                bad |= row_on && !isfinite(d);
+                ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
+            }
+            // the top row's columns [j0, j0 + 64): lane l holds column j0 + l
+            if (i0 > 0 && j0 + lane < m) { topC = wsC[j0 + lane]; topS = wsS[j0 + lane]; }
+            // (B) sweep steps t = j0 .. j0 + 63
+            float dnext = ring[((j0 - lane) & (AEW_ALIGN_RING - 1)) * 64 + lane];
+            for (int tt = 0; tt < 64; ++tt) {
+                const int j = j0 + tt - lane;
+                float upC = align_up1(cL);
+                int upS = align_up1(sL);
+                const float tC = align_lane(topC, tt);
+                const int tS = align_lane(topS, tt);
+                if (lane == 0) { upC = tC; upS = tS; }
+                const float d = dnext;
+                dnext = ring[((j + 1) & (AEW_ALIGN_RING - 1)) * 64 + lane];      // (the next step's, fetched under this one)
+                // selects, not branches: the lanes of a step differ in which predecessors exist
+                const bool on = row_on && j >= 0 && j < m;
+                const bool has_up = i > 0, has_left = j > 0;
+                const bool take_up = has_up && (!has_left || upC < upPrevC);     // (i-1, j) beats (i-1, j-1), or that one is missing
+                const float b1 = take_up ? upC : upPrevC;
+                const int s1 = take_up ? upS : upPrevS;
+                const bool take_left = has_left && (!has_up || cL < b1);         // (i, j-1) beats the better of the two
+                const float b2 = take_left ? cL : b1;
+                const int s2 = take_left ? sL : s1;
+                const bool origin = !has_up && !has_left;
+                const float C = origin ? d : d + b2;
+                const int S = origin ? 1 : s2 + 1;
+                const int which = take_left ? 2 : (take_up ? 1 : 0);
+                if (on) {
+                    if (back) back[(int64_t)i * m + j] = (uint8_t)which;
+                    if (keep_bottom && lane == 63) { wsC[j] = C; wsS[j] = S; }
+                }
+                upPrevC = on ? upC : upPrevC; upPrevS = on ? upS : upPrevS;
+                cL = on ? C : cL; sL = on ? S : sL;
+            }
+        }
+        __threadfence();                                                         // the bottom row's stores, before the next strip loads them
+    }
+    const float outC = __shfl(cL, (n - 1) & 63, 64);
+    const int outS = __shfl(sL, (n - 1) & 63, 64);
+    const bool any_bad = __any(bad ? 1 : 0) != 0;
+    if (lane == 0) {
+        p.cost[pi] = any_bad ? NAN : outC;
+        p.steps[pi] = any_bad ? 0 : outS;
+        if (any_bad) atomicAdd(p.bad, 1u);
+    }
+}
+
+// one wave per pair: lane 0 walks the back-pointers from (n-1, m-1), all lanes fill what is left of the capacity
+__global__ __launch_bounds__(64) void k_align_path(const aew_seq_align_t p, const int64_t wstride) {
+    const int pi = blockIdx.x, lane = threadIdx.x;
+    const align_pair_view v = align_load_pair(p, pi, wstride);
+    if (!v.ok) return;
+    const int n = v.sa.len, m = v.sb.len;
+    if (n == 0 || m == 0) return;
+    const int cap = n + m - 1;
+    int st = p.steps[pi];
+    if (st < 0 || st > cap) st = 0;
+    int32_t* out = p.path + 2 * v.pr.path_base;
+    for (int e = st + lane; e < cap; e += 64) { out[2 * e] = -1; out[2 * e + 1] = -1; }
+    if (lane != 0) return;
+    const uint8_t* back = p.back + v.pr.back_base;
+    int i = n - 1, j = m - 1;
+    for (int e = st - 1; e >= 0; --e) {
+        out[2 * e] = i; out[2 * e + 1] = j;
+        const int which = back[(int64_t)i * m + j];
+        if (which != 2) --i;
+        if (which != 1) --j;
+        if (i < 0) i = 0;                                                        // (bytes that are no path: stay inside the matrix)
+        if (j < 0) j = 0;
+    }
+}
+
+// ---- EDIT --------------------------------------------------------------------------------------------------------------
+// The same sweep over the integer recurrence with its virtual borders E(-1, j) = j + 1, E(i, -1) = i + 1, E(-1, -1) = 0.
+// Lane 0 takes symbol b[t] at step t, every other lane the symbol the lane below held a step earlier.
+__global__ __launch_bounds__(64 * AEW_ALIGN_EDIT_WAVES) void k_align_edit(const aew_seq_align_t p, const int64_t wstride) {
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * AEW_ALIGN_EDIT_WAVES + w;
+    if (pi >= p.n_pairs) return;
+    const align_pair_view v = align_load_pair(p, pi, wstride);
+    if (!v.ok) return;
+    const int n = v.sa.len, m = v.sb.len;
+    if (n == 0 || m == 0) {
+        if (lane == 0) { p.cost[pi] = (float)(n + m); p.steps[pi] = n + m; }
+        return;
+    }
+    const int64_t* A = (const int64_t*)p.feat_a + v.sa.base;
+    const int64_t* B = (const int64_t*)p.feat_b + v.sb.base;
+    const int64_t afs = v.sa.frame_stride, bfs = v.sb.frame_stride;
+    int* wsE = (int*)p.ws + (int64_t)pi * wstride;
+    const int nchunk = (m + 63 + 63) >> 6;
+    int left = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool row_on = i < n;
+        const int64_t asym = A[(int64_t)(row_on ? i : n - 1) * afs];
+        const bool keep_bottom = i0 + 64 < n;
+        int diag = i;                                                            // E(i-1, -1)
+        left = i + 1;                                                            // E(i, -1)
+        int topE = 0;
+        int64_t bsym = 0, bnext = 0;
+        for (int c = 0; c < nchunk; ++c) {
+            const int j0 = c << 6, jt = j0 + lane;
+            bnext = jt < m ? B[(int64_t)jt * bfs] : 0;
+            topE = i0 > 0 ? (jt < m ? wsE[jt] : 0) : jt + 1;
+            for (int tt = 0; tt < 64; ++tt) {
+                const int j = j0 + tt - lane;
+                int up = align_up1(left);
+                int64_t bs = align_up1(bsym);
+                const int tE = align_lane(topE, tt);
+                const int64_t tb = align_lane(bnext, tt);
+                if (lane == 0) { up = tE; bs = tb; }
+                bsym = bs;
+                if (row_on && j >= 0 && j < m) {
+                    int e = diag + (asym != bsym ? 1 : 0);
+                    e = up + 1 < e ? up + 1 : e;
+                    e = left + 1 < e ? left + 1 : e;
+                    if (keep_bottom && lane == 63) wsE[j] = e;
+                    diag = up;
+                    left = e;
+                }
+            }
+        }
+        __threadfence();
+    }
+    const int outE = __shfl(left, (n - 1) & 63, 64);
+    if (lane == 0) { p.cost[pi] = (float)outE; p.steps[pi] = outE; }
+}
+
+// ---- the launcher ------------------------------------------------------------------------------------------------------
+static int launch_seq_align(const aew_seq_align_t& p, hipStream_t st) {
+    const bool edit = p.mode == AEW_ALIGN_EDIT;
+    if (p.mode != AEW_ALIGN_DTW && !edit) return AEW_E_ARG;
+    if (!edit && p.metric != AEW_ALIGN_EUCLID && p.metric != AEW_ALIGN_SQEUCLID) return AEW_E_ARG;
+    if (p.D < 1 || p.D > AEW_ALIGN_MAX_D || (edit && p.D != 1)) return AEW_E_ARG;
+    if (p.n_pairs < 1 || p.n_pairs > (1 << 24) || p.n_a < 1 || p.n_b < 1) return AEW_E_ARG;
+    if (!p.seq_a || !p.seq_a_host || !p.seq_b || !p.seq_b_host || !p.pairs || !p.pairs_host || !p.cost || !p.steps || !p.bad)
+        return AEW_E_ARG;
+    const int64_t fmax = (int64_t)1 << 50;
+    if (p.n_feat_a < 0 || p.n_feat_a > fmax || p.n_feat_b < 0 || p.n_feat_b > fmax) return AEW_E_ARG;
+    if ((p.n_feat_a > 0 && !p.feat_a) || (p.n_feat_b > 0 && !p.feat_b)) return AEW_E_ARG;
+    if ((p.path && !p.back) || (edit && (p.back || p.path))) return AEW_E_ARG;
+    if ((p.back && p.n_back < 0) || (p.path && p.n_path < 0) || p.ws_bytes < 0) return AEW_E_ARG;
+    if (((uintptr_t)p.seq_a | (uintptr_t)p.seq_a_host | (uintptr_t)p.seq_b | (uintptr_t)p.seq_b_host | (uintptr_t)p.pairs |
+         (uintptr_t)p.pairs_host) & 7) return AEW_E_ALIGN;
+    if (((uintptr_t)p.feat_a | (uintptr_t)p.feat_b) & (edit ? 7 : 3)) return AEW_E_ALIGN;
+    if (((uintptr_t)p.cost | (uintptr_t)p.steps | (uintptr_t)p.bad | (uintptr_t)p.ws | (uintptr_t)p.path) & 3) return AEW_E_ALIGN;
+    for (int i = 0; i < p.n_a; ++i)
+        if (!align_seq_ok(p.seq_a_host[i], p.D, p.n_feat_a)) return AEW_E_ARG;
+    for (int i = 0; i < p.n_b; ++i)
+        if (!align_seq_ok(p.seq_b_host[i], p.D, p.n_feat_b)) return AEW_E_ARG;
+    int64_t wstride = 0;                                                         // longest B side among the pairs that need boundary rows
+    for (int i = 0; i < p.n_pairs; ++i) {
+        const aew_align_pair_t& pr = p.pairs_host[i];
+        if (!align_pair_ok(pr, p.n_a, p.n_b)) return AEW_E_ARG;
+        const int n = p.seq_a_host[pr.a].len, m = p.seq_b_host[pr.b].len;
+        if (p.back && !align_room_ok(pr, n, m, p.n_back, p.path != nullptr, p.n_path)) return AEW_E_ARG;
+        if (n > 64 && m > wstride) wstride = m;
+    }
+    if (wstride > 0 && (!p.ws || p.ws_bytes / 8 / p.n_pairs < wstride)) return AEW_E_ARG;
+    if (edit) {
+        const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_EDIT_WAVES - 1) / AEW_ALIGN_EDIT_WAVES);
+        hipLaunchKernelGGL(k_align_edit, dim3(g), dim3(64 * AEW_ALIGN_EDIT_WAVES), 0, st, p, wstride);
+        return (int)hipGetLastError();
+    }
+    const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_WAVES - 1) / AEW_ALIGN_WAVES);
+    const dim3 blk(64 * AEW_ALIGN_WAVES);
+    if (p.D <= 4) hipLaunchKernelGGL(k_align_dtw<4>, dim3(g), blk, 0, st, p, wstride);
+    else if (p.D <= 8) hipLaunchKernelGGL(k_align_dtw<8>, dim3(g), blk, 0, st, p, wstride);
+    else if (p.D <= 12) hipLaunchKernelGGL(k_align_dtw<12>, dim3(g), blk, 0, st, p, wstride);
+    else if (p.D <= 16) hipLaunchKernelGGL(k_align_dtw<16>, dim3(g), blk, 0, st, p, wstride);
+    else if (p.D <= 32) hipLaunchKernelGGL(k_align_dtw<32>, dim3(g), blk, 0, st, p, wstride);
+    else if (p.D <= 64) hipLaunchKernelGGL(k_align_dtw<64>, dim3(g), blk, 0, st, p, wstride);
+    else hipLaunchKernelGGL(k_align_dtw<0>, dim3(g), blk, 0, st, p, wstride);
+    int rc = (int)hipGetLastError();
+    if (rc || !p.path) return rc;
+    hipLaunchKernelGGL(k_align_path, dim3((unsigned)p.n_pairs), dim3(64), 0, st, p, wstride);
+    return (int)hipGetLastError();
+}

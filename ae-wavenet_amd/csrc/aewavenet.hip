@@ -12,6 +12,7 @@
 #include "aew_utterance.hip"
 #include "aew_cond_utterance.hip"
 #include "aew_score.hip"
+#include "aew_align.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -79,6 +80,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_WAV_TILE: return launch_wav_tile(op.u.wtile, st);
         case AEW_OP_NLL_STITCH: return launch_nll_stitch(op.u.nllst, st);
         case AEW_OP_SCORE_REDUCE: return launch_score_reduce(op.u.sred, st);
+        case AEW_OP_SEQ_ALIGN: return launch_seq_align(op.u.align, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -130,6 +132,9 @@ extern "C" int aew_sizeof(int which) {
         case 43: return (int)sizeof(aew_wav_tile_t);
         case 44: return (int)sizeof(aew_nll_stitch_t);
         case 45: return (int)sizeof(aew_score_reduce_t);
+        case 47: return (int)sizeof(aew_align_seq_t);      // (46 is left unused like 24, 26, 33 and 40)
+        case 48: return (int)sizeof(aew_align_pair_t);
+        case 49: return (int)sizeof(aew_seq_align_t);
         default: return -1;
     }
 }

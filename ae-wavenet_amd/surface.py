@@ -1293,6 +1293,79 @@ class HipModelBase(nn.Module):
         return CD.UtteranceScores(nll, torch.from_numpy(plan.offsets.copy()), out, acc, sg.o + sg.rf + 1, prob=prob, hit=hit,
                                   voice=torch.tensor(voices, dtype=torch.int64))
 
+    # ---- comparing utterances: DTW over codebook rows and over the front-end's cepstra (align.py) ---------------------
+    def code_distance(self, codes_a, codes_b=None, pairs=None, metric: str = "euclid", return_path: bool = False):
+        """Dynamic time warping between code sequences, over their codebook rows: codes_a / codes_b a
+        `codes.UtteranceCodes` or a list of 1-D int64 device tensors (codes_b=None: codes_a with itself), pairs (P, 2)
+        indices into the two (default: zip) -> `align.Alignment` with device tensors cost, steps and mean = cost / steps,
+        the distance inside ABX discrimination.  The rows of all sequences are looked up once (codes.lookup) into one
+        ragged buffer that the alignment reads in place; metric / return_path as in align.dtw().  A code outside [0, K)
+        raises AewError with the count before the alignment (the lookup never follows it; that check reads one word
+        back).  VQ bottlenecks only.  The codebook is read, nothing of the model is written: no EMA statistic, histogram,
+        loss or metric word; no collective under data parallel."""
+        from . import align as AL, codes as CD
+        what = "code_distance()"
+        self._need_codes(what)
+        if self._device.type != "cuda":
+            raise L.AewError(f"{what} runs on an MI355X only; move the model to a cuda device first")
+        rows_a = AL._symbol_rows(codes_a, f"{what}: codes_a")
+        rows_b = None if codes_b is None else AL._symbol_rows(codes_b, f"{what}: codes_b")
+        pr = AL.default_pairs(len(rows_a), None if rows_b is None else len(rows_b), pairs)
+        with torch.no_grad():
+            eng = self._engine if self._engine is not None else self._ensure_engine(int(self.hps.n_batch))
+            self._dp_finish()
+            emb = eng.emb.reshape(eng.K, -1)
+            d = int(emb.shape[1])
+            bad = torch.zeros(1, dtype=torch.int32, device=emb.device)
+            sides = []
+            for rows in (rows_a,) if rows_b is None else (rows_a, rows_b):
+                lens = [int(r.numel()) for r in rows]
+                base = [0]
+                for n in lens:
+                    base.append(base[-1] + n * d)
+                zq = CD.lookup(emb, torch.cat([r.to(emb.device) for r in rows]), bad=bad)
+                sides.append(AL.Ragged(zq.reshape(-1), base[:-1], lens, d, 1, d))
+            n_bad = int(bad[0].item()) & 0xFFFFFFFF
+            if n_bad:
+                raise L.AewError(f"{what}: {n_bad} codes lie outside the codebook [0, {eng.K}); nothing was aligned")
+            return AL.dtw(sides[0], None if rows_b is None else sides[1], pairs=pr, metric=metric, return_path=return_path)
+
+    def cepstral_distance(self, wavs_a, wavs_b=None, pairs=None, expand: bool = True):
+        """The mean DTW-aligned Euclidean distance between the cepstra of waveforms: wavs_a / wavs_b lists of 1-D device
+        tensors of mu-law values, whole utterances of any lengths (wavs_b=None: wavs_a with itself), pairs as in
+        align.dtw() -> `align.Alignment`; its `mean` is the distance, `cost` / `steps` what it is the quotient of.  The
+        frames are the STATIC coefficients 1 .. n_mfcc - 1 of this model's own front-end (`DeviceMfcc.ragged`, one record
+        per whole utterance): the energy coefficient 0 and the deltas are left out, and the channel-major arrays are
+        read in place (chan_stride = frames).  expand=True turns the mu-law values into linear amplitudes first
+        (codes.mu_decode) - the sound itself; expand=False feeds the mu-law values as the training front-end does.
+        THE SCALE IS THIS FRONT-END'S - MFCC of dB power, orthonormal DCT - so the numbers are comparable between runs
+        of this project and NOT with published mel-cepstral-distortion figures.  An utterance too short for
+        `DeviceMfcc.MIN_FRAMES` frames has none: its pairs give inf.  VQ bottlenecks only (the rule of the utterance
+        interface); nothing of the model is written and no collective is issued."""
+        from . import align as AL, codes as CD
+        what = "cepstral_distance()"
+        self._need_codes(what)
+        if self._device.type != "cuda":
+            raise L.AewError(f"{what} runs on an MI355X only; move the model to a cuda device first")
+        mf = self._utterance_mfcc()
+        n_mfcc = int(mf.n_mfcc)
+        if n_mfcc < 2:
+            raise L.AewError(f"{what}: the front-end yields {n_mfcc} coefficient(s); none is left behind the energy term")
+        sides = []
+        with torch.no_grad():
+            for wavs in (wavs_a,) if wavs_b is None else (wavs_a, wavs_b):
+                wavs = list(wavs)
+                for w in wavs:
+                    if not torch.is_tensor(w) or w.dim() != 1:
+                        raise L.AewError(f"{what}: lists of 1-D tensors of mu-law values expected")
+                if expand:
+                    wavs = [CD.mu_decode(w.to(self._device), int(self.n_quant)) for w in wavs]
+                else:
+                    wavs = [w.to(self._device) for w in wavs]
+                flat, frames, bases = mf.ragged(wavs)
+                sides.append(AL.Ragged(flat, [b + f for b, f in zip(bases, frames)], frames, 1, frames, n_mfcc - 1))
+            return AL.dtw(sides[0], None if wavs_b is None else sides[1], pairs=pairs, metric="euclid")
+
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared
         (FusedAdam.zero_grad(), or every .grad is None as zero_grad(set_to_none=True) leaves them), else a copy of the

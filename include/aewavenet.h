@@ -49,7 +49,8 @@ extern "C" {
  * without them).  Every later addition follows the same rule and is listed at aew_sizeof below (the last: 37 .. 39,
  * aew_cond_row_t, aew_code_tile_t / AEW_OP_CODE_TILE, aew_cond_stitch_t / AEW_OP_COND_STITCH; 41, aew_draw_t, with the
  * `draw` pointer appended to aew_sampler_t - index 40 stays unused, it answers -1; 42 .. 45, aew_score_row_t,
- * aew_wav_tile_t / AEW_OP_WAV_TILE, aew_nll_stitch_t / AEW_OP_NLL_STITCH, aew_score_reduce_t / AEW_OP_SCORE_REDUCE). */
+ * aew_wav_tile_t / AEW_OP_WAV_TILE, aew_nll_stitch_t / AEW_OP_NLL_STITCH, aew_score_reduce_t / AEW_OP_SCORE_REDUCE;
+ * 47 .. 49, aew_align_seq_t, aew_align_pair_t, aew_seq_align_t / AEW_OP_SEQ_ALIGN - index 46 stays unused). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -1076,6 +1077,92 @@ typedef struct {
     int32_t U, pad_;
 } aew_score_reduce_t;
 
+/* Comparing utterances (appended to ABI 28; AEW_OP_SEQ_ALIGN, aew_sizeof 47 / 48 / 49): dynamic time warping over two
+ * sequences of D-channel fp32 frames, or the Levenshtein distance of two strings of int64 symbols, for n_pairs
+ * independent pairs in one launch.  One wavefront owns a pair from start to end; nothing in the op waits on another
+ * wavefront - no flag, no spin, no barrier.
+ *
+ * THE RULE (tests/seq_align_emulator.py restates it).  fp32 throughout, every operation rounded on its own (no fused
+ * multiply-add).  With n = len(a), m = len(b):
+ *   local distance   acc = 0; for k = 0 .. D-1: t = a[i][k] - b[j][k]; acc = acc + t * t.
+ *                    d(i, j) = acc (SQEUCLID) or the correctly rounded square root of acc (EUCLID).
+ *   DTW              C(0,0) = d(0,0), S(0,0) = 1; otherwise C(i,j) = d(i,j) + C(pred), S(i,j) = S(pred) + 1 with pred the
+ *                    EXISTING predecessor of least C among (i-1,j-1), (i-1,j), (i,j-1) - ties go to the first in that
+ *                    order (strict < while scanning in that order).  cost = C(n-1,m-1), steps = S(n-1,m-1).
+ *                    An empty side: cost = +inf, steps = 0, no feature memory is read.  A pair in which any d(i,j) is not
+ *                    finite: cost = NaN, steps = 0, and *bad is raised by one (uint32, integer atomicAdd).
+ *   EDIT             unit-cost Levenshtein distance of the symbols (compared as 64-bit integers, never used as an index;
+ *                    D must be 1, chan_stride is not read).  An empty side: the other side's length.  steps = the distance,
+ *                    cost = the same number as a float.
+ *   path (DTW, when back and path are given)  back[back_base + i * m + j] = 0, 1 or 2: the predecessor of cell (i, j) in
+ *                    the order above (0 for cell (0,0), which has none).  A second kernel of the SAME op launch, ordered
+ *                    behind the first by the stream alone, walks back from (n-1, m-1) and writes the `steps` cells (i, j)
+ *                    from start to end as int32 pairs at path[2 * (path_base + e)], e < steps; the entries
+ *                    steps <= e < n + m - 1 are (-1, -1).  A pair with steps = 0 (not finite) has all n + m - 1 entries
+ *                    (-1, -1) and its back bytes are unspecified; a pair with an empty side owns neither back nor path
+ *                    elements.
+ * Element (i, k) of a sequence is feat[base + i * frame_stride + k * chan_stride]: frame-major embeddings (frame_stride
+ * = D, chan_stride = 1) and channel-major (channels, frames) arrays (frame_stride = 1, chan_stride = frames) are read in
+ * place.
+ * Every D in [1, AEW_ALIGN_MAX_D] gives these bits; D <= 64 holds the A row of a lane in registers.
+ *
+ * Tables: the A-side and B-side sequence tables and the pair table each come as a device copy and a host copy with the
+ * same records (the convention of aew_wav_tile_t).  The launcher checks every record of the host copies against the
+ * buffer sizes before anything is launched; the kernels repeat the checks on the device copies and leave a pair whose
+ * records fail them alone (nothing of it is written): no address is formed from an unchecked record.
+ * AEW_E_ARG: mode / metric outside their values, D outside [1, AEW_ALIGN_MAX_D] (EDIT: D != 1), n_pairs < 1 or > 2^24,
+ * n_a / n_b < 1, a NULL table, cost, steps or bad, a NULL feature buffer of n_feat > 0, n_feat outside [0, 2^50], a
+ * sequence with len outside [0, AEW_ALIGN_MAX_LEN], a negative stride or one above 2^40, base outside [0, n_feat) or an
+ * element (len-1, D-1) at or behind n_feat; a pair with a / b outside its table; `path` without `back` or either in EDIT
+ * mode; with back: back_base < 0 or back_base + n * m > n_back, path (where given) path_base < 0 or path_base + n + m - 1
+ * > n_path; a pair of more than 64 A frames without a workspace of the size stated at `ws`.  AEW_E_ALIGN: a table off 8
+ * bytes, int64 symbols off 8, any other pointer off 4.  A refused call launches and writes nothing. */
+#define AEW_ALIGN_DTW 0
+#define AEW_ALIGN_EDIT 1
+#define AEW_ALIGN_EUCLID 0
+#define AEW_ALIGN_SQEUCLID 1
+#define AEW_ALIGN_MAX_D 256
+#define AEW_ALIGN_MAX_LEN (1 << 20)
+typedef struct {
+    int64_t base;                /* element of the side's buffer that holds (frame 0, channel 0)                */
+    int64_t frame_stride;        /* elements between frames                                                     */
+    int64_t chan_stride;         /* elements between channels                                                   */
+    int32_t len;                 /* frames (symbols); 0 is allowed                                              */
+    int32_t pad_;
+} aew_align_seq_t;
+
+typedef struct {
+    int32_t a, b;                /* indices into the A-side / B-side sequence tables                            */
+    int64_t back_base;           /* first byte of the pair's n * m back-pointers in `back`                      */
+    int64_t path_base;           /* first (i, j) entry of the pair's n + m - 1 in `path` (int32 element 2 * path_base) */
+} aew_align_pair_t;
+
+typedef struct {
+    int32_t mode, metric;        /* AEW_ALIGN_DTW / _EDIT; AEW_ALIGN_EUCLID / _SQEUCLID (DTW)  */
+    int32_t D, n_pairs;
+    const aew_align_seq_t* seq_a;       /* device memory, n_a records                         */
+    const aew_align_seq_t* seq_a_host;  /* the same records in host memory                    */
+    const aew_align_seq_t* seq_b;
+    const aew_align_seq_t* seq_b_host;
+    const aew_align_pair_t* pairs;      /* device memory, n_pairs records                     */
+    const aew_align_pair_t* pairs_host;
+    int32_t n_a, n_b;
+    const void* feat_a;          /* fp32 (DTW) or int64 (EDIT), n_feat_a elements              */
+    const void* feat_b;
+    int64_t n_feat_a, n_feat_b;
+    float* cost;                 /* [n_pairs]                                                  */
+    int32_t* steps;              /* [n_pairs]                                                  */
+    uint32_t* bad;               /* one device word, added to                                  */
+    void* ws;                    /* boundary rows of pairs with more than 64 A frames (optional): ws_bytes >= 8 * n_pairs *
+                                    the longest B side among those pairs (the launcher takes that length from the host
+                                    tables).  Contents are scratch.                                                        */
+    int64_t ws_bytes;
+    uint8_t* back;               /* n_back bytes (optional, DTW)                               */
+    int64_t n_back;
+    int32_t* path;               /* n_path (i, j) entries = 2 * n_path int32 (optional, needs back) */
+    int64_t n_path;
+} aew_seq_align_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1397,7 +1484,7 @@ enum {
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
     AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH,
-    AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE
+    AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE, AEW_OP_SEQ_ALIGN
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1428,14 +1515,14 @@ typedef struct {
         aew_code_lookup_t clk; aew_code_runs_t crun; aew_adam_grouped_t adamg;
         aew_eval_groups_t evg; aew_mel_tile_t mtile; aew_code_stitch_t cstitch;
         aew_code_tile_t ctile; aew_cond_stitch_t cndst;
-        aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred;
+        aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred; aew_seq_align_t align;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce (24, 26, 33 and 40 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align (24, 26, 33, 40 and 46 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
