@@ -25,7 +25,8 @@ EF_OUT2_COPY = 1 << 10
  OP_REDUCE, OP_ADAM, OP_ZERO, OP_VAE, OP_AE_NORM, OP_JITTER, OP_VQ_DIAG, OP_MFCC, OP_MOMENTS, OP_GEMM_TN_GROUP,
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
- OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE, OP_SEQ_ALIGN) = range(1, 47)
+ OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE, OP_SEQ_ALIGN,
+ OP_FRAME_STITCH, OP_CODE_SEGMENT) = range(1, 49)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -352,6 +353,34 @@ class SeqAlign(C.Structure):
                 ("ws", vp), ("ws_bytes", i64), ("back", vp), ("n_back", i64), ("path", vp), ("n_path", i64)]
 
 
+SEG_MAX_K, SEG_MAX_D = 4096, 4096
+
+
+class SegUtt(C.Structure):
+    """aew_seg_utt_t: one utterance of a segmentation - its rows in the ragged frame buffer (and in codes / dist), the
+    first 64-bit word of its n_frames * (ceil(K / 64) + 1) in the workspace's back region, its switch penalty.
+    SEG_UTT_DTYPE is the same record for numpy."""
+    _fields_ = [("first_frame", i64), ("back_base", i64), ("n_frames", i32), ("lam", f32)]
+
+
+SEG_UTT_DTYPE = [("first_frame", "<i8"), ("back_base", "<i8"), ("n_frames", "<i4"), ("lam", "<f4")]
+
+
+class FrameStitch(C.Structure):
+    """aew_frame_stitch_t: the first n_valid encoder-output rows of each batch row to their place in the ragged frame
+    buffer (the aew_utt_row_t table of the code stitch)."""
+    _fields_ = [("table", vp), ("table_host", vp), ("first_row", i32), ("B", i32), ("lin", vp), ("lin_bs", i64),
+                ("frames", vp), ("n_dst", i64), ("E", i32), ("d_pitch", i32)]
+
+
+class CodeSegment(C.Structure):
+    """aew_code_segment_t: penalised Viterbi decoding of U utterances' frames over the K codebook entries - codes, their
+    distances, the total cost and the segment count of each; the table as device and host copies."""
+    _fields_ = [("frames", vp), ("n_elems", i64), ("emb", vp), ("K", i32), ("d", i32), ("d_pitch", i32), ("metric", i32),
+                ("table", vp), ("table_host", vp), ("U", i32), ("pad_", i32), ("codes", vp), ("dist", vp), ("n_out", i64),
+                ("cost", vp), ("n_seg", vp), ("n_bad", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 VQ_RESTART_MAX = 1024
 
 
@@ -494,7 +523,7 @@ class _OpU(C.Union):
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
                 ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
                 ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce),
-                ("align", SeqAlign)]
+                ("align", SeqAlign), ("fstitch", FrameStitch), ("cseg", CodeSegment)]
 
 
 class Op(C.Structure):
@@ -511,7 +540,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_WINDOW_GATHER: "wgat", OP_GRAD_WELFORD: "gwel", OP_SEG_SELECT: "ssel", OP_ACCUM: "accum",
             OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
             OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst",
-            OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred", OP_SEQ_ALIGN: "align"}
+            OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred", OP_SEQ_ALIGN: "align",
+            OP_FRAME_STITCH: "fstitch", OP_CODE_SEGMENT: "cseg"}
 
 
 
@@ -643,6 +673,8 @@ def load():
                                       C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.aew_utterance_locate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.aew_segment_ws_bytes.argtypes = [C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+    lib.aew_segment_host.argtypes = [C.c_void_p]
     lib.aew_seg_select_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.aew_select_key.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
     lib.aew_uw_chunks.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64,
@@ -653,7 +685,8 @@ def load():
                        (21, WindowGather), (22, GradWelford), (23, SegSelect), (25, Accum), (27, CodeLookup), (28, CodeRuns),
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
                        (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec), (42, ScoreRow), (43, WavTile),
-                       (44, NllStitch), (45, ScoreReduce), (47, AlignSeq), (48, AlignPair), (49, SeqAlign)):
+                       (44, NllStitch), (45, ScoreReduce), (47, AlignSeq), (48, AlignPair), (49, SeqAlign),
+                       (51, SegUtt), (52, FrameStitch), (53, CodeSegment)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
@@ -707,4 +740,5 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_sampler_run", "aew_set_fn", "aew_nt_kernel", "aew_set_tn_big", "aew_set_nt_window", "aew_set_fn_ring3", "aew_set_nt_small_n64", "aew_tn_group_check", "aew_set_nt_mem128", "aew_set_nt_deep", "aew_tuning_default", "aew_tuning_get",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
            "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles",
-           "aew_corpus_locate", "aew_seg_select_size", "aew_select_key", "aew_utterance_locate")
+           "aew_corpus_locate", "aew_seg_select_size", "aew_select_key", "aew_utterance_locate",
+           "aew_segment_ws_bytes", "aew_segment_host")

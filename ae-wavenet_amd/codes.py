@@ -13,6 +13,9 @@ of an utterance) and never synchronise with the host.  `model.encode()` / `model
 `convert_utterances()` consume them again at the utterance's length, from the work list `cond_tile_plan()` and the stream
 assignment `stream_groups()` (csrc/aew_cond_utterance.hip); `model.score_utterances()` scores a waveform under them with
 the teacher-forced decoder, from the work list `score_tile_plan()`, and returns an `UtteranceScores` (csrc/aew_score.hip).
+`segment()` chooses the code sequence of whole utterances jointly - penalised Viterbi decoding over the codebook, from the
+work list `segment_plan()` (csrc/aew_segment.hip); `model.segment_utterances()` / `segment_wavs()` / `segment_corpus()` are
+that call behind the encoder and return an `UtteranceCodes` with a `Segmentation` record.
 """
 from __future__ import annotations
 
@@ -253,6 +256,137 @@ class UtteranceCodes:
             return cls(put("codes"), torch.from_numpy(z["offsets"]), dist=put("dist") if "dist" in z else None,
                        voice=put("voice") if "voice" in z else None,
                        names=[str(n) for n in z["names"]] if "names" in z else None)
+
+
+# ---- segmenting utterances: the code sequence chosen jointly (csrc/aew_segment.hip) ------------------------------------------
+VQ_METRICS = {"scaled_l2": 0, "sq_l2": 1}                  # aew_vq_nearest_t.metric
+VQ_METRIC_NAMES = {v: k for k, v in VQ_METRICS.items()}
+
+
+@dataclass
+class SegmentPlan:
+    """segment_plan()'s result: the aew_seg_utt_t records (lam left 0 for the caller) of utterances that lie one behind
+    the other in the frame buffer, the row offsets and the bytes of workspace one launch over all of them needs."""
+    K: int
+    offsets: np.ndarray         # int64 [U + 1]: utterance u owns rows (and codes) [offsets[u], offsets[u + 1])
+    table: np.ndarray           # _lib.SEG_UTT_DTYPE [U]
+    ws_bytes: int
+
+    @property
+    def n_frames(self) -> int:
+        return int(self.offsets[-1])
+
+
+def segment_ws_bytes(n_frames: int, K: int) -> int:
+    """Bytes of workspace of one AEW_OP_CODE_SEGMENT over n_frames rows: the fp32 local costs, n_frames * K * 4 rounded up
+    to 8, then per row ceil(K / 64) + 1 words of back-pointers (aew_segment_ws_bytes states the same)."""
+    n, K = int(n_frames), int(K)
+    if n < 0 or not 1 <= K <= L.SEG_MAX_K:
+        raise ValueError(f"segment_ws_bytes(): n_frames >= 0 and K in [1, {L.SEG_MAX_K}] expected")
+    return (n * K * 4 + 7) // 8 * 8 + 8 * n * ((K + 63) // 64 + 1)
+
+
+def segment_plan(frames_per_utterance: Sequence[int], K: int) -> SegmentPlan:
+    """The work list of a segmentation, a pure function of the frame counts (it never reads the device): utterance u owns
+    the rows [offsets[u], offsets[u + 1]) and the ceil(K / 64) + 1 back words of each of them, in the same order."""
+    n = np.asarray(list(frames_per_utterance), np.int64).reshape(-1)
+    if (n < 0).any() or (n >= 1 << 31).any():
+        raise ValueError("segment_plan(): frame counts in [0, 2^31) expected")
+    offsets = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    ws = segment_ws_bytes(int(offsets[-1]), K)
+    t = np.zeros(len(n), dtype=L.SEG_UTT_DTYPE)
+    t["first_frame"], t["n_frames"] = offsets[:-1], n
+    t["back_base"] = offsets[:-1] * ((int(K) + 63) // 64 + 1)
+    return SegmentPlan(int(K), offsets, t, ws)
+
+
+@dataclass
+class Segmentation:
+    """What goes with the codes of a segmentation, all on the device: cost (U,) fp32 - the minimum of the objective,
+    n_segments (U,) int32 - 1 + the code changes (0 for an empty utterance), penalty (U,) fp32, n_bad int32 (1,) - a
+    uint32 count of the utterances whose cost is not finite.  Reading them is the caller's synchronisation."""
+    cost: torch.Tensor
+    n_segments: torch.Tensor
+    penalty: torch.Tensor
+    n_bad: torch.Tensor
+
+
+def _penalties(penalty, U: int, what: str) -> np.ndarray:
+    lam = np.asarray(penalty.cpu() if torch.is_tensor(penalty) else penalty, np.float64).reshape(-1)
+    if lam.size == 1:
+        lam = np.repeat(lam, U)
+    if lam.size != U:
+        raise L.AewError(f"{what}: penalty must be one number or one per utterance ({U}), got {lam.size}")
+    if U and not (lam >= 0).all():                                           # (a NaN fails the comparison)
+        raise L.AewError(f"{what}: penalty must be >= 0 (inf is allowed)")
+    with np.errstate(over="ignore"):
+        return lam.astype(np.float32)
+
+
+def segment(frames: torch.Tensor, offsets, emb: torch.Tensor, penalty, metric: str = "scaled_l2",
+            return_dist: bool = False):
+    """Penalised Viterbi decoding of codes on the device (AEW_OP_CODE_SEGMENT; include/aewavenet.h states the rule bit for
+    bit): for each utterance the labelling that minimises  sum_t dist(frame t, emb[codes[t]]) + penalty * (code changes).
+    frames: fp32 (n, d_pitch) device tensor, contiguous - the utterances' encoder outputs one behind the other, the first
+    d channels of a row are read (d = emb.shape[1]; d_pitch >= d); offsets: (U + 1,) host integers from 0 to n; emb fp32
+    (K, d), K <= 4096; penalty: one float or one per utterance, >= 0, inf allowed; metric "scaled_l2" or "sq_l2" as in
+    the nearest-code search.  penalty 0 gives that search's codes and distances bit for bit; inf gives one code per
+    utterance.  -> (codes int64 (n,), cost fp32 (U,), n_seg int32 (U,)), with return_dist=True (codes, dist, cost, n_seg).
+    The workspace holds n * K * 4 bytes of local costs.  One launch on torch's current stream, no host synchronisation;
+    `segment_full()` also returns the `Segmentation` record."""
+    codes, dist, info = segment_full(frames, offsets, emb, penalty, metric, return_dist)
+    return (codes, dist, info.cost, info.n_segments) if return_dist else (codes, info.cost, info.n_segments)
+
+
+def segment_full(frames: torch.Tensor, offsets, emb: torch.Tensor, penalty, metric: str = "scaled_l2",
+                 return_dist: bool = False):
+    """segment() -> (codes, dist or None, Segmentation)."""
+    what = "segment()"
+    if metric not in VQ_METRICS:
+        raise L.AewError(f"{what}: metric must be one of {sorted(VQ_METRICS)}, got '{metric}'")
+    if not torch.is_tensor(frames) or frames.dim() != 2 or frames.dtype != torch.float32 or not frames.is_contiguous():
+        raise L.AewError(f"{what}: frames fp32 (n, d_pitch) contiguous expected")
+    if emb.dim() != 2 or emb.dtype != torch.float32:
+        raise L.AewError(f"{what}: emb fp32 (K, d) expected")
+    dev = frames.device
+    if dev.type != "cuda" or emb.device != dev:
+        raise L.AewError(f"{what} runs on the GPU only (frames on '{dev}', emb on '{emb.device}'); there is no CPU path")
+    K, d = emb.shape
+    n, d_pitch = frames.shape
+    if not 1 <= K <= L.SEG_MAX_K or not 1 <= d <= d_pitch:
+        raise L.AewError(f"{what}: K in [1, {L.SEG_MAX_K}] and 1 <= d <= d_pitch expected, got K = {K}, d = {d}, d_pitch = {d_pitch}")
+    off = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets, np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise L.AewError(f"{what}: offsets (U + 1,) ascending from 0 to {n} expected")
+    U = off.size - 1
+    plan = segment_plan(np.diff(off), K)
+    plan.table["lam"] = _penalties(penalty, U, what)
+    emb = emb.contiguous()
+    codes = torch.empty(n, dtype=torch.int64, device=dev)
+    dist = torch.empty(n, dtype=torch.float32, device=dev) if return_dist else None
+    cost = torch.empty(U, dtype=torch.float32, device=dev)
+    n_seg = torch.empty(U, dtype=torch.int32, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    lam_host = torch.empty(U, dtype=torch.float32, pin_memory=True)
+    lam_host.numpy()[:] = plan.table["lam"]
+    info = Segmentation(cost, n_seg, lam_host.to(dev, non_blocking=True), n_bad)
+    if U == 0:
+        return codes, dist, info
+    host = torch.empty(max(plan.table.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:plan.table.nbytes] = plan.table.view(np.uint8).reshape(-1)
+    table = torch.empty_like(host, device=dev)
+    table.copy_(host, non_blocking=True)
+    ws = torch.empty(max(plan.ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+    cs = L.CodeSegment()
+    cs.frames, cs.n_elems = (frames.data_ptr() if n else None), frames.numel()
+    cs.emb, cs.K, cs.d, cs.d_pitch, cs.metric = emb.data_ptr(), K, d, d_pitch, VQ_METRICS[metric]
+    cs.table, cs.table_host, cs.U = table.data_ptr(), host.data_ptr(), U
+    cs.codes, cs.dist, cs.n_out = codes.data_ptr(), (dist.data_ptr() if dist is not None else None), n
+    cs.cost, cs.n_seg, cs.n_bad = cost.data_ptr(), n_seg.data_ptr(), n_bad.data_ptr()
+    cs.ws, cs.ws_bytes = ws.data_ptr(), 8 * ws.numel()
+    _run(L.OP_CODE_SEGMENT, cs, what, dev)
+    # table, host and ws return to torch's allocators, which order their reuse behind this stream's work
+    return codes, dist, info
 
 
 # ---- whole utterances, the other way: the work list of model.utterance_conditioning() / decode_utterances() ------------

@@ -137,3 +137,39 @@ static int launch_code_stitch(const aew_code_stitch_t& p, hipStream_t st) {
     hipLaunchKernelGGL(k_code_stitch, dim3((unsigned)p.B), dim3(AEW_WAVE), 0, st, p);
     return (int)hipGetLastError();
 }
+
+// ---- AEW_OP_FRAME_STITCH
+// The encoder outputs of a batch to their place in the ragged frame buffer: the first n_valid rows (d_pitch floats each)
+// of batch row b go to the rows dst .. of `frames` - one contiguous run of n_valid * d_pitch elements on both sides.
+// VEC: 16-byte moves (d_pitch and lin_bs multiples of 4, both buffers 16-byte aligned, so every run starts on 16 bytes).
+// The same record check as AEW_OP_CODE_STITCH; a record that fails it stores nothing.
+template <bool VEC>
+__global__ __launch_bounds__(AEW_UTT_THREADS) void k_frame_stitch(const aew_frame_stitch_t p) {
+    const int b = blockIdx.y;
+    const aew_utt_row_t r = p.table[(int64_t)p.first_row + b];
+    const int32_t n = utt_stitch_n(r, p.E, p.n_dst);
+    if (n <= 0) return;
+    const int64_t total = (int64_t)n * p.d_pitch;
+    const float* src = p.lin + (int64_t)b * p.lin_bs;
+    float* dst = p.frames + r.dst * p.d_pitch;
+    const int64_t q = (int64_t)blockIdx.x * AEW_UTT_THREADS + threadIdx.x;
+    if constexpr (VEC) {
+        if (4 * q < total) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(src)[q];
+    } else {
+        if (q < total) dst[q] = src[q];
+    }
+}
+
+static int launch_frame_stitch(const aew_frame_stitch_t& p, hipStream_t st) {
+    int rc = utt_table_check(p.table, p.table_host, p.first_row, p.B);
+    if (rc) return rc;
+    if (!p.lin || !p.frames || p.E < 1 || p.d_pitch < 1 || p.n_dst < 0 || p.lin_bs < (int64_t)p.E * p.d_pitch) return AEW_E_ARG;
+    if (((uintptr_t)p.lin | (uintptr_t)p.frames) & 3) return AEW_E_ALIGN;
+    for (int b = 0; b < p.B; ++b)
+        if (utt_stitch_n(p.table_host[(int64_t)p.first_row + b], p.E, p.n_dst) < 0) return AEW_E_ARG;
+    const bool vec = !(p.d_pitch & 3) && !(p.lin_bs & 3) && !(((uintptr_t)p.lin | (uintptr_t)p.frames) & 15);
+    const int64_t per_row = (int64_t)p.E * p.d_pitch / (vec ? 4 : 1);
+    const dim3 grid((unsigned)((per_row + AEW_UTT_THREADS - 1) / AEW_UTT_THREADS), (unsigned)p.B);
+    hipLaunchKernelGGL(vec ? k_frame_stitch<true> : k_frame_stitch<false>, grid, dim3(AEW_UTT_THREADS), 0, st, p);
+    return (int)hipGetLastError();
+}

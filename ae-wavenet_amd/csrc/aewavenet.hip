@@ -13,6 +13,7 @@
 #include "aew_cond_utterance.hip"
 #include "aew_score.hip"
 #include "aew_align.hip"
+#include "aew_segment.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -81,6 +82,8 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_NLL_STITCH: return launch_nll_stitch(op.u.nllst, st);
         case AEW_OP_SCORE_REDUCE: return launch_score_reduce(op.u.sred, st);
         case AEW_OP_SEQ_ALIGN: return launch_seq_align(op.u.align, st);
+        case AEW_OP_FRAME_STITCH: return launch_frame_stitch(op.u.fstitch, st);
+        case AEW_OP_CODE_SEGMENT: return launch_code_segment(op.u.cseg, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -135,6 +138,9 @@ extern "C" int aew_sizeof(int which) {
         case 47: return (int)sizeof(aew_align_seq_t);      // (46 is left unused like 24, 26, 33 and 40)
         case 48: return (int)sizeof(aew_align_pair_t);
         case 49: return (int)sizeof(aew_seq_align_t);
+        case 51: return (int)sizeof(aew_seg_utt_t);      // (50 is left unused like 24, 26, 33, 40 and 46)
+        case 52: return (int)sizeof(aew_frame_stitch_t);
+        case 53: return (int)sizeof(aew_code_segment_t);
         default: return -1;
     }
 }

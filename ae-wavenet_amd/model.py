@@ -784,6 +784,52 @@ class TrainEngine:
         # keep no address of them
         mt.table = cs.table = mt.table_host = cs.table_host = mt.mel = cs.codes = cs.dist = None
 
+    def segment_tiles(self, mel: torch.Tensor, table, offsets, penalty, return_dist: bool = False):
+        """Whole utterances through the fixed-geometry encoder and a penalised Viterbi pass over the codebook: `mel`, `table`
+        as in encode_tiles(); `offsets` (U + 1,) host integers, the codes each utterance owns (codes.TilePlan.offsets);
+        `penalty` one float or one per utterance.  Per batch of B rows one AEW_OP_MEL_TILE fills in_mel, _cond_plan_a runs
+        unchanged and one AEW_OP_FRAME_STITCH moves the encoder outputs (bn.lin rows) whose receptive field lies inside real
+        frames to a ragged (n_codes, pitch) buffer; behind the last batch ONE AEW_OP_CODE_SEGMENT chooses the codes of all
+        utterances against the live codebook under the engine's metric (codes.segment_full).  The nearest codes of the
+        batches stay in `ind` and are not stitched: they are no output of this call.  Writes what encode_tiles() writes and
+        nothing else of the engine; no host synchronisation.  -> (codes, dist or None, codes.Segmentation)."""
+        from . import codes as CD
+        mt, _ = self.utterance_ops()
+        self._cond_plans()
+        bn, n = self.bn, len(table)
+        if n % self.B or table.dtype.itemsize != C.sizeof(L.UttRow):
+            raise L.AewError(f"segment_tiles(): a multiple of B = {self.B} aew_utt_row_t records expected, got {n}")
+        if mel.dtype != torch.float32 or not mel.is_contiguous():
+            raise L.AewError("segment_tiles(): flat fp32 mel expected")
+        offsets = np.asarray(offsets, np.int64).reshape(-1)
+        n_codes = int(offsets[-1])
+        frames = torch.empty(n_codes, bn.nlin_p, dtype=torch.float32, device=self.device)
+        if n:
+            host = torch.empty(n * table.dtype.itemsize, dtype=torch.uint8, pin_memory=True)
+            host.numpy()[:] = table.view(np.uint8).reshape(-1)
+            dev = torch.empty_like(host, device=self.device)
+            dev.copy_(host, non_blocking=True)
+            mt.table, mt.table_host = dev.data_ptr(), host.data_ptr()
+            mt.mel, mt.n_src = mel.data_ptr(), mel.numel()
+            fs = L.FrameStitch()
+            fs.table, fs.table_host, fs.B, fs.E = dev.data_ptr(), host.data_ptr(), self.B, self.geom.embed_len
+            fs.lin, fs.lin_bs, fs.d_pitch = bn.lin.ptr, bn.lin.bs, bn.nlin_p
+            fs.frames, fs.n_dst = frames.data_ptr(), n_codes
+            stitch = Plan("utt.frames")
+            stitch.add(L.OP_FRAME_STITCH, fs, "utt.frames", TAG_VQ)
+            rec = stitch.array()[0].u.fstitch
+            self.act_epoch += 1
+            st = self._stream()
+            for first in range(0, n, self.B):
+                mt.first_row = rec.first_row = first
+                self.utt_tile.run(st)
+                self._run(self._cond_plan_a, False)
+                stitch.run(st)
+            self.lin_live = True
+            mt.table = mt.table_host = mt.mel = None
+        emb = self.emb.view(bn.K, bn.d)
+        return CD.segment_full(frames, offsets, emb, penalty, CD.VQ_METRIC_NAMES[bn.metric], return_dist)
+
     DECODE_DROP = ("diagnostics (codebook)",)
 
     def decode_plan(self) -> Plan:

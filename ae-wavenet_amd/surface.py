@@ -945,6 +945,117 @@ class HipModelBase(nn.Module):
         names = [str(s[3]) for s in corpus.samples] if all(len(s) > 3 for s in corpus.samples) else None
         return CD.UtteranceCodes(codes, torch.tensor(offsets, dtype=torch.int64), dist=dist, voice=voice, names=names)
 
+    # ---- whole utterances: the code sequence chosen jointly ---------------------------------------------------------
+    def _segment_ragged(self, what, flat, frames, bases, penalty, voice, batch, return_dist, names, return_info):
+        from . import codes as CD
+        if batch is not None and int(batch) < 1:
+            raise L.AewError(f"{what}: batch must be at least 1, got {batch}")
+        B = int(batch) if batch is not None else (self._engine.B if self._engine is not None else int(self.hps.n_batch))
+        U = len(frames)
+        lam = CD._penalties(penalty, U, what)                                # (refused before anything runs)
+        if voice is not None:
+            voice = torch.as_tensor(voice, dtype=torch.int64)
+            if tuple(voice.shape) != (U,):
+                raise L.AewError(f"{what}: voice ({U},) expected (one per utterance), got {tuple(voice.shape)}")
+        with torch.no_grad():
+            eng = self._ensure_engine(B)
+            self._dp_finish()
+            if eng.bn.K > L.SEG_MAX_K:
+                raise L.AewError(f"{what}: a codebook of at most {L.SEG_MAX_K} entries expected, this one has {eng.bn.K}")
+            E, s, rf, _ = G.utterance_geometry(eng.geom)
+            plan = CD.tile_plan(frames, E, s, rf, B)
+            codes, dist, info = eng.segment_tiles(flat, plan.table(bases), plan.offsets, lam, return_dist)
+        uc = CD.UtteranceCodes(codes, torch.from_numpy(plan.offsets), dist=dist, voice=voice, names=names)
+        return (uc, info) if return_info else uc
+
+    def segment_utterances(self, mels, penalty, voice=None, batch=None, return_dist: bool = False, names=None,
+                           return_info: bool = False):
+        """encode_utterances() with the code sequence of each utterance chosen JOINTLY: the labelling that minimises
+        sum over frames of the distance to the chosen entry + penalty * (number of code changes), a Viterbi pass over the
+        codebook on the device (AEW_OP_CODE_SEGMENT; include/aewavenet.h states the rule bit for bit).  penalty: one float
+        or one per utterance, >= 0; 0 gives encode_utterances()'s codes and distances bit for bit, inf one code per
+        utterance, in between it trades bitrate against distortion.  The distance is the bottleneck's own (scaled_l2 for
+        vqvae-ema, sq_l2 for vqvae) to the live codebook, which may hold at most 4096 entries.  -> `codes.UtteranceCodes`
+        (`dist` with return_dist=True: the distance of every frame to ITS chosen entry), so units(), save(),
+        decode_utterances(), score_utterances(codes=...), align.edit_distance() and voice_information() take it as it is;
+        return_info=True: (UtteranceCodes, `codes.Segmentation`) with the cost, the segment count and the penalty of every
+        utterance and the count of utterances whose cost is not finite, on the device.  Besides the result the call holds
+        the encoder outputs of all utterances and a workspace of n_codes * K * 4 bytes of local costs (segment_corpus()
+        bounds it).  Otherwise the rules of encode_utterances(): VQ bottlenecks only; no codebook, EMA statistic,
+        histogram, loss or metric word is written; inside `FusedAdam.averaged_weights()` the averaged weights are used; no
+        host synchronisation."""
+        self._need_codes("segment_utterances()")
+        mels = list(mels)
+        n_mel = self._opts["n_mel"] or 3 * self.hps.n_mfcc
+        for m in mels:
+            if m.dim() != 2 or m.shape[0] != n_mel or m.device.type != "cuda":
+                raise L.AewError(f"segment_utterances(): ({n_mel}, frames) device tensors expected, got {tuple(m.shape)} on "
+                                 f"'{m.device}'")
+        frames = [int(m.shape[1]) for m in mels]
+        bases, at = [], 0
+        for F in frames:
+            bases.append(at)
+            at += n_mel * F
+        flat = torch.cat([m.to(torch.float32).reshape(-1) for m in mels]) if at else \
+            torch.empty(0, dtype=torch.float32, device=self._device)
+        return self._segment_ragged("segment_utterances()", flat, frames, bases, penalty, voice, batch, return_dist, names,
+                                    return_info)
+
+    def segment_wavs(self, wavs, penalty, voice=None, batch=None, return_dist: bool = False, names=None,
+                     return_info: bool = False):
+        """segment_utterances() from the waveforms: the whole-utterance MFCC of encode_wavs(), then the joint choice."""
+        self._need_codes("segment_wavs()")
+        if self._device.type != "cuda":
+            raise L.AewError("segment_wavs() runs on an MI355X only; move the model to a cuda device first")
+        flat, frames, bases = self._utterance_mfcc().ragged(wavs)
+        return self._segment_ragged("segment_wavs()", flat, frames, bases, penalty, voice, batch, return_dist, names, return_info)
+
+    def segment_corpus(self, corpus, penalty, batch=None, max_frames_per_chunk: int = 1 << 15, return_dist: bool = False,
+                       return_info: bool = False):
+        """Segment a `corpus.DeviceCorpus` as encode_corpus() tokenises it: every utterance of `corpus.samples`, in that
+        order, in chunks of at most max_frames_per_chunk mel frames (one utterance at least).  penalty: one float or one
+        per utterance.  The utterances are independent, so the chunking does not change a bit; it bounds what a chunk
+        holds besides the result - above all the local costs, codes_in_chunk * K * 4 bytes (at most
+        max_frames_per_chunk * K * 4: 512 MiB at the default and K = 4096)."""
+        from . import codes as CD
+        self._need_codes("segment_corpus()")
+        if corpus.snd is None:
+            corpus._need_device()
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[corpus.snd_bytes]
+        snd = corpus.snd[:corpus.n_snd * corpus.snd_bytes].view(dt)
+        mf = self._utterance_mfcc()
+        lam = CD._penalties(penalty, len(corpus.samples), "segment_corpus()")
+        chunks, cur, held = [], [], 0
+        for i, sam in enumerate(corpus.samples):
+            F = max(0, mf.n_frames(int(sam[2]) - int(sam[1])))
+            if cur and held + F > int(max_frames_per_chunk):
+                chunks.append(cur)
+                cur, held = [], 0
+            cur.append(i)
+            held += F
+        if cur:
+            chunks.append(cur)
+        sams = corpus.samples
+        parts = [self.segment_wavs([snd[int(sams[i][1]):int(sams[i][2])] for i in ch], lam[ch], batch=batch,
+                                   return_dist=return_dist, return_info=True) for ch in chunks]
+        dev = self._device
+        cat = lambda ts, dtype: torch.cat(ts) if ts else torch.empty(0, dtype=dtype, device=dev)
+        codes = cat([p.codes for p, _ in parts], torch.int64)
+        dist = cat([p.dist for p, _ in parts], torch.float32) if return_dist else None
+        offsets, at = [0], 0
+        for p, _ in parts:
+            offsets += [at + o for o in p._off[1:]]
+            at = offsets[-1]
+        voice = torch.tensor([int(s[0]) for s in sams], dtype=torch.int64)
+        names = [str(s[3]) for s in sams] if all(len(s) > 3 for s in sams) else None
+        uc = CD.UtteranceCodes(codes, torch.tensor(offsets, dtype=torch.int64), dist=dist, voice=voice, names=names)
+        if not return_info:
+            return uc
+        n_bad = torch.stack([i.n_bad for _, i in parts]).sum(0) if parts else torch.zeros(1, dtype=torch.int32, device=dev)
+        info = CD.Segmentation(cat([i.cost for _, i in parts], torch.float32), cat([i.n_segments for _, i in parts], torch.int32),
+                               cat([i.penalty for _, i in parts], torch.float32), n_bad.to(torch.int32))
+        return uc, info
+
     def zero_amplitude_code(self) -> int:
         """The mu-law value a sample of amplitude 0 encodes to (codes.mu_encode with this model's n_quant)."""
         from . import codes as CD

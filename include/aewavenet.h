@@ -50,7 +50,8 @@ extern "C" {
  * aew_cond_row_t, aew_code_tile_t / AEW_OP_CODE_TILE, aew_cond_stitch_t / AEW_OP_COND_STITCH; 41, aew_draw_t, with the
  * `draw` pointer appended to aew_sampler_t - index 40 stays unused, it answers -1; 42 .. 45, aew_score_row_t,
  * aew_wav_tile_t / AEW_OP_WAV_TILE, aew_nll_stitch_t / AEW_OP_NLL_STITCH, aew_score_reduce_t / AEW_OP_SCORE_REDUCE;
- * 47 .. 49, aew_align_seq_t, aew_align_pair_t, aew_seq_align_t / AEW_OP_SEQ_ALIGN - index 46 stays unused). */
+ * 47 .. 49, aew_align_seq_t, aew_align_pair_t, aew_seq_align_t / AEW_OP_SEQ_ALIGN - index 46 stays unused; 51 .. 53, aew_seg_utt_t,
+ * aew_frame_stitch_t / AEW_OP_FRAME_STITCH, aew_code_segment_t / AEW_OP_CODE_SEGMENT - index 50 stays unused). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -1163,6 +1164,113 @@ typedef struct {
     int64_t n_path;
 } aew_seq_align_t;
 
+/* Segmenting utterances (appended to ABI 28; AEW_OP_FRAME_STITCH / AEW_OP_CODE_SEGMENT, aew_sizeof 51 / 52 / 53 -
+ * index 50 stays unused, it answers -1): the
+ * code sequence of a whole utterance chosen JOINTLY - the labelling that minimises
+ *     sum over frames of the distance to the chosen entry  +  lam * (number of code changes)
+ * by a Viterbi pass over the K codebook entries with a uniform switch cost, U independent utterances in one launch.  One
+ * wavefront owns an utterance's pass from start to end; nothing in the op waits on another wavefront - no flag, no spin,
+ * no barrier.
+ *
+ * THE RULE (tests/segment_emulator.py restates it).  Inputs of one utterance: T >= 1 fp32 frames z_t of d values at pitch
+ * d_pitch, the codebook emb[K][d], the metric (0 scaled_l2, 1 sq_l2, the meanings of aew_vq_nearest_t) and lam >= 0 (+inf
+ * allowed).  fp32 throughout, every operation rounded on its own.
+ *   local cost       c(t,k) is the value AEW_OP_VQ_NEAREST compares for query z_t and entry k, the same operations in
+ *                    the same order: dd = 0, qq = 0; for j ascending: u = z_t[j] - e_k[j]; dd = fma(u, u, dd);
+ *                    qq = fma(e_k[j], e_k[j], qq).  sq_l2: c = dd.  scaled_l2: zz = 0; for j ascending:
+ *                    zz = fma(z_t[j], z_t[j], zz); c = sqrt(dd) / (sqrt(zz) + sqrt(qq)), sqrt and the division correctly
+ *                    rounded.
+ *   recurrence       r(0,k) = c(0,k); acc = 0
+ *                    for t = 1 .. T-1:
+ *                        m = +inf; a = 0; for k ascending: if r(t-1,k) < m: m = r(t-1,k); a = k
+ *                                                       (the lowest index among ties; a NaN never wins)
+ *                        A(t-1) = a; acc = acc + m
+ *                        p(k) = r(t-1,k) - m;  stay(t,k) = p(k) < lam  (false for a NaN)
+ *                        r(t,k) = c(t,k) + (stay(t,k) ? p(k) : lam)
+ *                    (m, a) of r(T-1, .) as above; cost = acc + m; k = a
+ *   walk back        for t = T-1 .. 1: codes[t] = k; if not stay(t,k): k = A(t-1).   codes[0] = k
+ *   outputs          dist[t] = c(t, codes[t]); n_seg = 1 + #{t >= 1 : codes[t] != codes[t-1]}
+ * The minimum is taken out at every step: the values stay at the scale of one frame's distances however long the
+ * utterance is, and lam = 0 gives r(t,k) = c(t,k) exactly - codes and dist are then those of AEW_OP_VQ_NEAREST bit for
+ * bit, ties included.  lam = +inf gives one code for the whole utterance.  The rule is total: an utterance whose cost
+ * is not finite (a NaN or inf frame) still gets the outputs above and raises *n_bad by one (uint32, integer atomicAdd).
+ * T = 0: cost = 0, n_seg = 0, no code is written.
+ *
+ * Utterance u is the rows [first_frame, first_frame + n_frames) of the ragged frame buffer; its codes and distances go to
+ * the same indices of the flat outputs.  With W = ceil(K / 64) it owns the 64-bit words [back_base, back_base +
+ * n_frames * (W + 1)) of the workspace's back region: per frame t the W words of stay(t, .) (bit k & 63 of word k >> 6)
+ * and one word holding A(t-1).
+ *
+ * Workspace: the bytes aew_segment_ws_bytes(n_rows, K) states, 8-byte aligned - the [n_rows][K] fp32 local costs of ALL rows of the
+ * frame buffer (n_rows * K * 4 bytes, rounded up to 8), then the back region of n_rows * (W + 1) words.  Contents are
+ * scratch.  n_rows = the rows that lie inside n_elems: 0 if n_elems < d, else (n_elems - d) / d_pitch + 1.
+ *
+ * The table comes as a device copy and a host copy with the same records.  The launcher checks every record of the host
+ * copy before anything is launched; the kernels repeat the record checks on the device copy and leave an utterance whose
+ * record fails them alone (nothing of it is written).
+ * AEW_E_ARG: a NULL emb / table / table_host / codes / cost / n_seg / n_bad / ws, NULL frames with n_elems > 0, metric
+ * outside {0, 1}, K outside [1, AEW_SEG_MAX_K], d < 1 or > AEW_SEG_MAX_D, d_pitch < d, U < 0 or > 2^24, n_elems < 0,
+ * n_out < n_rows, ws_bytes below what aew_segment_ws_bytes states; a record with n_frames < 0, lam negative or NaN, or -
+ * n_frames > 0 - rows outside [0, n_rows), a back range outside the back region, or a back range that overlaps that
+ * of another record.  AEW_E_ALIGN: table / table_host / codes / ws off 8 bytes, any other pointer off 4.  A refused
+ * call launches and writes nothing; U = 0 launches nothing. */
+#define AEW_SEG_MAX_K 4096
+#define AEW_SEG_MAX_D 4096
+typedef struct {
+    int64_t first_frame;         /* first row of the utterance in the ragged frame buffer (and in codes / dist)   */
+    int64_t back_base;           /* first 64-bit word of its n_frames * (W + 1) in the workspace's back region    */
+    int32_t n_frames;            /* T; 0 is allowed                                                               */
+    float lam;                   /* the switch penalty, >= 0, +inf allowed                                        */
+} aew_seg_utt_t;
+
+typedef struct {
+    const float* frames;         /* ragged [n_rows][d_pitch] fp32                              */
+    int64_t n_elems;             /* elements of `frames`                                       */
+    const float* emb;            /* [K][d]                                                     */
+    int32_t K, d, d_pitch;
+    int32_t metric;              /* 0 scaled_l2, 1 sq_l2                                       */
+    const aew_seg_utt_t* table;       /* device memory, U records                              */
+    const aew_seg_utt_t* table_host;  /* the same records in host memory (read by the launcher) */
+    int32_t U, pad_;
+    int64_t* codes;              /* flat output, n_out elements                                */
+    float* dist;                 /* optional flat output, n_out elements                       */
+    int64_t n_out;
+    float* cost;                 /* [U]                                                        */
+    int32_t* n_seg;              /* [U]                                                        */
+    uint32_t* n_bad;             /* one device word, added to                                  */
+    void* ws;
+    int64_t ws_bytes;
+} aew_code_segment_t;
+
+/* *bytes = the workspace an AEW_OP_CODE_SEGMENT over a frame buffer of n_rows rows needs; AEW_E_ARG for a NULL pointer,
+ * n_rows outside [0, 2^40] or K outside [1, AEW_SEG_MAX_K].  Host-only. */
+int aew_segment_ws_bytes(int64_t n_rows, int K, int64_t* bytes);
+
+/* The host twin of AEW_OP_CODE_SEGMENT: the same descriptor with every pointer in HOST memory (table is not read,
+ * table_host is), the launcher's checks and then the rule on the CPU through the one __host__ __device__ definition of
+ * the local cost, the recurrence step and the walk back that the kernels run (fmaf in place of __fmaf_rn).  The CPU
+ * tests run this very code. */
+int aew_segment_host(const aew_code_segment_t* p);
+
+/* AEW_OP_FRAME_STITCH does for the encoder outputs what AEW_OP_CODE_STITCH does for the indices: for b < B, with
+ * r = table[first_row + b], frames[(r.dst + j) * d_pitch + c] = lin[b * lin_bs + j * d_pitch + c] for j < r.n_valid,
+ * c < d_pitch; it writes nothing else.  The same aew_utt_row_t table and the same record check (n_valid in [0, E],
+ * [dst, dst + n_valid) inside [0, n_dst) rows); a record that fails it on the device copy stores nothing.  16-byte
+ * moves where d_pitch and lin_bs are multiples of 4 and both buffers 16-byte aligned, 4-byte ones otherwise.
+ * AEW_E_ARG: a NULL table / table_host / lin / frames, B < 1 or > 65535, first_row < 0, E < 1, d_pitch < 1,
+ * lin_bs < E * d_pitch, n_dst < 0 or a row the check refuses; AEW_E_ALIGN: the tables not 8-byte, lin / frames not
+ * 4-byte aligned.  All before any launch. */
+typedef struct {
+    const aew_utt_row_t* table;       /* device memory                                         */
+    const aew_utt_row_t* table_host;  /* the same records in host memory (read by the launcher) */
+    int32_t first_row, B;
+    const float* lin;            /* [B][E][d_pitch], batch stride lin_bs elements              */
+    int64_t lin_bs;
+    float* frames;               /* ragged output, n_dst rows of d_pitch                       */
+    int64_t n_dst;
+    int32_t E, d_pitch;
+} aew_frame_stitch_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1484,7 +1592,8 @@ enum {
     AEW_OP_SWAP, AEW_OP_VQ_RESTART, AEW_OP_EVAL_ACC, AEW_OP_WINDOW_GATHER, AEW_OP_GRAD_WELFORD, AEW_OP_SEG_SELECT,
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
     AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH,
-    AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE, AEW_OP_SEQ_ALIGN
+    AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE, AEW_OP_SEQ_ALIGN,
+    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1516,13 +1625,14 @@ typedef struct {
         aew_eval_groups_t evg; aew_mel_tile_t mtile; aew_code_stitch_t cstitch;
         aew_code_tile_t ctile; aew_cond_stitch_t cndst;
         aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred; aew_seq_align_t align;
+        aew_frame_stitch_t fstitch; aew_code_segment_t cseg;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align (24, 26, 33, 40 and 46 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment (24, 26, 33, 40, 46 and 50 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
