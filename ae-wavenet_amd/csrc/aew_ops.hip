@@ -2374,6 +2374,12 @@ static int launch_mfcc(const aew_mfcc_t& p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 static int launch_softmax(const aew_softmax_nll_t& p, hipStream_t st) {
+    // peak / amax leave only the register path of k_softmax_nll (256 classes, rows that are whole float4s); the general
+    // path would return with both arrays unwritten, so such a descriptor is refused here (same predicate as the kernel's)
+    if (!p.backward && (p.peak || p.amax)) {
+        if (!p.peak || !p.amax) return AEW_E_ARG;
+        if (p.Q != 256 || p.Q_pad != 256 || (p.pitch & 3) != 0 || (p.bs & 3) != 0) return AEW_E_UNSUP;
+    }
     hipLaunchKernelGGL(k_softmax_nll, dim3(cdiv64((int64_t)p.B * p.w, 4)), dim3(256), 0, st, p);
     return (int)hipGetLastError();
 }

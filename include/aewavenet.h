@@ -387,8 +387,13 @@ typedef struct {                 /* per-(batch,layer) gated bias incl. speaker t
     float* gc;                   /* [B][G] saved for backward                                 */
 } aew_spk_bias_t;
 
-typedef struct {                 /* backward of the above from per-batch column sums of dfg; B <= 16, G <= 16
-                                    (AEW_E_UNSUP beyond: the kernel holds both in registers)  */
+typedef struct {                 /* backward of the above from per-batch column sums of dfg; G <= 16 (AEW_E_UNSUP beyond: the
+                                    kernel holds a projection row in registers).  The batch is cut into chunks of 16
+                                    elements.  B <= 16: one chunk, the bias / projection gradients of the op's layers are
+                                    plain stores.  B > 16: every chunk ADDS its partial bias / projection sums with fp32
+                                    atomics, so the caller zeroes those gradients first; two chunks (B <= 32) add
+                                    commutatively and the result is still bit-reproducible, three or more (B > 32) add in
+                                    the scheduler's order, WITH OR WITHOUT aew_tuning_t.deterministic              */
     const float* params; const int64_t* voice;
     const int64_t* off_bias_sig; const int64_t* off_bias_gate;
     const int64_t* off_proj_sig; const int64_t* off_proj_gate;
@@ -437,7 +442,9 @@ typedef struct {                 /* fused log-softmax + NLL (+ gradient)  wavene
     const float* gmul;           /* optional device scalar: upstream d(L)/d(loss), multiplies scale at run time */
     float* peak; int32_t* amax;  /* fwd, optional: [B][w] peak log-probability max_c log p(c) and its (lowest) class per
                                     position - what aew_vq_diag_t reduces (vqema_bn.py:261-263) without reading the
-                                    logits again                                               */
+                                    logits again.  Set both or neither (AEW_E_ARG).  Only the 256-class register form
+                                    writes them: Q == 256, Q_pad == 256, pitch % 4 == 0 and bs % 4 == 0; any other forward
+                                    descriptor that sets them is refused with AEW_E_UNSUP before any launch      */
 } aew_softmax_nll_t;
 
 typedef struct {                 /* MFCC + delta + delta-delta front-end on the device (mfcc.py:39-76: librosa.feature.mfcc
@@ -1689,7 +1696,10 @@ typedef struct {
     int32_t nt_chain;            /* ABI 19: 1 (default) AEW_OP_NT_CHAIN ops launch their chain, 0 their stage ops run one by one */
     int32_t deterministic;       /* ABI 20: 1 (default) every sum of the training step has ONE order: column sums and the
                                     speaker-embedding gradient use their ticketed forms where the descriptor carries
-                                    det_scratch / det_tickets; 0 = fp32 atomics (A/B of the cost)                   */
+                                    det_scratch / det_tickets; 0 = fp32 atomics (A/B of the cost).  One exception: the
+                                    bias / projection gradients of aew_spk_bwd_t are order-fixed only up to 32 batch
+                                    elements (beyond, their 16-element chunk sums meet in fp32 atomics in either mode;
+                                    the speaker-embedding sums stay ticketed for every B)                              */
     int32_t tn_mfma32;           /* ABI 20: 1 = the grouped weight-gradient launch (tile = 128, no cursor) on v_mfma_f32_32x32x16_bf16:
                                     half the MFMA instructions per stage; same products, 16-row instead of 32-row partial sums
                                     (equal to fp32 rounding, not bit for bit, to the 16 x 16 x 32 form).  0 (default)            */

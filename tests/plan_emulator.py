@@ -307,7 +307,9 @@ class Emu:
             u = (t ** 2).sum(-1, keepdim=True).sqrt()
             zn = (z ** 2).sum(-1, keepdim=True).sqrt()
             v = zn + (emb_rows ** 2).sum(-1, keepdim=True).sqrt()
-            dj = t / (u * v) - u * z / (v * v * zn)
+            # guarded as the kernel and the header's rule: first term 0 at u == 0 (z equals its code), second 0 at ||z|| == 0
+            zero = torch.zeros_like(t)
+            dj = torch.where(u > 0, t / (u * v), zero) - torch.where(zn > 0, u * z / (v * v * zn), zero)
         else:
             dj = 2 * t
         gm = self._gmul(p)
@@ -445,12 +447,19 @@ class Emu:
             self.wr(p.nll, torch.arange(p.B * p.w), (-lp * live).reshape(-1))
             if p.ptgt:
                 self.wr(p.ptgt, torch.arange(p.B * p.w), (lp.exp() * live).reshape(-1))
-            if p.peak:
-                pk, am = lsm.max(-1)
+            if p.peak or p.amax:
+                # the launcher's contract (aewavenet.h): both or neither, and only the 256-class register form writes them
+                if not (p.peak and p.amax):
+                    raise ValueError("softmax_nll: peak and amax come together (AEW_E_ARG)")
+                if p.Q != 256 or p.Q_pad != 256 or p.pitch % 4 or p.bs % 4:
+                    raise ValueError("softmax_nll: peak / amax outside the 256-class form (AEW_E_UNSUP)")
+                pk = lsm.max(-1)[0]
+                am = lg.argmax(-1)               # the lowest class holding the maximum, taken on the logits themselves
                 self.wr(p.peak, torch.arange(p.B * p.w), pk.reshape(-1))
                 self.wr(p.amax, torch.arange(p.B * p.w), am.reshape(-1).int())
         else:
-            g = (lsm.exp() - torch.nn.functional.one_hot(tgt, p.Q).float()) * (p.scale * self._gmul(p)) * live[:, :, None]
+            g = (lsm.exp() - torch.nn.functional.one_hot(tgt, p.Q).float()) * (p.scale * self._gmul(p))
+            g = torch.where(live[:, :, None] > 0, g, torch.zeros_like(g))       # the dropped position: +0, as the kernel stores it
             out = torch.zeros(p.B, p.w, p.Q_pad)
             out[:, :, :p.Q] = g
             idx = (torch.arange(p.B)[:, None, None] * p.dl_bs + torch.arange(p.w)[None, :, None] * p.dl_pitch
@@ -522,7 +531,8 @@ class Emu:
         if not p.backward:
             self.wr(p.term, torch.arange(p.Q), (nrm - 1).abs())
         else:
-            g = self.rd(p.dze_in, q * p.d_pitch + j) + p.coef * self._gmul(p) * torch.sign(nrm - 1)[:, None] * z / nrm[:, None]
+            unit = torch.where(nrm[:, None] > 0, z / nrm[:, None], torch.zeros_like(z))    # the term is 0 at norm 0 (kernel, header)
+            g = self.rd(p.dze_in, q * p.d_pitch + j) + p.coef * self._gmul(p) * torch.sign(nrm - 1)[:, None] * unit
             out = torch.zeros(p.Q, p.d_pitch)
             out[:, :p.d] = g
             self.wr(p.dze, torch.arange(p.Q * p.d_pitch), out.reshape(-1))
