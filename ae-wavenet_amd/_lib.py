@@ -26,7 +26,7 @@ EF_OUT2_COPY = 1 << 10
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
  OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE, OP_SEQ_ALIGN,
- OP_FRAME_STITCH, OP_CODE_SEGMENT) = range(1, 49)
+ OP_FRAME_STITCH, OP_CODE_SEGMENT, OP_SEQ_SEARCH) = range(1, 50)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -353,6 +353,30 @@ class SeqAlign(C.Structure):
                 ("ws", vp), ("ws_bytes", i64), ("back", vp), ("n_back", i64), ("path", vp), ("n_path", i64)]
 
 
+SEARCH_MEAN, SEARCH_COST = 0, 1
+SEARCH_MAX_HITS = 32
+
+
+class SearchPair(C.Structure):
+    """aew_search_pair_t: which query and which document a pair searches, where the document's m profile entries start.
+    SEARCH_PAIR_DTYPE is the same record for numpy."""
+    _fields_ = [("a", i32), ("b", i32), ("prof_base", i64)]
+
+
+SEARCH_PAIR_DTYPE = [("a", "<i4"), ("b", "<i4"), ("prof_base", "<i8")]
+
+
+class SeqSearch(C.Structure):
+    """aew_seq_search_t: subsequence DTW of n_pairs (query, document) pairs - the per-end profile (cost, steps, start) and
+    the n_hits best non-overlapping matches of each; the tables as device and host copies."""
+    _fields_ = [("metric", i32), ("rank", i32), ("D", i32), ("n_pairs", i32), ("n_hits", i32), ("min_len", i32),
+                ("max_len", i32), ("pad_", i32), ("seq_a", vp), ("seq_a_host", vp), ("seq_b", vp), ("seq_b_host", vp),
+                ("pairs", vp), ("pairs_host", vp), ("n_a", i32), ("n_b", i32), ("feat_a", vp), ("feat_b", vp),
+                ("n_feat_a", i64), ("n_feat_b", i64), ("prof_cost", vp), ("prof_steps", vp), ("prof_start", vp),
+                ("n_prof", i64), ("hits", vp), ("hit_cost", vp), ("hit_steps", vp), ("count", vp), ("bad", vp),
+                ("ws", vp), ("ws_bytes", i64)]
+
+
 SEG_MAX_K, SEG_MAX_D = 4096, 4096
 
 
@@ -523,7 +547,7 @@ class _OpU(C.Union):
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
                 ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
                 ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce),
-                ("align", SeqAlign), ("fstitch", FrameStitch), ("cseg", CodeSegment)]
+                ("align", SeqAlign), ("fstitch", FrameStitch), ("cseg", CodeSegment), ("search", SeqSearch)]
 
 
 class Op(C.Structure):
@@ -541,7 +565,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
             OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst",
             OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred", OP_SEQ_ALIGN: "align",
-            OP_FRAME_STITCH: "fstitch", OP_CODE_SEGMENT: "cseg"}
+            OP_FRAME_STITCH: "fstitch", OP_CODE_SEGMENT: "cseg", OP_SEQ_SEARCH: "search"}
 
 
 
@@ -686,7 +710,7 @@ def load():
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
                        (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec), (42, ScoreRow), (43, WavTile),
                        (44, NllStitch), (45, ScoreReduce), (47, AlignSeq), (48, AlignPair), (49, SeqAlign),
-                       (51, SegUtt), (52, FrameStitch), (53, CodeSegment)):
+                       (51, SegUtt), (52, FrameStitch), (53, CodeSegment), (55, SearchPair), (56, SeqSearch)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

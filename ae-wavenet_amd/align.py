@@ -7,9 +7,12 @@ states the rule bit for bit).
     al = dtw(a, pairs=[(0, 1), (0, 2)], return_path=True);  al.path(0)      # (steps, 2) int32 cells - the ONE call that waits
     ed = edit_distance(codes_a, codes_b, collapse=True);    ed.distance, ed.rate
     err = abx(d_ax, d_bx)                   # ABX error of paired distances, a device scalar
+    mt = search(queries, docs, pairs=..., n_hits=3)         # subsequence DTW (AEW_OP_SEQ_SEARCH, csrc/aew_search.hip)
+    mt.start, mt.end, mt.cost, mt.steps, mt.mean, mt.count  # (P, n_hits): where each query occurs, best first; mt.profile(p)
 
 `model.code_distance()` and `model.cepstral_distance()` (surface.py) are these calls over the codebook rows of code
-sequences and over the model's own MFCC front-end.  Everything runs as one-op plans on torch's current stream; nothing
+sequences and over the model's own MFCC front-end; `model.search_codes()` and `model.search_wavs()` are `search` over the
+same two feature sources.  Everything runs as one-op plans on torch's current stream; nothing
 but `Alignment.path()` (and `edit_distance(collapse=True)`, which has to learn the number of units) synchronises with
 the host.  There is no CPU path: a tensor that is not on the GPU is refused.
 """
@@ -232,6 +235,131 @@ def dtw(a, b=None, pairs=None, metric: str = "euclid", return_path: bool = False
     rb = ra if b is None else _ragged(b, "dtw(): b", torch.float32)
     pr = default_pairs(len(ra), None if b is None else len(rb), pairs)
     return Alignment(_Launches(L.ALIGN_DTW, METRICS[metric], ra, rb, pr, bool(return_path), int(max_back_bytes)).run("dtw()"))
+
+
+RANKS = {"mean": L.SEARCH_MEAN, "cost": L.SEARCH_COST}
+
+
+def search_pair_table(lens_q: Sequence[int], lens_d: Sequence[int], pairs: np.ndarray):
+    """(records, n_prof, wstride).  records: aew_search_pair_t with prof_base = the prefix sum of the document lengths over
+    the pairs in order (disjoint profile ranges); n_prof: their total; wstride: the longest document among the pairs whose
+    query has more than STRIP frames (the workspace is 12 * pairs * wstride bytes)."""
+    lq, ld = np.asarray(lens_q, np.int64)[pairs[:, 0]], np.asarray(lens_d, np.int64)[pairs[:, 1]]
+    t = np.zeros(len(pairs), dtype=L.SEARCH_PAIR_DTYPE)
+    t["a"], t["b"] = pairs[:, 0], pairs[:, 1]
+    t["prof_base"] = np.concatenate([[0], np.cumsum(ld)[:-1]])
+    return t, int(ld.sum()), int(np.where(lq > STRIP, ld, 0).max())
+
+
+def _upload(table: np.ndarray, dev) -> torch.Tensor:
+    """The bytes of a host table on the device, copied from pinned memory behind the stream: the host does not wait."""
+    host = torch.empty(max(table.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:table.nbytes] = table.view(np.uint8).reshape(-1)
+    return host.to(dev, non_blocking=True)
+
+
+class _SearchLaunch:
+    """The op record of one search and everything it points to."""
+
+    def __init__(self, metric: int, rank: int, rq: Ragged, rd: Ragged, pairs: np.ndarray, n_hits: int, min_len: int,
+                 max_len: int):
+        dev = rq.flat.device
+        if rd.flat.device != dev:
+            raise L.AewError(f"the two sides lie on different devices ('{dev}' and '{rd.flat.device}')")
+        if rq.D != rd.D:
+            raise L.AewError(f"the two sides have {rq.D} and {rd.D} channels")
+        if not 1 <= rq.D <= L.ALIGN_MAX_D:
+            raise L.AewError(f"D must lie in [1, {L.ALIGN_MAX_D}], got {rq.D}")
+        if dev.type != "cuda":
+            raise L.AewError(f"the search runs on the GPU only (tensor on '{dev}'); there is no CPU path")
+        self.dev, self.P = dev, len(pairs)
+        tq, td = rq.table(), rd.table()
+        tp, n_prof, wstride = search_pair_table(rq.length, rd.length, pairs)
+        self.host = (tq, td, tp)                                     # the launcher reads these at every launch
+        self.tables = tuple(_upload(t, dev) for t in self.host)
+        P = self.P
+        self.prof = (torch.empty(max(n_prof, 1), dtype=torch.float32, device=dev),
+                     torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev),
+                     torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev))
+        self.hits = torch.empty(P, n_hits, 2, dtype=torch.int32, device=dev)
+        self.cost = torch.empty(P, n_hits, dtype=torch.float32, device=dev)
+        self.steps = torch.empty(P, n_hits, dtype=torch.int32, device=dev)
+        self.count = torch.empty(P, dtype=torch.int32, device=dev)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(3 * P * wstride, dtype=torch.float32, device=dev) if wstride else None
+        self.prof_base, self.doc_len = tp["prof_base"].copy(), np.asarray(rd.length, np.int64)[pairs[:, 1]]
+        self.keep = (rq.flat, rd.flat)
+        r = self.rec = L.SeqSearch()
+        r.metric, r.rank, r.D, r.n_pairs = metric, rank, rq.D, P
+        r.n_hits, r.min_len, r.max_len = n_hits, min_len, max_len
+        r.seq_a, r.seq_a_host, r.n_a = self.tables[0].data_ptr(), tq.ctypes.data, len(tq)
+        r.seq_b, r.seq_b_host, r.n_b = self.tables[1].data_ptr(), td.ctypes.data, len(td)
+        r.pairs, r.pairs_host = self.tables[2].data_ptr(), tp.ctypes.data
+        r.feat_a, r.n_feat_a = (rq.flat.data_ptr() if rq.flat.numel() else None), rq.flat.numel()
+        r.feat_b, r.n_feat_b = (rd.flat.data_ptr() if rd.flat.numel() else None), rd.flat.numel()
+        r.prof_cost, r.prof_steps, r.prof_start = (x.data_ptr() for x in self.prof)
+        r.n_prof = n_prof
+        r.hits, r.hit_cost, r.hit_steps = self.hits.data_ptr(), self.cost.data_ptr(), self.steps.data_ptr()
+        r.count, r.bad = self.count.data_ptr(), self.bad.data_ptr()
+        if self.ws is not None:
+            r.ws, r.ws_bytes = self.ws.data_ptr(), 4 * self.ws.numel()
+
+    def run(self, what: str):
+        op, fail = L.Op(), C.c_int(-1)
+        op.kind, op.u.search = L.OP_SEQ_SEARCH, self.rec
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream(self.dev).cuda_stream
+            L.check(L.load().aew_run_plan(C.byref(op), 1, C.c_void_p(st), C.byref(fail)), what,
+                    fail.value if fail.value >= 0 else None)
+        return self
+
+
+class Matches:
+    """What search() returns.  start, end (P, n_hits) int32: the document frames [start, end] of hit r of pair p, best
+    first, (-1, -1) behind the `count[p]` hits that exist; cost (P, n_hits) fp32 (+inf there), steps (P, n_hits) int32
+    (0 there), mean = cost / steps; count (P,) int32; bad: int32 (1,), a uint32 count of the pairs that were not finite.
+    All on the device; reading them is the caller's synchronisation."""
+
+    def __init__(self, run: _SearchLaunch):
+        self.start, self.end = run.hits[:, :, 0], run.hits[:, :, 1]
+        self.cost, self.steps, self.count, self.bad = run.cost, run.steps, run.count, run.bad
+        self.mean = run.cost / run.steps
+        self._run = run
+
+    def __len__(self) -> int:
+        return self._run.P
+
+    def profile(self, p: int):
+        """(end_cost, end_steps, end_start) of pair p: views of length m, entry j the best match that ENDS at document
+        frame j - its summed distance, its path length and the frame it starts at ((NaN, 0, -1) for a pair that was
+        not finite, (+inf, 0, -1) for an empty query).  The lengths come from the host tables: no wait on the device."""
+        p = range(len(self))[p]
+        lo, m = int(self._run.prof_base[p]), int(self._run.doc_len[p])
+        return tuple(x[lo:lo + m] for x in self._run.prof)
+
+
+def search(query, doc=None, pairs=None, metric: str = "euclid", n_hits: int = 1, rank: str = "mean", min_len: int = 1,
+           max_len: int = 0) -> Matches:
+    """Where does a query occur inside a document: subsequence DTW (AEW_OP_SEQ_SEARCH) of pairs of sequences of D-channel
+    fp32 frames.  query, doc: `Ragged` views or lists of (n_u, D) float32 device tensors, exactly as for dtw() (doc=None
+    searches `query` in itself); pairs (P, 2) integers, pair p = (query[pairs[p, 0]], doc[pairs[p, 1]]), default zip.
+    The whole query is matched against ANY stretch of the document under dtw()'s step pattern and local distance; the
+    n_hits (1 .. 32) best stretches that do not overlap are returned best first, ranked by "mean" (cost / steps) or
+    "cost".  A match may collapse onto very few document frames - min_len / max_len (document frames, max_len 0: no
+    limit) bound the stretches that count.  Nothing here synchronises with the host.  -> `Matches`."""
+    if metric not in METRICS:
+        raise L.AewError(f"search(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    if rank not in RANKS:
+        raise L.AewError(f"search(): rank must be one of {sorted(RANKS)}, got '{rank}'")
+    n_hits, min_len, max_len = int(n_hits), int(min_len), int(max_len)
+    if not 1 <= n_hits <= L.SEARCH_MAX_HITS:
+        raise L.AewError(f"search(): n_hits must lie in [1, {L.SEARCH_MAX_HITS}], got {n_hits}")
+    if min_len < 0 or max_len < 0:
+        raise L.AewError(f"search(): min_len and max_len must not be negative, got {min_len} and {max_len}")
+    rq = _ragged(query, "search(): query", torch.float32)
+    rd = rq if doc is None else _ragged(doc, "search(): doc", torch.float32)
+    pr = default_pairs(len(rq), None if doc is None else len(rd), pairs)
+    return Matches(_SearchLaunch(METRICS[metric], RANKS[rank], rq, rd, pr, n_hits, min_len, max_len).run("search()"))
 
 
 class EditDistances:

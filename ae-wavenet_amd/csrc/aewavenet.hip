@@ -14,6 +14,7 @@
 #include "aew_score.hip"
 #include "aew_align.hip"
 #include "aew_segment.hip"
+#include "aew_search.hip"
 
 #include <vector>
 #include <cstdlib>
@@ -84,6 +85,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_SEQ_ALIGN: return launch_seq_align(op.u.align, st);
         case AEW_OP_FRAME_STITCH: return launch_frame_stitch(op.u.fstitch, st);
         case AEW_OP_CODE_SEGMENT: return launch_code_segment(op.u.cseg, st);
+        case AEW_OP_SEQ_SEARCH: return launch_seq_search(op.u.search, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -141,6 +143,8 @@ extern "C" int aew_sizeof(int which) {
         case 51: return (int)sizeof(aew_seg_utt_t);      // (50 is left unused like 24, 26, 33, 40 and 46)
         case 52: return (int)sizeof(aew_frame_stitch_t);
         case 53: return (int)sizeof(aew_code_segment_t);
+        case 55: return (int)sizeof(aew_search_pair_t);      // (54 is left unused like 24, 26, 33, 40, 46 and 50)
+        case 56: return (int)sizeof(aew_seq_search_t);
         default: return -1;
     }
 }

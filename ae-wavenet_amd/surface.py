@@ -1414,8 +1414,14 @@ class HipModelBase(nn.Module):
         raises AewError with the count before the alignment (the lookup never follows it; that check reads one word
         back).  VQ bottlenecks only.  The codebook is read, nothing of the model is written: no EMA statistic, histogram,
         loss or metric word; no collective under data parallel."""
+        from . import align as AL
+        sides, pr = self._code_sides("code_distance()", codes_a, codes_b, pairs)
+        return AL.dtw(sides[0], None if codes_b is None else sides[1], pairs=pr, metric=metric, return_path=return_path)
+
+    def _code_sides(self, what: str, codes_a, codes_b, pairs):
+        """The front half of code_distance() / search_codes(): ([Ragged of the looked-up codebook rows per side], pairs);
+        a code outside [0, K) raises before anything is compared."""
         from . import align as AL, codes as CD
-        what = "code_distance()"
         self._need_codes(what)
         if self._device.type != "cuda":
             raise L.AewError(f"{what} runs on an MI355X only; move the model to a cuda device first")
@@ -1439,7 +1445,7 @@ class HipModelBase(nn.Module):
             n_bad = int(bad[0].item()) & 0xFFFFFFFF
             if n_bad:
                 raise L.AewError(f"{what}: {n_bad} codes lie outside the codebook [0, {eng.K}); nothing was aligned")
-            return AL.dtw(sides[0], None if rows_b is None else sides[1], pairs=pr, metric=metric, return_path=return_path)
+            return sides, pr
 
     def cepstral_distance(self, wavs_a, wavs_b=None, pairs=None, expand: bool = True):
         """The mean DTW-aligned Euclidean distance between the cepstra of waveforms: wavs_a / wavs_b lists of 1-D device
@@ -1453,8 +1459,14 @@ class HipModelBase(nn.Module):
         of this project and NOT with published mel-cepstral-distortion figures.  An utterance too short for
         `DeviceMfcc.MIN_FRAMES` frames has none: its pairs give inf.  VQ bottlenecks only (the rule of the utterance
         interface); nothing of the model is written and no collective is issued."""
+        from . import align as AL
+        sides = self._cepstral_sides("cepstral_distance()", wavs_a, wavs_b, expand)
+        return AL.dtw(sides[0], None if wavs_b is None else sides[1], pairs=pairs, metric="euclid")
+
+    def _cepstral_sides(self, what: str, wavs_a, wavs_b, expand: bool):
+        """The front half of cepstral_distance() / search_wavs(): [Ragged of the static cepstra 1 .. n_mfcc - 1 per side],
+        the channel-major arrays of `DeviceMfcc.ragged` read in place."""
         from . import align as AL, codes as CD
-        what = "cepstral_distance()"
         self._need_codes(what)
         if self._device.type != "cuda":
             raise L.AewError(f"{what} runs on an MI355X only; move the model to a cuda device first")
@@ -1475,7 +1487,38 @@ class HipModelBase(nn.Module):
                     wavs = [w.to(self._device) for w in wavs]
                 flat, frames, bases = mf.ragged(wavs)
                 sides.append(AL.Ragged(flat, [b + f for b, f in zip(bases, frames)], frames, 1, frames, n_mfcc - 1))
-            return AL.dtw(sides[0], None if wavs_b is None else sides[1], pairs=pairs, metric="euclid")
+        return sides
+
+    # ---- finding a query inside utterances: subsequence DTW over the same two feature sources (align.search) ----------
+    def search_codes(self, query_codes, codes, pairs=None, metric: str = "euclid", n_hits: int = 1, rank: str = "mean",
+                     min_len: int = 1, max_len: int = 0):
+        """Where do the code sequences `query_codes` occur inside the code sequences `codes`: subsequence DTW over their
+        codebook rows (align.search(); metric, n_hits, rank, min_len, max_len as there).  Both sides a
+        `codes.UtteranceCodes` or a list of 1-D int64 device tensors, pairs (P, 2) = (query, document) indices (default:
+        zip) -> `align.Matches`; start / end of a hit are CODE FRAMES of the document.  The front half is
+        code_distance()'s: one lookup per side into a ragged buffer read in place, and a code outside [0, K) raises
+        AewError before anything is searched.  VQ bottlenecks only; the codebook is read, nothing of the model is
+        written and no collective is issued."""
+        from . import align as AL
+        sides, pr = self._code_sides("search_codes()", query_codes, codes, pairs)
+        return AL.search(sides[0], sides[1], pairs=pr, metric=metric, n_hits=n_hits, rank=rank, min_len=min_len,
+                         max_len=max_len)
+
+    def search_wavs(self, query_wavs, wavs, pairs=None, expand: bool = True, n_hits: int = 1, rank: str = "mean",
+                    min_len: int = 1, max_len: int = 0):
+        """Where do the waveforms `query_wavs` occur inside the waveforms `wavs`: subsequence DTW (align.search(),
+        Euclidean) over the static cepstra 1 .. n_mfcc - 1 of this model's own front-end - cepstral_distance()'s front
+        half, `expand` as there.  Lists of 1-D device tensors of mu-law values, pairs (P, 2) = (query, document) indices
+        (default: zip) -> `align.Matches`.  start / end of a hit are MFCC FRAMES of the document: consecutive frames lie
+        `hop_sz` samples apart (160 by default) and each looks at `win_sz` samples (400), so a hit [start, end] covers
+        about the samples start * hop_sz .. end * hop_sz + win_sz of the document.  Every utterance gets its own dB floor
+        and delta edges, so a slice's cepstra are close to, not the bits of, the cepstra of the same samples inside a
+        longer waveform.  A waveform too short for `DeviceMfcc.MIN_FRAMES` frames has none: its pairs find nothing.  VQ
+        bottlenecks only; nothing of the model is written and no collective is issued."""
+        from . import align as AL
+        sides = self._cepstral_sides("search_wavs()", query_wavs, wavs, expand)
+        return AL.search(sides[0], sides[1], pairs=pairs, metric="euclid", n_hits=n_hits, rank=rank, min_len=min_len,
+                         max_len=max_len)
 
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared

@@ -51,7 +51,8 @@ extern "C" {
  * `draw` pointer appended to aew_sampler_t - index 40 stays unused, it answers -1; 42 .. 45, aew_score_row_t,
  * aew_wav_tile_t / AEW_OP_WAV_TILE, aew_nll_stitch_t / AEW_OP_NLL_STITCH, aew_score_reduce_t / AEW_OP_SCORE_REDUCE;
  * 47 .. 49, aew_align_seq_t, aew_align_pair_t, aew_seq_align_t / AEW_OP_SEQ_ALIGN - index 46 stays unused; 51 .. 53, aew_seg_utt_t,
- * aew_frame_stitch_t / AEW_OP_FRAME_STITCH, aew_code_segment_t / AEW_OP_CODE_SEGMENT - index 50 stays unused). */
+ * aew_frame_stitch_t / AEW_OP_FRAME_STITCH, aew_code_segment_t / AEW_OP_CODE_SEGMENT - index 50 stays unused; 55 / 56,
+ * aew_search_pair_t, aew_seq_search_t / AEW_OP_SEQ_SEARCH - index 54 stays unused). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -1278,6 +1279,81 @@ typedef struct {
     int32_t E, d_pitch;
 } aew_frame_stitch_t;
 
+/* Finding a query inside utterances (appended to ABI 28; AEW_OP_SEQ_SEARCH, aew_sizeof 55 / 56 - index 54 stays unused,
+ * it answers -1): subsequence dynamic time warping of a query a (n frames) against a document b (m frames) - the match
+ * may start and end at any document frame - for n_pairs independent pairs in one op, then the n_hits best
+ * non-overlapping matches of each pair.  Two launches of the one op, ordered by the stream alone: the sweep (one
+ * wavefront per pair, the shape of AEW_OP_SEQ_ALIGN's DTW kernel) and the pick (one wavefront per pair).  Nothing waits
+ * on another wavefront - no flag, no spin, no barrier, no atomic but the count of pairs that are not finite.
+ *
+ * THE RULE (tests/seq_search_emulator.py restates it).  The arithmetic is AEW_OP_SEQ_ALIGN's: fp32 throughout, every
+ * operation rounded on its own, d(i, j) that op's local distance for the metrics EUCLID and SQEUCLID over D channels.
+ *   sweep    Row 0 starts a match anywhere: C(0,j) = d(0,j), S(0,j) = 1, B(0,j) = j for every j (row 0 has no left
+ *            predecessor).  For i >= 1, pred = the EXISTING predecessor of least C among (i-1,j-1), (i-1,j), (i,j-1), ties to
+ *            the first in that order (strict < while scanning in that order, exactly as DTW does); then
+ *            C(i,j) = d(i,j) + C(pred), S(i,j) = S(pred) + 1, B(i,j) = B(pred).
+ *   profile  The pair's m entries from prof_base on: end_cost[j] = C(n-1,j), end_steps[j] = S(n-1,j), end_start[j] =
+ *            B(n-1,j).  The match that ends at document frame j starts at frame end_start[j].
+ *   pick     key[j] = end_cost[j] / (float)end_steps[j], the correctly rounded fp32 quotient (rank MEAN), or end_cost[j]
+ *            (rank COST).  An end is eligible when its key is finite and min_len <= j - end_start[j] + 1 and, when
+ *            max_len > 0, that length is <= max_len.  For r = 0 .. n_hits-1: take the eligible, unsuppressed end of least
+ *            key, ties to the least j; write hit r = (start, end, cost, steps); then suppress every end k whose interval
+ *            [end_start[k], k] meets [start, end], that is end_start[k] <= end and k >= start.  count[p] = the hits
+ *            found; the remaining hit slots are (-1, -1, +inf, 0).
+ *   special  An empty side reads no feature memory.  m = 0 owns no profile entries; n = 0, m > 0 writes (+inf, 0, -1) to
+ *            each; in both cases count = 0 and all hits are empty.  A pair with any d(i,j) not finite gets every profile
+ *            entry (NaN, 0, -1), count = 0, empty hits, and *bad is raised by one (DTW's convention).
+ *   caveat   The symmetric step pattern lets a match collapse onto one document frame; min_len / max_len are the remedy
+ *            on offer, the step pattern itself does not change.
+ *   slices   For every end j, C(n-1,j) is, bit for bit, the closed DTW cost of a against b[B(n-1,j) .. j] under
+ *            AEW_OP_SEQ_ALIGN (and S the steps wherever no tie decides the path).
+ * Tables and checks follow AEW_OP_SEQ_ALIGN: the two aew_align_seq_t tables (reused unchanged) and the pair table each
+ * come as a device copy and a host copy; the launcher checks every host record before anything is launched, the kernels
+ * repeat the checks on the device copies and leave a failing pair alone; no address is formed from an unchecked record.
+ * The profile ranges [prof_base, prof_base + m) of the pairs must be disjoint - the caller's contract (prefix sums).
+ * AEW_E_ARG: metric / rank outside their values, D outside [1, AEW_ALIGN_MAX_D], n_pairs < 1 or > 2^24, n_a / n_b < 1,
+ * n_hits outside [1, AEW_SEARCH_MAX_HITS], min_len or max_len negative, a NULL table or output (prof_*, hits, hit_cost,
+ * hit_steps, count, bad), a NULL feature buffer of n_feat > 0, n_feat outside [0, 2^50], n_prof < 0, a sequence record
+ * AEW_OP_SEQ_ALIGN refuses, a pair with a / b outside its table, prof_base < 0 or prof_base + m > n_prof, a query of more
+ * than 64 frames without a workspace of the size stated at `ws`.  AEW_E_ALIGN: a table off 8 bytes, any other pointer
+ * off 4.  A refused call launches and writes nothing. */
+#define AEW_SEARCH_MEAN 0
+#define AEW_SEARCH_COST 1
+#define AEW_SEARCH_MAX_HITS 32
+typedef struct {
+    int32_t a, b;                /* indices into the query / document sequence tables                           */
+    int64_t prof_base;           /* first of the pair's m entries in prof_cost / prof_steps / prof_start         */
+} aew_search_pair_t;
+
+typedef struct {
+    int32_t metric, rank;        /* AEW_ALIGN_EUCLID / _SQEUCLID; AEW_SEARCH_MEAN / _COST       */
+    int32_t D, n_pairs;
+    int32_t n_hits, min_len, max_len, pad_;   /* max_len 0: no upper limit                      */
+    const aew_align_seq_t* seq_a;       /* the queries: device memory, n_a records             */
+    const aew_align_seq_t* seq_a_host;  /* the same records in host memory                     */
+    const aew_align_seq_t* seq_b;       /* the documents                                       */
+    const aew_align_seq_t* seq_b_host;
+    const aew_search_pair_t* pairs;     /* device memory, n_pairs records                      */
+    const aew_search_pair_t* pairs_host;
+    int32_t n_a, n_b;
+    const float* feat_a;         /* n_feat_a elements                                          */
+    const float* feat_b;
+    int64_t n_feat_a, n_feat_b;
+    float* prof_cost;            /* [n_prof]                                                   */
+    int32_t* prof_steps;         /* [n_prof]                                                   */
+    int32_t* prof_start;         /* [n_prof]                                                   */
+    int64_t n_prof;
+    int32_t* hits;               /* [n_pairs][n_hits][2]: (start, end) document frames         */
+    float* hit_cost;             /* [n_pairs][n_hits]                                          */
+    int32_t* hit_steps;          /* [n_pairs][n_hits]                                          */
+    int32_t* count;              /* [n_pairs]; between the two launches it carries the sweep's verdict on the pair */
+    uint32_t* bad;               /* one device word, added to                                  */
+    void* ws;                    /* boundary rows (C, S, B) of pairs with more than 64 query frames (optional): ws_bytes >=
+                                    12 * n_pairs * the longest document among those pairs (the launcher takes that length
+                                    from the host tables).  Contents are scratch.                                          */
+    int64_t ws_bytes;
+} aew_seq_search_t;
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1600,7 +1676,7 @@ enum {
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
     AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH,
     AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE, AEW_OP_SEQ_ALIGN,
-    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT
+    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT, AEW_OP_SEQ_SEARCH
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1632,14 +1708,14 @@ typedef struct {
         aew_eval_groups_t evg; aew_mel_tile_t mtile; aew_code_stitch_t cstitch;
         aew_code_tile_t ctile; aew_cond_stitch_t cndst;
         aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred; aew_seq_align_t align;
-        aew_frame_stitch_t fstitch; aew_code_segment_t cseg;
+        aew_frame_stitch_t fstitch; aew_code_segment_t cseg; aew_seq_search_t search;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment (24, 26, 33, 40, 46 and 50 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment, 55 search_pair, 56 seq_search (24, 26, 33, 40, 46, 50 and 54 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
