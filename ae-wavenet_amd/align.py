@@ -12,7 +12,10 @@ states the rule bit for bit).
 
 `model.code_distance()` and `model.cepstral_distance()` (surface.py) are these calls over the codebook rows of code
 sequences and over the model's own MFCC front-end; `model.search_codes()` and `model.search_wavs()` are `search` over the
-same two feature sources.  Everything runs as one-op plans on torch's current stream; nothing
+same two feature sources.  On the device dtw() and search() run one sweep (`align_sweep` in csrc/aew_align.hip), and here
+the two ops share one launch path, `_SeqPlan`: it checks the two sides, fills the record fields the ops have in common
+and runs the records as a plan on torch's current stream; every host table (and edit_distance()'s denominator) goes up
+through `_upload` - pinned, behind the stream.  Nothing
 but `Alignment.path()` (and `edit_distance(collapse=True)`, which has to learn the number of units) synchronises with
 the host.  There is no CPU path: a tensor that is not on the GPU is refused.
 """
@@ -136,11 +139,19 @@ def pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, 
     return t, chunks, n_back, int(cap.sum()), wstride
 
 
-class _Launches:
-    """The op records of one call and everything they point to."""
+def _upload(table: np.ndarray, dev) -> torch.Tensor:
+    """The bytes of a host table on the device, copied from pinned memory behind the stream: the host does not wait."""
+    host = torch.empty(max(table.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:table.nbytes] = table.view(np.uint8).reshape(-1)
+    return host.to(dev, non_blocking=True)
 
-    def __init__(self, mode: int, metric: int, ra: Ragged, rb: Ragged, pairs: np.ndarray, want_path: bool,
-                 max_back_bytes: Optional[int]):
+
+class _SeqPlan:
+    """The launch path dtw() / edit_distance() (`_Launches`) and search() (`_SearchLaunch`) share: the checks of the two
+    sides, the three tables, the fields aew_seq_align_t and aew_seq_search_t have in common, the run as one plan."""
+    KIND, FIELD, NOUN = None, None, None
+
+    def _open(self, ra: Ragged, rb: Ragged):
         dev = ra.flat.device
         if rb.flat.device != dev:
             raise L.AewError(f"the two sides lie on different devices ('{dev}' and '{rb.flat.device}')")
@@ -149,15 +160,51 @@ class _Launches:
         if not 1 <= ra.D <= L.ALIGN_MAX_D:
             raise L.AewError(f"D must lie in [1, {L.ALIGN_MAX_D}], got {ra.D}")
         if dev.type != "cuda":
-            raise L.AewError(f"the alignment runs on the GPU only (tensor on '{dev}'); there is no CPU path")
-        self.dev, self.P, self.want_path = dev, len(pairs), want_path
-        ta, tb = ra.table(), rb.table()
+            raise L.AewError(f"the {self.NOUN} runs on the GPU only (tensor on '{dev}'); there is no CPU path")
+        self.dev, self.sides, self.recs = dev, (ra, rb), []
+        return dev
+
+    def _tables(self, tp: np.ndarray):
+        self.host = (self.sides[0].table(), self.sides[1].table(), tp)   # the launcher reads these at every launch
+        self.tables = tuple(_upload(t, self.dev) for t in self.host)     # uploaded once per call
+
+    def _add(self, r, ws, lo: int = 0):
+        """Record r, its common fields filled (the pair table from record `lo` on), joins the plan."""
+        (ra, rb), (ta, tb, tp) = self.sides, self.host
+        r.seq_a, r.seq_a_host, r.n_a = self.tables[0].data_ptr(), ta.ctypes.data, len(ta)
+        r.seq_b, r.seq_b_host, r.n_b = self.tables[1].data_ptr(), tb.ctypes.data, len(tb)
+        r.pairs, r.pairs_host = self.tables[2].data_ptr() + lo * tp.itemsize, tp.ctypes.data + lo * tp.itemsize
+        r.feat_a, r.n_feat_a = (ra.flat.data_ptr() if ra.flat.numel() else None), ra.flat.numel()
+        r.feat_b, r.n_feat_b = (rb.flat.data_ptr() if rb.flat.numel() else None), rb.flat.numel()
+        if ws is not None:
+            r.ws, r.ws_bytes = ws.data_ptr(), 4 * ws.numel()
+        self.recs.append(r)
+
+    def run(self, what: str):
+        fail = C.c_int(-1)
+        ops = (L.Op * len(self.recs))()
+        for op, r in zip(ops, self.recs):
+            op.kind = self.KIND
+            setattr(op.u, self.FIELD, r)
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream(self.dev).cuda_stream
+            L.check(L.load().aew_run_plan(C.cast(ops, C.c_void_p), len(self.recs), C.c_void_p(st), C.byref(fail)), what,
+                    fail.value if fail.value >= 0 else None)
+        return self
+
+
+class _Launches(_SeqPlan):
+    """The op records of one call and everything they point to."""
+    KIND, FIELD, NOUN = L.OP_SEQ_ALIGN, "align", "alignment"
+
+    def __init__(self, mode: int, metric: int, ra: Ragged, rb: Ragged, pairs: np.ndarray, want_path: bool,
+                 max_back_bytes: Optional[int]):
+        dev = self._open(ra, rb)
+        P = self.P = len(pairs)
+        self.want_path = want_path
         tp, self.chunks, n_back, self.n_path, wstride = pair_table(ra.length, rb.length, pairs,
                                                                    max_back_bytes if want_path else None)
-        self.host = (ta, tb, tp)                                     # the launcher reads these at every launch
-        up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)
-        self.tables = (up(ta), up(tb), up(tp))                       # uploaded once per call
-        P = self.P
+        self._tables(tp)
         self.cost = torch.empty(P, dtype=torch.float32, device=dev)
         self.steps = torch.empty(P, dtype=torch.int32, device=dev)
         self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -166,35 +213,14 @@ class _Launches:
         self.back = torch.empty(max(n_back, 1), dtype=torch.uint8, device=dev) if want_path else None
         self.path = torch.empty(max(self.n_path, 1), 2, dtype=torch.int32, device=dev) if want_path else None
         self.path_base = tp["path_base"].copy()
-        self.keep = (ra.flat, rb.flat)
-        psz = C.sizeof(L.AlignPair)
-        self.recs: List[L.SeqAlign] = []
         for lo, hi in self.chunks:
             r = L.SeqAlign()
             r.mode, r.metric, r.D, r.n_pairs = mode, metric, ra.D, hi - lo
-            r.seq_a, r.seq_a_host, r.n_a = self.tables[0].data_ptr(), ta.ctypes.data, len(ta)
-            r.seq_b, r.seq_b_host, r.n_b = self.tables[1].data_ptr(), tb.ctypes.data, len(tb)
-            r.pairs, r.pairs_host = self.tables[2].data_ptr() + lo * psz, tp.ctypes.data + lo * psz
-            r.feat_a, r.n_feat_a = (ra.flat.data_ptr() if ra.flat.numel() else None), ra.flat.numel()
-            r.feat_b, r.n_feat_b = (rb.flat.data_ptr() if rb.flat.numel() else None), rb.flat.numel()
             r.cost, r.steps, r.bad = self.cost.data_ptr() + 4 * lo, self.steps.data_ptr() + 4 * lo, self.bad.data_ptr()
-            if self.ws is not None:
-                r.ws, r.ws_bytes = self.ws.data_ptr(), 4 * self.ws.numel()
             if want_path:
                 r.back, r.n_back = self.back.data_ptr(), self.back.numel()
                 r.path, r.n_path = self.path.data_ptr(), self.path.shape[0]
-            self.recs.append(r)
-
-    def run(self, what: str):
-        fail = C.c_int(-1)
-        ops = (L.Op * len(self.recs))()
-        for op, r in zip(ops, self.recs):
-            op.kind, op.u.align = L.OP_SEQ_ALIGN, r
-        with torch.cuda.device(self.dev):
-            st = torch.cuda.current_stream(self.dev).cuda_stream
-            L.check(L.load().aew_run_plan(C.cast(ops, C.c_void_p), len(self.recs), C.c_void_p(st), C.byref(fail)), what,
-                    fail.value if fail.value >= 0 else None)
-        return self
+            self._add(r, self.ws, lo)
 
 
 class Alignment:
@@ -251,33 +277,16 @@ def search_pair_table(lens_q: Sequence[int], lens_d: Sequence[int], pairs: np.nd
     return t, int(ld.sum()), int(np.where(lq > STRIP, ld, 0).max())
 
 
-def _upload(table: np.ndarray, dev) -> torch.Tensor:
-    """The bytes of a host table on the device, copied from pinned memory behind the stream: the host does not wait."""
-    host = torch.empty(max(table.nbytes, 1), dtype=torch.uint8, pin_memory=True)
-    host.numpy()[:table.nbytes] = table.view(np.uint8).reshape(-1)
-    return host.to(dev, non_blocking=True)
-
-
-class _SearchLaunch:
+class _SearchLaunch(_SeqPlan):
     """The op record of one search and everything it points to."""
+    KIND, FIELD, NOUN = L.OP_SEQ_SEARCH, "search", "search"
 
     def __init__(self, metric: int, rank: int, rq: Ragged, rd: Ragged, pairs: np.ndarray, n_hits: int, min_len: int,
                  max_len: int):
-        dev = rq.flat.device
-        if rd.flat.device != dev:
-            raise L.AewError(f"the two sides lie on different devices ('{dev}' and '{rd.flat.device}')")
-        if rq.D != rd.D:
-            raise L.AewError(f"the two sides have {rq.D} and {rd.D} channels")
-        if not 1 <= rq.D <= L.ALIGN_MAX_D:
-            raise L.AewError(f"D must lie in [1, {L.ALIGN_MAX_D}], got {rq.D}")
-        if dev.type != "cuda":
-            raise L.AewError(f"the search runs on the GPU only (tensor on '{dev}'); there is no CPU path")
-        self.dev, self.P = dev, len(pairs)
-        tq, td = rq.table(), rd.table()
+        dev = self._open(rq, rd)
+        P = self.P = len(pairs)
         tp, n_prof, wstride = search_pair_table(rq.length, rd.length, pairs)
-        self.host = (tq, td, tp)                                     # the launcher reads these at every launch
-        self.tables = tuple(_upload(t, dev) for t in self.host)
-        P = self.P
+        self._tables(tp)
         self.prof = (torch.empty(max(n_prof, 1), dtype=torch.float32, device=dev),
                      torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev),
                      torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev))
@@ -288,30 +297,14 @@ class _SearchLaunch:
         self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ws = torch.empty(3 * P * wstride, dtype=torch.float32, device=dev) if wstride else None
         self.prof_base, self.doc_len = tp["prof_base"].copy(), np.asarray(rd.length, np.int64)[pairs[:, 1]]
-        self.keep = (rq.flat, rd.flat)
-        r = self.rec = L.SeqSearch()
+        r = L.SeqSearch()
         r.metric, r.rank, r.D, r.n_pairs = metric, rank, rq.D, P
         r.n_hits, r.min_len, r.max_len = n_hits, min_len, max_len
-        r.seq_a, r.seq_a_host, r.n_a = self.tables[0].data_ptr(), tq.ctypes.data, len(tq)
-        r.seq_b, r.seq_b_host, r.n_b = self.tables[1].data_ptr(), td.ctypes.data, len(td)
-        r.pairs, r.pairs_host = self.tables[2].data_ptr(), tp.ctypes.data
-        r.feat_a, r.n_feat_a = (rq.flat.data_ptr() if rq.flat.numel() else None), rq.flat.numel()
-        r.feat_b, r.n_feat_b = (rd.flat.data_ptr() if rd.flat.numel() else None), rd.flat.numel()
         r.prof_cost, r.prof_steps, r.prof_start = (x.data_ptr() for x in self.prof)
         r.n_prof = n_prof
         r.hits, r.hit_cost, r.hit_steps = self.hits.data_ptr(), self.cost.data_ptr(), self.steps.data_ptr()
         r.count, r.bad = self.count.data_ptr(), self.bad.data_ptr()
-        if self.ws is not None:
-            r.ws, r.ws_bytes = self.ws.data_ptr(), 4 * self.ws.numel()
-
-    def run(self, what: str):
-        op, fail = L.Op(), C.c_int(-1)
-        op.kind, op.u.search = L.OP_SEQ_SEARCH, self.rec
-        with torch.cuda.device(self.dev):
-            st = torch.cuda.current_stream(self.dev).cuda_stream
-            L.check(L.load().aew_run_plan(C.byref(op), 1, C.c_void_p(st), C.byref(fail)), what,
-                    fail.value if fail.value >= 0 else None)
-        return self
+        self._add(r, self.ws)
 
 
 class Matches:
@@ -425,7 +418,7 @@ def edit_distance(a, b=None, pairs=None, collapse: bool = False) -> EditDistance
     run = _Launches(L.ALIGN_EDIT, 0, ra, rb, pr, False, None).run("edit_distance()")
     la, lb = np.asarray(ra.length, np.int64)[pr[:, 0]], np.asarray(rb.length, np.int64)[pr[:, 1]]
     longest = np.maximum(la, lb)
-    denom = torch.from_numpy(np.maximum(longest, 1).astype(np.float32)).to(run.dev)       # (both empty: 0 / 1)
+    denom = _upload(np.maximum(longest, 1).astype(np.float32), run.dev).view(torch.float32)   # (both empty: 0 / 1)
     return EditDistances(run.steps, run.steps.to(torch.float32) / denom, la, lb)
 
 

@@ -12,12 +12,18 @@
 // (ring[column & 127][lane]: a lane reads back only what it wrote itself, bank = lane, no conflict); (B) the 64 sweep
 // steps that have all their columns by then.  EDIT needs no ring: the B symbols travel up the lanes, one lane per step.
 //
+// The DTW strip loop is ONE device function, align_sweep<DR, SUB>: k_align_dtw calls it with SUB = false, k_search_sweep
+// (aew_search.hip, subsequence DTW) with SUB = true; what only one of the two carries is compiled out of the other.
+// The two ops also share the device pair loader (seq_load_pair), the host checks of the fields the two records have in
+// common (align_check_record) and the ladder D -> DR (align_dispatch_D).
+//
 // Nothing here waits on another wave: no __syncthreads (the waves of a block share nothing), no flag, no atomic but the
 // count of pairs that are not finite.  The path kernel is a second launch behind the first on the same stream.
 // Part of the library's one translation unit (aewavenet.hip includes it behind aew_score.hip).
 #pragma once
 #include "aew_common.h"
 #include <math.h>
+#include <type_traits>
 
 #define AEW_ALIGN_WAVES 2          // waves (pairs) per workgroup of the DTW kernel: 2 x 32 KiB of ring = 64 KiB of LDS
 #define AEW_ALIGN_EDIT_WAVES 4     // the EDIT kernel holds no LDS
@@ -34,8 +40,8 @@ __host__ __device__ __forceinline__ int align_seq_ok(const aew_align_seq_t& s, i
     const int64_t last = s.base + (int64_t)(s.len - 1) * s.frame_stride + (int64_t)(D - 1) * s.chan_stride;   // < 2^50 + 2^60 + 2^48
     return last < n_elems;
 }
-__host__ __device__ __forceinline__ int align_pair_ok(const aew_align_pair_t& p, int n_a, int n_b) {
-    return p.a >= 0 && p.a < n_a && p.b >= 0 && p.b < n_b;
+__host__ __device__ __forceinline__ int align_pair_ok(int a, int b, int n_a, int n_b) {
+    return a >= 0 && a < n_a && b >= 0 && b < n_b;
 }
 // 1 if the pair's n * m back bytes and - where a path is kept - its n + m - 1 path entries lie inside their buffers
 __host__ __device__ __forceinline__ int align_room_ok(const aew_align_pair_t& p, int n, int m, int64_t n_back, bool path, int64_t n_path) {
@@ -46,23 +52,31 @@ __host__ __device__ __forceinline__ int align_room_ok(const aew_align_pair_t& p,
     return 1;
 }
 
-// what a wave needs of its pair, read and checked from the device copies; ok = 0: the pair is left alone
-struct align_pair_view {
-    aew_align_pair_t pr;
+// what a wave needs of its pair, read and checked from the device copies; ok = 0: the pair is left alone.  Rec is
+// aew_seq_align_t or aew_seq_search_t, Pair its pair record; each op puts only its own room check on top
+template <class Pair>
+struct seq_pair_view {
+    Pair pr;
     aew_align_seq_t sa, sb;
     int ok;
 };
-__device__ __forceinline__ align_pair_view align_load_pair(const aew_seq_align_t& p, int pi, int64_t wstride) {
-    align_pair_view v;
+template <class Rec>
+__device__ __forceinline__ auto seq_load_pair(const Rec& p, int pi, int64_t wstride) {
+    seq_pair_view<std::decay_t<decltype(p.pairs[0])>> v;
     v.ok = 0;
     v.pr = p.pairs[pi];
-    if (!align_pair_ok(v.pr, p.n_a, p.n_b)) return v;
+    if (!align_pair_ok(v.pr.a, v.pr.b, p.n_a, p.n_b)) return v;
     v.sa = p.seq_a[v.pr.a];
     v.sb = p.seq_b[v.pr.b];
     if (!align_seq_ok(v.sa, p.D, p.n_feat_a) || !align_seq_ok(v.sb, p.D, p.n_feat_b)) return v;
-    if (p.back && !align_room_ok(v.pr, v.sa.len, v.sb.len, p.n_back, p.path != nullptr, p.n_path)) return v;
     if (v.sa.len > 64 && v.sb.len > 0 && (!p.ws || v.sb.len > wstride)) return v;   // (the tables changed under a captured graph)
     v.ok = 1;
+    return v;
+}
+typedef seq_pair_view<aew_align_pair_t> align_pair_view;
+__device__ __forceinline__ align_pair_view align_load_pair(const aew_seq_align_t& p, int pi, int64_t wstride) {
+    align_pair_view v = seq_load_pair(p, pi, wstride);
+    if (v.ok && p.back && !align_room_ok(v.pr, v.sa.len, v.sb.len, p.n_back, p.path != nullptr, p.n_path)) v.ok = 0;
     return v;
 }
 
@@ -82,31 +96,46 @@ __device__ __forceinline__ int64_t align_lane(int64_t v, int l) {
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
-// ---- DTW ---------------------------------------------------------------------------------------------------------------
+// ---- the DTW sweep, for AEW_OP_SEQ_ALIGN and AEW_OP_SEQ_SEARCH -------------------------------------------------------------
+// what the sweep reads and writes of one pair (n, m >= 1, every record checked)
+struct align_sweep_in {
+    const float *A, *B;                                 // element (0, 0) of the two sequences
+    int64_t afs, acs, bfs, bcs;
+    int n, m, D, metric;
+    float* wsC;                                         // the boundary row: m entries each (formed, not followed, where the
+    int *wsS, *wsB;                                     // record's ws is NULL); wsB: SUB only
+    uint8_t* back;                                      // !SUB: n * m back bytes, or NULL
+    float* pc;                                          // SUB: the profile, m entries each
+    int *ps, *pb;
+};
+struct align_sweep_out {
+    float C;                                            // what each lane carried last: lane (n - 1) & 63 holds cell (n-1, m-1)
+    int S;
+    bool bad;                                           // this lane met a local distance that is not finite
+};
+// the sweep's input as both ops fill it; the caller adds `back`, or wsB and the profile
+template <class Rec, class View>
+__device__ __forceinline__ align_sweep_in align_sweep_of(const Rec& p, const View& v, int pi, int64_t wstride) {
+    align_sweep_in q = {};
+    q.A = (const float*)p.feat_a + v.sa.base;
+    q.B = (const float*)p.feat_b + v.sb.base;
+    q.afs = v.sa.frame_stride; q.acs = v.sa.chan_stride; q.bfs = v.sb.frame_stride; q.bcs = v.sb.chan_stride;
+    q.n = v.sa.len; q.m = v.sb.len; q.D = p.D; q.metric = p.metric;
+    q.wsC = (float*)p.ws + (int64_t)pi * wstride;
+    q.wsS = (int*)p.ws + ((int64_t)p.n_pairs + pi) * wstride;
+    return q;
+}
 // DR > 0: D <= DR, the lane's A row in DR registers (zeros behind D: t = 0 - 0, acc + 0 * 0 = acc, the same bits).
 // DR == 0: any D, the A row is read again for every column.
-template <int DR>
-__global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_align_dtw(const aew_seq_align_t p, const int64_t wstride) {
-    __shared__ float ring_all[AEW_ALIGN_WAVES][AEW_ALIGN_RING * 64];
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int pi = blockIdx.x * AEW_ALIGN_WAVES + w;
-    if (pi >= p.n_pairs) return;                                                 // wave-uniform, like every return below
-    const align_pair_view v = align_load_pair(p, pi, wstride);
-    if (!v.ok) return;
-    const int n = v.sa.len, m = v.sb.len, D = p.D;
-    if (n == 0 || m == 0) {
-        if (lane == 0) { p.cost[pi] = INFINITY; p.steps[pi] = 0; }
-        return;
-    }
-    float* ring = ring_all[w];
-    const float* A = (const float*)p.feat_a + v.sa.base;
-    const float* B = (const float*)p.feat_b + v.sb.base;
-    const int64_t afs = v.sa.frame_stride, acs = v.sa.chan_stride, bfs = v.sb.frame_stride, bcs = v.sb.chan_stride;
-    float* wsC = (float*)p.ws + (int64_t)pi * wstride;                           // (formed, not followed, where ws is NULL)
-    int* wsS = (int*)p.ws + ((int64_t)p.n_pairs + pi) * wstride;
-    uint8_t* back = p.back ? p.back + v.pr.back_base : nullptr;
-    const bool sq = p.metric == AEW_ALIGN_SQEUCLID;
+// SUB: subsequence DTW.  Row 0 has no left predecessor - every column starts a match - so the start column (B, O beside
+// C, S) travels with every carried value, through a third boundary row; the lane that owns row n - 1 stores the three
+// profile entries of each column; there is no back byte.  Without SUB none of that exists.
+template <int DR, bool SUB>
+__device__ __forceinline__ align_sweep_out align_sweep(const align_sweep_in& q, float* ring, const int lane) {
+    const float *A = q.A, *B = q.B;
+    const int64_t afs = q.afs, acs = q.acs, bfs = q.bfs, bcs = q.bcs;
+    const int n = q.n, m = q.m, D = q.D;
+    const bool sq = q.metric == AEW_ALIGN_SQEUCLID;
     const int nchunk = (m + 63 + 63) >> 6;                                       // sweep steps t = 0 .. m + 62
     bool bad = false;
     float cL = 0.f;
@@ -121,8 +150,9 @@ __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_align_dtw(const aew_se
             for (int k = 0; k < DR; ++k) a[k] = k < D ? arow[k * acs] : 0.f;
         }
         const bool keep_bottom = i0 + 64 < n;                                    // a strip follows: its top row is this one's bottom
+        const bool last_row = i == n - 1;                                        // (SUB) this lane's cells are the profile
         float upPrevC = 0.f, topC = 0.f;
-        int upPrevS = 0, topS = 0;
+        int upPrevS = 0, topS = 0, upPrevB = 0, topB = 0, bL = 0;
         cL = 0.f; sL = 0;
         for (int c = 0; c < nchunk; ++c) {
             const int j0 = c << 6;
@@ -159,44 +189,86 @@ __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_align_dtw(const aew_se
                 ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
             }
             // the top row's columns [j0, j0 + 64): lane l holds column j0 + l
-            if (i0 > 0 && j0 + lane < m) { topC = wsC[j0 + lane]; topS = wsS[j0 + lane]; }
+            if (i0 > 0 && j0 + lane < m) {
+                topC = q.wsC[j0 + lane]; topS = q.wsS[j0 + lane];
+                if constexpr (SUB) topB = q.wsB[j0 + lane];
+            }
             // (B) sweep steps t = j0 .. j0 + 63
             float dnext = ring[((j0 - lane) & (AEW_ALIGN_RING - 1)) * 64 + lane];
             for (int tt = 0; tt < 64; ++tt) {
                 const int j = j0 + tt - lane;
                 float upC = align_up1(cL);
-                int upS = align_up1(sL);
+                int upS = align_up1(sL), upB = 0;
+                if constexpr (SUB) upB = align_up1(bL);
                 const float tC = align_lane(topC, tt);
                 const int tS = align_lane(topS, tt);
                 if (lane == 0) { upC = tC; upS = tS; }
+                if constexpr (SUB) {
+                    const int tB = align_lane(topB, tt);
+                    if (lane == 0) upB = tB;
+                }
                 const float d = dnext;
                 dnext = ring[((j + 1) & (AEW_ALIGN_RING - 1)) * 64 + lane];      // (the next step's, fetched under this one)
-                // selects, not branches: the lanes of a step differ in which predecessors exist
+                // selects, not branches: the lanes of a step differ in which predecessors exist.  The terms in SUB state at
+                // compile time what SUB implies - has_left only under has_up; row 0, all origins, uses none of b1 .. o2 -
+                // and keep the serial chain of each mode as short as it was alone: one more scalar op per step costs ~1 %.
                 const bool on = row_on && j >= 0 && j < m;
-                const bool has_up = i > 0, has_left = j > 0;
-                const bool take_up = has_up && (!has_left || upC < upPrevC);     // (i-1, j) beats (i-1, j-1), or that one is missing
+                const bool has_up = i > 0, has_left = SUB ? (has_up && j > 0) : (j > 0);
+                const bool take_up = (SUB || has_up) && (!has_left || upC < upPrevC);    // (i-1, j) beats (i-1, j-1), or that one is missing
                 const float b1 = take_up ? upC : upPrevC;
                 const int s1 = take_up ? upS : upPrevS;
-                const bool take_left = has_left && (!has_up || cL < b1);         // (i, j-1) beats the better of the two
+                const int o1 = take_up ? upB : upPrevB;                          // (the start column: zeros without SUB, and unused)
+                const bool take_left = has_left && ((!SUB && !has_up) || cL < b1);       // (i, j-1) beats the better of the two
                 const float b2 = take_left ? cL : b1;
                 const int s2 = take_left ? sL : s1;
-                const bool origin = !has_up && !has_left;
+                const int o2 = take_left ? bL : o1;
+                const bool origin = !has_up && (SUB || !has_left);               // (SUB: all of row 0)
                 const float C = origin ? d : d + b2;
                 const int S = origin ? 1 : s2 + 1;
-                const int which = take_left ? 2 : (take_up ? 1 : 0);
+                const int O = origin ? j : o2;
+                const int which = take_left ? 2 : (take_up ? 1 : 0);             // (the back byte: unused under SUB)
                 if (on) {
-                    if (back) back[(int64_t)i * m + j] = (uint8_t)which;
-                    if (keep_bottom && lane == 63) { wsC[j] = C; wsS[j] = S; }
+                    if constexpr (SUB) {
+                        if (last_row) { q.pc[j] = C; q.ps[j] = S; q.pb[j] = O; }
+                    } else {
+                        if (q.back) q.back[(int64_t)i * m + j] = (uint8_t)which;
+                    }
+                    if (keep_bottom && lane == 63) {
+                        q.wsC[j] = C; q.wsS[j] = S;
+                        if constexpr (SUB) q.wsB[j] = O;
+                    }
                 }
                 upPrevC = on ? upC : upPrevC; upPrevS = on ? upS : upPrevS;
                 cL = on ? C : cL; sL = on ? S : sL;
+                if constexpr (SUB) { upPrevB = on ? upB : upPrevB; bL = on ? O : bL; }
             }
         }
         __threadfence();                                                         // the bottom row's stores, before the next strip loads them
     }
-    const float outC = __shfl(cL, (n - 1) & 63, 64);
-    const int outS = __shfl(sL, (n - 1) & 63, 64);
-    const bool any_bad = __any(bad ? 1 : 0) != 0;
+    return {cL, sL, bad};
+}
+
+// ---- DTW ---------------------------------------------------------------------------------------------------------------
+template <int DR>
+__global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_align_dtw(const aew_seq_align_t p, const int64_t wstride) {
+    __shared__ float ring_all[AEW_ALIGN_WAVES][AEW_ALIGN_RING * 64];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * AEW_ALIGN_WAVES + w;
+    if (pi >= p.n_pairs) return;                                                 // wave-uniform, like every return below
+    const align_pair_view v = align_load_pair(p, pi, wstride);
+    if (!v.ok) return;
+    const int n = v.sa.len, m = v.sb.len;
+    if (n == 0 || m == 0) {
+        if (lane == 0) { p.cost[pi] = INFINITY; p.steps[pi] = 0; }
+        return;
+    }
+    align_sweep_in q = align_sweep_of(p, v, pi, wstride);
+    q.back = p.back ? p.back + v.pr.back_base : nullptr;
+    const align_sweep_out r = align_sweep<DR, false>(q, ring_all[w], lane);
+    const float outC = __shfl(r.C, (n - 1) & 63, 64);
+    const int outS = __shfl(r.S, (n - 1) & 63, 64);
+    const bool any_bad = __any(r.bad ? 1 : 0) != 0;
     if (lane == 0) {
         p.cost[pi] = any_bad ? NAN : outC;
         p.steps[pi] = any_bad ? 0 : outS;
@@ -287,51 +359,76 @@ __global__ __launch_bounds__(64 * AEW_ALIGN_EDIT_WAVES) void k_align_edit(const 
     if (lane == 0) { p.cost[pi] = (float)outE; p.steps[pi] = outE; }
 }
 
-// ---- the launcher ------------------------------------------------------------------------------------------------------
-static int launch_seq_align(const aew_seq_align_t& p, hipStream_t st) {
-    const bool edit = p.mode == AEW_ALIGN_EDIT;
-    if (p.mode != AEW_ALIGN_DTW && !edit) return AEW_E_ARG;
-    if (!edit && p.metric != AEW_ALIGN_EUCLID && p.metric != AEW_ALIGN_SQEUCLID) return AEW_E_ARG;
-    if (p.D < 1 || p.D > AEW_ALIGN_MAX_D || (edit && p.D != 1)) return AEW_E_ARG;
+// ---- the launchers' shared parts (launch_seq_search, aew_search.hip, is the other caller) ------------------------------
+// The host checks of what aew_seq_align_t and aew_seq_search_t have in common, in the order that fixes which code a
+// record with several defects gets: the fields (AEW_E_ARG) - own_ok is the verdict on the op's own ones -, the pointers'
+// alignment (AEW_E_ALIGN; own_ptrs: the op's own 4-byte pointers or-ed together), then every record of the host tables
+// (AEW_E_ARG), with room(pair, n, m) the op's own check of a pair.  frames: fp32 frames under a metric, else int64
+// symbols.  ws_col: workspace bytes per pair and column.  -> 0 and *wstride_out, the longest B side among the pairs
+// that need boundary rows.
+template <class Rec, class Room>
+static int align_check_record(const Rec& p, bool frames, bool own_ok, uintptr_t own_ptrs, int ws_col, Room room, int64_t* wstride_out) {
+    if (frames && p.metric != AEW_ALIGN_EUCLID && p.metric != AEW_ALIGN_SQEUCLID) return AEW_E_ARG;
+    if (p.D < 1 || p.D > AEW_ALIGN_MAX_D) return AEW_E_ARG;
     if (p.n_pairs < 1 || p.n_pairs > (1 << 24) || p.n_a < 1 || p.n_b < 1) return AEW_E_ARG;
-    if (!p.seq_a || !p.seq_a_host || !p.seq_b || !p.seq_b_host || !p.pairs || !p.pairs_host || !p.cost || !p.steps || !p.bad)
-        return AEW_E_ARG;
+    if (!p.seq_a || !p.seq_a_host || !p.seq_b || !p.seq_b_host || !p.pairs || !p.pairs_host) return AEW_E_ARG;
     const int64_t fmax = (int64_t)1 << 50;
     if (p.n_feat_a < 0 || p.n_feat_a > fmax || p.n_feat_b < 0 || p.n_feat_b > fmax) return AEW_E_ARG;
     if ((p.n_feat_a > 0 && !p.feat_a) || (p.n_feat_b > 0 && !p.feat_b)) return AEW_E_ARG;
-    if ((p.path && !p.back) || (edit && (p.back || p.path))) return AEW_E_ARG;
-    if ((p.back && p.n_back < 0) || (p.path && p.n_path < 0) || p.ws_bytes < 0) return AEW_E_ARG;
+    if (p.ws_bytes < 0 || !own_ok) return AEW_E_ARG;
     if (((uintptr_t)p.seq_a | (uintptr_t)p.seq_a_host | (uintptr_t)p.seq_b | (uintptr_t)p.seq_b_host | (uintptr_t)p.pairs |
          (uintptr_t)p.pairs_host) & 7) return AEW_E_ALIGN;
-    if (((uintptr_t)p.feat_a | (uintptr_t)p.feat_b) & (edit ? 7 : 3)) return AEW_E_ALIGN;
-    if (((uintptr_t)p.cost | (uintptr_t)p.steps | (uintptr_t)p.bad | (uintptr_t)p.ws | (uintptr_t)p.path) & 3) return AEW_E_ALIGN;
+    if (((uintptr_t)p.feat_a | (uintptr_t)p.feat_b) & (frames ? 3 : 7)) return AEW_E_ALIGN;
+    if (((uintptr_t)p.ws | own_ptrs) & 3) return AEW_E_ALIGN;
     for (int i = 0; i < p.n_a; ++i)
         if (!align_seq_ok(p.seq_a_host[i], p.D, p.n_feat_a)) return AEW_E_ARG;
     for (int i = 0; i < p.n_b; ++i)
         if (!align_seq_ok(p.seq_b_host[i], p.D, p.n_feat_b)) return AEW_E_ARG;
-    int64_t wstride = 0;                                                         // longest B side among the pairs that need boundary rows
+    int64_t wstride = 0;
     for (int i = 0; i < p.n_pairs; ++i) {
-        const aew_align_pair_t& pr = p.pairs_host[i];
-        if (!align_pair_ok(pr, p.n_a, p.n_b)) return AEW_E_ARG;
+        const auto& pr = p.pairs_host[i];
+        if (!align_pair_ok(pr.a, pr.b, p.n_a, p.n_b)) return AEW_E_ARG;
         const int n = p.seq_a_host[pr.a].len, m = p.seq_b_host[pr.b].len;
-        if (p.back && !align_room_ok(pr, n, m, p.n_back, p.path != nullptr, p.n_path)) return AEW_E_ARG;
+        if (!room(pr, n, m)) return AEW_E_ARG;
         if (n > 64 && m > wstride) wstride = m;
     }
-    if (wstride > 0 && (!p.ws || p.ws_bytes / 8 / p.n_pairs < wstride)) return AEW_E_ARG;
+    if (wstride > 0 && (!p.ws || p.ws_bytes / ws_col / p.n_pairs < wstride)) return AEW_E_ARG;
+    *wstride_out = wstride;
+    return 0;
+}
+
+// D -> DR, the one ladder: f(std::integral_constant<int, DR>) with the least DR >= D of 4 .. 64, or 0 (any D)
+template <class F>
+static void align_dispatch_D(int D, F f) {
+    if (D <= 4) f(std::integral_constant<int, 4>());
+    else if (D <= 8) f(std::integral_constant<int, 8>());
+    else if (D <= 12) f(std::integral_constant<int, 12>());
+    else if (D <= 16) f(std::integral_constant<int, 16>());
+    else if (D <= 32) f(std::integral_constant<int, 32>());
+    else if (D <= 64) f(std::integral_constant<int, 64>());
+    else f(std::integral_constant<int, 0>());
+}
+
+// ---- the launcher ------------------------------------------------------------------------------------------------------
+static int launch_seq_align(const aew_seq_align_t& p, hipStream_t st) {
+    const bool edit = p.mode == AEW_ALIGN_EDIT;
+    const bool own_ok = (p.mode == AEW_ALIGN_DTW || edit) && !(edit && p.D != 1) && p.cost && p.steps && p.bad &&
+                        !(p.path && !p.back) && !(edit && (p.back || p.path)) && !(p.back && p.n_back < 0) && !(p.path && p.n_path < 0);
+    const uintptr_t own_ptrs = (uintptr_t)p.cost | (uintptr_t)p.steps | (uintptr_t)p.bad | (uintptr_t)p.path;
+    int64_t wstride = 0;
+    const int bad = align_check_record(p, !edit, own_ok, own_ptrs, 8, [&](const aew_align_pair_t& pr, int n, int m) {
+        return !p.back || align_room_ok(pr, n, m, p.n_back, p.path != nullptr, p.n_path);
+    }, &wstride);
+    if (bad) return bad;
     if (edit) {
         const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_EDIT_WAVES - 1) / AEW_ALIGN_EDIT_WAVES);
         hipLaunchKernelGGL(k_align_edit, dim3(g), dim3(64 * AEW_ALIGN_EDIT_WAVES), 0, st, p, wstride);
         return (int)hipGetLastError();
     }
     const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_WAVES - 1) / AEW_ALIGN_WAVES);
-    const dim3 blk(64 * AEW_ALIGN_WAVES);
-    if (p.D <= 4) hipLaunchKernelGGL(k_align_dtw<4>, dim3(g), blk, 0, st, p, wstride);
-    else if (p.D <= 8) hipLaunchKernelGGL(k_align_dtw<8>, dim3(g), blk, 0, st, p, wstride);
-    else if (p.D <= 12) hipLaunchKernelGGL(k_align_dtw<12>, dim3(g), blk, 0, st, p, wstride);
-    else if (p.D <= 16) hipLaunchKernelGGL(k_align_dtw<16>, dim3(g), blk, 0, st, p, wstride);
-    else if (p.D <= 32) hipLaunchKernelGGL(k_align_dtw<32>, dim3(g), blk, 0, st, p, wstride);
-    else if (p.D <= 64) hipLaunchKernelGGL(k_align_dtw<64>, dim3(g), blk, 0, st, p, wstride);
-    else hipLaunchKernelGGL(k_align_dtw<0>, dim3(g), blk, 0, st, p, wstride);
+    align_dispatch_D(p.D, [&](auto dr) {
+        hipLaunchKernelGGL(k_align_dtw<decltype(dr)::value>, dim3(g), dim3(64 * AEW_ALIGN_WAVES), 0, st, p, wstride);
+    });
     int rc = (int)hipGetLastError();
     if (rc || !p.path) return rc;
     hipLaunchKernelGGL(k_align_path, dim3((unsigned)p.n_pairs), dim3(64), 0, st, p, wstride);

@@ -291,6 +291,30 @@ def test_a_call_split_by_max_back_bytes_gives_the_bits_of_the_unsplit_call():
         plain.path(0)
 
 
+def test_dtw_and_edit_distance_do_not_synchronise_the_host():
+    A, B = _seqs("normal", 3, SMALL)
+    a, b = [_dev(x) for x in A], [_dev(x) for x in B]
+    rs = np.random.RandomState(2)
+    sa, sb = [_dev(rs.randint(0, 2, n).astype(np.int64)) for n in SMALL], [_dev(rs.randint(0, 2, n).astype(np.int64)) for n in SMALL]
+    pairs = [(x, y) for x in range(len(SMALL)) for y in range(len(SMALL)) if x != y]       # 12 pairs, 3 of 129 A frames
+    warm = AL.dtw(a, b, pairs=pairs), AL.dtw(a, b, pairs=pairs, return_path=True), AL.edit_distance(sa, sb, pairs=pairs, collapse=False)
+    torch.cuda.synchronize()
+    prev = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")                                  # .item() / .cpu() / a blocking copy would raise
+    try:
+        al = AL.dtw(a, b, pairs=pairs)
+        alp = AL.dtw(a, b, pairs=pairs, return_path=True)
+        ed = AL.edit_distance(sa, sb, pairs=pairs, collapse=False)
+    finally:
+        torch.cuda.set_sync_debug_mode(prev)
+    for got, want in ((al, warm[0]), (alp, warm[1])):
+        assert torch.equal(_bits(got.cost), _bits(want.cost)) and torch.equal(got.steps, want.steps)
+        assert torch.equal(_bits(got.mean), _bits(want.mean)) and int(got.bad[0]) == 0
+    assert torch.equal(alp._run.path, warm[1]._run.path) and int(alp.steps.min()) > 0
+    assert torch.equal(ed.distance, warm[2].distance) and torch.equal(_bits(ed.rate), _bits(warm[2].rate))
+    assert int(ed.distance.max()) > 0
+
+
 # ---- refused records -----------------------------------------------------------------------------------------------------
 def test_malformed_records_are_refused_with_nothing_launched():
     rs = np.random.RandomState(5)
