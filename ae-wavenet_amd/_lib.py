@@ -26,7 +26,7 @@ EF_OUT2_COPY = 1 << 10
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
  OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE, OP_SEQ_ALIGN,
- OP_FRAME_STITCH, OP_CODE_SEGMENT, OP_SEQ_SEARCH) = range(1, 50)
+ OP_FRAME_STITCH, OP_CODE_SEGMENT, OP_SEQ_SEARCH, OP_ABX_COUNT) = range(1, 51)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -377,6 +377,27 @@ class SeqSearch(C.Structure):
                 ("ws", vp), ("ws_bytes", i64)]
 
 
+ABX_WITHIN, ABX_ACROSS = 0, 1
+ABX_MAX_N = 16384
+
+
+class AbxGroup(C.Structure):
+    """aew_abx_group_t: one non-empty (category, speaker) group - its sorted positions [lo, hi), its category and speaker
+    indices.  ABX_GROUP_DTYPE is the same record for numpy."""
+    _fields_ = [("lo", i32), ("hi", i32), ("cat", i32), ("spk", i32)]
+
+
+ABX_GROUP_DTYPE = [("lo", "<i4"), ("hi", "<i4"), ("cat", "<i4"), ("spk", "<i4")]
+
+
+class AbxCount(C.Structure):
+    """aew_abx_count_t: per sorted position x and group g the number of (A, B, X) triples and twice the wrong ones over
+    an N x N distance matrix read through the permutation; the three tables as device and host copies."""
+    _fields_ = [("mode", i32), ("N", i32), ("G", i32), ("C", i32), ("S", i32), ("pad_", i32), ("ld", i64), ("dist", vp),
+                ("perm", vp), ("perm_host", vp), ("groups", vp), ("groups_host", vp), ("partner", vp),
+                ("partner_host", vp), ("n", vp), ("wrong2", vp)]
+
+
 SEG_MAX_K, SEG_MAX_D = 4096, 4096
 
 
@@ -547,7 +568,8 @@ class _OpU(C.Union):
                 ("gwel", GradWelford), ("ssel", SegSelect), ("accum", Accum), ("clk", CodeLookup), ("crun", CodeRuns),
                 ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
                 ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce),
-                ("align", SeqAlign), ("fstitch", FrameStitch), ("cseg", CodeSegment), ("search", SeqSearch)]
+                ("align", SeqAlign), ("fstitch", FrameStitch), ("cseg", CodeSegment), ("search", SeqSearch),
+                ("abx", AbxCount)]
 
 
 class Op(C.Structure):
@@ -565,7 +587,8 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_CODE_LOOKUP: "clk", OP_CODE_RUNS: "crun", OP_ADAM_GROUPS: "adamg", OP_EVAL_GROUPS: "evg",
             OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst",
             OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred", OP_SEQ_ALIGN: "align",
-            OP_FRAME_STITCH: "fstitch", OP_CODE_SEGMENT: "cseg", OP_SEQ_SEARCH: "search"}
+            OP_FRAME_STITCH: "fstitch", OP_CODE_SEGMENT: "cseg", OP_SEQ_SEARCH: "search",
+            OP_ABX_COUNT: "abx"}
 
 
 
@@ -699,6 +722,7 @@ def load():
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.aew_segment_ws_bytes.argtypes = [C.c_int64, C.c_int, C.POINTER(C.c_int64)]
     lib.aew_segment_host.argtypes = [C.c_void_p]
+    lib.aew_abx_host.argtypes = [C.c_void_p]
     lib.aew_seg_select_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.aew_select_key.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
     lib.aew_uw_chunks.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64,
@@ -710,7 +734,8 @@ def load():
                        (29, AdamTensor), (30, AdamGroups), (31, AdamGrouped), (32, EvalGroups), (34, UttRow), (35, MelTile),
                        (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec), (42, ScoreRow), (43, WavTile),
                        (44, NllStitch), (45, ScoreReduce), (47, AlignSeq), (48, AlignPair), (49, SeqAlign),
-                       (51, SegUtt), (52, FrameStitch), (53, CodeSegment), (55, SearchPair), (56, SeqSearch)):
+                       (51, SegUtt), (52, FrameStitch), (53, CodeSegment), (55, SearchPair), (56, SeqSearch),
+                       (58, AbxGroup), (59, AbxCount)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "
@@ -765,4 +790,4 @@ EXPORTS = ("aew_abi_version", "aew_sizeof", "aew_run_plan", "aew_timing_enable",
            "aew_tuning_set", "aew_run_plan_tuned", "aew_graph_capture_tuned", "aew_nt_chain_build", "aew_nt_chain_dep_tiles", "aew_probe_box", "aew_gemm_nt_small_split", "aew_colsum_det_size", "aew_nt_chain_build_tuned",
            "aew_grad_norm_size", "aew_uw_chunks", "aew_nt_pick", "aew_lc_scatter_needs_zero", "aew_tn_pick", "aew_tn_group_pick", "aew_tn_group_tiles",
            "aew_corpus_locate", "aew_seg_select_size", "aew_select_key", "aew_utterance_locate",
-           "aew_segment_ws_bytes", "aew_segment_host")
+           "aew_segment_ws_bytes", "aew_segment_host", "aew_abx_host")

@@ -9,6 +9,9 @@ states the rule bit for bit).
     err = abx(d_ax, d_bx)                   # ABX error of paired distances, a device scalar
     mt = search(queries, docs, pairs=..., n_hits=3)         # subsequence DTW (AEW_OP_SEQ_SEARCH, csrc/aew_search.hip)
     mt.start, mt.end, mt.cost, mt.steps, mt.mean, mt.count  # (P, n_hits): where each query occurs, best first; mt.profile(p)
+    dist = distance_matrix(items)                           # (N, N) fp32: every pair i < j through dtw(), mirrored, diagonal 0
+    res = abx_score(dist, category, speaker, mode="within") # ABX discriminability of the item set (AEW_OP_ABX_COUNT,
+    res.error, res.pooled, res.by_category, res.n_triples   # csrc/aew_abx.hip); abx_task(items, ...) is the two in one call
 
 `model.code_distance()` and `model.cepstral_distance()` (surface.py) are these calls over the codebook rows of code
 sequences and over the model's own MFCC front-end; `model.search_codes()` and `model.search_wavs()` are `search` over the
@@ -18,6 +21,17 @@ and runs the records as a plan on torch's current stream; every host table (and 
 through `_upload` - pinned, behind the stream.  Nothing
 but `Alignment.path()` (and `edit_distance(collapse=True)`, which has to learn the number of units) synchronises with
 the host.  There is no CPU path: a tensor that is not on the GPU is refused.
+
+ABX over an item set.  `abx_tables` turns the labels into the three host tables of the op (a pure host function),
+`abx_score` uploads them through `_upload`, runs the op as a one-record plan and hands its integer counts to
+`abx_aggregate`, which is pure torch, dense throughout (no step has a data-dependent size, nothing synchronises) and
+therefore also runs on CPU tensors.  The aggregation: the counts of every X are pooled inside a (category of X, category
+of B, speaker of X, speaker of A and B) cell; a cell with triples has the error wrong2 / (2 n); `by_category[cX][cB]` is
+the plain mean of the cells of that category pair over the speaker combinations present, and `error` the plain mean of
+`by_category` over its present ORDERED pairs - so neither a frequent category nor a talkative speaker weighs more than
+another.  With mode "within" (A, B and X of one speaker) and "across" (A and B of one speaker, X of another) these are
+the usual within- and across-speaker ABX scores without a context ("by") label: fold a context into `category` to get
+one.  `pooled` is every triple in one pool.
 """
 from __future__ import annotations
 
@@ -420,6 +434,195 @@ def edit_distance(a, b=None, pairs=None, collapse: bool = False) -> EditDistance
     longest = np.maximum(la, lb)
     denom = _upload(np.maximum(longest, 1).astype(np.float32), run.dev).view(torch.float32)   # (both empty: 0 / 1)
     return EditDistances(run.steps, run.steps.to(torch.float32) / denom, la, lb)
+
+
+def _pair_run(N: int, k0: int, k1: int) -> np.ndarray:
+    """(k1 - k0, 2) int64: the unordered pairs i < j of N items number k0 .. k1 - 1 in row-major order."""
+    first = np.arange(N, dtype=np.int64) * (2 * N - np.arange(N, dtype=np.int64) - 1) // 2    # number of pair (i, i + 1)
+    k = np.arange(k0, k1, dtype=np.int64)
+    i = np.searchsorted(first, k, side="right") - 1
+    return np.stack([i, k - first[i] + i + 1], 1)
+
+
+def distance_matrix(items, metric: str = "euclid", value: str = "mean", max_pairs: int = 1 << 20) -> torch.Tensor:
+    """The (N, N) fp32 matrix of DTW distances between all items: `items` a `Ragged` or a list of (n_u, D) float32 device
+    tensors as for dtw().  The N (N - 1) / 2 pairs i < j go through dtw()'s op in runs of at most max_pairs pairs (the
+    host pair table and its pinned upload stay bounded; the result does not depend on max_pairs) and each run is
+    mirrored into both triangles by one index write.  value "mean": cost / steps, "cost": the summed distance - entry
+    (i, j) carries the bits dtw(items, pairs=[(i, j)]) gives, +inf for a pair with an empty side and NaN for one that
+    is not finite.  The diagonal is 0.  Nothing here synchronises with the host."""
+    if metric not in METRICS:
+        raise L.AewError(f"distance_matrix(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    if value not in RANKS:
+        raise L.AewError(f"distance_matrix(): value must be one of {sorted(RANKS)}, got '{value}'")
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise L.AewError(f"distance_matrix(): max_pairs must be positive, got {max_pairs}")
+    ra = _ragged(items, "distance_matrix(): items", torch.float32)
+    dev, N = ra.flat.device, len(ra)
+    if dev.type != "cuda":
+        raise L.AewError(f"the alignment runs on the GPU only (tensor on '{dev}'); there is no CPU path")
+    out = torch.zeros(N, N, dtype=torch.float32, device=dev)
+    P = N * (N - 1) // 2
+    for k0 in range(0, P, max_pairs):
+        pr = _pair_run(N, k0, min(P, k0 + max_pairs))
+        run = _Launches(L.ALIGN_DTW, METRICS[metric], ra, ra, pr, False, None).run("distance_matrix()")
+        v = run.cost / run.steps if value == "mean" else run.cost
+        ij = _upload(np.concatenate([pr, pr[:, ::-1]]), dev).view(torch.int64).reshape(-1, 2)
+        out[ij[:, 0], ij[:, 1]] = torch.cat([v, v])
+    return out
+
+
+ABX_MODES = {"within": L.ABX_WITHIN, "across": L.ABX_ACROSS, "any": L.ABX_WITHIN}
+
+
+class AbxTables:
+    """What abx_tables() returns, all on the host.  perm (N,) int32: the item at every sorted position; groups: (G,)
+    aew_abx_group_t records; partner (C, S) int32: the group of (category index, speaker index) or -1; categories /
+    speakers: the labels by index, in order of first appearance; group_of (N,) int64: the group of every sorted
+    position; mode and the op's own mode."""
+
+    def __init__(self, perm, groups, partner, categories, speakers, mode):
+        self.perm, self.groups, self.partner = perm, groups, partner
+        self.categories, self.speakers, self.mode, self.op_mode = categories, speakers, mode, ABX_MODES[mode]
+        self.group_of = np.repeat(np.arange(len(groups), dtype=np.int64), groups["hi"] - groups["lo"])
+
+    N, G = property(lambda self: len(self.perm)), property(lambda self: len(self.groups))
+    C, S = property(lambda self: len(self.categories)), property(lambda self: len(self.speakers))
+
+    def __iter__(self):
+        return iter((self.perm, self.groups, self.partner, self.categories, self.speakers))
+
+
+def _labels(x, what: str) -> list:
+    x = x.tolist() if isinstance(x, (np.ndarray, torch.Tensor)) else list(x)
+    for v in x:
+        try:
+            hash(v)
+        except TypeError:
+            raise L.AewError(f"abx_tables(): {what} labels must be hashable, got {type(v).__name__}") from None
+    return x
+
+
+def abx_tables(category, speaker=None, mode: str = "within") -> AbxTables:
+    """The host tables of AEW_OP_ABX_COUNT from the labels of N items: category / speaker any sequences of N hashable
+    labels (integers, strings, ...).  mode "within": A, B and X of one speaker; "across": A and B of one speaker, X of
+    another; "any": speaker-blind - every item gets speaker 0 (speaker=None is allowed only here).  The items are sorted
+    stably by (speaker index, category index), indices in order of first appearance.  -> `AbxTables`."""
+    if mode not in ABX_MODES:
+        raise L.AewError(f"abx_tables(): mode must be one of {sorted(ABX_MODES)}, got '{mode}'")
+    cat = _labels(category, "category")
+    N = len(cat)
+    if N < 1:
+        raise L.AewError("abx_tables(): at least one item expected")
+    if speaker is None:
+        if mode != "any":
+            raise L.AewError(f"abx_tables(): mode '{mode}' needs speaker labels; only mode 'any' goes without")
+        spk = [0] * N
+    else:
+        spk = _labels(speaker, "speaker")
+        if len(spk) != N:
+            raise L.AewError(f"abx_tables(): {N} category labels and {len(spk)} speaker labels")
+        if mode == "any":
+            spk = [0] * N
+    cats, spks = list(dict.fromkeys(cat)), list(dict.fromkeys(spk))
+    ci_of, si_of = {c: k for k, c in enumerate(cats)}, {s: k for k, s in enumerate(spks)}
+    ci, si = np.array([ci_of[c] for c in cat], np.int64), np.array([si_of[s] for s in spk], np.int64)
+    perm = np.lexsort((ci, si))                                               # stable: ties keep the items' order
+    key = (si * len(cats) + ci)[perm]
+    lo = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+    groups = np.zeros(len(lo), dtype=L.ABX_GROUP_DTYPE)
+    groups["lo"], groups["hi"] = lo, np.concatenate([lo[1:], [N]])
+    groups["cat"], groups["spk"] = key[lo] % len(cats), key[lo] // len(cats)
+    partner = np.full((len(cats), len(spks)), -1, np.int32)
+    partner[groups["cat"], groups["spk"]] = np.arange(len(lo), dtype=np.int32)
+    return AbxTables(perm.astype(np.int32), groups, partner, cats, spks, mode)
+
+
+class AbxResult:
+    """What abx_score() returns; every tensor lies where the counts lie (the device).  error: fp64 scalar, the mean of
+    by_category over its present ordered pairs (NaN when no cell is valid); pooled: fp64 scalar, all triples in one pool,
+    sum wrong2 / (2 sum n); by_category (C, C) fp64: [cX][cB], NaN where no cell is present; cells: (wrong2, n), two
+    (G, G) int64 sums [group of X][group of B]; n_triples: int64 scalar; n_nan: int64 scalar, the NaNs off the diagonal
+    of the distance matrix (None from abx_aggregate alone); categories / speakers: the labels by index; tables: the
+    `AbxTables`; wrong2 / n: the op's (N, G) counts, rows in sorted order (tables.perm)."""
+
+    def __init__(self, error, pooled, by_category, cells, n_triples, tables, wrong2, n, n_nan=None):
+        self.error, self.pooled, self.by_category, self.cells, self.n_triples = error, pooled, by_category, cells, n_triples
+        self.tables, self.categories, self.speakers = tables, tables.categories, tables.speakers
+        self.wrong2, self.n, self.n_nan = wrong2, n, n_nan
+
+
+def abx_aggregate(wrong2: torch.Tensor, n: torch.Tensor, tables: AbxTables) -> AbxResult:
+    """The op's (N, G) counts (any integer dtype, on any device) -> `AbxResult`: pure torch and dense throughout.  An
+    index_add of the rows over X's group gives the int64 (G, G) sums; a cell with n > 0 has the error wrong2 / (2 n); the
+    mean over the cells present of a category pair gives by_category, the mean over its present pairs the error."""
+    dev, G, C = wrong2.device, tables.G, tables.C
+    if wrong2.shape != (tables.N, G) or n.shape != (tables.N, G) or n.device != dev:
+        raise L.AewError(f"abx_aggregate(): two ({tables.N}, {G}) tensors on one device expected")
+    put = (lambda a: _upload(a, dev).view(torch.int64)) if dev.type == "cuda" else torch.from_numpy
+    group_of, cat = put(tables.group_of), put(tables.groups["cat"].astype(np.int64))
+    W = torch.zeros(G, G, dtype=torch.int64, device=dev).index_add_(0, group_of, wrong2.to(torch.int64))
+    Nn = torch.zeros(G, G, dtype=torch.int64, device=dev).index_add_(0, group_of, n.to(torch.int64))
+    present = Nn > 0
+    err = torch.where(present, W.to(torch.float64) / (2.0 * Nn.clamp(min=1).to(torch.float64)), 0.0)
+    pair = (cat[:, None] * C + cat[None, :]).reshape(-1)
+    total = torch.zeros(C * C, dtype=torch.float64, device=dev).index_add_(0, pair, err.reshape(-1))
+    count = torch.zeros(C * C, dtype=torch.float64, device=dev).index_add_(0, pair, present.reshape(-1).to(torch.float64))
+    by_category = (total / count).reshape(C, C)                               # 0 / 0: NaN where nothing is present
+    have = count > 0
+    error = torch.where(have, total / count.clamp(min=1.0), 0.0).sum() / have.sum().to(torch.float64)
+    n_triples = Nn.sum()
+    pooled = W.sum().to(torch.float64) / (2.0 * n_triples.to(torch.float64))
+    return AbxResult(error, pooled, by_category, (W, Nn), n_triples, tables, wrong2, n)
+
+
+def abx_score(dist: torch.Tensor, category, speaker=None, mode: str = "within") -> AbxResult:
+    """ABX discriminability of N labelled items from their (N, N) fp32 device matrix of distances (row X, column A or B;
+    no symmetry is assumed): for every X, every A of X's category and every B of another one - A and B of one speaker,
+    which is X's ("within") or another ("across"); "any" ignores speakers - the triple is wrong when
+    dist[X, A] > dist[X, B] and half wrong when neither is smaller (a tie or a NaN).  AEW_OP_ABX_COUNT counts on the
+    device, abx_aggregate() averages (see the module text for the rule).  A row pitch is passed on (dist[:, :N] of a
+    wider matrix is read in place); any other layout is refused.  N <= 16384.  Nothing here synchronises with the
+    host.  -> `AbxResult`."""
+    if not torch.is_tensor(dist) or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or dist.dtype != torch.float32:
+        raise L.AewError("abx_score(): an (N, N) float32 tensor expected")
+    dev, N = dist.device, int(dist.shape[0])
+    if dev.type != "cuda":
+        raise L.AewError(f"abx_score() runs on the GPU only (tensor on '{dev}'); there is no CPU path")
+    ld = int(dist.stride(0)) if N > 1 else max(int(dist.stride(0)), 1)
+    if N < 1 or (N > 1 and (dist.stride(1) != 1 or ld < N)):
+        raise L.AewError(f"abx_score(): rows of unit stride and a pitch >= N expected, got strides {tuple(dist.stride())}")
+    tb = abx_tables(category, speaker, mode)
+    if tb.N != N:
+        raise L.AewError(f"abx_score(): {tb.N} labels for a matrix of {N} items")
+    partner = np.ascontiguousarray(tb.partner)
+    d_perm, d_groups, d_partner = (_upload(t, dev) for t in (tb.perm, tb.groups, partner))
+    n = torch.empty(N, tb.G, dtype=torch.int32, device=dev)                   # (uint32 words; no count reaches 2^31)
+    wrong2 = torch.empty(N, tb.G, dtype=torch.int32, device=dev)
+    r = L.AbxCount()
+    r.mode, r.N, r.G, r.C, r.S, r.ld = tb.op_mode, N, tb.G, tb.C, tb.S, ld
+    r.dist = dist.data_ptr()
+    r.perm, r.perm_host = d_perm.data_ptr(), tb.perm.ctypes.data
+    r.groups, r.groups_host = d_groups.data_ptr(), tb.groups.ctypes.data
+    r.partner, r.partner_host = d_partner.data_ptr(), partner.ctypes.data
+    r.n, r.wrong2 = n.data_ptr(), wrong2.data_ptr()
+    op, fail = L.Op(), C.c_int(-1)
+    op.kind, op.u.abx = L.OP_ABX_COUNT, r
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.load().aew_run_plan(C.byref(op), 1, C.c_void_p(st), C.byref(fail)), "abx_score()")
+    res = abx_aggregate(wrong2, n, tb)
+    nan = torch.isnan(dist)
+    res.n_nan = nan.sum() - nan.diagonal().sum()
+    return res
+
+
+def abx_task(items, category, speaker=None, mode: str = "within", metric: str = "euclid", value: str = "mean",
+             max_pairs: int = 1 << 20) -> AbxResult:
+    """abx_score(distance_matrix(items, metric, value, max_pairs), category, speaker, mode): the ABX discriminability of
+    labelled sequences under DTW, from the features to the score without a host wait."""
+    return abx_score(distance_matrix(items, metric=metric, value=value, max_pairs=max_pairs), category, speaker, mode)
 
 
 def abx(d_ax: torch.Tensor, d_bx: torch.Tensor) -> torch.Tensor:

@@ -1520,6 +1520,35 @@ class HipModelBase(nn.Module):
         return AL.search(sides[0], sides[1], pairs=pairs, metric="euclid", n_hits=n_hits, rank=rank, min_len=min_len,
                          max_len=max_len)
 
+    # ---- ABX discriminability of a labelled item set over the same two feature sources (align.abx_task) ---------------
+    def abx_codes(self, codes, category, speaker=None, mode: str = "within", metric: str = "euclid", value: str = "mean",
+                  max_pairs: int = 1 << 20):
+        """How well do the code sequences `codes` (a `codes.UtteranceCodes` or a list of 1-D int64 device tensors) keep
+        their categories apart: the ABX error of the item set under DTW over the codebook rows.  category / speaker:
+        one hashable label per item; mode "within" (A, B and X of one speaker), "across" (A and B of one speaker, X of
+        another) or "any" (speakers ignored; speaker=None allowed).  All N (N - 1) / 2 distances are code_distance()'s
+        (align.distance_matrix: metric, value "mean" = cost / steps or "cost", max_pairs pairs per launch), the triples
+        are counted on the device (AEW_OP_ABX_COUNT) -> `align.AbxResult`: error (the mean over category pairs of the
+        mean over speaker combinations), pooled, by_category, n_triples, all device tensors.  The rules of
+        code_distance() apply: a code outside [0, K) raises AewError before anything is compared (that check reads one
+        word back - the only wait); VQ bottlenecks only; the codebook is read, nothing of the model is written and no
+        collective is issued."""
+        from . import align as AL
+        sides, _ = self._code_sides("abx_codes()", codes, None, None)
+        return AL.abx_task(sides[0], category, speaker, mode=mode, metric=metric, value=value, max_pairs=max_pairs)
+
+    def abx_wavs(self, wavs, category, speaker=None, mode: str = "within", expand: bool = True, value: str = "mean",
+                 max_pairs: int = 1 << 20):
+        """The ABX error of the waveforms `wavs` (a list of 1-D device tensors of mu-law values) under DTW over the static
+        cepstra 1 .. n_mfcc - 1 of this model's own front-end - cepstral_distance()'s front half, `expand` as there,
+        Euclidean frames; labels, mode, value, max_pairs and the result as in abx_codes().  It is the score of the
+        model's INPUT features, the figure its codes are compared with.  A waveform too short for
+        `DeviceMfcc.MIN_FRAMES` frames has no frames: its distances are +inf and every triple it enters counts as the
+        order of +inf says.  VQ bottlenecks only; nothing of the model is written and no collective is issued."""
+        from . import align as AL
+        sides = self._cepstral_sides("abx_wavs()", wavs, None, expand)
+        return AL.abx_task(sides[0], category, speaker, mode=mode, metric="euclid", value=value, max_pairs=max_pairs)
+
     def _grads_carried(self):
         """What the coming backward has to ADD to the gradients it writes: None when the gradients were cleared
         (FusedAdam.zero_grad(), or every .grad is None as zero_grad(set_to_none=True) leaves them), else a copy of the

@@ -52,7 +52,10 @@ extern "C" {
  * aew_wav_tile_t / AEW_OP_WAV_TILE, aew_nll_stitch_t / AEW_OP_NLL_STITCH, aew_score_reduce_t / AEW_OP_SCORE_REDUCE;
  * 47 .. 49, aew_align_seq_t, aew_align_pair_t, aew_seq_align_t / AEW_OP_SEQ_ALIGN - index 46 stays unused; 51 .. 53, aew_seg_utt_t,
  * aew_frame_stitch_t / AEW_OP_FRAME_STITCH, aew_code_segment_t / AEW_OP_CODE_SEGMENT - index 50 stays unused; 55 / 56,
- * aew_search_pair_t, aew_seq_search_t / AEW_OP_SEQ_SEARCH - index 54 stays unused). */
+ * aew_search_pair_t, aew_seq_search_t / AEW_OP_SEQ_SEARCH - index 54 stays unused; 58 / 59, aew_abx_group_t,
+ * aew_abx_count_t / AEW_OP_ABX_COUNT with the host function aew_abx_host - index 57 stays unused.  The number does NOT
+ * move for AEW_OP_ABX_COUNT either: one op kind behind the last, a descriptor inside the union's size, no existing
+ * record, op number or function changed). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
 
@@ -1354,6 +1357,59 @@ typedef struct {
     int64_t ws_bytes;
 } aew_seq_search_t;
 
+/* ABX discriminability of a labelled item set (appended to ABI 28; AEW_OP_ABX_COUNT, aew_sizeof 58 / 59 - index 57 stays
+ * unused, it answers -1): over an N x N distance matrix D (row = X, column = A or B; no symmetry is assumed) count, for
+ * every X and every group of B items, the (A, B, X) triples and how many of them D gets wrong.  One launch, one
+ * workgroup per X; nothing waits on another workgroup - no flag, no spin, no atomic, no floating-point sum.
+ *
+ * THE RULE (tests/abx_emulator.py restates it from the labels alone).  Item i carries a category and a speaker.  The
+ * host sorts the items stably by (speaker, category): perm[x] = the item at sorted position x.  The G non-empty
+ * (category, speaker) groups are contiguous ranges [lo, hi) of sorted positions; partner[cat * S + spk] = the group of
+ * that (category index, speaker index), -1 where there is none.  D is read in place through the permutation:
+ * d(x, j) = D[perm[x] * ld + perm[j]].
+ *   cell     For a sorted position x in group (cX, sX) and a group g = (cB, sB), cell (x, g) is VALID when cB != cX, the
+ *            speaker condition holds (WITHIN: sB == sX; ACROSS: sB != sX) and A = group(cX, sB) \ {x} is not empty.  A and
+ *            B share a speaker; X has it too (WITHIN) or another one (ACROSS).
+ *   counts   valid:   n[x][g] = |A| * |g|,  wrong2[x][g] = sum over a in A, b in g of w(d(x, a), d(x, b)),
+ *                     w(p, q) = 2 if p > q; 0 if p < q; 1 otherwise (equal, or a NaN on either side);
+ *            invalid: n[x][g] = wrong2[x][g] = 0.
+ *            Rows of n / wrong2 are SORTED positions.  Every one of the N * G words of both outputs is written.  The sums
+ *            are integers: no order of evaluation changes a bit.  wrong2 / (2 n) is the ABX error of the cell.
+ * The launcher reads the HOST copies of the three tables before anything is launched; the kernel reads the device copies
+ * and forms no address from a value it has not range-checked.  AEW_E_ARG: a mode outside the two, N outside
+ * [1, AEW_ABX_MAX_N] (2 |A| |g| <= 2 (N / 2)^2 then fits 32 bits), G outside [1, N], C or S < 1, N * G > 2^27,
+ * C * S > N * G (the launcher reads every word of the three host tables at every launch: that bounds it), ld < N, a NULL pointer, perm_host no permutation of [0, N), group ranges that do not tile [0, N) in
+ * order (lo of the first 0, hi > lo, lo of the next = hi, hi of the last N), a category / speaker index outside
+ * [0, C) / [0, S), a partner table that is not the inverse of the group table.  AEW_E_ALIGN: a pointer off 4 bytes.  A
+ * refused call launches and writes nothing. */
+#define AEW_ABX_WITHIN 0
+#define AEW_ABX_ACROSS 1
+#define AEW_ABX_MAX_N 16384
+typedef struct {
+    int32_t lo, hi;              /* sorted positions [lo, hi)                                   */
+    int32_t cat, spk;            /* category index in [0, C), speaker index in [0, S)           */
+} aew_abx_group_t;
+
+typedef struct {
+    int32_t mode;                /* AEW_ABX_WITHIN / _ACROSS                                    */
+    int32_t N, G, C, S, pad_;
+    int64_t ld;                  /* row pitch of dist in elements, >= N                         */
+    const float* dist;           /* device memory, (N - 1) * ld + N elements; only read         */
+    const int32_t* perm;         /* device memory, [N]                                          */
+    const int32_t* perm_host;    /* the same words in host memory                               */
+    const aew_abx_group_t* groups;       /* device memory, [G]                                  */
+    const aew_abx_group_t* groups_host;
+    const int32_t* partner;      /* device memory, [C][S]                                       */
+    const int32_t* partner_host;
+    uint32_t* n;                 /* [N][G]                                                      */
+    uint32_t* wrong2;            /* [N][G]                                                      */
+} aew_abx_count_t;
+
+/* The op on the CPU: the same descriptor with HOST pointers everywhere (perm / groups / partner may be NULL, the _host
+ * copies are read), the launcher's checks and return codes, the kernel's own definitions of w and of cell validity.
+ * Host logic only (tests). */
+int aew_abx_host(const aew_abx_count_t* p);
+
 /* Reduce the chunk sums of a step to per-tensor norms (ABI 22).  One block of 256 threads per tensor: thread t adds the
  * contiguous run [t * per, (t + 1) * per) of the tensor's chunks, per = ceil(chunks / 256), ascending, then the fixed
  * wave / block tree of the gradient norm - separately for the two sums.
@@ -1676,7 +1732,7 @@ enum {
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
     AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH,
     AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE, AEW_OP_SEQ_ALIGN,
-    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT, AEW_OP_SEQ_SEARCH
+    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT, AEW_OP_SEQ_SEARCH, AEW_OP_ABX_COUNT
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1709,13 +1765,14 @@ typedef struct {
         aew_code_tile_t ctile; aew_cond_stitch_t cndst;
         aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred; aew_seq_align_t align;
         aew_frame_stitch_t fstitch; aew_code_segment_t cseg; aew_seq_search_t search;
+        aew_abx_count_t abx;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment, 55 search_pair, 56 seq_search (24, 26, 33, 40, 46, 50 and 54 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment, 55 search_pair, 56 seq_search, 58 abx_group, 59 abx_count (24, 26, 33, 40, 46, 50, 54 and 57 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
