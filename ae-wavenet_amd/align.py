@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .plan import pinned_upload
 
 METRICS = {"euclid": L.ALIGN_EUCLID, "sqeuclid": L.ALIGN_SQEUCLID}
 STRIP = 64                                   # A frames a wave holds at a time: longer A sides carry a boundary row in the workspace
@@ -154,10 +155,8 @@ def pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, 
 
 
 def _upload(table: np.ndarray, dev) -> torch.Tensor:
-    """The bytes of a host table on the device, copied from pinned memory behind the stream: the host does not wait."""
-    host = torch.empty(max(table.nbytes, 1), dtype=torch.uint8, pin_memory=True)
-    host.numpy()[:table.nbytes] = table.view(np.uint8).reshape(-1)
-    return host.to(dev, non_blocking=True)
+    """The bytes of a host table on the device (plan.pinned_upload: the host does not wait)."""
+    return pinned_upload(dev, table)[0]
 
 
 class _SeqPlan:

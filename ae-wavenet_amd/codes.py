@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .plan import pinned_upload
 
 
 def _run(kind: int, rec, what: str, dev: torch.device):
@@ -121,6 +122,45 @@ def voice_information(codes: torch.Tensor, voice: torch.Tensor, K: int, n_voices
     return info
 
 
+# ---- whole utterances in tiles: what the three work lists (tile_plan, cond_tile_plan, score_tile_plan) share --------------
+def _pack_rows(nw: np.ndarray, B: int):
+    """Windows per utterance `nw` [U] -> (R, n_rows, utt int32 [R], window int32 [R]): the windows of all utterances, in
+    order, fill batches of B rows - n_rows live ones, R rows with the idle ones (utt -1, window 0) that pad the last batch."""
+    n_rows = int(nw.sum())
+    R = -(-n_rows // B) * B
+    utt, window = np.full(R, -1, np.int32), np.zeros(R, np.int32)
+    utt[:n_rows] = np.repeat(np.arange(len(nw)), nw)
+    window[:n_rows] = np.arange(n_rows) - np.repeat(np.concatenate([[0], np.cumsum(nw)])[:-1], nw)
+    return R, n_rows, utt, window
+
+
+def _live(R: int, n_rows: int, values, dtype) -> np.ndarray:
+    """A per-row array [R]: `values` in the n_rows live rows, 0 in the idle ones."""
+    out = np.zeros(R, dtype)
+    out[:n_rows] = values
+    return out
+
+
+def _code_window(w: np.ndarray, hop: int, p: int, N: np.ndarray, E: int):
+    """The code window of windows `w` at a hop of `hop` codes behind `p` pad codes, over utterances of N codes (one per
+    window) -> (c0, lo, hi): the window's first code relative to the utterance's, and the window codes [lo, hi) that exist."""
+    c0 = w * hop - p
+    lo = np.clip(-c0, 0, E)
+    return c0, lo, np.maximum(np.clip(N - c0, 0, E), lo)
+
+
+def _fill_table(rec: np.ndarray, utt: np.ndarray, per_utt: dict, per_row: dict) -> np.ndarray:
+    """The live rows of the records `rec`: field = values[utt] for `per_utt` (values one per utterance), field = the row's
+    own value for `per_row`; idle rows keep what they hold."""
+    live = utt >= 0
+    u = utt[live]
+    for name, values in per_utt.items():
+        rec[name][live] = np.asarray(values, np.int64).reshape(-1)[u]
+    for name, values in per_row.items():
+        rec[name][live] = values[live]
+    return rec
+
+
 # ---- whole utterances: the work list of model.encode_utterances() and the codes it returns ------------------------------
 @dataclass
 class TilePlan:
@@ -153,12 +193,9 @@ class TilePlan:
     def table(self, bases) -> np.ndarray:
         """The aew_utt_row_t records (a structured array, _lib.UTT_ROW_DTYPE) for utterances whose (n_mel, F_u) arrays start
         at the element offsets `bases` [U] of the ragged mel buffer."""
-        rec = np.zeros(len(self.utt), np.dtype(L.UTT_ROW_DTYPE))
-        live = self.utt >= 0
-        u = self.utt[live]
-        rec["src"][live] = np.asarray(bases, np.int64)[u] + self.start[live]
-        rec["pitch"][live] = self.frames[u]
-        rec["dst"], rec["avail"], rec["n_valid"] = self.dst, self.avail, self.n_valid
+        rec = _fill_table(np.zeros(len(self.utt), np.dtype(L.UTT_ROW_DTYPE)), self.utt, dict(src=bases, pitch=self.frames),
+                          dict(dst=self.dst, avail=self.avail, n_valid=self.n_valid))
+        rec["src"] += self.start                                             # (0 in idle rows)
         return rec
 
 
@@ -177,21 +214,12 @@ def tile_plan(frames: Sequence[int], E: int, s: int, rf: int, B: int) -> TilePla
     mel_len = s * (E - 1) + rf
     N = np.where(F < rf, 0, (F - rf) // s + 1)
     offsets = np.concatenate([[0], np.cumsum(N)]).astype(np.int64)
-    nw = -(-N // E)
-    n_rows = int(nw.sum())
-    R = -(-n_rows // B) * B
-    first = np.concatenate([[0], np.cumsum(nw)])[:-1]
-    utt = np.full(R, -1, np.int32)
-    window, start, avail = np.zeros(R, np.int32), np.zeros(R, np.int64), np.zeros(R, np.int32)
-    n_valid, dst = np.zeros(R, np.int32), np.zeros(R, np.int64)
-    u = np.repeat(np.arange(len(F)), nw)
-    w = np.arange(n_rows) - np.repeat(first, nw)
-    utt[:n_rows], window[:n_rows] = u, w
-    start[:n_rows] = w * (s * E)
-    avail[:n_rows] = np.minimum(mel_len, F[u] - w * (s * E))
-    n_valid[:n_rows] = np.minimum(E, N[u] - w * E)
-    dst[:n_rows] = offsets[u] + w * E
-    return TilePlan(E, s, rf, mel_len, B, F, offsets, utt, window, start, avail, n_valid, dst, n_rows)
+    R, n_rows, utt, window = _pack_rows(-(-N // E), B)
+    u, w = utt[:n_rows], window[:n_rows].astype(np.int64)
+    row = lambda values, dtype=np.int32: _live(R, n_rows, values, dtype)
+    return TilePlan(E, s, rf, mel_len, B, F, offsets, utt, window, start=row(w * (s * E), np.int64),
+                    avail=row(np.minimum(mel_len, F[u] - w * (s * E))), n_valid=row(np.minimum(E, N[u] - w * E)),
+                    dst=row(offsets[u] + w * E, np.int64), n_rows=n_rows)
 
 
 class UtteranceCodes:
@@ -367,15 +395,11 @@ def segment_full(frames: torch.Tensor, offsets, emb: torch.Tensor, penalty, metr
     cost = torch.empty(U, dtype=torch.float32, device=dev)
     n_seg = torch.empty(U, dtype=torch.int32, device=dev)
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    lam_host = torch.empty(U, dtype=torch.float32, pin_memory=True)
-    lam_host.numpy()[:] = plan.table["lam"]
-    info = Segmentation(cost, n_seg, lam_host.to(dev, non_blocking=True), n_bad)
+    lam = np.ascontiguousarray(plan.table["lam"])
+    info = Segmentation(cost, n_seg, pinned_upload(dev, lam)[0][:lam.nbytes].view(torch.float32), n_bad)
     if U == 0:
         return codes, dist, info
-    host = torch.empty(max(plan.table.nbytes, 1), dtype=torch.uint8, pin_memory=True)
-    host.numpy()[:plan.table.nbytes] = plan.table.view(np.uint8).reshape(-1)
-    table = torch.empty_like(host, device=dev)
-    table.copy_(host, non_blocking=True)
+    table, host = pinned_upload(dev, plan.table)
     ws = torch.empty(max(plan.ws_bytes // 8, 1), dtype=torch.int64, device=dev)
     cs = L.CodeSegment()
     cs.frames, cs.n_elems = (frames.data_ptr() if n else None), frames.numel()
@@ -432,15 +456,10 @@ class CondTilePlan:
         indices `bases` [U] of the flat code buffer and whose voices are `voices` [U]."""
         rec = np.zeros(len(self.utt), np.dtype(L.COND_ROW_DTYPE))
         rec["utt"] = -1
-        live = self.utt >= 0
-        u = self.utt[live]
-        rec["utt"][live] = rec["stream"][live] = u
-        rec["code0"][live] = np.asarray(bases, np.int64).reshape(-1)[u] + self.start[live]
-        rec["voice"][live] = np.asarray(voices, np.int64).reshape(-1)[u]
-        rec["pitch"][live] = self.pitch
-        for name, arr in (("lo", self.lo), ("hi", self.hi), ("src_row", self.src_row), ("n_rows", self.owned),
-                          ("dst_row", self.dst_row), ("first", self.first)):
-            rec[name][live] = arr[live]
+        _fill_table(rec, self.utt, dict(code0=bases, voice=voices),
+                    dict(utt=self.utt, stream=self.utt, lo=self.lo, hi=self.hi, src_row=self.src_row, n_rows=self.owned,
+                         dst_row=self.dst_row, first=self.first, pitch=np.full(len(self.utt), self.pitch)))
+        rec["code0"] += self.start                                           # (0 in idle rows)
         return rec
 
 
@@ -466,31 +485,18 @@ def cond_tile_plan(n_codes: Sequence[int], E: int, S: int, T: int, trim0: int, B
     if (Ln < 0).any() or (Ln > np.maximum(N, 0) * S).any():
         raise ValueError("cond_tile_plan(): L(n) must lie in [0, n * S]")
     hop = h * S
-    nw = -(-Ln // hop)
-    n_rows = int(nw.sum())
-    R = -(-n_rows // B) * B
+    R, n_rows, utt, window = _pack_rows(-(-Ln // hop), B)
     t_max = max(int(Ln.max()) if len(Ln) else 0, 1)
     if pitch is None:
         pitch = t_max
     elif int(pitch) < t_max:
         raise ValueError(f"cond_tile_plan(): pitch {pitch} is shorter than the longest conditioning, {t_max} rows")
-    firstw = np.concatenate([[0], np.cumsum(nw)])[:-1]
-    utt = np.full(R, -1, np.int32)
-    window, start = np.zeros(R, np.int32), np.zeros(R, np.int64)
-    lo, hi, src_row = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
-    rows, dst_row, first = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
-    u = np.repeat(np.arange(len(N)), nw)
-    w = np.arange(n_rows) - np.repeat(firstw, nw)
-    c0 = w * h - p
-    utt[:n_rows], window[:n_rows], start[:n_rows] = u, w, c0
-    lo[:n_rows] = np.clip(-c0, 0, E)
-    hi[:n_rows] = np.maximum(np.clip(N[u] - c0, 0, E), lo[:n_rows])
-    src_row[:n_rows] = lead
-    dst_row[:n_rows] = w * hop
-    rows[:n_rows] = np.minimum(hop, Ln[u] - w * hop)
-    first[:n_rows] = w == 0
-    return CondTilePlan(E, S, T, trim0, p, h, B, N, Ln, int(pitch), utt, window, start, lo, hi, src_row, rows, dst_row,
-                        first, n_rows)
+    u, w = utt[:n_rows], window[:n_rows].astype(np.int64)
+    c0, lo, hi = _code_window(w, h, p, N[u], E)
+    row = lambda values, dtype=np.int32: _live(R, n_rows, values, dtype)
+    return CondTilePlan(E, S, T, trim0, p, h, B, N, Ln, int(pitch), utt, window, start=row(c0, np.int64), lo=row(lo), hi=row(hi),
+                        src_row=row(lead), owned=row(np.minimum(hop, Ln[u] - w * hop)), dst_row=row(w * hop), first=row(w == 0),
+                        n_rows=n_rows)
 
 
 def stream_groups(lengths: Sequence[int], seed: int, width: int = 16):
@@ -550,16 +556,9 @@ class ScoreTilePlan:
         flat waveform buffer and whose voices are `voices` [U]."""
         rec = np.zeros(len(self.utt), np.dtype(L.SCORE_ROW_DTYPE))
         rec["utt"] = -1
-        live = self.utt >= 0
-        u = self.utt[live]
-        rec["utt"][live] = u
-        rec["code0"][live] = np.asarray(code_bases, np.int64).reshape(-1)[u] + self.start[live]
-        rec["wav_base"][live] = np.asarray(wav_bases, np.int64).reshape(-1)[u]
-        rec["wav_len"][live] = self.wav_lens[u]
-        rec["voice"][live] = np.asarray(voices, np.int64).reshape(-1)[u]
-        for name, arr in (("lo", self.lo), ("hi", self.hi), ("wav0", self.wav0), ("src", self.src), ("n_out", self.n_out),
-                          ("dst", self.dst)):
-            rec[name][live] = arr[live]
+        _fill_table(rec, self.utt, dict(code0=code_bases, wav_base=wav_bases, wav_len=self.wav_lens, voice=voices),
+                    dict(utt=self.utt, lo=self.lo, hi=self.hi, wav0=self.wav0, src=self.src, n_out=self.n_out, dst=self.dst))
+        rec["code0"] += self.start                                           # (0 in idle rows)
         return rec
 
 
@@ -589,25 +588,13 @@ def score_tile_plan(n_codes: Sequence[int], wav_lens: Sequence[int], geom_tuple,
     n_sc = np.maximum(n_u - rf - 1, 0)
     offsets = np.concatenate([[0], np.cumsum(n_sc)]).astype(np.int64)
     hop = h_s * S
-    nw = -(-n_sc // hop)
-    n_rows = int(nw.sum())
-    R = -(-n_rows // B) * B
-    firstw = np.concatenate([[0], np.cumsum(nw)])[:-1]
-    utt = np.full(R, -1, np.int32)
-    window, start, wav0, dst = np.zeros(R, np.int32), np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64)
-    lo, hi, src, n_out = np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32), np.zeros(R, np.int32)
-    u = np.repeat(np.arange(len(N)), nw)
-    j = np.arange(n_rows) - np.repeat(firstw, nw)
-    c0 = j * h_s - p
-    utt[:n_rows], window[:n_rows], start[:n_rows] = u, j, c0
-    lo[:n_rows] = np.clip(-c0, 0, E)
-    hi[:n_rows] = np.maximum(np.clip(N[u] - c0, 0, E), lo[:n_rows])
-    wav0[:n_rows] = o + j * hop - r0
-    src[:n_rows] = r0
-    n_out[:n_rows] = np.minimum(hop, n_sc[u] - j * hop)
-    dst[:n_rows] = offsets[u] + j * hop
-    return ScoreTilePlan(E, S, T, rf, r0, p, h_s, o, B, N, W, n_u, n_sc, offsets, utt, window, start, lo, hi, wav0, src,
-                         n_out, dst, n_rows)
+    R, n_rows, utt, window = _pack_rows(-(-n_sc // hop), B)
+    u, j = utt[:n_rows], window[:n_rows].astype(np.int64)
+    c0, lo, hi = _code_window(j, h_s, p, N[u], E)
+    row = lambda values, dtype=np.int32: _live(R, n_rows, values, dtype)
+    return ScoreTilePlan(E, S, T, rf, r0, p, h_s, o, B, N, W, n_u, n_sc, offsets, utt, window, start=row(c0, np.int64), lo=row(lo),
+                         hi=row(hi), wav0=row(o + j * hop - r0, np.int64), src=row(r0), n_out=row(np.minimum(hop, n_sc[u] - j * hop)),
+                         dst=row(offsets[u] + j * hop, np.int64), n_rows=n_rows)
 
 
 class UtteranceScores:

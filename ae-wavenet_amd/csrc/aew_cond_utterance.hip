@@ -11,11 +11,7 @@
 // codes of the window that are read - hi - lo, 0 for an idle row - or -1 for a record AEW_OP_CODE_TILE refuses: the reads
 // of a good record stay inside [0, n_codes)
 __host__ __device__ __forceinline__ int32_t cond_tile_n(const aew_cond_row_t& r, int E, int64_t n_codes, int n_voice) {
-    if (r.utt < 0) return 0;
-    if (r.lo < 0 || r.hi < r.lo || r.hi > E || r.voice < 0 || r.voice >= n_voice) return -1;
-    if (r.hi == r.lo) return 0;
-    if (r.code0 < -(int64_t)E || r.code0 > n_codes) return -1;                 // (keeps the sums below far from overflow)
-    return (r.code0 + r.lo >= 0 && r.code0 + r.hi <= n_codes) ? r.hi - r.lo : -1;
+    return r.utt < 0 ? 0 : code_window_n(r, E, n_codes, n_voice);
 }
 // rows of the window that are moved, 0 for an idle row, or -1 for a record AEW_OP_COND_STITCH refuses: the reads of a good
 // record stay inside the T rows of cond[b], its writes inside stream r.stream of cond_utt (n_dst elements) and of bias_utt
@@ -29,12 +25,6 @@ __host__ __device__ __forceinline__ int32_t cond_stitch_n(const aew_cond_row_t& 
     return r.n_rows;
 }
 
-static int cond_table_check(const aew_cond_row_t* table, const aew_cond_row_t* host, int first_row, int B) {
-    if (!table || !host || B < 1 || B > 65535 || first_row < 0) return AEW_E_ARG;
-    if (((uintptr_t)table | (uintptr_t)host) & 15) return AEW_E_ALIGN;
-    return 0;
-}
-
 // ---- AEW_OP_CODE_TILE
 // One wave per batch row.  The record is read through the kernel argument at a block-uniform index, so every lane holds
 // the same values; a record that fails the launcher's check (the table changed under a captured graph) is treated as
@@ -44,28 +34,18 @@ __global__ __launch_bounds__(AEW_WAVE) void k_code_tile(const aew_code_tile_t p)
     const aew_cond_row_t r = p.table[(int64_t)p.first_row + b];
     const int32_t n = cond_tile_n(r, p.E, p.n_codes, p.n_voice);
     const bool live = r.utt >= 0 && n >= 0;
-    int64_t* ind = p.ind + (int64_t)b * p.E;
-    unsigned int bad = 0;
-    for (int j = threadIdx.x; j < p.E; j += AEW_WAVE) {
-        int64_t c = 0;
-        if (live && j >= r.lo && j < r.hi) {
-            c = p.codes[r.code0 + j];
-            if (c < 0 || c >= (int64_t)p.K) { c = 0; ++bad; }
-        }
-        ind[j] = c;
-    }
+    const unsigned int bad = code_window_cut<AEW_WAVE>(p, r, live, b);
     if (bad) atomicAdd(p.bad, bad);
     if (threadIdx.x == 0) p.in_voice[b] = live ? (int64_t)r.voice : 0;
 }
 
 static int launch_code_tile(const aew_code_tile_t& p, hipStream_t st) {
-    int rc = cond_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.codes || !p.ind || !p.in_voice || !p.bad || p.E < 1 || p.K < 1 || p.n_voice < 1 || p.n_codes < 0) return AEW_E_ARG;
     if (((uintptr_t)p.codes | (uintptr_t)p.ind | (uintptr_t)p.in_voice) & 15) return AEW_E_ALIGN;
     if ((uintptr_t)p.bad & 3) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (cond_tile_n(p.table_host[(int64_t)p.first_row + b], p.E, p.n_codes, p.n_voice) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return cond_tile_n(r, p.E, p.n_codes, p.n_voice); })) return AEW_E_ARG;
     hipLaunchKernelGGL(k_code_tile, dim3((unsigned)p.B), dim3(AEW_WAVE), 0, st, p);
     return (int)hipGetLastError();
 }
@@ -101,14 +81,13 @@ __global__ __launch_bounds__(AEW_CONDST_THREADS) void k_cond_stitch(const aew_co
 }
 
 static int launch_cond_stitch(const aew_cond_stitch_t& p, hipStream_t st) {
-    int rc = cond_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.cond || !p.cond_utt || !p.bias || !p.bias_utt || p.T < 1 || p.Cp < 8 || (p.Cp & 7) || p.cond_pitch < p.Cp ||
         (p.cond_pitch & 7) || p.cond_bs < 0 || (p.cond_bs & 7) || p.bias_n < 4 || (p.bias_n & 3) || p.n_streams < 1 || p.n_dst < 0)
         return AEW_E_ARG;
     if (((uintptr_t)p.cond | (uintptr_t)p.cond_utt | (uintptr_t)p.bias | (uintptr_t)p.bias_utt) & 15) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (cond_stitch_n(p.table_host[(int64_t)p.first_row + b], p.T, p.Cp, p.n_streams, p.n_dst) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return cond_stitch_n(r, p.T, p.Cp, p.n_streams, p.n_dst); })) return AEW_E_ARG;
     const int64_t per_row = (int64_t)p.T * (p.Cp / 8);
     int64_t gx = (per_row + AEW_CONDST_THREADS - 1) / AEW_CONDST_THREADS;
     if (gx > 1024) gx = 1024;                                                   // (the loops stride over the rest)

@@ -13,11 +13,7 @@
 // inside [0, n_codes) and [0, n_wav)
 __host__ __device__ __forceinline__ int32_t score_tile_n(const aew_score_row_t& r, int E, int64_t n_codes, int n_voice, int64_t n_wav) {
     if (r.utt < 0) return 0;
-    if (r.lo < 0 || r.hi < r.lo || r.hi > E || r.voice < 0 || r.voice >= n_voice) return -1;
-    if (r.hi > r.lo) {
-        if (r.code0 < -(int64_t)E || r.code0 > n_codes) return -1;              // (keeps the sums below far from overflow)
-        if (r.code0 + r.lo < 0 || r.code0 + r.hi > n_codes) return -1;
-    }
+    if (code_window_n(r, E, n_codes, n_voice) < 0) return -1;
     if (r.wav_len < 0 || r.wav_base < 0 || r.wav_len > n_wav || r.wav_base > n_wav - r.wav_len) return -1;
     const int64_t lim = (int64_t)1 << 40;
     if (r.wav0 <= -lim || r.wav0 >= lim) return -1;
@@ -30,12 +26,6 @@ __host__ __device__ __forceinline__ int32_t score_stitch_n(const aew_score_row_t
     if (r.n_out < 0 || r.src < 0 || r.n_out > w - 1 || r.src > w - 1 - r.n_out) return -1;
     if (r.dst < 0 || r.n_out > n_dst || r.dst > n_dst - r.n_out) return -1;
     return r.n_out;
-}
-
-static int score_table_check(const aew_score_row_t* table, const aew_score_row_t* host, int first_row, int B) {
-    if (!table || !host || B < 1 || B > 65535 || first_row < 0) return AEW_E_ARG;
-    if (((uintptr_t)table | (uintptr_t)host) & 15) return AEW_E_ALIGN;
-    return 0;
 }
 
 // ---- AEW_OP_WAV_TILE
@@ -63,22 +53,13 @@ __global__ __launch_bounds__(AEW_SCORE_THREADS) void k_wav_tile(const aew_wav_ti
     }
     if (bad) atomicAdd(p.bad_wav, bad);
     if (blockIdx.x != 0) return;
-    int64_t* ind = p.ind + (int64_t)b * p.E;
-    bad = 0;
-    for (int j = threadIdx.x; j < p.E; j += AEW_SCORE_THREADS) {
-        int64_t c = 0;
-        if (live && j >= r.lo && j < r.hi) {
-            c = p.codes[r.code0 + j];
-            if (c < 0 || c >= (int64_t)p.K) { c = 0; ++bad; }
-        }
-        ind[j] = c;
-    }
+    bad = code_window_cut<AEW_SCORE_THREADS>(p, r, live, b);
     if (bad) atomicAdd(p.bad_codes, bad);
     if (threadIdx.x == 0) p.in_voice[b] = live ? (int64_t)r.voice : 0;
 }
 
 static int launch_wav_tile(const aew_wav_tile_t& p, hipStream_t st) {
-    int rc = score_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.codes || !p.wavs || !p.ind || !p.in_voice || !p.wav || !p.bad_codes || !p.bad_wav) return AEW_E_ARG;
     if (p.E < 1 || p.K < 1 || p.n_voice < 1 || p.n_quant < 1 || p.T < 1 || p.n_codes < 0 || p.n_wav < 0 || p.wav_off < 0 ||
@@ -86,8 +67,7 @@ static int launch_wav_tile(const aew_wav_tile_t& p, hipStream_t st) {
         return AEW_E_ARG;
     if (((uintptr_t)p.codes | (uintptr_t)p.wavs | (uintptr_t)p.ind | (uintptr_t)p.in_voice | (uintptr_t)p.wav) & 15) return AEW_E_ALIGN;
     if (((uintptr_t)p.bad_codes | (uintptr_t)p.bad_wav) & 3) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (score_tile_n(p.table_host[(int64_t)p.first_row + b], p.E, p.n_codes, p.n_voice, p.n_wav) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return score_tile_n(r, p.E, p.n_codes, p.n_voice, p.n_wav); })) return AEW_E_ARG;
     int gx = (p.T + AEW_SCORE_THREADS - 1) / AEW_SCORE_THREADS;
     if (gx > 64) gx = 64;                                                       // (the loop strides over the rest)
     hipLaunchKernelGGL(k_wav_tile, dim3((unsigned)gx, (unsigned)p.B), dim3(AEW_SCORE_THREADS), 0, st, p);
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(AEW_SCORE_THREADS) void k_nll_stitch(const aew_nll_
 }
 
 static int launch_nll_stitch(const aew_nll_stitch_t& p, hipStream_t st) {
-    int rc = score_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.nll || !p.dst_nll || (p.dst_ptgt && !p.ptgt) || p.w < 2 || p.n_dst < 0) return AEW_E_ARG;
     if (p.dst_hit) {
@@ -137,8 +117,7 @@ static int launch_nll_stitch(const aew_nll_stitch_t& p, hipStream_t st) {
     }
     if (((uintptr_t)p.nll | (uintptr_t)p.ptgt | (uintptr_t)p.amax | (uintptr_t)p.logits | (uintptr_t)p.wav | (uintptr_t)p.dst_nll |
          (uintptr_t)p.dst_ptgt) & 3) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (score_stitch_n(p.table_host[(int64_t)p.first_row + b], p.w, p.n_dst) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return score_stitch_n(r, p.w, p.n_dst); })) return AEW_E_ARG;
     int gx = (p.w + AEW_SCORE_THREADS - 1) / AEW_SCORE_THREADS;
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(k_nll_stitch, dim3((unsigned)gx, (unsigned)p.B), dim3(AEW_SCORE_THREADS), 0, st, p);

@@ -6,6 +6,52 @@
 #pragma once
 #include "aew_common.h"
 
+// ---- what the whole-utterance files share (this one is included first; aew_cond_utterance.hip and aew_score.hip follow)
+// the table of a tile or stitch record: a device copy the kernel reads and a host copy the launcher checks, aligned to 8
+// bytes for aew_utt_row_t and to 16 for aew_cond_row_t / aew_score_row_t
+template <typename Row>
+static int tile_table_check(const Row* table, const Row* host, int first_row, int B) {
+    if (!table || !host || B < 1 || B > 65535 || first_row < 0) return AEW_E_ARG;
+    if (((uintptr_t)table | (uintptr_t)host) & (std::is_same<Row, aew_utt_row_t>::value ? 7 : 15)) return AEW_E_ALIGN;
+    return 0;
+}
+// the launchers' walk over the host copy of the batch's rows: n_of is the record's check, negative for a row it refuses
+template <typename P, typename F>
+static bool tile_rows_ok(const P& p, F n_of) {
+    for (int b = 0; b < p.B; ++b)
+        if (n_of(p.table_host[(int64_t)p.first_row + b]) < 0) return false;
+    return true;
+}
+// the code window aew_cond_row_t and aew_score_row_t share: the codes that are read - hi - lo - or -1 for a window
+// AEW_OP_CODE_TILE and AEW_OP_WAV_TILE refuse: the reads of a good one stay inside [0, n_codes)
+template <typename Row>
+__host__ __device__ __forceinline__ int32_t code_window_n(const Row& r, int E, int64_t n_codes, int n_voice) {
+    if (r.lo < 0 || r.hi < r.lo || r.hi > E || r.voice < 0 || r.voice >= n_voice) return -1;
+    if (r.hi > r.lo) {
+        if (r.code0 < -(int64_t)E || r.code0 > n_codes) return -1;              // (keeps the sums below far from overflow)
+        if (r.code0 + r.lo < 0 || r.code0 + r.hi > n_codes) return -1;
+    }
+    return r.hi - r.lo;
+}
+// the cut of batch row b's code window by the STRIDE threads of a block, for a record p with codes / ind / E / K
+// (aew_code_tile_t, aew_wav_tile_t): ind[b][j] = codes[code0 + j] for j in [lo, hi) of a live row, code 0 elsewhere and
+// where the code lies outside [0, K).  -> this thread's count of such codes; the caller adds it to its own counter and
+// stores the row's voice behind that
+template <int STRIDE, typename P, typename Row>
+__device__ __forceinline__ unsigned int code_window_cut(const P& p, const Row& r, bool live, int b) {
+    int64_t* ind = p.ind + (int64_t)b * p.E;
+    unsigned int bad = 0;
+    for (int j = threadIdx.x; j < p.E; j += STRIDE) {
+        int64_t c = 0;
+        if (live && j >= r.lo && j < r.hi) {
+            c = p.codes[r.code0 + j];
+            if (c < 0 || c >= (int64_t)p.K) { c = 0; ++bad; }
+        }
+        ind[j] = c;
+    }
+    return bad;
+}
+
 // ---- the index arithmetic, ONE definition for the kernels, the launchers' checks and aew_utterance_locate (the CPU tests
 // run this very code)
 // frames of the row's window that exist, or -1 for a record AEW_OP_MEL_TILE refuses: the reads of a good record stay
@@ -89,19 +135,12 @@ __global__ __launch_bounds__(AEW_UTT_THREADS) void k_mel_tile(const aew_mel_tile
     }
 }
 
-static int utt_table_check(const aew_utt_row_t* table, const aew_utt_row_t* host, int first_row, int B) {
-    if (!table || !host || B < 1 || B > 65535 || first_row < 0) return AEW_E_ARG;
-    if (((uintptr_t)table | (uintptr_t)host) & 7) return AEW_E_ALIGN;
-    return 0;
-}
-
 static int launch_mel_tile(const aew_mel_tile_t& p, hipStream_t st) {
-    int rc = utt_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.mel || !p.in_mel || p.n_mel < 1 || p.mel_len < 1 || p.n_src < 0) return AEW_E_ARG;
     if (((uintptr_t)p.mel | (uintptr_t)p.in_mel) & 3) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (utt_tile_avail(p.table_host[(int64_t)p.first_row + b], p.n_mel, p.mel_len, p.n_src) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return utt_tile_avail(r, p.n_mel, p.mel_len, p.n_src); })) return AEW_E_ARG;
     const int64_t row_n = (int64_t)p.n_mel * p.mel_len;
     const bool vec = !(row_n & 3) && !((uintptr_t)p.in_mel & 15);
     const int64_t per_row = vec ? row_n / 4 : row_n;
@@ -127,13 +166,12 @@ __global__ __launch_bounds__(AEW_WAVE) void k_code_stitch(const aew_code_stitch_
 }
 
 static int launch_code_stitch(const aew_code_stitch_t& p, hipStream_t st) {
-    int rc = utt_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.ind || !p.codes || p.E < 1 || p.n_dst < 0 || (p.dist && !p.min_dist)) return AEW_E_ARG;
     if (((uintptr_t)p.ind | (uintptr_t)p.codes) & 7) return AEW_E_ALIGN;
     if (((uintptr_t)p.min_dist | (uintptr_t)p.dist) & 3) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (utt_stitch_n(p.table_host[(int64_t)p.first_row + b], p.E, p.n_dst) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return utt_stitch_n(r, p.E, p.n_dst); })) return AEW_E_ARG;
     hipLaunchKernelGGL(k_code_stitch, dim3((unsigned)p.B), dim3(AEW_WAVE), 0, st, p);
     return (int)hipGetLastError();
 }
@@ -161,12 +199,11 @@ __global__ __launch_bounds__(AEW_UTT_THREADS) void k_frame_stitch(const aew_fram
 }
 
 static int launch_frame_stitch(const aew_frame_stitch_t& p, hipStream_t st) {
-    int rc = utt_table_check(p.table, p.table_host, p.first_row, p.B);
+    int rc = tile_table_check(p.table, p.table_host, p.first_row, p.B);
     if (rc) return rc;
     if (!p.lin || !p.frames || p.E < 1 || p.d_pitch < 1 || p.n_dst < 0 || p.lin_bs < (int64_t)p.E * p.d_pitch) return AEW_E_ARG;
     if (((uintptr_t)p.lin | (uintptr_t)p.frames) & 3) return AEW_E_ALIGN;
-    for (int b = 0; b < p.B; ++b)
-        if (utt_stitch_n(p.table_host[(int64_t)p.first_row + b], p.E, p.n_dst) < 0) return AEW_E_ARG;
+    if (!tile_rows_ok(p, [&](auto& r) { return utt_stitch_n(r, p.E, p.n_dst); })) return AEW_E_ARG;
     const bool vec = !(p.d_pitch & 3) && !(p.lin_bs & 3) && !(((uintptr_t)p.lin | (uintptr_t)p.frames) & 15);
     const int64_t per_row = (int64_t)p.E * p.d_pitch / (vec ? 4 : 1);
     const dim3 grid((unsigned)((per_row + AEW_UTT_THREADS - 1) / AEW_UTT_THREADS), (unsigned)p.B);

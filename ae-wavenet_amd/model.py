@@ -20,7 +20,7 @@ from . import _lib as L
 from . import geometry as G
 from .engine import (F3, BottleneckPlan, DecoderPlan, EncoderPlan, Packer, ParamStore, TAG_ADAM, TAG_LOSS, TAG_PACK, TAG_UPS, TAG_VQ,
                      bottleneck_param_specs, decoder_param_specs, encoder_param_specs, reduce_op)
-from .plan import CopyTableBuilder, Mat, Plan, Workspace, insert_nt_chains, ru, split_small_nt
+from .plan import CopyTableBuilder, Mat, Plan, Workspace, insert_nt_chains, pinned_upload, ru, split_small_nt
 
 MEAN_LOSS = {"none": True, "ae": True, "vae": True, "vqvae": False, "vqvae-ema": False}
 
@@ -728,105 +728,128 @@ class TrainEngine:
             self.utt_stitch.add(L.OP_CODE_STITCH, cs, "utt.stitch", TAG_VQ)
         return self.utt_tile.array()[0].u.mtile, self.utt_stitch.array()[0].u.cstitch
 
+    # ---- whole utterances in tiles: the path encode / segment / conditioning / score share ---------------------------------
+    @staticmethod
+    def _tile_rec(plan: Plan):
+        """The record of a one-op plan, as the plan runs it (a view into plan.array())."""
+        op = plan.array()[0]
+        return getattr(op.u, L.OP_FIELD[op.kind])
+
+    @staticmethod
+    def _tile_fill(recs, fields, table: int, table_host: int, first_row: int = 0):
+        """The table's two addresses and a first row on the tile and the stitch record, then each one's own `fields`."""
+        for rec, own in zip(recs, fields):
+            rec.table, rec.table_host, rec.first_row = table, table_host, first_row
+            for name, value in own.items():
+                setattr(rec, name, value)
+
+    def _tile_rows(self, what: str, table, row, c_name: str) -> int:
+        """len(table), or raises unless it holds a multiple of B records of the struct `row`."""
+        n = len(table)
+        if n % self.B or table.dtype.itemsize != C.sizeof(row):
+            raise L.AewError(f"{what}: a multiple of B = {self.B} {c_name} records expected, got {n}")
+        return n
+
+    def _run_tiles(self, tile: Plan, body: Plan, stitch: Plan, fields, table, extra=()):
+        """`table` (a checked numpy array of row records) - and the bytes of the arrays `extra` behind it - go to the device
+        once (plan.pinned_upload); then per batch of B rows: the one-op plan `tile`, the engine's `body` unchanged, the
+        one-op plan `stitch`.  fields = (the tile record's own fields, the stitch record's).  The host sets first_row and
+        runs three plans per batch, nothing else.  Whatever happens, both records end as they were built: they keep no
+        address of the caller's tensors nor of the table, which returns to torch's allocators - those order its reuse
+        behind this stream's work.  -> (device bytes, pinned host bytes) of table + extra."""
+        dev, host = pinned_upload(self.device, table, *extra)
+        n, recs = len(table), (self._tile_rec(tile), self._tile_rec(stitch))
+        built = [bytes(r) for r in recs]
+        try:
+            self._tile_fill(recs, fields, dev.data_ptr(), host.data_ptr())
+            st = self._stream()
+            for first in range(0, n, self.B):
+                recs[0].first_row = recs[1].first_row = first
+                tile.run(st)
+                self._run(body, False)
+                stitch.run(st)
+        finally:
+            for rec, was in zip(recs, built):
+                C.memmove(C.addressof(rec), was, len(was))
+        return dev, host
+
+    def _tile_batch_plan(self, name: str, tile: Plan, body: Plan, stitch: Plan, fields, table: torch.Tensor,
+                         table_host: torch.Tensor, first_row: int, join: bool = False) -> Plan:
+        """[tile] + the ops of `body` (the same records) + [stitch] as one plan for a caller's captured graph: copies of
+        the two records, filled as _run_tiles() fills them, over the rows [first_row, first_row + B) of `table`."""
+        recs = [type(r).from_buffer_copy(r) for r in (self._tile_rec(tile), self._tile_rec(stitch))]
+        self._tile_fill(recs, fields, table.data_ptr(), table_host.data_ptr(), int(first_row))
+        p = Plan(name)
+        p.add(tile.ops[0].kind, recs[0], tile.labels[0], tile.ops[0].tag)
+        p.splice(1, self._sub_plan(body.name, body, lambda i, lab: True))
+        p.add(stitch.ops[0].kind, recs[1], stitch.labels[0], stitch.ops[0].tag, join=join)
+        return p
+
+    @staticmethod
+    def _utt_fields(mel, codes=None, dist=None):
+        return (dict(mel=mel.data_ptr(), n_src=mel.numel()),
+                {} if codes is None else dict(codes=codes.data_ptr(), n_dst=codes.numel(),
+                                              dist=dist.data_ptr() if dist is not None else None))
+
     def utterance_batch_plan(self, mel: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor, first_row: int,
                              codes: torch.Tensor, dist: Optional[torch.Tensor] = None) -> Plan:
         """One batch of a whole-utterance encode as a plan of its own (for a caller's captured graph): [utt.tile] + the
         ops of _cond_plan_a (the same records) + [utt.stitch] over the rows [first_row, first_row + B) of `table` (uint8
         device bytes of aew_utt_row_t records; table_host: the same bytes in pinned host memory, read at capture).  The
         caller keeps the tensors alive."""
-        mt0, cs0 = self.utterance_ops()
+        self.utterance_ops()
         self._cond_plans()
-        mt, cs = L.MelTile.from_buffer_copy(mt0), L.CodeStitch.from_buffer_copy(cs0)
-        mt.table, mt.table_host, mt.first_row = table.data_ptr(), table_host.data_ptr(), int(first_row)
-        mt.mel, mt.n_src = mel.data_ptr(), mel.numel()
-        cs.table, cs.table_host, cs.first_row = mt.table, mt.table_host, mt.first_row
-        cs.codes, cs.n_dst, cs.dist = codes.data_ptr(), codes.numel(), (dist.data_ptr() if dist is not None else None)
-        p = Plan("utt.batch")
-        p.add(L.OP_MEL_TILE, mt, "utt.tile", TAG_VQ)
-        p.splice(1, self._sub_plan("conditioning_a", self._cond_plan_a, lambda i, lab: True))
-        p.add(L.OP_CODE_STITCH, cs, "utt.stitch", TAG_VQ)
-        return p
+        return self._tile_batch_plan("utt.batch", self.utt_tile, self._cond_plan_a, self.utt_stitch,
+                                     self._utt_fields(mel, codes, dist), table, table_host, first_row)
 
     def encode_tiles(self, mel: torch.Tensor, table, codes: torch.Tensor, dist: Optional[torch.Tensor] = None):
         """Whole utterances through the fixed-geometry encoder: `mel` flat fp32, the ragged buffer of the utterances'
         (n_mel, F_u) arrays; `table` a numpy array of aew_utt_row_t records (_lib.UTT_ROW_DTYPE), a multiple of B rows
         (codes.TilePlan.table); `codes` int64 - and `dist` fp32 - flat outputs.  The table goes to the device once (pinned,
         non-blocking); per batch of B rows one AEW_OP_MEL_TILE fills in_mel, _cond_plan_a runs unchanged and one
-        AEW_OP_CODE_STITCH moves the codes whose receptive field lies inside real frames.  Writes what encode_codes()
-        writes and nothing else of the engine; no host synchronisation."""
-        mt, cs = self.utterance_ops()
+        AEW_OP_CODE_STITCH moves the codes whose receptive field lies inside real frames (_run_tiles).  Writes what
+        encode_codes() writes and nothing else of the engine; no host synchronisation."""
+        self.utterance_ops()
         self._cond_plans()
-        n = len(table)
-        if n % self.B or table.dtype.itemsize != C.sizeof(L.UttRow):
-            raise L.AewError(f"encode_tiles(): a multiple of B = {self.B} aew_utt_row_t records expected, got {n}")
+        n = self._tile_rows("encode_tiles()", table, L.UttRow, "aew_utt_row_t")
         if mel.dtype != torch.float32 or codes.dtype != torch.int64 or not mel.is_contiguous() or not codes.is_contiguous() \
                 or (dist is not None and (dist.dtype != torch.float32 or dist.numel() != codes.numel())):
             raise L.AewError("encode_tiles(): flat fp32 mel, int64 codes and fp32 dist (one per code) expected")
         if n == 0:
             return
-        host = torch.empty(n * table.dtype.itemsize, dtype=torch.uint8, pin_memory=True)
-        host.numpy()[:] = table.view(np.uint8).reshape(-1)
-        dev = torch.empty_like(host, device=self.device)
-        dev.copy_(host, non_blocking=True)
-        mt.table = cs.table = dev.data_ptr()
-        mt.table_host = cs.table_host = host.data_ptr()
-        mt.mel, mt.n_src = mel.data_ptr(), mel.numel()
-        cs.codes, cs.n_dst, cs.dist = codes.data_ptr(), codes.numel(), (dist.data_ptr() if dist is not None else None)
         self.act_epoch += 1
-        st = self._stream()
-        for first in range(0, n, self.B):
-            mt.first_row = cs.first_row = first
-            self.utt_tile.run(st)
-            self._run(self._cond_plan_a, False)
-            self.utt_stitch.run(st)
+        self._run_tiles(self.utt_tile, self._cond_plan_a, self.utt_stitch, self._utt_fields(mel, codes, dist), table)
         self.lin_live = True
-        # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
-        # keep no address of them
-        mt.table = cs.table = mt.table_host = cs.table_host = mt.mel = cs.codes = cs.dist = None
 
     def segment_tiles(self, mel: torch.Tensor, table, offsets, penalty, return_dist: bool = False):
         """Whole utterances through the fixed-geometry encoder and a penalised Viterbi pass over the codebook: `mel`, `table`
         as in encode_tiles(); `offsets` (U + 1,) host integers, the codes each utterance owns (codes.TilePlan.offsets);
         `penalty` one float or one per utterance.  Per batch of B rows one AEW_OP_MEL_TILE fills in_mel, _cond_plan_a runs
         unchanged and one AEW_OP_FRAME_STITCH moves the encoder outputs (bn.lin rows) whose receptive field lies inside real
-        frames to a ragged (n_codes, pitch) buffer; behind the last batch ONE AEW_OP_CODE_SEGMENT chooses the codes of all
-        utterances against the live codebook under the engine's metric (codes.segment_full).  The nearest codes of the
-        batches stay in `ind` and are not stitched: they are no output of this call.  Writes what encode_tiles() writes and
-        nothing else of the engine; no host synchronisation.  -> (codes, dist or None, codes.Segmentation)."""
+        frames to a ragged (n_codes, pitch) buffer (_run_tiles); behind the last batch ONE AEW_OP_CODE_SEGMENT chooses the
+        codes of all utterances against the live codebook under the engine's metric (codes.segment_full).  The nearest
+        codes of the batches stay in `ind` and are not stitched: they are no output of this call.  Writes what
+        encode_tiles() writes and nothing else of the engine; no host synchronisation.
+        -> (codes, dist or None, codes.Segmentation)."""
         from . import codes as CD
-        mt, _ = self.utterance_ops()
+        self.utterance_ops()
         self._cond_plans()
-        bn, n = self.bn, len(table)
-        if n % self.B or table.dtype.itemsize != C.sizeof(L.UttRow):
-            raise L.AewError(f"segment_tiles(): a multiple of B = {self.B} aew_utt_row_t records expected, got {n}")
+        bn = self.bn
+        n = self._tile_rows("segment_tiles()", table, L.UttRow, "aew_utt_row_t")
         if mel.dtype != torch.float32 or not mel.is_contiguous():
             raise L.AewError("segment_tiles(): flat fp32 mel expected")
         offsets = np.asarray(offsets, np.int64).reshape(-1)
         n_codes = int(offsets[-1])
         frames = torch.empty(n_codes, bn.nlin_p, dtype=torch.float32, device=self.device)
         if n:
-            host = torch.empty(n * table.dtype.itemsize, dtype=torch.uint8, pin_memory=True)
-            host.numpy()[:] = table.view(np.uint8).reshape(-1)
-            dev = torch.empty_like(host, device=self.device)
-            dev.copy_(host, non_blocking=True)
-            mt.table, mt.table_host = dev.data_ptr(), host.data_ptr()
-            mt.mel, mt.n_src = mel.data_ptr(), mel.numel()
             fs = L.FrameStitch()
-            fs.table, fs.table_host, fs.B, fs.E = dev.data_ptr(), host.data_ptr(), self.B, self.geom.embed_len
-            fs.lin, fs.lin_bs, fs.d_pitch = bn.lin.ptr, bn.lin.bs, bn.nlin_p
+            fs.B, fs.E, fs.lin, fs.lin_bs, fs.d_pitch = self.B, self.geom.embed_len, bn.lin.ptr, bn.lin.bs, bn.nlin_p
             fs.frames, fs.n_dst = frames.data_ptr(), n_codes
             stitch = Plan("utt.frames")
             stitch.add(L.OP_FRAME_STITCH, fs, "utt.frames", TAG_VQ)
-            rec = stitch.array()[0].u.fstitch
             self.act_epoch += 1
-            st = self._stream()
-            for first in range(0, n, self.B):
-                mt.first_row = rec.first_row = first
-                self.utt_tile.run(st)
-                self._run(self._cond_plan_a, False)
-                stitch.run(st)
+            self._run_tiles(self.utt_tile, self._cond_plan_a, stitch, self._utt_fields(mel), table)
             self.lin_live = True
-            mt.table = mt.table_host = mt.mel = None
         emb = self.emb.view(bn.K, bn.d)
         return CD.segment_full(frames, offsets, emb, penalty, CD.VQ_METRIC_NAMES[bn.metric], return_dist)
 
@@ -924,6 +947,11 @@ class TrainEngine:
             raise L.AewError(f"{what}: bias_utt fp32 ({cond_utt.shape[0]}, {d.NL}, {2 * d.Dp}) contiguous expected, got "
                              f"{tuple(bias_utt.shape)} {bias_utt.dtype}")
 
+    @staticmethod
+    def _cond_fields(codes_flat, cond_utt, bias_utt):
+        return (dict(codes=codes_flat.data_ptr(), n_codes=codes_flat.numel()),
+                dict(cond_utt=cond_utt.data_ptr(), n_dst=cond_utt.numel(), bias_utt=bias_utt.data_ptr(), n_streams=cond_utt.shape[0]))
+
     def conditioning_batch_plan(self, codes_flat: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor, first_row: int,
                                 cond_utt: torch.Tensor, bias_utt: torch.Tensor) -> Plan:
         """One batch of a whole-utterance conditioning as a plan of its own (for a caller's captured graph): [code.tile] +
@@ -932,21 +960,13 @@ class TrainEngine:
         capture).  in_jitter is set to the identity and the decoder's weight layouts are packed here, once (after a change
         of the weights the caller runs decoder_pack_plan() again); the caller zeroes codes_bad and cond_utt and keeps the
         tensors alive."""
-        ct0, cs0 = self.conditioning_ops()
+        self.conditioning_ops()
         self._cond_utt_check("conditioning_batch_plan()", codes_flat, cond_utt, bias_utt)
-        ct, cs = L.CodeTile.from_buffer_copy(ct0), L.CondStitch.from_buffer_copy(cs0)
-        ct.table, ct.table_host, ct.first_row = table.data_ptr(), table_host.data_ptr(), int(first_row)
-        ct.codes, ct.n_codes = codes_flat.data_ptr(), codes_flat.numel()
-        cs.table, cs.table_host, cs.first_row = ct.table, ct.table_host, ct.first_row
-        cs.cond_utt, cs.n_dst, cs.bias_utt, cs.n_streams = cond_utt.data_ptr(), cond_utt.numel(), bias_utt.data_ptr(), cond_utt.shape[0]
         self.finish_ema()                                            # (a deferred EMA accumulation first, as evaluate())
         self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
         self.decoder_pack_plan().run(self._stream())
-        p = Plan("cond.batch")
-        p.add(L.OP_CODE_TILE, ct, "code.tile", TAG_VQ)
-        p.splice(1, self._sub_plan("codes_to_conditioning", self.decode_plan(), lambda i, lab: True))
-        p.add(L.OP_COND_STITCH, cs, "cond.stitch", TAG_UPS)
-        return p
+        return self._tile_batch_plan("cond.batch", self.cond_tile, self.decode_plan(), self.cond_stitch,
+                                     self._cond_fields(codes_flat, cond_utt, bias_utt), table, table_host, first_row)
 
     def conditioning_tiles(self, codes_flat: torch.Tensor, table, cond_utt: torch.Tensor, bias_utt: torch.Tensor):
         """The conditioning of whole utterances through the fixed-geometry chain: `codes_flat` int64, the flat code
@@ -955,42 +975,22 @@ class TrainEngine:
         2 * Dp), contiguous - the caller zero-fills cond_utt once, rows behind an utterance's length are not written.  The
         table goes to the device once (pinned, non-blocking); per batch of B rows one AEW_OP_CODE_TILE fills ind and
         in_voice, decode_plan() runs unchanged with in_jitter the identity, and one AEW_OP_COND_STITCH moves the rows each
-        window owns and the gated bias of first windows.  Codes outside [0, K) become code 0 and count in `codes_bad[0]`
-        (zeroed here; non-zero: the caller decides - reading the word synchronises).  Writes what codes_to_conditioning()
-        writes, the packed layouts of the decoder's weights (decoder_pack_plan(), once per call: what the head of a
-        training forward writes) and nothing else of the engine; no host synchronisation."""
-        ct, cs = self.conditioning_ops()
-        dp = self.decode_plan()
-        n = len(table)
-        if n % self.B or table.dtype.itemsize != C.sizeof(L.CondRow):
-            raise L.AewError(f"conditioning_tiles(): a multiple of B = {self.B} aew_cond_row_t records expected, got {n}")
+        window owns and the gated bias of first windows (_run_tiles).  Codes outside [0, K) become code 0 and count in
+        `codes_bad[0]` (zeroed here; non-zero: the caller decides - reading the word synchronises).  Writes what
+        codes_to_conditioning() writes, the packed layouts of the decoder's weights (decoder_pack_plan(), once per call:
+        what the head of a training forward writes) and nothing else of the engine; no host synchronisation."""
+        self.conditioning_ops()
+        n = self._tile_rows("conditioning_tiles()", table, L.CondRow, "aew_cond_row_t")
         self._cond_utt_check("conditioning_tiles()", codes_flat, cond_utt, bias_utt)
         self.codes_bad.zero_()
         if n == 0:
             return
-        host = torch.empty(n * table.dtype.itemsize, dtype=torch.uint8, pin_memory=True)
-        host.numpy()[:] = table.view(np.uint8).reshape(-1)
-        dev = torch.empty_like(host, device=self.device)
-        dev.copy_(host, non_blocking=True)
-        ct.table = cs.table = dev.data_ptr()
-        ct.table_host = cs.table_host = host.data_ptr()
-        ct.codes, ct.n_codes = codes_flat.data_ptr(), codes_flat.numel()
-        cs.cond_utt, cs.n_dst, cs.bias_utt, cs.n_streams = cond_utt.data_ptr(), cond_utt.numel(), bias_utt.data_ptr(), cond_utt.shape[0]
         self.finish_ema()                                            # (a deferred EMA accumulation first, as evaluate())
         self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
+        self.decoder_pack_plan().run(self._stream())
         self.act_epoch += 1
-        st = self._stream()
-        self.decoder_pack_plan().run(st)
-        try:
-            for first in range(0, n, self.B):
-                ct.first_row = cs.first_row = first
-                self.cond_tile.run(st)
-                self._run(dp, False)
-                self.cond_stitch.run(st)
-        finally:
-            # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
-            # keep no address of them
-            ct.table = cs.table = ct.table_host = cs.table_host = ct.codes = cs.cond_utt = cs.bias_utt = None
+        self._run_tiles(self.cond_tile, self.decode_plan(), self.cond_stitch, self._cond_fields(codes_flat, cond_utt, bias_utt),
+                        table)
 
     # ---- whole utterances through the teacher-forced decoder: the likelihood of a waveform given codes and a voice ---------
     def score_decoder_plan(self) -> Plan:
@@ -1057,13 +1057,11 @@ class TrainEngine:
             if t is not None and (t.dtype != dt or t.shape != nll.shape or not t.is_contiguous()):
                 raise L.AewError(f"{what}: {name} must be {dt}, contiguous, one value per nll element")
 
-    def _score_fill(self, wt, ns, table_ptr, host_ptr, codes_flat, wav_flat, nll, ptgt, hit):
-        wt.table = ns.table = table_ptr
-        wt.table_host = ns.table_host = host_ptr
-        wt.codes, wt.n_codes, wt.wavs, wt.n_wav = codes_flat.data_ptr(), codes_flat.numel(), wav_flat.data_ptr(), wav_flat.numel()
-        ns.dst_nll, ns.n_dst = nll.data_ptr(), nll.numel()
-        ns.dst_ptgt = ptgt.data_ptr() if ptgt is not None else None
-        ns.dst_hit = hit.data_ptr() if hit is not None else None
+    @staticmethod
+    def _score_fields(codes_flat, wav_flat, nll, ptgt, hit):
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        return (dict(codes=codes_flat.data_ptr(), n_codes=codes_flat.numel(), wavs=wav_flat.data_ptr(), n_wav=wav_flat.numel()),
+                dict(dst_nll=nll.data_ptr(), n_dst=nll.numel(), dst_ptgt=ptr(ptgt), dst_hit=ptr(hit)))
 
     def score_batch_plan(self, codes_flat: torch.Tensor, wav_flat: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor,
                          first_row: int, nll: torch.Tensor, ptgt: Optional[torch.Tensor] = None,
@@ -1074,19 +1072,14 @@ class TrainEngine:
         set to the identity and the decoder's weight layouts are packed here, once (after a change of the weights the
         caller runs decoder_pack_plan() again); the caller zeroes codes_bad / score_bad and keeps the tensors alive.  A
         deferred EMA accumulation is applied here, once, as evaluate() does at its head."""
-        wt0, ns0, _ = self.scoring_ops()
+        self.scoring_ops()
         self._score_check("score_batch_plan()", codes_flat, wav_flat, nll, ptgt, hit)
-        wt, ns = L.WavTile.from_buffer_copy(wt0), L.NllStitch.from_buffer_copy(ns0)
-        self._score_fill(wt, ns, table.data_ptr(), table_host.data_ptr(), codes_flat, wav_flat, nll, ptgt, hit)
-        wt.first_row = ns.first_row = int(first_row)
-        self.finish_ema()
+        self.finish_ema()                                            # (a deferred EMA accumulation first, as evaluate())
         self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
         self.decoder_pack_plan().run(self._stream())
-        p = Plan("score.batch")
-        p.add(L.OP_WAV_TILE, wt, "wav.tile", TAG_VQ)
-        p.splice(1, self._sub_plan("score", self.score_plan(), lambda i, lab: True))
-        p.add(L.OP_NLL_STITCH, ns, "nll.stitch", TAG_LOSS, join=True)
-        return p
+        return self._tile_batch_plan("score.batch", self.score_tile, self.score_plan(), self.score_stitch,
+                                     self._score_fields(codes_flat, wav_flat, nll, ptgt, hit), table, table_host, first_row,
+                                     join=True)
 
     def score_tiles(self, codes_flat: torch.Tensor, wav_flat: torch.Tensor, table, nll: torch.Tensor,
                     ptgt: Optional[torch.Tensor] = None, hit: Optional[torch.Tensor] = None, *, offsets, acc: torch.Tensor,
@@ -1098,19 +1091,17 @@ class TrainEngine:
         (`offsets`: U + 1 host integers); `acc` float64 (U, 4) and `out` float32 (U, 4), what AEW_OP_SCORE_REDUCE writes.
         The table and the offsets go to the device once (one pinned buffer, non-blocking); per batch of B rows one
         AEW_OP_WAV_TILE fills in_wav / ind / in_voice, score_plan() runs with in_jitter the identity, and one
-        AEW_OP_NLL_STITCH moves the outputs each window owns; then one AEW_OP_SCORE_REDUCE.  Codes outside [0, K) become
-        code 0 and count in `codes_bad[0]`, samples outside [0, n_quant) become the zero-amplitude code and count in
-        `score_bad[0]` (both zeroed here; reading them synchronises).  Writes what codes_to_conditioning() writes, the
-        decoder's activations and logits (act_epoch), the packed layouts of the decoder's weights (decoder_pack_plan(),
-        once per call) and nothing else of the engine: none of emb, the EMA accumulators and statistics, ind_hist,
-        loss_buf, met_buf, diag, eval_acc / eval_hist, the parameters, gradients, moments or the average.  A deferred EMA
-        accumulation (forward() with an asynchronous statistics collective and no backward since) is applied first, as
-        evaluate() does: the codebook read is the one behind that update.  No host synchronisation otherwise."""
-        wt, ns, sr = self.scoring_ops()
-        sp = self.score_plan()
-        n = len(table)
-        if n % self.B or table.dtype.itemsize != C.sizeof(L.ScoreRow):
-            raise L.AewError(f"score_tiles(): a multiple of B = {self.B} aew_score_row_t records expected, got {n}")
+        AEW_OP_NLL_STITCH moves the outputs each window owns (_run_tiles); then one AEW_OP_SCORE_REDUCE.  Codes outside
+        [0, K) become code 0 and count in `codes_bad[0]`, samples outside [0, n_quant) become the zero-amplitude code and
+        count in `score_bad[0]` (both zeroed here; reading them synchronises).  Writes what codes_to_conditioning() writes,
+        the decoder's activations and logits (act_epoch), the packed layouts of the decoder's weights
+        (decoder_pack_plan(), once per call) and nothing else of the engine: none of emb, the EMA accumulators and
+        statistics, ind_hist, loss_buf, met_buf, diag, eval_acc / eval_hist, the parameters, gradients, moments or the
+        average.  A deferred EMA accumulation (forward() with an asynchronous statistics collective and no backward since)
+        is applied first, as evaluate() does: the codebook read is the one behind that update.  No host synchronisation
+        otherwise."""
+        _, _, sr = self.scoring_ops()
+        n = self._tile_rows("score_tiles()", table, L.ScoreRow, "aew_score_row_t")
         self._score_check("score_tiles()", codes_flat, wav_flat, nll, ptgt, hit)
         off = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
         U = len(off) - 1
@@ -1127,38 +1118,22 @@ class TrainEngine:
             return
         self._chain_watch("check")
         self.finish_ema()
-        n_tbl = n * table.dtype.itemsize                                  # (a multiple of 64: the offsets behind it stay aligned)
-        host = torch.empty(n_tbl + off.nbytes, dtype=torch.uint8, pin_memory=True)
-        host.numpy()[:n_tbl] = table.view(np.uint8).reshape(-1)
-        host.numpy()[n_tbl:] = off.view(np.uint8)
-        dev = torch.empty_like(host, device=self.device)
-        dev.copy_(host, non_blocking=True)
-        self._score_fill(wt, ns, dev.data_ptr(), host.data_ptr(), codes_flat, wav_flat, nll, ptgt, hit)
-        sr.offsets, sr.offsets_host, sr.U = dev.data_ptr() + n_tbl, host.data_ptr() + n_tbl, U
-        sr.nll, sr.n_src = nll.data_ptr(), nll.numel()
-        sr.ptgt = ptgt.data_ptr() if ptgt is not None else None
-        sr.hit = hit.data_ptr() if hit is not None else None
-        sr.acc, sr.out = acc.data_ptr(), out.data_ptr()
         self.in_jitter.copy_(torch.arange(self.geom.embed_len, device=self.device).expand(self.B, -1))
-        st = self._stream()
+        if n:
+            self.act_epoch += 1
+            self.decoder_pack_plan().run(self._stream())
+        tile_f, stitch_f = self._score_fields(codes_flat, wav_flat, nll, ptgt, hit)
+        # (a table is a multiple of 64 bytes long: the offsets behind it stay aligned)
+        dev, host = self._run_tiles(self.score_tile, self.score_plan(), self.score_stitch, (tile_f, stitch_f), table, (off,))
         try:
-            if n:
-                self.act_epoch += 1
-                self.decoder_pack_plan().run(st)
-            for first in range(0, n, self.B):
-                wt.first_row = ns.first_row = first
-                self.score_tile.run(st)
-                self._run(sp, False)
-                self.score_stitch.run(st)
-            self.score_reduce.run(st)
+            sr.offsets, sr.offsets_host, sr.U = dev.data_ptr() + table.nbytes, host.data_ptr() + table.nbytes, U
+            sr.nll, sr.n_src, sr.ptgt, sr.hit = stitch_f["dst_nll"], stitch_f["n_dst"], stitch_f["dst_ptgt"], stitch_f["dst_hit"]
+            sr.acc, sr.out = acc.data_ptr(), out.data_ptr()
+            self.score_reduce.run(self._stream())
             if n:
                 self._chain_watch("fwd")
         finally:
-            # `dev` and `host` return to torch's allocators, which order their reuse behind this stream's work; the records
-            # keep no address of them
-            wt.table = ns.table = wt.table_host = ns.table_host = wt.codes = wt.wavs = None
-            ns.dst_nll = ns.dst_ptgt = ns.dst_hit = None
-            sr.offsets = sr.offsets_host = sr.nll = sr.ptgt = sr.hit = sr.acc = sr.out = None
+            sr.offsets = sr.offsets_host = sr.nll = sr.ptgt = sr.hit = sr.acc = sr.out = None     # (as _run_tiles leaves its two)
 
     def conditioning(self):
         """Encoder / bottleneck and the conditioning half of the decoder forward only (jitter gather, lc_conv,

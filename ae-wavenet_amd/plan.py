@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -20,6 +21,18 @@ ESIZE = {L.BF16: 2, L.F32: 4}
 
 def ru(x: int, m: int) -> int:
     return (x + m - 1) // m * m
+
+
+def pinned_upload(dev, *arrays: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The bytes of host arrays, one behind the other, on the device `dev`: written to pinned memory and copied from
+    there behind the stream, so the host does not wait.  -> (device bytes, pinned host bytes), uint8, at least one byte
+    long; a launcher that checks its table on the host reads the second."""
+    host = torch.empty(max(sum(a.nbytes for a in arrays), 1), dtype=torch.uint8, pin_memory=True)
+    at = 0
+    for a in arrays:
+        host.numpy()[at:at + a.nbytes] = a.view(np.uint8).reshape(-1)
+        at += a.nbytes
+    return host.to(dev, non_blocking=True), host
 
 
 class Workspace:

@@ -838,13 +838,26 @@ class HipModelBase(nn.Module):
             return (codes, dist.view(B, self.embed_len).clone()) if return_dist else codes
 
     # ---- whole utterances: codes for any length and for a corpus ----------------------------------------------------
-    def _encode_ragged(self, what, flat, frames, bases, voice, batch, return_dist, names):
-        """flat: the ragged fp32 buffer of the utterances' (n_mel, frames[u]) arrays at the element offsets `bases`."""
-        from . import codes as CD
+    def _ragged_mels(self, what, mels):
+        """A list of (n_mel, F_u) device tensors -> (flat, frames, bases): the ragged fp32 buffer of the arrays one behind
+        the other, the frame count of each and the element offset it starts at."""
+        mels = list(mels)
+        n_mel = self._opts["n_mel"] or 3 * self.hps.n_mfcc
+        for m in mels:
+            if m.dim() != 2 or m.shape[0] != n_mel or m.device.type != "cuda":
+                raise L.AewError(f"{what}: ({n_mel}, frames) device tensors expected, got {tuple(m.shape)} on '{m.device}'")
+        frames = [int(m.shape[1]) for m in mels]
+        bases = [0] + np.cumsum([n_mel * F for F in frames[:-1]], dtype=np.int64).tolist() if frames else []
+        flat = torch.cat([m.to(torch.float32).reshape(-1) for m in mels]) if sum(frames) else \
+            torch.empty(0, dtype=torch.float32, device=self._device)
+        return flat, frames, bases
+
+    def _ragged_engine(self, what, U, voice, batch):
+        """The batch and voice checks of a call over U whole utterances -> (B, voice as an int64 tensor or None, the engine
+        of B rows)."""
         if batch is not None and int(batch) < 1:
             raise L.AewError(f"{what}: batch must be at least 1, got {batch}")
         B = int(batch) if batch is not None else (self._engine.B if self._engine is not None else int(self.hps.n_batch))
-        U = len(frames)
         if voice is not None:
             voice = torch.as_tensor(voice, dtype=torch.int64)
             if tuple(voice.shape) != (U,):
@@ -852,6 +865,50 @@ class HipModelBase(nn.Module):
         with torch.no_grad():
             eng = self._ensure_engine(B)
             self._dp_finish()
+        return B, voice, eng
+
+    def _corpus_chunks(self, corpus, max_frames_per_chunk):
+        """The utterances of a `corpus.DeviceCorpus` in chunks of at most max_frames_per_chunk mel frames (one utterance at
+        least) -> (the resident sound as a 1-D tensor of samples, [[indices into corpus.samples of one chunk]])."""
+        if corpus.snd is None:
+            corpus._need_device()
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[corpus.snd_bytes]
+        snd = corpus.snd[:corpus.n_snd * corpus.snd_bytes].view(dt)
+        mf = self._utterance_mfcc()
+        chunks, cur, held = [], [], 0
+        for i, sam in enumerate(corpus.samples):
+            F = max(0, mf.n_frames(int(sam[2]) - int(sam[1])))
+            if cur and held + F > int(max_frames_per_chunk):
+                chunks.append(cur)
+                cur, held = [], 0
+            cur.append(i)
+            held += F
+        if cur:
+            chunks.append(cur)
+        return snd, chunks
+
+    def _cat(self, tensors, dtype):
+        return torch.cat(tensors) if tensors else torch.empty(0, dtype=dtype, device=self._device)
+
+    def _corpus_codes(self, corpus, parts, return_dist):
+        """The `codes.UtteranceCodes` of the chunks `parts`, one behind the other, with the corpus's voices and names."""
+        from . import codes as CD
+        offsets = [0]
+        for p in parts:
+            at = offsets[-1]
+            offsets += [at + o for o in p._off[1:]]
+        sams = corpus.samples
+        voice = torch.tensor([int(s[0]) for s in sams], dtype=torch.int64)
+        names = [str(s[3]) for s in sams] if all(len(s) > 3 for s in sams) else None
+        return CD.UtteranceCodes(self._cat([p.codes for p in parts], torch.int64), torch.tensor(offsets, dtype=torch.int64),
+                                 dist=self._cat([p.dist for p in parts], torch.float32) if return_dist else None,
+                                 voice=voice, names=names)
+
+    def _encode_ragged(self, what, flat, frames, bases, voice, batch, return_dist, names):
+        """flat: the ragged fp32 buffer of the utterances' (n_mel, frames[u]) arrays at the element offsets `bases`."""
+        from . import codes as CD
+        B, voice, eng = self._ragged_engine(what, len(frames), voice, batch)
+        with torch.no_grad():
             E, s, rf, _ = G.utterance_geometry(eng.geom)
             plan = CD.tile_plan(frames, E, s, rf, B)
             codes = torch.empty(plan.n_codes, dtype=torch.int64, device=eng.device)
@@ -873,19 +930,7 @@ class HipModelBase(nn.Module):
         averaged weights are used; a pending `loss.backward()` raises afterwards; no host synchronisation and no
         collective (under data parallel each rank encodes what it is given)."""
         self._need_codes("encode_utterances()")
-        mels = list(mels)
-        n_mel = self._opts["n_mel"] or 3 * self.hps.n_mfcc
-        for m in mels:
-            if m.dim() != 2 or m.shape[0] != n_mel or m.device.type != "cuda":
-                raise L.AewError(f"encode_utterances(): ({n_mel}, frames) device tensors expected, got {tuple(m.shape)} on "
-                                 f"'{m.device}'")
-        frames = [int(m.shape[1]) for m in mels]
-        bases, at = [], 0
-        for F in frames:
-            bases.append(at)
-            at += n_mel * F
-        flat = torch.cat([m.to(torch.float32).reshape(-1) for m in mels]) if at else \
-            torch.empty(0, dtype=torch.float32, device=self._device)
+        flat, frames, bases = self._ragged_mels("encode_utterances()", mels)
         return self._encode_ragged("encode_utterances()", flat, frames, bases, voice, batch, return_dist, names)
 
     def _utterance_mfcc(self):
@@ -915,51 +960,19 @@ class HipModelBase(nn.Module):
         `names` = their file_path (where the records carry one).  The utterances are taken in chunks of at most
         max_frames_per_chunk mel frames (one utterance at least), which bounds the memory held besides the result;
         every utterance is encoded on its own, so the chunking does not change a bit."""
-        from . import codes as CD
         self._need_codes("encode_corpus()")
-        if corpus.snd is None:
-            corpus._need_device()
-        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[corpus.snd_bytes]
-        snd = corpus.snd[:corpus.n_snd * corpus.snd_bytes].view(dt)
-        mf = self._utterance_mfcc()
-        chunks, cur, held = [], [], 0
-        for sam in corpus.samples:
-            F = max(0, mf.n_frames(int(sam[2]) - int(sam[1])))
-            if cur and held + F > int(max_frames_per_chunk):
-                chunks.append(cur)
-                cur, held = [], 0
-            cur.append(sam)
-            held += F
-        if cur:
-            chunks.append(cur)
-        parts = [self.encode_wavs([snd[int(s[1]):int(s[2])] for s in ch], batch=batch, return_dist=return_dist) for ch in chunks]
-        dev = self._device
-        codes = torch.cat([p.codes for p in parts]) if parts else torch.empty(0, dtype=torch.int64, device=dev)
-        dist = (torch.cat([p.dist for p in parts]) if parts else torch.empty(0, dtype=torch.float32, device=dev)) \
-            if return_dist else None
-        offsets, at = [0], 0
-        for p in parts:
-            offsets += [at + o for o in p._off[1:]]
-            at = offsets[-1]
-        voice = torch.tensor([int(s[0]) for s in corpus.samples], dtype=torch.int64)
-        names = [str(s[3]) for s in corpus.samples] if all(len(s) > 3 for s in corpus.samples) else None
-        return CD.UtteranceCodes(codes, torch.tensor(offsets, dtype=torch.int64), dist=dist, voice=voice, names=names)
+        snd, chunks = self._corpus_chunks(corpus, max_frames_per_chunk)
+        sams = corpus.samples
+        parts = [self.encode_wavs([snd[int(sams[i][1]):int(sams[i][2])] for i in ch], batch=batch, return_dist=return_dist)
+                 for ch in chunks]
+        return self._corpus_codes(corpus, parts, return_dist)
 
     # ---- whole utterances: the code sequence chosen jointly ---------------------------------------------------------
     def _segment_ragged(self, what, flat, frames, bases, penalty, voice, batch, return_dist, names, return_info):
         from . import codes as CD
-        if batch is not None and int(batch) < 1:
-            raise L.AewError(f"{what}: batch must be at least 1, got {batch}")
-        B = int(batch) if batch is not None else (self._engine.B if self._engine is not None else int(self.hps.n_batch))
-        U = len(frames)
-        lam = CD._penalties(penalty, U, what)                                # (refused before anything runs)
-        if voice is not None:
-            voice = torch.as_tensor(voice, dtype=torch.int64)
-            if tuple(voice.shape) != (U,):
-                raise L.AewError(f"{what}: voice ({U},) expected (one per utterance), got {tuple(voice.shape)}")
+        lam = CD._penalties(penalty, len(frames), what)                      # (refused before anything runs)
+        B, voice, eng = self._ragged_engine(what, len(frames), voice, batch)
         with torch.no_grad():
-            eng = self._ensure_engine(B)
-            self._dp_finish()
             if eng.bn.K > L.SEG_MAX_K:
                 raise L.AewError(f"{what}: a codebook of at most {L.SEG_MAX_K} entries expected, this one has {eng.bn.K}")
             E, s, rf, _ = G.utterance_geometry(eng.geom)
@@ -985,19 +998,7 @@ class HipModelBase(nn.Module):
         histogram, loss or metric word is written; inside `FusedAdam.averaged_weights()` the averaged weights are used; no
         host synchronisation."""
         self._need_codes("segment_utterances()")
-        mels = list(mels)
-        n_mel = self._opts["n_mel"] or 3 * self.hps.n_mfcc
-        for m in mels:
-            if m.dim() != 2 or m.shape[0] != n_mel or m.device.type != "cuda":
-                raise L.AewError(f"segment_utterances(): ({n_mel}, frames) device tensors expected, got {tuple(m.shape)} on "
-                                 f"'{m.device}'")
-        frames = [int(m.shape[1]) for m in mels]
-        bases, at = [], 0
-        for F in frames:
-            bases.append(at)
-            at += n_mel * F
-        flat = torch.cat([m.to(torch.float32).reshape(-1) for m in mels]) if at else \
-            torch.empty(0, dtype=torch.float32, device=self._device)
+        flat, frames, bases = self._ragged_mels("segment_utterances()", mels)
         return self._segment_ragged("segment_utterances()", flat, frames, bases, penalty, voice, batch, return_dist, names,
                                     return_info)
 
@@ -1019,41 +1020,17 @@ class HipModelBase(nn.Module):
         max_frames_per_chunk * K * 4: 512 MiB at the default and K = 4096)."""
         from . import codes as CD
         self._need_codes("segment_corpus()")
-        if corpus.snd is None:
-            corpus._need_device()
-        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[corpus.snd_bytes]
-        snd = corpus.snd[:corpus.n_snd * corpus.snd_bytes].view(dt)
-        mf = self._utterance_mfcc()
-        lam = CD._penalties(penalty, len(corpus.samples), "segment_corpus()")
-        chunks, cur, held = [], [], 0
-        for i, sam in enumerate(corpus.samples):
-            F = max(0, mf.n_frames(int(sam[2]) - int(sam[1])))
-            if cur and held + F > int(max_frames_per_chunk):
-                chunks.append(cur)
-                cur, held = [], 0
-            cur.append(i)
-            held += F
-        if cur:
-            chunks.append(cur)
+        snd, chunks = self._corpus_chunks(corpus, max_frames_per_chunk)
         sams = corpus.samples
+        lam = CD._penalties(penalty, len(sams), "segment_corpus()")
         parts = [self.segment_wavs([snd[int(sams[i][1]):int(sams[i][2])] for i in ch], lam[ch], batch=batch,
                                    return_dist=return_dist, return_info=True) for ch in chunks]
-        dev = self._device
-        cat = lambda ts, dtype: torch.cat(ts) if ts else torch.empty(0, dtype=dtype, device=dev)
-        codes = cat([p.codes for p, _ in parts], torch.int64)
-        dist = cat([p.dist for p, _ in parts], torch.float32) if return_dist else None
-        offsets, at = [0], 0
-        for p, _ in parts:
-            offsets += [at + o for o in p._off[1:]]
-            at = offsets[-1]
-        voice = torch.tensor([int(s[0]) for s in sams], dtype=torch.int64)
-        names = [str(s[3]) for s in sams] if all(len(s) > 3 for s in sams) else None
-        uc = CD.UtteranceCodes(codes, torch.tensor(offsets, dtype=torch.int64), dist=dist, voice=voice, names=names)
+        uc = self._corpus_codes(corpus, [p for p, _ in parts], return_dist)
         if not return_info:
             return uc
-        n_bad = torch.stack([i.n_bad for _, i in parts]).sum(0) if parts else torch.zeros(1, dtype=torch.int32, device=dev)
-        info = CD.Segmentation(cat([i.cost for _, i in parts], torch.float32), cat([i.n_segments for _, i in parts], torch.int32),
-                               cat([i.penalty for _, i in parts], torch.float32), n_bad.to(torch.int32))
+        n_bad = torch.stack([i.n_bad for _, i in parts]).sum(0) if parts else torch.zeros(1, dtype=torch.int32, device=self._device)
+        info = CD.Segmentation(self._cat([i.cost for _, i in parts], torch.float32), self._cat([i.n_segments for _, i in parts], torch.int32),
+                               self._cat([i.penalty for _, i in parts], torch.float32), n_bad.to(torch.int32))
         return uc, info
 
     def zero_amplitude_code(self) -> int:

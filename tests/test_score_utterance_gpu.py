@@ -168,6 +168,68 @@ def test_the_three_ops_equal_the_emulators_bit_for_bit(hit_from):
     assert g_acc[:4].tolist() == [0, 0, 0, 0] and g_out[:4].tolist() == [0, 0, 0, 0]       # nothing to score: a zero summary
 
 
+# The code window is cut by one device function for AEW_OP_CODE_TILE (64 threads a row) and AEW_OP_WAV_TILE (256): windows
+# one code longer than each stride, so that thread 0 comes round a second time - to a live code of row 0 - in one of the two
+# ops at either size; T = 257 lets the sample loop of AEW_OP_WAV_TILE wrap as well.
+@pytest.mark.parametrize("E,T", [(65, 9), (257, 257)])
+def test_code_tile_and_wav_tile_cut_the_same_windows(E, T):
+    B, Q, zero, pitch, wav_off, n_voice = 3, 8, 4.0, T + 16, 9, 5
+    # row 0 starts 3 codes in front of the buffer (lo > 0, code0 < 0) and reads the codes [0, E - 3), its last one at
+    # j = E - 1; two codes no window reads; row 1 reads the last E - 5 codes of the buffer (hi < E); row 2 is idle
+    n_codes = 2 * E - 6
+    win = [dict(utt=0, code0=-3, lo=3, hi=E, voice=4), dict(utt=1, code0=E - 1, lo=0, hi=E - 5, voice=2)]
+    ctbl, stbl = np.zeros(B, np.dtype(L.COND_ROW_DTYPE)), np.zeros(B, np.dtype(L.SCORE_ROW_DTYPE))
+    ctbl["utt"] = stbl["utt"] = -1
+    for b, w in enumerate(win):
+        for name, value in w.items():
+            ctbl[name][b] = stbl[name][b] = value
+    ctbl["stream"][:2], ctbl["pitch"][:2] = [0, 1], 1
+    stbl["wav_base"][:2], stbl["wav_len"][:2], stbl["wav0"][:2] = [0, T + 3], [T + 3, T - 4], [-2, 0]
+    rs = np.random.RandomState(E)
+    codes = rs.randint(1, K, n_codes).astype(np.int64)
+    codes[[1, E - 4]] = [K, np.iinfo(np.int64).max]                        # inside row 0's window, at j = 4 and j = E - 1: counted
+    codes[E - 3] = -1                                                      # outside the codebook, but read by no window
+    wavs = rs.randint(0, Q, 2 * T - 1).astype(np.float32)
+    assert int(stbl["code0"][1] + stbl["hi"][1]) == n_codes and int(stbl["wav_base"][1] + stbl["wav_len"][1]) == wavs.size
+    w_ind, w_voice, w_bad = CE.code_tile(ctbl, 0, B, codes, E, K)
+    s_wav, s_ind, s_voice, s_bad, s_bad_wav = SE.wav_tile(stbl, 0, B, codes, wavs, E, K, T, Q, zero)
+    assert w_bad == s_bad == 2 and s_bad_wav == 0 and w_ind.tobytes() == s_ind.tobytes() and w_voice.tolist() == s_voice.tolist() == [4, 2, 0]
+    assert w_ind[0, E - 1] == 0 and w_ind[0, E - 2] == codes[E - 5] and (w_ind[0, :3] == 0).all() and (w_ind[1, E - 5:] == 0).all()
+    codes_d, wavs_d = _dev(codes), _dev(wavs)
+    got = {}
+    for kind in (L.OP_CODE_TILE, L.OP_WAV_TILE):
+        tbl = ctbl if kind == L.OP_CODE_TILE else stbl
+        tbl_d, tbl_h = _dev(tbl.view(np.uint8).reshape(-1)), _pinned(tbl)
+        ind = torch.full((B * E + 64,), -9, dtype=torch.int64, device=DEV)
+        voice = torch.full((B + 64,), -9, dtype=torch.int64, device=DEV)
+        wav = torch.full((B * pitch + 64,), -5.0, dtype=torch.float32, device=DEV)
+        bad = torch.zeros(4, dtype=torch.int32, device=DEV)
+        rec = L.CodeTile() if kind == L.OP_CODE_TILE else L.WavTile()
+        rec.table, rec.table_host, rec.first_row, rec.B = tbl_d.data_ptr(), tbl_h.data_ptr(), 0, B
+        rec.codes, rec.n_codes, rec.ind, rec.in_voice = codes_d.data_ptr(), n_codes, ind.data_ptr(), voice.data_ptr()
+        rec.E, rec.K, rec.n_voice = E, K, n_voice
+        if kind == L.OP_CODE_TILE:
+            rec.bad = bad.data_ptr()
+        else:
+            rec.bad_codes, rec.bad_wav = bad.data_ptr(), bad.data_ptr() + 4
+            rec.wavs, rec.n_wav, rec.wav = wavs_d.data_ptr(), wavs.size, wav.data_ptr()
+            rec.wav_pitch, rec.wav_off, rec.T, rec.n_quant, rec.zero = pitch, wav_off, T, Q, zero
+        _run(kind, rec)
+        got[kind] = (ind.cpu().numpy(), voice.cpu().numpy(), bad.cpu().tolist(), wav.cpu().numpy())
+    for kind, want_i, want_v, want_bad in ((L.OP_CODE_TILE, w_ind, w_voice, w_bad), (L.OP_WAV_TILE, s_ind, s_voice, s_bad)):
+        g_i, g_v, g_bad, _ = got[kind]
+        assert g_i[:B * E].tobytes() == want_i.tobytes() and (g_i[B * E:] == -9).all(), kind
+        assert g_v[:B].tobytes() == want_v.tobytes() and (g_v[B:] == -9).all(), kind
+        assert g_bad == [want_bad, 0, 0, 0], kind
+    rows = got[L.OP_WAV_TILE][3][:B * pitch].reshape(B, pitch)
+    assert rows[:, wav_off:wav_off + T].tobytes() == s_wav.tobytes() and (rows[:, :wav_off] == -5.0).all()
+    assert (rows[:, wav_off + T:] == -5.0).all() and (got[L.OP_WAV_TILE][3][B * pitch:] == -5.0).all()
+    assert (got[L.OP_CODE_TILE][3] == -5.0).all()
+    # ... and so the two ops agree with each other: the same ind, the same in_voice, the same count
+    assert got[L.OP_CODE_TILE][0].tobytes() == got[L.OP_WAV_TILE][0].tobytes()
+    assert got[L.OP_CODE_TILE][1].tobytes() == got[L.OP_WAV_TILE][1].tobytes() and got[L.OP_CODE_TILE][2][0] == got[L.OP_WAV_TILE][2][0] == 2
+
+
 def test_reduce_follows_the_fixed_order_over_long_utterances():
     rs = np.random.RandomState(7)
     n = 9001
