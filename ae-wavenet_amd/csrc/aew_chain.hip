@@ -43,7 +43,7 @@ __host__ __device__ __forceinline__ void chain_dep_tiles(const aew_chain_dep_t& 
     t_hi = b / d.bm;
 }
 
-template <int SET>
+template <int SET, bool LINES = false>       // LINES: the STORE / DFG stages leave through the row-contiguous epilogue
 __global__ __launch_bounds__(CHAIN_THREADS, 4) void k_nt_chain(const aew_nt_stage_t* __restrict__ stages,
                                                               const uint16_t* __restrict__ block_stage,
                                                               unsigned* counters, int n_counters, int spin_max, int flags,
@@ -114,15 +114,15 @@ __global__ __launch_bounds__(CHAIN_THREADS, 4) void k_nt_chain(const aew_nt_stag
             else if (kind == 2) win_tile<AEW_EPI_GATED, 4, 4, true>(S.g, smem, L);
             else nt_tile<AEW_EPI_GATED, false, 4, 1, 256, NT_STAGES, true>(S.g, smem, L);
         } else {
-            nt_tile<AEW_EPI_STORE, false, 4, 1, 256, NT_STAGES, true>(S.g, smem, L);
+            nt_tile<AEW_EPI_STORE, false, 4, 1, 256, NT_STAGES, true, LINES>(S.g, smem, L);
         }
     } else {
         if (epi == AEW_EPI_DFG) {
-            nt_tile<AEW_EPI_DFG, false, 4, 1, 256, NT_STAGES, true>(S.g, smem, L);
+            nt_tile<AEW_EPI_DFG, false, 4, 1, 256, NT_STAGES, true, LINES>(S.g, smem, L);
         } else {
-            if (kind == 1) win_tile<AEW_EPI_STORE, 4, 1, true>(S.g, smem, L);
-            else if (kind == 2) win_tile<AEW_EPI_STORE, 4, 4, true>(S.g, smem, L);
-            else nt_tile<AEW_EPI_STORE, false, 4, 1, 256, NT_STAGES, true>(S.g, smem, L);
+            if (kind == 1) win_tile<AEW_EPI_STORE, 4, 1, true, LINES>(S.g, smem, L);
+            else if (kind == 2) win_tile<AEW_EPI_STORE, 4, 4, true, LINES>(S.g, smem, L);
+            else nt_tile<AEW_EPI_STORE, false, 4, 1, 256, NT_STAGES, true, LINES>(S.g, smem, L);
         }
     }
     if (S.publish) {
@@ -139,6 +139,17 @@ static int win_dwp(const aew_gemm_nt_t& g, const aew_tuning_t& T);
 static void nt_pick(const aew_gemm_nt_t& g, const aew_tuning_t& T, NtPick* out);
 static int check_seg(const aew_seg_t& s, int esize, int ktile);
 static int launch_zero(const aew_zero_t& z, hipStream_t st);
+
+// aew_set_nt_epi_lines for a chained launch: one epilogue form per launch, so the row-contiguous one needs every STORE /
+// DFG stage to qualify (the stage ops that follow the chain op in the plan; both forms compute the same bits)
+static bool chain_lines_ok(const aew_op_t* stage_ops, int n) {
+    if (!g_nt_epi_lines) return false;
+    for (int k = 0; k < n; ++k) {
+        const aew_gemm_nt_t& g = stage_ops[k].u.nt;
+        if (g.epi != AEW_EPI_GATED && !epi_lines_ok(g)) return false;
+    }
+    return true;
+}
 
 struct ChainRef {                                            // one operand / result of a stage as rows of a buffer
     const char* ptr; int64_t bs; int pitch, step, off, lo, hi, es;
@@ -373,7 +384,8 @@ extern "C" int aew_nt_chain_build_tuned(const aew_gemm_nt_t* descs, int n, aew_n
     return rc;
 }
 
-static int launch_nt_chain(const aew_nt_chain_t& c, hipStream_t st) {
+// lines: the STORE / DFG stages run the row-contiguous epilogue (the caller has checked every stage op: chain_lines_ok)
+static int launch_nt_chain(const aew_nt_chain_t& c, hipStream_t st, bool lines) {
     if (!c.stages || !c.block_stage || !c.counters || c.n_stages < 1 || c.n_blocks < 8 || (c.n_blocks & 7) || c.n_counters < 1 ||
         (c.set != 0 && c.set != 1))
         return AEW_E_ARG;
@@ -385,11 +397,15 @@ static int launch_nt_chain(const aew_nt_chain_t& c, hipStream_t st) {
         if (zr) return zr;
     }
     const int spin = c.spin_max > 0 ? c.spin_max : (1 << 18);
-    if (c.set == 0)
-        hipLaunchKernelGGL((k_nt_chain<0>), dim3(c.n_blocks), dim3(CHAIN_THREADS), CHAIN_LDS_BYTES, st, c.stages, c.block_stage,
-                           c.counters, c.n_counters, spin, c.flags, c.sticky);
-    else
-        hipLaunchKernelGGL((k_nt_chain<1>), dim3(c.n_blocks), dim3(CHAIN_THREADS), CHAIN_LDS_BYTES, st, c.stages, c.block_stage,
-                           c.counters, c.n_counters, spin, c.flags, c.sticky);
+    // one instantiation per (body set, epilogue form)
+    const void* const fns[4] = {reinterpret_cast<const void*>(k_nt_chain<0>), reinterpret_cast<const void*>(k_nt_chain<1>),
+                                reinterpret_cast<const void*>(k_nt_chain<0, true>), reinterpret_cast<const void*>(k_nt_chain<1, true>)};
+    const aew_nt_stage_t* stages = c.stages;
+    const uint16_t* block_stage = c.block_stage;
+    unsigned* counters = c.counters;
+    unsigned* sticky = c.sticky;
+    int n_counters = c.n_counters, spin_max = spin, flags = c.flags;
+    void* args[] = {&stages, &block_stage, &counters, &n_counters, &spin_max, &flags, &sticky};
+    (void)hipLaunchKernel(fns[c.set + (lines ? 2 : 0)], dim3(c.n_blocks), dim3(CHAIN_THREADS), args, CHAIN_LDS_BYTES, st);
     return (int)hipGetLastError();
 }

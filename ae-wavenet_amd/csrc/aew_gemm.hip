@@ -395,11 +395,11 @@ struct EpiViewCtx {
     const char* base;            // the view's buffer (wave-uniform)
     char* p;                     // lane's pointer for j = 0, nullptr if the view is absent
     int row;                     // lane's view row for j = 0
-    int64_t inc;                 // bytes per 16 GEMM rows           (wave-uniform)
-    int dstep, lo, hi;           // view rows per 16 GEMM rows, range (wave-uniform)
+    int64_t inc;                 // bytes per step of 16 (row-contiguous form: 8) GEMM rows   (wave-uniform)
+    int dstep, lo, hi;           // view rows per step, range        (wave-uniform)
 };
 
-__device__ __forceinline__ EpiViewCtx epi_view_ctx(const aew_view_t& vref, int b, int m) {
+__device__ __forceinline__ EpiViewCtx epi_view_ctx(const aew_view_t& vref, int b, int m, int rows = 16) {   // rows: GEMM rows per step j
     const aew_view_t v = vref;                                // one batch of scalar loads, no branches below
     EpiViewCtx c;
     const int es = v.dtype == AEW_BF16 ? 2 : 4;
@@ -408,8 +408,8 @@ __device__ __forceinline__ EpiViewCtx epi_view_ctx(const aew_view_t& vref, int b
     char* q = reinterpret_cast<char*>(v.ptr) + ((int64_t)b * v.batch_stride + row * v.row_pitch) * es;
     c.p = v.ptr ? q : nullptr;
     c.base = reinterpret_cast<const char*>(v.ptr);
-    c.inc = (int64_t)16 * v.row_step * v.row_pitch * es;
-    c.dstep = 16 * v.row_step;
+    c.inc = (int64_t)rows * v.row_step * v.row_pitch * es;
+    c.dstep = rows * v.row_step;
     c.lo = (int)v.row_lo;
     c.hi = (int)v.row_hi;
     return c;
@@ -420,15 +420,178 @@ __device__ __forceinline__ char* epi_view_row(const EpiViewCtx& c, int j) {
     return (c.p && row >= c.lo && row < c.hi) ? c.p + j * c.inc : nullptr;
 }
 
+// ---- row-contiguous form of the STORE and DFG epilogues of the thin (64-column slab, MT <= 4) bf16 shapes.
+// In the MFMA layout one 16-byte wave access touches 16 rows x 64 B: the two halves of a row's 128-byte line (the wave's
+// 64-channel slab in bf16) leave in two instructions.  Here every 16-row group's accumulators are exchanged across
+// lanes once, in registers (ds_bpermute_b32: no LDS memory, no barrier), so that lane l holds channel octet l & 7 of
+// row l >> 3 (steps 2j, 2j + 1: rows 0-7, 8-15 of group j), and everything after - aux loads, the flag arithmetic, the
+// stores - runs in that layout: one wave access = 8 rows x one whole 128-byte line.  The arithmetic is element-wise
+// and keeps the order of epi_store8_pf / epi_dfg8_pf, so the outputs are bit-identical to nt_epilogue's.
+//
+// Exchange, two bpermutes per register k (each source lane is pulled exactly once per instruction): source lane
+// (fi, fg) offers r1 = fi < 8 ? v[u=0][k] : v[u=1][k] and r2 = the other one; lanes with octet o < 4 pull r1 from
+// (rr, o) - rows 0-7 - and r2 from (rr + 8, o) - rows 8-15; lanes with o >= 4 pull r1 from (rr + 8, o - 4) and r2
+// from (rr, o - 4).
+struct EpiLinesLane {
+    int s1, s2;                  // byte addresses (lane * 4) of the two bpermute sources
+    bool low, left;              // source side: fi < 8; destination side: octet < 4
+};
+__device__ __forceinline__ EpiLinesLane epi_lines_lane(int lane) {
+    EpiLinesLane x;
+    const int rr = lane >> 3, o = lane & 7;
+    x.low = (lane & 15) < 8;
+    x.left = o < 4;
+    x.s1 = (x.left ? rr + 16 * o : rr + 8 + 16 * (o - 4)) * 4;
+    x.s2 = (x.left ? rr + 8 + 16 * o : rr + 16 * (o - 4)) * 4;
+    return x;
+}
+__device__ __forceinline__ void epi_lines_exchange(const EpiLinesLane& x, const f32x4_t& a0, const f32x4_t& a1, const f32x4_t& a2,
+                                                   const f32x4_t& a3, float lo[8], float hi[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float v0 = k < 4 ? a0[k & 3] : a1[k & 3], v1 = k < 4 ? a2[k & 3] : a3[k & 3];
+        const int r1 = __float_as_int(x.low ? v0 : v1), r2 = __float_as_int(x.low ? v1 : v0);
+        const int o1 = __builtin_amdgcn_ds_bpermute(x.s1, r1), o2 = __builtin_amdgcn_ds_bpermute(x.s2, r2);
+        lo[k] = __int_as_float(x.left ? o1 : o2);
+        hi[k] = __int_as_float(x.left ? o2 : o1);
+    }
+}
+
+// The descriptors the row-contiguous form runs; everything else keeps nt_epilogue.  Decided on the HOST, per launch
+// (launch_gemm_nt) and per chained launch (chain_lines_ok): the LINES instantiations carry nt_epilogue_lines only - with
+// both epilogues in one kernel the thin shape spilled inside its K loop.  The chain's choice is made when it is LAUNCHED,
+// from the stage ops that follow it in the plan, not when its stage table is built: aew_nt_chain_t and the tables stay
+// exactly what they were, whatever the setter says.
+static bool epi_lines_ok(const aew_gemm_nt_t& g) {
+    if (g.dtype != AEW_BF16 || (g.epi != AEW_EPI_STORE && g.epi != AEW_EPI_DFG)) return false;
+    bool ok = (!g.out0.ptr || g.out0.dtype == AEW_BF16) && (!g.aux0.ptr || g.aux0.dtype == AEW_BF16) &&
+              (!g.aux1.ptr || g.aux1.dtype == AEW_BF16);
+    if (g.epi == AEW_EPI_STORE) ok = ok && (!g.out1.ptr || g.out1.dtype == AEW_BF16) && !(g.flags & AEW_EF_COUNT_ZERO);
+    return ok;
+}
+
+template <bool WT>
+__device__ __forceinline__ void epi_lines_put16(char* p, const uint32_t w[4]) {
+    if (WT) store16_wt(p, (u32x4_t){w[0], w[1], w[2], w[3]});
+    else *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <int EPI, int MT, bool WT>
+__device__ __forceinline__ void nt_epilogue_lines(const aew_gemm_nt_t& g, f32x4_t (&acc)[4][MT], int b, int m0, int n0,
+                                                  int wm, int wn, int lane) {
+    static_assert(EPI == AEW_EPI_STORE || EPI == AEW_EPI_DFG, "row-contiguous epilogues: STORE and DFG");
+    const int fg = lane >> 4, o = lane & 7;
+    const int mrow = m0 + wm * (16 * MT) + (lane >> 3);       // the lane's GEMM row at step 0; step s = 2j + h adds 8 s
+    const int nw = n0 + wn * 64, n = nw + 8 * o;              // the wave's slab, the lane's 8 channels
+    const EpiLinesLane X = epi_lines_lane(lane);
+    const EpiViewCtx c0 = epi_view_ctx(g.out0, b, mrow, 8);
+    EpiViewCtx c1 = c0;
+    if (EPI == AEW_EPI_STORE) c1 = epi_view_ctx(g.out1, b, mrow, 8);
+    const EpiViewCtx ca0 = epi_view_ctx(g.aux0, b, mrow, 8), ca1 = epi_view_ctx(g.aux1, b, mrow, 8);
+    const EpiUni U = epi_uni(g);
+    const unsigned fl = U.fl;
+    unsigned zc = 0;                                          // (AEW_EF_COUNT_ZERO keeps nt_epilogue: epi_lines_ok)
+    if (EPI == AEW_EPI_STORE && (fl & AEW_EF_BIAS)) {         // bias fold, still in the MFMA layout (as nt_epilogue's)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int nb = nw + u * 32 + 8 * fg;
+            if (nb < U.N) {
+                const float* bp = g.bias + (int64_t)b * g.bias_bs + nb;
+                const float4 b0 = *reinterpret_cast<const float4*>(bp), b1 = *reinterpret_cast<const float4*>(bp + 4);
+#pragma unroll
+                for (int j = 0; j < MT; ++j) {
+                    acc[2 * u][j][0] += b0.x; acc[2 * u][j][1] += b0.y; acc[2 * u][j][2] += b0.z; acc[2 * u][j][3] += b0.w;
+                    acc[2 * u + 1][j][0] += b1.x; acc[2 * u + 1][j][1] += b1.y; acc[2 * u + 1][j][2] += b1.z; acc[2 * u + 1][j][3] += b1.w;
+                }
+            }
+        }
+    }
+    // aux operands one step ahead of their use, as in nt_epilogue (same single-operand budget for STORE)
+    const bool need0 = EPI == AEW_EPI_DFG || (fl & AEW_EF_ADD_AUX0);
+    const bool need1 = EPI == AEW_EPI_DFG || (fl & (AEW_EF_MUL_POS1 | AEW_EF_OUT1_POS1));
+    const bool pf1 = need1 && (EPI == AEW_EPI_DFG || !need0);
+    uint4 raw0[2 * MT], raw1[2 * MT];
+    const __amdgpu_buffer_rsrc_t rs0 = buf_rsrc(WT ? ca0.base : nullptr), rs1 = buf_rsrc(WT ? ca1.base : nullptr);
+    auto aux_get = [&](const EpiViewCtx& c, const __amdgpu_buffer_rsrc_t& rs, int s) -> uint4 {
+        const char* p = epi_view_row(c, s);
+        if (WT) return ld16_sc1(rs, p ? (uint32_t)(p - c.base) + (uint32_t)(n * 2) : AEW_BUF_OOB);
+        const char* z = reinterpret_cast<const char*>(aew_zero_region);
+        return *reinterpret_cast<const uint4*>((p ? p : z) + n * 2);
+    };
+    auto aux_load = [&](int s) {
+        raw0[s] = make_uint4(0, 0, 0, 0);
+        raw1[s] = make_uint4(0, 0, 0, 0);
+        if (need0) raw0[s] = aux_get(ca0, rs0, s);
+        if (EPI == AEW_EPI_DFG) raw1[s] = aux_get(ca1, rs1, s);
+        else if (pf1) raw0[s] = aux_get(ca1, rs1, s);
+    };
+    aux_load(0);
+    // DFG: the packed (16 f | 16 g) row of the slab is two lines; line A holds df / dg of octets 0-3, line B of 4-7, in
+    // 16-byte pieces k = 0..7: df(2q), df(2q+1), dg(2q), dg(2q+1) with q = k >> 2.  Lane k's pieces come from lane
+    // sA = (k >> 2) * 2 + (k & 1) (line A) and sA + 4 (line B) of its 8-lane row, by the same two-bpermute scheme
+    const int t = (o >> 1) & 1, sA = (o >> 2) * 2 + (o & 1);
+    const int d1 = ((lane & ~7) + sA + (t ? 4 : 0)) * 4, d2 = ((lane & ~7) + sA + (t ? 0 : 4)) * 4;
+    const int nA = nw + 8 * sA;                               // channel octet whose products the lane stores into line A
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+        float ex[2][8];
+        epi_lines_exchange(X, acc[0][j], acc[1][j], acc[2][j], acc[3][j], ex[0], ex[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int s = 2 * j + h;
+            if (s + 1 < 2 * MT) aux_load(s + 1);
+            const bool row_ok = mrow + 8 * s < g.M;
+            char* const p0 = epi_view_row(c0, s);
+            if (EPI == AEW_EPI_STORE) {
+                EpiRow R;
+                R.o0 = p0; R.o1 = epi_view_row(c1, s); R.o2 = nullptr; R.a0 = nullptr; R.a1 = nullptr;
+                if (row_ok && n < U.N) {
+                    uint4 a1 = raw0[s];                              // aux1 rode in raw0 (pf1) ...
+                    if (need1 && !pf1) a1 = aux_get(ca1, rs1, s);    // ... or is fetched now (both operands in use)
+                    epi_store8_pf<WT>(U, R, n, ex[h], zc, fl, raw0[s], a1);
+                }
+            } else {
+                float pf[8], pg[8];
+                unpack8_bf16(raw0[s], pf);
+                unpack8_bf16(raw1[s], pg);
+                uint32_t df[4], dg[4], la[4], lb[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    df[q] = pack2_bf16(ex[h][2 * q] * pf[2 * q], ex[h][2 * q + 1] * pf[2 * q + 1]);
+                    dg[q] = pack2_bf16(ex[h][2 * q] * pg[2 * q], ex[h][2 * q + 1] * pg[2 * q + 1]);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int r1 = (int)(o < 4 ? df[q] : dg[q]), r2 = (int)(o < 4 ? dg[q] : df[q]);
+                    const int o1 = __builtin_amdgcn_ds_bpermute(d1, r1), o2 = __builtin_amdgcn_ds_bpermute(d2, r2);
+                    la[q] = (uint32_t)(t ? o2 : o1);
+                    lb[q] = (uint32_t)(t ? o1 : o2);
+                }
+                if (row_ok && p0) {
+                    char* const pl = p0 + nw * 4 + o * 16;           // packed column 2 * nw: byte 4 * nw of the row
+                    if (nA < U.N) epi_lines_put16<WT>(pl, la);
+                    if (nA + 32 < U.N) epi_lines_put16<WT>(pl + 128, lb);
+                }
+            }
+        }
+    }
+}
+
 // (Round 4, measured and removed: the row loop below compiles to one `s_waitcnt vmcnt(0)` per 16-row group - its masks
 // and flags are branches, and at a control-flow join the compiler's wait-count insertion gives up counting - so every
 // group also waits for the stores of the one before.  A branch-free form of the gated / dz / STORE epilogues (masked
 // stores into a sink, flags as selects: counted waits only, no store ever waited for; commit ae1bb12) changed nothing:
 // 6.995 vs 6.968 ms per step.  The epilogue is bound by what it moves, not by how its instructions wait:
 // tools/phase_clock.py, tools/overlap_probe.py, profiles/r04_notes.md.)
-template <int EPI, bool ABL, int MT, bool WT = false>       // WT: out0 stored write-through (stage of a chained launch)
+// LINES: the STORE / DFG epilogues are nt_epilogue_lines (the host launches these instantiations for descriptors
+// that epi_lines_ok accepts: aew_set_nt_epi_lines)
+template <int EPI, bool ABL, int MT, bool WT = false, bool LINES = false>   // WT: out0 stored write-through (stage of a chained launch)
 __device__ __forceinline__ void nt_epilogue(const aew_gemm_nt_t& g, f32x4_t (&acc)[4][MT], int b, int m0, int n0,
                                             int wm, int wn, int lane) {
+    if constexpr (LINES && !ABL && MT <= 4 && (EPI == AEW_EPI_STORE || EPI == AEW_EPI_DFG)) {
+        nt_epilogue_lines<EPI, MT, WT>(g, acc, b, m0, n0, wm, wn, lane);
+        return;
+    }
     const int fi = lane & 15, fg = lane >> 4;
     const int mbase = m0 + wm * (16 * MT) + fi;
     // views each epilogue touches: GATED o0 o1 o2 | RES_SKIP o0 o1 o2 a0 | DFG o0 a0 a1 | STORE o0 o1 a0 a1
@@ -548,7 +711,7 @@ template <int N>
 __device__ __forceinline__ void nt_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // one output tile: block index L of the launch's tile order
-template <int EPI, bool ABL, int MT, int NB, int BMV, int ST, bool WT = false>
+template <int EPI, bool ABL, int MT, int NB, int BMV, int ST, bool WT = false, bool LINES = false>
 __device__ __forceinline__ void nt_tile(const aew_gemm_nt_t& g, char* smem, const int L_) {
     typedef NtCfg<MT, NB, BMV> Cfg;
     static_assert(ST >= 3 && (ST - 2) * (Cfg::XP + Cfg::WP) <= 63 && ST * Cfg::STAGE_BYTES <= 160 * 1024, "ring depth");
@@ -772,13 +935,13 @@ __device__ __forceinline__ void nt_tile(const aew_gemm_nt_t& g, char* smem, cons
             for (int j = 0; j < MT; ++j) asm volatile("" ::"v"(acc[i][j]));
         return;
     }
-    nt_epilogue<EPI, ABL, MT, WT>(g, acc, b, m0, n0, wm, wn, lane);
+    nt_epilogue<EPI, ABL, MT, WT, LINES>(g, acc, b, m0, n0, wm, wn, lane);
 }
 
-template <int EPI, bool ABL = false, int MT = 8, int NB = 1, int BMV = NT_BM, int ST = NT_STAGES>
+template <int EPI, bool ABL = false, int MT = 8, int NB = 1, int BMV = NT_BM, int ST = NT_STAGES, bool LINES = false>
 __global__ __launch_bounds__((NtCfg<MT, NB, BMV>::THREADS), (NtCfg<MT, NB, BMV>::MINW)) void k_gemm_nt_bf16(const aew_gemm_nt_t g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    nt_tile<EPI, ABL, MT, NB, BMV, ST>(g, smem, blockIdx.x);
+    nt_tile<EPI, ABL, MT, NB, BMV, ST, false, LINES>(g, smem, blockIdx.x);
 }
 
 // (Round 4, measured and removed: the same tiles as PERSISTENT blocks - a grid of two blocks per CU, each walking the tile
@@ -2637,6 +2800,12 @@ __global__ void k_gemm_tn_check(const aew_gemm_tn_t g, int splits, int rows_per_
 // what nt_pick (host section below) answers: the aew_nt_kernel code, the row of the variant table (-1: a full-N kernel), that
 // row's tile and block, the launch's grid.x (all K ranges), the split-K ranges it runs and the window pieces (0: not the window body)
 struct NtPick { int kernel, variant, bm, bn, threads, lds_bytes, grid, k_split, dwp; };
+// aew_set_nt_epi_lines: 1 = STORE / DFG launches of the thin default shapes (and chained launches) run the
+// instantiations with the row-contiguous epilogue (nt_epilogue_lines), 0 = the MFMA-layout epilogue.  Process-wide, like
+// aew_set_nt_window; not part of aew_tuning_t (both forms compute the same bits, so no plan depends on it).
+#define AEW_NT_EPI_LINES_DEFAULT 1
+static int g_nt_epi_lines = AEW_NT_EPI_LINES_DEFAULT;
+
 #include "aew_win.hip"                                // k_gemm_nt_bf16_win: one LDS window for both dilation taps
 #include "aew_chain.hip"                              // k_nt_chain: a run of dependent NT GEMMs as one launch
 
@@ -2718,6 +2887,23 @@ typedef TnCfg<TN_BT, TN_BT, TN_THREADS> Tn128;
 static const NtRow g_tn_rows[] = {AEW_TN_ROWS(AEW_ROW)};
 enum { AEW_TN_ROWS(AEW_ID) TNV_COUNT };
 
+// the row-contiguous-epilogue twin of a table row (aew_set_nt_epi_lines), or nullptr: the 256- / 192-row default body and
+// the one-window body, STORE and DFG.  Same Cfg, grid, block and LDS as the row itself - only the function differs.
+static const void* nt_lines_fn(int variant) {
+    switch (variant) {
+#define AEW_LINES(V, K) case V: return reinterpret_cast<const void*>(K);
+    AEW_LINES(NTV_DEF_0, (k_gemm_nt_bf16<AEW_EPI_STORE, false, 4, 1, NT_BM, NT_STAGES, true>))
+    AEW_LINES(NTV_DEF_3, (k_gemm_nt_bf16<AEW_EPI_DFG, false, 4, 1, NT_BM, NT_STAGES, true>))
+    AEW_LINES(NTV_T192_0, (k_gemm_nt_bf16<AEW_EPI_STORE, false, 3, 1, 192, NT_STAGES, true>))
+    AEW_LINES(NTV_T192_3, (k_gemm_nt_bf16<AEW_EPI_DFG, false, 3, 1, 192, NT_STAGES, true>))
+    AEW_LINES(NTV_WIN1_0, (k_gemm_nt_bf16_win<AEW_EPI_STORE, 4, 1, true>))
+    AEW_LINES(NTV_WIN4_0, (k_gemm_nt_bf16_win<AEW_EPI_STORE, 4, 4, true>))
+    AEW_LINES(NTV_WIN192_0, (k_gemm_nt_bf16_win<AEW_EPI_STORE, 3, 4, true>))
+#undef AEW_LINES
+    default: return nullptr;
+    }
+}
+
 // kernels using more than 64 KiB of dynamic LDS must opt in once per process
 static int ensure_big_lds() {
     static std::atomic<unsigned long long> done{0};               // one bit per device
@@ -2731,10 +2917,14 @@ static int ensure_big_lds() {
     if (e != hipSuccess) return (int)e;
     for (const NtRow& r : g_nt_rows)
         if (r.lds) { AEW_SET_LDS(r.fn, r.lds) }
+    for (int v = 0; v < NTV_COUNT; ++v)
+        if (nt_lines_fn(v) && g_nt_rows[v].lds) { AEW_SET_LDS(nt_lines_fn(v), g_nt_rows[v].lds) }
     for (const NtRow& r : g_tn_rows)
         if (r.lds) { AEW_SET_LDS(r.fn, r.lds) }
     AEW_SET_LDS((k_nt_chain<0>), CHAIN_LDS_BYTES)
     AEW_SET_LDS((k_nt_chain<1>), CHAIN_LDS_BYTES)
+    AEW_SET_LDS((k_nt_chain<0, true>), CHAIN_LDS_BYTES)
+    AEW_SET_LDS((k_nt_chain<1, true>), CHAIN_LDS_BYTES)
 #undef AEW_SET_LDS
     done.fetch_or(dev_bit, std::memory_order_release);
     return 0;
@@ -2945,7 +3135,8 @@ static int launch_gemm_nt(const aew_gemm_nt_t& g, hipStream_t st) {
     const NtRow& r = g_nt_rows[p.variant];
     if (r.lds && (rc = ensure_big_lds())) return rc;
     void* args[] = {const_cast<aew_gemm_nt_t*>(&g)};
-    (void)hipLaunchKernel(r.fn, g.impl == 1 ? dim3(p.grid, g.M, g.batch) : dim3(p.grid), dim3(r.threads), args, r.lds, st);
+    const void* const lines = g_nt_epi_lines && epi_lines_ok(g) ? nt_lines_fn(p.variant) : nullptr;
+    (void)hipLaunchKernel(lines ? lines : r.fn, g.impl == 1 ? dim3(p.grid, g.M, g.batch) : dim3(p.grid), dim3(r.threads), args, r.lds, st);
     return (int)hipGetLastError();
 }
 
@@ -2957,6 +3148,8 @@ static void row_name(const char* s, char* name) {
 
 // Which kernel launch_gemm_nt runs for this descriptor under the current settings (the codes: aewavenet.h; bench.py groups
 // its per-kernel rooflines by it), or the launcher's refusal
+extern "C" int aew_set_nt_epi_lines(int on) { g_nt_epi_lines = on ? 1 : 0; return 0; }
+
 extern "C" int aew_nt_kernel(const aew_gemm_nt_t* g) {
     NtPick p;
     const int rc = g ? nt_check(*g, AEW_T(), &p) : AEW_E_ARG;

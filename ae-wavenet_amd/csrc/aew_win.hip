@@ -118,7 +118,7 @@ __device__ __forceinline__ const char* win_src(const aew_seg_t& sref, int b, int
 // the loop is not waiting on latency), starting the blocks in odd thread-group slots of a CU a few us late so that the
 // two resident blocks run out of phase (null to slightly worse).
 // one output tile: block index L of the launch's tile order (WT: out0 stored write-through, see nt_epilogue)
-template <int EPI, int MT, int DWP, bool WT = false>
+template <int EPI, int MT, int DWP, bool WT = false, bool LINES = false>
 __device__ __forceinline__ void win_tile(const aew_gemm_nt_t& g, char* smem, const int L) {
     typedef WinCfg<MT, DWP> Cfg;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -242,13 +242,13 @@ __device__ __forceinline__ void win_tile(const aew_gemm_nt_t& g, char* smem, con
         win_advance<MT>(g, b, m0, wave, lane, klen, P);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the idle-tail LDS-DMA must land before the LDS is released
-    nt_epilogue<EPI, false, MT, WT>(g, acc, b, m0, n0, wm, wn, lane);
+    nt_epilogue<EPI, false, MT, WT, LINES>(g, acc, b, m0, n0, wm, wn, lane);
 }
 
-template <int EPI, int MT, int DWP>
+template <int EPI, int MT, int DWP, bool LINES = false>
 __global__ __launch_bounds__(512, 4) void k_gemm_nt_bf16_win(const aew_gemm_nt_t g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    win_tile<EPI, MT, DWP>(g, smem, blockIdx.x);
+    win_tile<EPI, MT, DWP, false, LINES>(g, smem, blockIdx.x);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------

@@ -249,7 +249,7 @@ static int run_ops(const aew_op_t* ops, int n, hipStream_t st, int* fail_index, 
             // other kernels - another summation order - than the stage ops: those then run one by one)
             if (timing != 1 && AEW_T().nt_chain && c.stages && c.built_window == AEW_T().nt_window) {   // (timing 2: the chain is timed as ONE op)
                 rc = ensure_big_lds();
-                if (rc == 0) rc = launch_nt_chain(c, target);
+                if (rc == 0) rc = launch_nt_chain(c, target, chain_lines_ok(ops + i + 1, c.n_ops));
                 skip = c.n_ops;
             }
         } else

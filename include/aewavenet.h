@@ -1924,6 +1924,13 @@ int aew_set_nt_rows192(int mode);
  * 256 + d rows per K tile and issue both taps' MFMAs from it (k_gemm_nt_bf16_win).  Default 64 (the largest
  * supported), 0 = never.  Results agree with the two-segment kernel to fp32 accumulation order, not bit for bit. */
 int aew_set_nt_window(int max_dist);
+/* 1 (default): STORE and DFG launches of the default 256- / 192-row bf16 NT bodies, of the one-window body and the
+ * chained launches whose STORE / DFG stages all qualify store and load their epilogue rows as whole 128-byte lines: the
+ * accumulators of a 16-row group are exchanged across lanes so that a wave access covers 8 rows x 128 B instead of
+ * 16 rows x 64 B.  0: the MFMA-layout epilogue.  Bit-identical results; fp32 views, AEW_EF_COUNT_ZERO and every other
+ * shape run the MFMA-layout epilogue under either value.  Read at LAUNCH time (a captured graph keeps the form it was
+ * captured under); no plan, stage table or record depends on it.  Process-wide; not a field of aew_tuning_t. */
+int aew_set_nt_epi_lines(int on);
 /* 0 (default): ignore aew_op_t.lane - every op on the caller's stream, in plan order.  1: side-lane ops on private
  * streams (branches of a captured graph).  Same results either way (the atomically accumulated bias sums up to order). */
 int aew_set_lanes(int on);

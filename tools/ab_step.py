@@ -19,7 +19,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-DEFAULTS = {"nt_window": 64, "nt_small_deep": 256, "nt_rows192": 1, "nt_small_tiles": 128, "lanes": 0, "fn": 1, "fn_ring3": 16, "graphs": 1, "nt_small_n64": 256, "nt_mem128": 0, "nt_deep": 0, "tn_cursor": 0, "deterministic": 1, "tn_mfma32": 0}
+DEFAULTS = {"nt_window": 64, "nt_small_deep": 256, "nt_rows192": 1, "nt_small_tiles": 128, "lanes": 0, "fn": 1, "fn_ring3": 16, "graphs": 1, "nt_small_n64": 256, "nt_mem128": 0, "nt_deep": 0, "tn_cursor": 0, "deterministic": 1, "tn_mfma32": 0,
+            "nt_epi_lines": None}    # None: the library's default (ae_wavenet_amd._lib.NT_EPI_LINES_DEFAULT)
 
 
 def main():
@@ -50,6 +51,8 @@ def main():
                     evals[k[2:]] = int(v)
                 else:
                     vals[k] = int(v)
+        if vals["nt_epi_lines"] is None:
+            vals["nt_epi_lines"] = L.NT_EPI_LINES_DEFAULT
         return vals, tuple(sorted(evals.items()))
 
     engines = {}
