@@ -27,7 +27,7 @@ NT_EPI_LINES_DEFAULT = 1            # the library's aew_set_nt_epi_lines default
  OP_NT_CHAIN, OP_GRAD_NORM, OP_UPDATE_RATIO, OP_SWAP, OP_VQ_RESTART, OP_EVAL_ACC, OP_WINDOW_GATHER,
  OP_GRAD_WELFORD, OP_SEG_SELECT, OP_ACCUM, OP_CODE_LOOKUP, OP_CODE_RUNS, OP_ADAM_GROUPS, OP_EVAL_GROUPS,
  OP_MEL_TILE, OP_CODE_STITCH, OP_CODE_TILE, OP_COND_STITCH, OP_WAV_TILE, OP_NLL_STITCH, OP_SCORE_REDUCE, OP_SEQ_ALIGN,
- OP_FRAME_STITCH, OP_CODE_SEGMENT, OP_SEQ_SEARCH, OP_ABX_COUNT) = range(1, 51)
+ OP_FRAME_STITCH, OP_CODE_SEGMENT, OP_SEQ_SEARCH, OP_ABX_COUNT, OP_SEQ_DISCOVER) = range(1, 52)
 
 vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 
@@ -378,6 +378,27 @@ class SeqSearch(C.Structure):
                 ("ws", vp), ("ws_bytes", i64)]
 
 
+class DiscoverPair(C.Structure):
+    """aew_discover_pair_t: which two sequences a pair aligns locally, its band (cells with j - i < band are dead) and
+    where its n profile entries start.  DISCOVER_PAIR_DTYPE is the same record for numpy."""
+    _fields_ = [("a", i32), ("b", i32), ("band", i32), ("pad_", i32), ("prof_base", i64)]
+
+
+DISCOVER_PAIR_DTYPE = [("a", "<i4"), ("b", "<i4"), ("band", "<i4"), ("pad_", "<i4"), ("prof_base", "<i8")]
+
+
+class SeqDiscover(C.Structure):
+    """aew_seq_discover_t: local-alignment DTW of n_pairs pairs - the per-row profile (score, end column, origin row,
+    origin column, steps) and the n_hits best alignments of each whose A ranges do not overlap; the tables as device and
+    host copies."""
+    _fields_ = [("metric", i32), ("n_hits", i32), ("D", i32), ("n_pairs", i32), ("min_len", i32), ("max_len", i32),
+                ("threshold", f32), ("pad_", i32), ("seq_a", vp), ("seq_a_host", vp), ("seq_b", vp), ("seq_b_host", vp),
+                ("pairs", vp), ("pairs_host", vp), ("n_a", i32), ("n_b", i32), ("feat_a", vp), ("feat_b", vp),
+                ("n_feat_a", i64), ("n_feat_b", i64), ("prof_score", vp), ("prof_end", vp), ("prof_row", vp),
+                ("prof_col", vp), ("prof_steps", vp), ("n_prof", i64), ("hits", vp), ("hit_score", vp), ("hit_steps", vp),
+                ("count", vp), ("bad", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 ABX_WITHIN, ABX_ACROSS = 0, 1
 ABX_MAX_N = 16384
 
@@ -570,7 +591,7 @@ class _OpU(C.Union):
                 ("adamg", AdamGrouped), ("evg", EvalGroups), ("mtile", MelTile), ("cstitch", CodeStitch),
                 ("ctile", CodeTile), ("cndst", CondStitch), ("wtile", WavTile), ("nllst", NllStitch), ("sred", ScoreReduce),
                 ("align", SeqAlign), ("fstitch", FrameStitch), ("cseg", CodeSegment), ("search", SeqSearch),
-                ("abx", AbxCount)]
+                ("abx", AbxCount), ("discover", SeqDiscover)]
 
 
 class Op(C.Structure):
@@ -589,7 +610,7 @@ OP_FIELD = {OP_GEMM_NT: "nt", OP_GEMM_TN: "tn", OP_COPY_TABLE: "copy", OP_VQ_NEA
             OP_MEL_TILE: "mtile", OP_CODE_STITCH: "cstitch", OP_CODE_TILE: "ctile", OP_COND_STITCH: "cndst",
             OP_WAV_TILE: "wtile", OP_NLL_STITCH: "nllst", OP_SCORE_REDUCE: "sred", OP_SEQ_ALIGN: "align",
             OP_FRAME_STITCH: "fstitch", OP_CODE_SEGMENT: "cseg", OP_SEQ_SEARCH: "search",
-            OP_ABX_COUNT: "abx"}
+            OP_ABX_COUNT: "abx", OP_SEQ_DISCOVER: "discover"}
 
 
 
@@ -736,7 +757,7 @@ def load():
                        (36, CodeStitch), (37, CondRow), (38, CodeTile), (39, CondStitch), (41, DrawRec), (42, ScoreRow), (43, WavTile),
                        (44, NllStitch), (45, ScoreReduce), (47, AlignSeq), (48, AlignPair), (49, SeqAlign),
                        (51, SegUtt), (52, FrameStitch), (53, CodeSegment), (55, SearchPair), (56, SeqSearch),
-                       (58, AbxGroup), (59, AbxCount)):
+                       (58, AbxGroup), (59, AbxCount), (61, DiscoverPair), (62, SeqDiscover)):
         want = lib.aew_sizeof(which)
         if want != C.sizeof(cls):
             raise AewError(f"ABI mirror drift: sizeof({cls.__name__}) = {C.sizeof(cls)} in Python, "

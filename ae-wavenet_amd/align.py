@@ -9,16 +9,19 @@ states the rule bit for bit).
     err = abx(d_ax, d_bx)                   # ABX error of paired distances, a device scalar
     mt = search(queries, docs, pairs=..., n_hits=3)         # subsequence DTW (AEW_OP_SEQ_SEARCH, csrc/aew_search.hip)
     mt.start, mt.end, mt.cost, mt.steps, mt.mean, mt.count  # (P, n_hits): where each query occurs, best first; mt.profile(p)
+    rp = discover(utts, threshold=0.5, n_hits=3, min_len=5) # local-alignment DTW (AEW_OP_SEQ_DISCOVER, csrc/aew_discover.hip)
+    rp.a_start, rp.a_end, rp.b_start, rp.b_end, rp.score    # (P, n_hits): which stretches of a pair repeat each other
     dist = distance_matrix(items)                           # (N, N) fp32: every pair i < j through dtw(), mirrored, diagonal 0
     res = abx_score(dist, category, speaker, mode="within") # ABX discriminability of the item set (AEW_OP_ABX_COUNT,
     res.error, res.pooled, res.by_category, res.n_triples   # csrc/aew_abx.hip); abx_task(items, ...) is the two in one call
 
 `model.code_distance()` and `model.cepstral_distance()` (surface.py) are these calls over the codebook rows of code
 sequences and over the model's own MFCC front-end; `model.search_codes()` and `model.search_wavs()` are `search` over the
-same two feature sources.  On the device dtw() and search() run one sweep (`align_sweep` in csrc/aew_align.hip), and here
-the two ops share one launch path, `_SeqPlan`: it checks the two sides, fills the record fields the ops have in common
-and runs the records as a plan on torch's current stream; every host table (and edit_distance()'s denominator) goes up
-through `_upload` - pinned, behind the stream.  Nothing
+same two feature sources, `model.discover_codes()` and `model.discover_wavs()` are `discover`.  On the device dtw() and
+search() run one sweep (`align_sweep` in csrc/aew_align.hip), discover() its sibling over the same ring of local
+distances, and here the three ops share one launch path, `_SeqPlan`: it checks the two sides, fills the record fields
+the ops have in common and runs the records as a plan on torch's current stream; every host table (and
+edit_distance()'s denominator) goes up through `_upload` - pinned, behind the stream.  Nothing
 but `Alignment.path()` (and `edit_distance(collapse=True)`, which has to learn the number of units) synchronises with
 the host.  There is no CPU path: a tensor that is not on the GPU is refused.
 
@@ -160,8 +163,9 @@ def _upload(table: np.ndarray, dev) -> torch.Tensor:
 
 
 class _SeqPlan:
-    """The launch path dtw() / edit_distance() (`_Launches`) and search() (`_SearchLaunch`) share: the checks of the two
-    sides, the three tables, the fields aew_seq_align_t and aew_seq_search_t have in common, the run as one plan."""
+    """The launch path dtw() / edit_distance() (`_Launches`), search() (`_SearchLaunch`) and discover()
+    (`_DiscoverLaunch`) share: the checks of the two sides, the three tables, the fields aew_seq_align_t,
+    aew_seq_search_t and aew_seq_discover_t have in common, the run as one plan."""
     KIND, FIELD, NOUN = None, None, None
 
     def _open(self, ra: Ragged, rb: Ragged):
@@ -366,6 +370,117 @@ def search(query, doc=None, pairs=None, metric: str = "euclid", n_hits: int = 1,
     rd = rq if doc is None else _ragged(doc, "search(): doc", torch.float32)
     pr = default_pairs(len(rq), None if doc is None else len(rd), pairs)
     return Matches(_SearchLaunch(METRICS[metric], RANKS[rank], rq, rd, pr, n_hits, min_len, max_len).run("search()"))
+
+
+def discover_pairs(n_a: int, n_b: Optional[int], pairs) -> np.ndarray:
+    """(P, 2) int64: `pairs` as given; else, for one list (n_b None), every unordered pair u <= v INCLUDING (u, u) in
+    row-major order, and for two lists zip(a, b) as everywhere here."""
+    if pairs is None and n_b is None:
+        u, v = np.triu_indices(n_a)
+        return np.stack([u, v], 1).astype(np.int64)
+    return default_pairs(n_a, n_b, pairs)
+
+
+def discover_pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, band: np.ndarray):
+    """(records, n_prof, wstride).  records: aew_discover_pair_t with prof_base = the prefix sum of the A lengths over the
+    pairs in order (disjoint profile ranges) and the pair's band; n_prof: their total; wstride: the longest B side among
+    the pairs whose A side has more than STRIP frames (the workspace is 16 * pairs * wstride bytes)."""
+    la, lb = np.asarray(lens_a, np.int64)[pairs[:, 0]], np.asarray(lens_b, np.int64)[pairs[:, 1]]
+    t = np.zeros(len(pairs), dtype=L.DISCOVER_PAIR_DTYPE)
+    t["a"], t["b"], t["band"] = pairs[:, 0], pairs[:, 1], band
+    t["prof_base"] = np.concatenate([[0], np.cumsum(la)[:-1]])
+    return t, int(la.sum()), int(np.where(la > STRIP, lb, 0).max())
+
+
+class _DiscoverLaunch(_SeqPlan):
+    """The op record of one discovery and everything it points to."""
+    KIND, FIELD, NOUN = L.OP_SEQ_DISCOVER, "discover", "discovery"
+
+    def __init__(self, metric: int, threshold: float, ra: Ragged, rb: Ragged, pairs: np.ndarray, band: np.ndarray,
+                 n_hits: int, min_len: int, max_len: int):
+        dev = self._open(ra, rb)
+        P = self.P = len(pairs)
+        tp, n_prof, wstride = discover_pair_table(ra.length, rb.length, pairs, band)
+        self._tables(tp)
+        self.prof = (torch.empty(max(n_prof, 1), dtype=torch.float32, device=dev),) + tuple(
+            torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev) for _ in range(4))
+        self.hits = torch.empty(P, n_hits, 4, dtype=torch.int32, device=dev)
+        self.score = torch.empty(P, n_hits, dtype=torch.float32, device=dev)
+        self.steps = torch.empty(P, n_hits, dtype=torch.int32, device=dev)
+        self.count = torch.empty(P, dtype=torch.int32, device=dev)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(4 * P * wstride, dtype=torch.float32, device=dev) if wstride else None
+        self.prof_base, self.a_len = tp["prof_base"].copy(), np.asarray(ra.length, np.int64)[pairs[:, 0]]
+        self.threshold = threshold
+        r = L.SeqDiscover()
+        r.metric, r.n_hits, r.D, r.n_pairs = metric, n_hits, ra.D, P
+        r.min_len, r.max_len, r.threshold = min_len, max_len, threshold
+        r.prof_score, r.prof_end, r.prof_row, r.prof_col, r.prof_steps = (x.data_ptr() for x in self.prof)
+        r.n_prof = n_prof
+        r.hits, r.hit_score, r.hit_steps = self.hits.data_ptr(), self.score.data_ptr(), self.steps.data_ptr()
+        r.count, r.bad = self.count.data_ptr(), self.bad.data_ptr()
+        self._add(r, self.ws)
+
+
+class Repeats:
+    """What discover() returns.  a_start, a_end, b_start, b_end (P, n_hits) int32: hit r of pair p aligns the frames
+    [a_start, a_end] of its A side with the frames [b_start, b_end] of its B side, best first, -1 behind the `count[p]`
+    hits that exist; score (P, n_hits) fp32: the summed gains threshold - d along the alignment (NaN there); steps
+    (P, n_hits) int32: its cells (0 there); mean = threshold - score / steps: the mean local distance along it; count
+    (P,) int32; bad: int32 (1,), a uint32 count of the pairs that were not finite.  All on the device; reading them is
+    the caller's synchronisation."""
+
+    def __init__(self, run: _DiscoverLaunch):
+        self.a_start, self.a_end, self.b_start, self.b_end = (run.hits[:, :, k] for k in range(4))
+        self.score, self.steps, self.count, self.bad = run.score, run.steps, run.count, run.bad
+        self.mean = run.threshold - run.score / run.steps
+        self._run = run
+
+    def __len__(self) -> int:
+        return self._run.P
+
+    def profile(self, p: int):
+        """(score, end, origin_row, origin_col, steps) of pair p: views of length n, entry i the best local alignment that
+        ENDS in row i of the A side - its score E(i), the B frame it ends at, the (A, B) frames it starts at and its cells;
+        (0, -1, -1, -1, 0) where nothing ends, (NaN, -1, -1, -1, 0) for a pair that was not finite.  The lengths come
+        from the host tables: no wait on the device."""
+        p = range(len(self))[p]
+        lo, n = int(self._run.prof_base[p]), int(self._run.a_len[p])
+        return tuple(x[lo:lo + n] for x in self._run.prof)
+
+
+def discover(a, b=None, pairs=None, threshold: Optional[float] = None, metric: str = "euclid", n_hits: int = 3,
+             min_len: int = 1, max_len: int = 0, band: Optional[int] = None) -> Repeats:
+    """Which stretches of two utterances say the same thing: local-alignment DTW (AEW_OP_SEQ_DISCOVER) of pairs of
+    sequences of D-channel fp32 frames - nobody names a query, an alignment may start and end at any cell.  a, b:
+    `Ragged` views or lists of (n_u, D) float32 device tensors as for dtw().  b=None compares `a` with itself over every
+    unordered pair u <= v INCLUDING (u, u) - a repeat inside one utterance; with b, or with pairs (P, 2) integers, pair
+    p = (a[pairs[p, 0]], b[pairs[p, 1]]), default zip.  A cell gains threshold - d(i, j) (metric as in dtw()): frames
+    closer than `threshold` extend an alignment, farther ones wear it down, and it ends where its score would fall to
+    zero.  The n_hits (1 .. 32) best alignments whose A ranges do not overlap are returned best first; both spans of a
+    hit are at least min_len and, with max_len > 0, at most max_len frames.  A pair (u, u) of one list skips the cells
+    with j - i < band - the trivial diagonal and the lower triangle; the default band is max(min_len, 1), an explicit
+    band= replaces it, every other pair has band 0.  Nothing here synchronises with the host.  -> `Repeats`."""
+    if metric not in METRICS:
+        raise L.AewError(f"discover(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    with np.errstate(over="ignore"):
+        finite = threshold is not None and bool(np.isfinite(np.float32(threshold)))
+    if not finite:
+        raise L.AewError(f"discover(): a finite threshold is needed, got {threshold}")
+    n_hits, min_len, max_len = int(n_hits), int(min_len), int(max_len)
+    if not 1 <= n_hits <= L.SEARCH_MAX_HITS:
+        raise L.AewError(f"discover(): n_hits must lie in [1, {L.SEARCH_MAX_HITS}], got {n_hits}")
+    if min_len < 0 or max_len < 0:
+        raise L.AewError(f"discover(): min_len and max_len must not be negative, got {min_len} and {max_len}")
+    self_band = max(min_len, 1) if band is None else int(band)
+    if not 0 <= self_band < 1 << 31:
+        raise L.AewError(f"discover(): band must not be negative, got {band}")
+    ra = _ragged(a, "discover(): a", torch.float32)
+    rb = ra if b is None else _ragged(b, "discover(): b", torch.float32)
+    pr = discover_pairs(len(ra), None if b is None else len(rb), pairs)
+    bands = np.where(pr[:, 0] == pr[:, 1], self_band, 0) if rb is ra else np.zeros(len(pr), np.int64)
+    return Repeats(_DiscoverLaunch(METRICS[metric], float(np.float32(threshold)), ra, rb, pr, bands, n_hits, min_len,
+                                   max_len).run("discover()"))
 
 
 class EditDistances:

@@ -14,8 +14,10 @@
 //
 // The DTW strip loop is ONE device function, align_sweep<DR, SUB>: k_align_dtw calls it with SUB = false, k_search_sweep
 // (aew_search.hip, subsequence DTW) with SUB = true; what only one of the two carries is compiled out of the other.
-// The two ops also share the device pair loader (seq_load_pair), the host checks of the fields the two records have in
-// common (align_check_record) and the ladder D -> DR (align_dispatch_D).
+// Phase (A) is a function of its own, align_fill_ring<DR>: k_discover_sweep (aew_discover.hip, local-alignment DTW) runs
+// a sibling sweep with another recurrence over the same ring.  The three ops also share the device pair loader
+// (seq_load_pair), the host checks of the fields their records have in common (align_check_record) and the ladder
+// D -> DR (align_dispatch_D).
 //
 // Nothing here waits on another wave: no __syncthreads (the waves of a block share nothing), no flag, no atomic but the
 // count of pairs that are not finite.  The path kernel is a second launch behind the first on the same stream.
@@ -125,6 +127,50 @@ __device__ __forceinline__ align_sweep_in align_sweep_of(const Rec& p, const Vie
     q.wsS = (int*)p.ws + ((int64_t)p.n_pairs + pi) * wstride;
     return q;
 }
+// Phase (A) of a sweep, shared by align_sweep and discover_sweep (aew_discover.hip): the local distances of the columns
+// [j0, j0 + 64) that exist, for the lane's row, into its ring.  a: the lane's A row in registers (DR > 0), arow: the same
+// row in memory (DR == 0 reads it again for every column).  live(j): does column j of this row count towards the
+// verdict.  bad: raised when this lane meets a local distance that is not finite in a cell that counts.
+template <int DR, class Live>
+__device__ __forceinline__ void align_fill_ring(const align_sweep_in& q, const float* a, const float* arow, const int j0,
+                                                const bool row_on, float* ring, const int lane, bool& bad, Live live) {
+    const float* B = q.B;
+    const int64_t acs = q.acs, bfs = q.bfs, bcs = q.bcs;
+    const int m = q.m, D = q.D;
+    const bool sq = q.metric == AEW_ALIGN_SQEUCLID;
+    const int jn = m - j0 < 64 ? m - j0 : 64;
+    if (DR > 0 && jn > 0) {
+        // lane l fetches frame j0 + l (the last frame again behind m); column jj's frame is then lane jj's registers,
+        // handed to the whole wave by a uniform-index lane read: no memory access inside the column loop
+        float b[DR > 0 ? DR : 1];
+        const float* bl = B + (int64_t)(j0 + lane < m ? j0 + lane : m - 1) * bfs;
+#pragma unroll
+        for (int k = 0; k < DR; ++k) b[k] = k < D ? bl[k * bcs] : 0.f;
+        for (int jj = 0; jj < jn; ++jj) {
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < DR; ++k) {
+                const float t = a[k] - align_lane(b[k], jj);
+                acc = acc + t * t;
+            }
+            const float d = sq ? acc : sqrtf(acc);                               // sqrtf is IEEE-rounded here
+            bad |= row_on && live(j0 + jj) && !isfinite(d);
+            ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
+        }
+    }
+    for (int jj = 0; DR == 0 && jj < jn; ++jj) {
+        const float* brow = B + (int64_t)(j0 + jj) * bfs;
+        float acc = 0.f;
+        for (int k = 0; k < D; ++k) {
+            const float t = arow[k * acs] - brow[k * bcs];
+            acc = acc + t * t;
+        }
+        const float d = sq ? acc : sqrtf(acc);
+        bad |= row_on && live(j0 + jj) && !isfinite(d);
+        ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
+    }
+}
+
 // DR > 0: D <= DR, the lane's A row in DR registers (zeros behind D: t = 0 - 0, acc + 0 * 0 = acc, the same bits).
 // DR == 0: any D, the A row is read again for every column.
 // SUB: subsequence DTW.  Row 0 has no left predecessor - every column starts a match - so the start column (B, O beside
@@ -132,10 +178,9 @@ __device__ __forceinline__ align_sweep_in align_sweep_of(const Rec& p, const Vie
 // profile entries of each column; there is no back byte.  Without SUB none of that exists.
 template <int DR, bool SUB>
 __device__ __forceinline__ align_sweep_out align_sweep(const align_sweep_in& q, float* ring, const int lane) {
-    const float *A = q.A, *B = q.B;
-    const int64_t afs = q.afs, acs = q.acs, bfs = q.bfs, bcs = q.bcs;
+    const float* A = q.A;
+    const int64_t afs = q.afs, acs = q.acs;
     const int n = q.n, m = q.m, D = q.D;
-    const bool sq = q.metric == AEW_ALIGN_SQEUCLID;
     const int nchunk = (m + 63 + 63) >> 6;                                       // sweep steps t = 0 .. m + 62
     bool bad = false;
     float cL = 0.f;
@@ -157,37 +202,7 @@ __device__ __forceinline__ align_sweep_out align_sweep(const align_sweep_in& q, 
         for (int c = 0; c < nchunk; ++c) {
             const int j0 = c << 6;
             // (A) local distances of the columns [j0, j0 + 64) that exist
-            const int jn = m - j0 < 64 ? m - j0 : 64;
-            if (DR > 0 && jn > 0) {
-                // lane l fetches frame j0 + l (the last frame again behind m); column jj's frame is then lane jj's registers,
-                // handed to the whole wave by a uniform-index lane read: no memory access inside the column loop
-                float b[DR > 0 ? DR : 1];
-                const float* bl = B + (int64_t)(j0 + lane < m ? j0 + lane : m - 1) * bfs;
-#pragma unroll
-                for (int k = 0; k < DR; ++k) b[k] = k < D ? bl[k * bcs] : 0.f;
-                for (int jj = 0; jj < jn; ++jj) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < DR; ++k) {
-                        const float t = a[k] - align_lane(b[k], jj);
-                        acc = acc + t * t;
-                    }
-                    const float d = sq ? acc : sqrtf(acc);                       // sqrtf is IEEE-rounded here
-                    bad |= row_on && !isfinite(d);
-                    ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
-                }
-            }
-            for (int jj = 0; DR == 0 && jj < jn; ++jj) {
-                const float* brow = B + (int64_t)(j0 + jj) * bfs;
-                float acc = 0.f;
-                for (int k = 0; k < D; ++k) {
-                    const float t = arow[k * acs] - brow[k * bcs];
-                    acc = acc + t * t;
-                }
-                const float d = sq ? acc : sqrtf(acc);
-                bad |= row_on && !isfinite(d);
-                ring[((j0 + jj) & (AEW_ALIGN_RING - 1)) * 64 + lane] = d;
-            }
+            align_fill_ring<DR>(q, a, arow, j0, row_on, ring, lane, bad, [](int) { return true; });
             // the top row's columns [j0, j0 + 64): lane l holds column j0 + l
             if (i0 > 0 && j0 + lane < m) {
                 topC = q.wsC[j0 + lane]; topS = q.wsS[j0 + lane];

@@ -15,6 +15,7 @@
 #include "aew_align.hip"
 #include "aew_segment.hip"
 #include "aew_search.hip"
+#include "aew_discover.hip"
 #include "aew_abx.hip"
 
 #include <vector>
@@ -88,6 +89,7 @@ static int dispatch(const aew_op_t& op, hipStream_t st) {
         case AEW_OP_CODE_SEGMENT: return launch_code_segment(op.u.cseg, st);
         case AEW_OP_SEQ_SEARCH: return launch_seq_search(op.u.search, st);
         case AEW_OP_ABX_COUNT: return launch_abx_count(op.u.abx, st);
+        case AEW_OP_SEQ_DISCOVER: return launch_seq_discover(op.u.discover, st);
         case AEW_OP_NT_CHAIN: return 0;      // chaining off / timing mode: the stage ops that follow run one by one (run_ops)
         default: return AEW_E_UNSUP;
     }
@@ -149,6 +151,8 @@ extern "C" int aew_sizeof(int which) {
         case 56: return (int)sizeof(aew_seq_search_t);
         case 58: return (int)sizeof(aew_abx_group_t);      // (57 is left unused like 24, 26, 33, 40, 46, 50 and 54)
         case 59: return (int)sizeof(aew_abx_count_t);
+        case 61: return (int)sizeof(aew_discover_pair_t);  // (60 is left unused like 24, 26, 33, 40, 46, 50, 54 and 57)
+        case 62: return (int)sizeof(aew_seq_discover_t);
         default: return -1;
     }
 }

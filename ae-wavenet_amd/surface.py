@@ -1497,6 +1497,37 @@ class HipModelBase(nn.Module):
         return AL.search(sides[0], sides[1], pairs=pairs, metric="euclid", n_hits=n_hits, rank=rank, min_len=min_len,
                          max_len=max_len)
 
+    # ---- discovering repeats between utterances: local-alignment DTW over the same two feature sources (align.discover) --
+    def discover_codes(self, codes, codes_b=None, pairs=None, threshold: Optional[float] = None, metric: str = "euclid",
+                       n_hits: int = 3, min_len: int = 1, max_len: int = 0, band: Optional[int] = None):
+        """Which stretches of the code sequences `codes` repeat each other: local-alignment DTW over their codebook rows
+        (align.discover(); threshold, metric, n_hits, min_len, max_len, band as there).  codes / codes_b a
+        `codes.UtteranceCodes` or a list of 1-D int64 device tensors; codes_b=None compares `codes` with itself over
+        every unordered pair including (u, u), pairs (P, 2) indices into the two -> `align.Repeats`; the starts and ends
+        of a hit are CODE FRAMES.  The front half is code_distance()'s: one lookup per side into a ragged buffer read in
+        place, and a code outside [0, K) raises AewError before anything is aligned.  VQ bottlenecks only; the codebook
+        is read, nothing of the model is written and no collective is issued."""
+        from . import align as AL
+        if codes_b is None:
+            pairs = AL.discover_pairs(len(codes), None, pairs)
+        sides, pr = self._code_sides("discover_codes()", codes, codes_b, pairs)
+        return AL.discover(sides[0], None if codes_b is None else sides[1], pairs=pr, threshold=threshold, metric=metric,
+                           n_hits=n_hits, min_len=min_len, max_len=max_len, band=band)
+
+    def discover_wavs(self, wavs, wavs_b=None, pairs=None, threshold: Optional[float] = None, expand: bool = True,
+                      n_hits: int = 3, min_len: int = 1, max_len: int = 0, band: Optional[int] = None):
+        """Which stretches of the waveforms `wavs` repeat each other: local-alignment DTW (align.discover(), Euclidean)
+        over the static cepstra 1 .. n_mfcc - 1 of this model's own front-end - cepstral_distance()'s front half, `expand`
+        as there, `threshold` on that front-end's scale.  Lists of 1-D device tensors of mu-law values; wavs_b=None
+        compares `wavs` with itself over every unordered pair including (u, u) -> `align.Repeats`.  The starts and ends
+        of a hit are MFCC FRAMES (see search_wavs() for what a frame covers).  A waveform too short for
+        `DeviceMfcc.MIN_FRAMES` frames has none: its pairs find nothing.  VQ bottlenecks only; nothing of the model is
+        written and no collective is issued."""
+        from . import align as AL
+        sides = self._cepstral_sides("discover_wavs()", wavs, wavs_b, expand)
+        return AL.discover(sides[0], None if wavs_b is None else sides[1], pairs=pairs, threshold=threshold,
+                           metric="euclid", n_hits=n_hits, min_len=min_len, max_len=max_len, band=band)
+
     # ---- ABX discriminability of a labelled item set over the same two feature sources (align.abx_task) ---------------
     def abx_codes(self, codes, category, speaker=None, mode: str = "within", metric: str = "euclid", value: str = "mean",
                   max_pairs: int = 1 << 20):

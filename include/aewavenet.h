@@ -53,8 +53,9 @@ extern "C" {
  * 47 .. 49, aew_align_seq_t, aew_align_pair_t, aew_seq_align_t / AEW_OP_SEQ_ALIGN - index 46 stays unused; 51 .. 53, aew_seg_utt_t,
  * aew_frame_stitch_t / AEW_OP_FRAME_STITCH, aew_code_segment_t / AEW_OP_CODE_SEGMENT - index 50 stays unused; 55 / 56,
  * aew_search_pair_t, aew_seq_search_t / AEW_OP_SEQ_SEARCH - index 54 stays unused; 58 / 59, aew_abx_group_t,
- * aew_abx_count_t / AEW_OP_ABX_COUNT with the host function aew_abx_host - index 57 stays unused.  The number does NOT
- * move for AEW_OP_ABX_COUNT either: one op kind behind the last, a descriptor inside the union's size, no existing
+ * aew_abx_count_t / AEW_OP_ABX_COUNT with the host function aew_abx_host - index 57 stays unused; 61 / 62,
+ * aew_discover_pair_t, aew_seq_discover_t / AEW_OP_SEQ_DISCOVER - index 60 stays unused.  The number does NOT
+ * move for AEW_OP_SEQ_DISCOVER either: one op kind behind the last, a descriptor inside the union's size, no existing
  * record, op number or function changed). */
 #define AEW_ABI_VERSION 28
 #define AEW_MAX_SEGS 32
@@ -1357,6 +1358,91 @@ typedef struct {
     int64_t ws_bytes;
 } aew_seq_search_t;
 
+/* Discovering repeats between utterances (appended to ABI 28; AEW_OP_SEQ_DISCOVER, aew_sizeof 61 / 62 - index 60 stays
+ * unused, it answers -1): local-alignment dynamic time warping (segmental DTW) of a (n frames) against b (m frames) -
+ * the alignment may start and end at any cell, nobody names a query - for n_pairs independent pairs in one op, then the
+ * n_hits best alignments of each pair whose A ranges do not overlap.  Two launches of the one op, ordered by the stream
+ * alone: the sweep (one wavefront per pair, the shape of AEW_OP_SEQ_ALIGN's DTW kernel) and the pick (one wavefront per
+ * pair).  Nothing waits on another wavefront - no flag, no spin, no barrier, no atomic but the count of pairs that are
+ * not finite.
+ *
+ * THE RULE (tests/seq_discover_emulator.py restates it).  The arithmetic is AEW_OP_SEQ_ALIGN's: fp32 throughout, every
+ * operation rounded on its own, d(i, j) that op's local distance for the metrics EUCLID and SQEUCLID over D channels.
+ * `threshold` is one finite fp32 for the launch, `band` >= 0 one int32 per pair.
+ *   gain     g(i, j) = threshold - d(i, j), one fp32 subtraction.
+ *   dead     Cell (i, j) lies OUTSIDE THE BAND when band > 0 and j - i < band: it is dead, H = 0 and S = 0, whatever d is.
+ *            A pair of one utterance with itself (band >= 1) so looks only at the upper triangle, away from the trivial
+ *            diagonal.  band = 0: every cell is inside.
+ *   sweep    For a cell inside the band, scan the predecessors (i-1,j-1), (i-1,j), (i,j-1) that exist and have H > 0 in
+ *            that order and keep the one of largest H (strict > while scanning: ties go to the first).  With such a
+ *            predecessor H(i,j) = H(pred) + g(i,j), S(i,j) = S(pred) + 1, O(i,j) = O(pred); without one H(i,j) = g(i,j),
+ *            S(i,j) = 1, O(i,j) = (i, j).  If the resulting H is not > 0 the cell is dead: H = 0, S = 0.  H is the score
+ *            of the best local alignment that ends at the cell, S its cells, O = (row, column) the cell it starts at.
+ *   profile  The pair's n entries from prof_base on, one per ROW i: E(i) = max over j of H(i,j) and, of the LEAST such j,
+ *            prof_end[i] = j, prof_row[i] / prof_col[i] = O(i,j), prof_steps[i] = S(i,j).  E(i) = 0 - no alignment ends in
+ *            this row - gives (0, -1, -1, -1, 0).
+ *   pick     Row i is eligible when E(i) > 0 and both spans, i - prof_row[i] + 1 and prof_end[i] - prof_col[i] + 1, are
+ *            >= min_len and, when max_len > 0, <= max_len.  For r = 0 .. n_hits-1: take the eligible, unsuppressed row
+ *            of largest E, ties to the least i; write hit r = (a_start, a_end, b_start, b_end) = (prof_row[i], i,
+ *            prof_col[i], prof_end[i]) with score E(i) and steps prof_steps[i]; then suppress every row k whose own A
+ *            range [prof_row[k], k] meets [a_start, a_end], that is prof_row[k] <= a_end and k >= a_start.  count[p] =
+ *            the hits found; the remaining hit slots are (-1, -1, -1, -1), NaN, 0.
+ *   special  An empty side reads no feature memory: count = 0, all hits empty; n > 0, m = 0 writes (0, -1, -1, -1, 0) to
+ *            each of the n profile entries, n = 0 owns none.  A pair in which d(i,j) is not finite for any cell INSIDE
+ *            the band gets every profile entry (NaN, -1, -1, -1, 0), count = 0, empty hits, and *bad is raised by one
+ *            (DTW's convention); what lies outside the band is not looked at.
+ *   mean     steps * threshold - score is the summed local distance along a hit up to rounding, so threshold - score /
+ *            steps its mean distance per cell; the closed DTW of the hit's two ranges under AEW_OP_SEQ_ALIGN costs at
+ *            most that sum (the hit's path is one of the paths DTW minimises over), exactly where all sums are exact.
+ * Tables and checks follow AEW_OP_SEQ_ALIGN: the two aew_align_seq_t tables (reused unchanged) and the pair table each
+ * come as a device copy and a host copy; the launcher checks every host record before anything is launched, the kernels
+ * repeat the checks on the device copies and leave a failing pair alone; no address is formed from an unchecked record.
+ * The profile ranges [prof_base, prof_base + n) of the pairs must be disjoint - the caller's contract (prefix sums).
+ * AEW_E_ARG: metric outside its values, D outside [1, AEW_ALIGN_MAX_D], n_pairs < 1 or > 2^24, n_a / n_b < 1, n_hits
+ * outside [1, AEW_SEARCH_MAX_HITS], min_len or max_len negative, a threshold that is not finite, a NULL table or output
+ * (prof_*, hits, hit_score, hit_steps, count, bad), a NULL feature buffer of n_feat > 0, n_feat outside [0, 2^50],
+ * n_prof < 0, a sequence record AEW_OP_SEQ_ALIGN refuses, a pair with a / b outside its table, a negative band,
+ * prof_base < 0 or prof_base + n > n_prof, an a of more than 64 frames without a workspace of the size stated at `ws`.
+ * AEW_E_ALIGN: a table off 8 bytes, any other pointer off 4.  A refused call launches and writes nothing. */
+typedef struct {
+    int32_t a, b;                /* indices into the A-side / B-side sequence tables                            */
+    int32_t band, pad_;          /* cells with j - i < band are dead (0: none); >= 0                            */
+    int64_t prof_base;           /* first of the pair's n entries in the five profile arrays                    */
+} aew_discover_pair_t;
+
+typedef struct {
+    int32_t metric, n_hits;      /* AEW_ALIGN_EUCLID / _SQEUCLID; 1 .. AEW_SEARCH_MAX_HITS      */
+    int32_t D, n_pairs;
+    int32_t min_len, max_len;    /* bounds on both spans of a hit; max_len 0: no upper limit    */
+    float threshold;             /* the local distance at which a cell neither gains nor loses  */
+    int32_t pad_;
+    const aew_align_seq_t* seq_a;       /* device memory, n_a records                          */
+    const aew_align_seq_t* seq_a_host;  /* the same records in host memory                     */
+    const aew_align_seq_t* seq_b;
+    const aew_align_seq_t* seq_b_host;
+    const aew_discover_pair_t* pairs;   /* device memory, n_pairs records                      */
+    const aew_discover_pair_t* pairs_host;
+    int32_t n_a, n_b;
+    const float* feat_a;         /* n_feat_a elements                                          */
+    const float* feat_b;
+    int64_t n_feat_a, n_feat_b;
+    float* prof_score;           /* [n_prof]: E(i)                                             */
+    int32_t* prof_end;           /* [n_prof]: the column the row's best alignment ends at      */
+    int32_t* prof_row;           /* [n_prof]: the row it starts at                             */
+    int32_t* prof_col;           /* [n_prof]: the column it starts at                          */
+    int32_t* prof_steps;         /* [n_prof]: its cells                                        */
+    int64_t n_prof;
+    int32_t* hits;               /* [n_pairs][n_hits][4]: (a_start, a_end, b_start, b_end)     */
+    float* hit_score;            /* [n_pairs][n_hits]                                          */
+    int32_t* hit_steps;          /* [n_pairs][n_hits]                                          */
+    int32_t* count;              /* [n_pairs]; between the two launches it carries the sweep's verdict on the pair */
+    uint32_t* bad;               /* one device word, added to                                  */
+    void* ws;                    /* boundary rows (H, S, origin row, origin column) of pairs with more than 64 A frames
+                                    (optional): ws_bytes >= 16 * n_pairs * the longest B side among those pairs (the
+                                    launcher takes that length from the host tables).  Contents are scratch.             */
+    int64_t ws_bytes;
+} aew_seq_discover_t;
+
 /* ABX discriminability of a labelled item set (appended to ABI 28; AEW_OP_ABX_COUNT, aew_sizeof 58 / 59 - index 57 stays
  * unused, it answers -1): over an N x N distance matrix D (row = X, column = A or B; no symmetry is assumed) count, for
  * every X and every group of B items, the (A, B, X) triples and how many of them D gets wrong.  One launch, one
@@ -1732,7 +1818,7 @@ enum {
     AEW_OP_ACCUM, AEW_OP_CODE_LOOKUP, AEW_OP_CODE_RUNS, AEW_OP_ADAM_GROUPS,
     AEW_OP_EVAL_GROUPS, AEW_OP_MEL_TILE, AEW_OP_CODE_STITCH, AEW_OP_CODE_TILE, AEW_OP_COND_STITCH,
     AEW_OP_WAV_TILE, AEW_OP_NLL_STITCH, AEW_OP_SCORE_REDUCE, AEW_OP_SEQ_ALIGN,
-    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT, AEW_OP_SEQ_SEARCH, AEW_OP_ABX_COUNT
+    AEW_OP_FRAME_STITCH, AEW_OP_CODE_SEGMENT, AEW_OP_SEQ_SEARCH, AEW_OP_ABX_COUNT, AEW_OP_SEQ_DISCOVER
 };
 
 /* Lanes.  A plan is a sequential program; `lane` lets the caller mark ops that are OFF the
@@ -1765,14 +1851,14 @@ typedef struct {
         aew_code_tile_t ctile; aew_cond_stitch_t cndst;
         aew_wav_tile_t wtile; aew_nll_stitch_t nllst; aew_score_reduce_t sred; aew_seq_align_t align;
         aew_frame_stitch_t fstitch; aew_code_segment_t cseg; aew_seq_search_t search;
-        aew_abx_count_t abx;
+        aew_abx_count_t abx; aew_seq_discover_t discover;
     } u;
 } aew_op_t;
 
 /* Library / build identification. */
 int aew_abi_version(void);
 /* sizeof(aew_op_t) etc. so the binding can verify its struct mirrors. */
-int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment, 55 search_pair, 56 seq_search, 58 abx_group, 59 abx_count (24, 26, 33, 40, 46, 50, 54 and 57 are unused: -1, like every index behind the last) */
+int aew_sizeof(int which);      /* 0 op, 1 gemm_nt, 2 gemm_tn, 3 seg, 4 view, 5 copy_rec, 6 actor, 7 sampler, 8 tuning, 9 nt_stage, 10 nt_chain, 11 adam, 12 grad_norm, 13 uw_chunk, 14 uw_track, 15 update_ratio, 16 nt_pick, 17 swap, 18 vq_restart, 19 tn_pick, 20 eval_acc, 21 window_gather, 22 grad_welford, 23 seg_select, 25 accum, 27 code_lookup, 28 code_runs, 29 adam_tensor, 30 adam_groups, 31 adam_grouped, 32 eval_groups, 34 utt_row, 35 mel_tile, 36 code_stitch, 37 cond_row, 38 code_tile, 39 cond_stitch, 41 draw, 42 score_row, 43 wav_tile, 44 nll_stitch, 45 score_reduce, 47 align_seq, 48 align_pair, 49 seq_align, 51 seg_utt, 52 frame_stitch, 53 code_segment, 55 search_pair, 56 seq_search, 58 abx_group, 59 abx_count, 61 discover_pair, 62 seq_discover (24, 26, 33, 40, 46, 50, 54, 57 and 60 are unused: -1, like every index behind the last) */
 
 /* Execute ops[0..n) in order on `stream` (a hipStream_t).  Returns at the first error and
  * writes the failing index to *fail_index if non-NULL. */
