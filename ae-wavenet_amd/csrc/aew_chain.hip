@@ -26,12 +26,24 @@
 // Kernel bodies: nt_tile<EPI, .., 4, 1, 256, 3> and win_tile<EPI, 4, 1 | 4> - the stand-alone launches' own code,
 // same tile order inside a stage (the N tiles of a row tile consecutive, block L of a stage on XCD L % 8 since stages
 // start at multiples of 8), same summation order: bit-identical to the serial plan.
+//
+// Row-tile height per stage (aew_nt_chain_build_bm): a DFG / STORE stage of the backward set may run on 128-row tiles -
+// aew_nt_stage_t.kind + CHAIN_KIND_128, bodies nt_tile<EPI, .., 2, 1, 128, 3> and win_tile<EPI, 2, 1 | 4>: the same eight
+// waves as 4 x 2, each 32 rows x 64 columns.  A dz stage is then 640-896 tiles instead of 320-448 - more than the 512
+// resident slots, so a tile's producers have normally finished before it is resident - and a hand-off waits for half a
+// tile's latency.  The K order per element is the 256-row body's (one 32-channel K tile per step, taps interleaved per K
+// tile in the one-window body), so the bits are the same; W is staged once per 128 rows instead of once per 256.
 #pragma once
 
 #define CHAIN_BM 256
+#define CHAIN_KIND_128 4                     // aew_nt_stage_t.kind bit: the stage's row tiles are 128 rows (body kind = kind & 3)
+__host__ __device__ __forceinline__ int chain_kind_bm(int kind) { return (kind & CHAIN_KIND_128) ? 128 : CHAIN_BM; }
 #define CHAIN_THREADS 512
 #define CHAIN_LDS_BYTES (NtCfg<4, 1, 256>::LDS_BYTES > WinCfg<4, 4>::LDS_BYTES ? NtCfg<4, 1, 256>::LDS_BYTES : WinCfg<4, 4>::LDS_BYTES)
 static_assert(WinCfg<4, 1>::LDS_BYTES <= CHAIN_LDS_BYTES && 2 * CHAIN_LDS_BYTES <= 160 * 1024, "two chain blocks per CU");
+static_assert(NtCfg<2, 1, 128>::LDS_BYTES <= CHAIN_LDS_BYTES && WinCfg<2, 1>::LDS_BYTES <= CHAIN_LDS_BYTES &&
+              WinCfg<2, 4>::LDS_BYTES <= CHAIN_LDS_BYTES && NtCfg<2, 1, 128>::THREADS == CHAIN_THREADS &&
+              WinCfg<2, 4>::THREADS == CHAIN_THREADS, "the 128-row bodies run in the chain's block");
 
 // producer row tiles [t_lo, t_hi] a consumer tile with rows [m0, m_last] waits for (empty: t_lo > t_hi)
 __host__ __device__ __forceinline__ void chain_dep_tiles(const aew_chain_dep_t& d, int m0, int m_last, int& t_lo, int& t_hi) {
@@ -56,8 +68,10 @@ __global__ __launch_bounds__(CHAIN_THREADS, 4) void k_nt_chain(const aew_nt_stag
     const int rt = ((L >> 3) / n_nt) * 8 + (L & 7);           // the bodies' own tile order
     if (rt >= n_mt * S.g.batch) return;                       // padding block of the stage's last group of 8
     const int b = rt / n_mt;
-    const int m0 = (rt - b * n_mt) * CHAIN_BM;
-    const int m_last = (m0 + CHAIN_BM < S.g.M ? m0 + CHAIN_BM : S.g.M) - 1;
+    const int kind = S.kind, epi = S.g.epi;
+    const int bm = chain_kind_bm(kind);
+    const int m0 = (rt - b * n_mt) * bm;
+    const int m_last = (m0 + bm < S.g.M ? m0 + bm : S.g.M) - 1;
     const int tid = threadIdx.x;
     const int n_deps = S.n_deps;
     if (n_deps > 0) {
@@ -107,14 +121,21 @@ __global__ __launch_bounds__(CHAIN_THREADS, 4) void k_nt_chain(const aew_nt_stag
         }
         __syncthreads();
     }
-    const int kind = S.kind, epi = S.g.epi;
-    if (SET == 0) {
+    if (SET == 0) {                                           // (the builder keeps this set on 256 rows)
         if (epi == AEW_EPI_GATED) {
             if (kind == 1) win_tile<AEW_EPI_GATED, 4, 1, true>(S.g, smem, L);
             else if (kind == 2) win_tile<AEW_EPI_GATED, 4, 4, true>(S.g, smem, L);
             else nt_tile<AEW_EPI_GATED, false, 4, 1, 256, NT_STAGES, true>(S.g, smem, L);
         } else {
             nt_tile<AEW_EPI_STORE, false, 4, 1, 256, NT_STAGES, true, LINES>(S.g, smem, L);
+        }
+    } else if (kind & CHAIN_KIND_128) {
+        if (epi == AEW_EPI_DFG) {
+            nt_tile<AEW_EPI_DFG, false, 2, 1, 128, NT_STAGES, true, LINES>(S.g, smem, L);
+        } else {
+            if (kind == CHAIN_KIND_128 + 1) win_tile<AEW_EPI_STORE, 2, 1, true, LINES>(S.g, smem, L);
+            else if (kind == CHAIN_KIND_128 + 2) win_tile<AEW_EPI_STORE, 2, 4, true, LINES>(S.g, smem, L);
+            else nt_tile<AEW_EPI_STORE, false, 2, 1, 128, NT_STAGES, true, LINES>(S.g, smem, L);
         }
     } else {
         if (epi == AEW_EPI_DFG) {
@@ -224,15 +245,20 @@ static int chain_desc_ok(const aew_gemm_nt_t& g, int force) {
 
 extern "C" int aew_nt_chain_dep_tiles(const aew_nt_stage_t* stage, int dep, int m0, int* t_lo, int* t_hi) {
     if (!stage || dep < 0 || dep >= stage->n_deps || !t_lo || !t_hi || m0 < 0 || m0 >= stage->g.M) return AEW_E_ARG;
-    const int m_last = (m0 + CHAIN_BM < stage->g.M ? m0 + CHAIN_BM : stage->g.M) - 1;
+    const int bm = chain_kind_bm(stage->kind);                // (m0: first row of a tile of the stage's own height)
+    const int m_last = (m0 + bm < stage->g.M ? m0 + bm : stage->g.M) - 1;
     chain_dep_tiles(stage->dep[dep], m0, m_last, *t_lo, *t_hi);
     return 0;
 }
 
-extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* out, uint16_t* block_stage,
-                                  int cap_blocks, int* n_blocks_out, int* n_counters_out, int* set_out, int force) {
+// stage_bm: row-tile height of every stage, 256 | 128 (nullptr: 256 throughout)
+static int chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* out, uint16_t* block_stage, int cap_blocks,
+                       int* n_blocks_out, int* n_counters_out, int* set_out, int force, const int32_t* stage_bm) {
     if (!descs || !out || !block_stage || n < 1 || n > 65535 || !n_blocks_out || !n_counters_out || !set_out) return AEW_E_ARG;
-    bool has_gated = false, has_dfg = false, store_win = false;
+    for (int s = 0; stage_bm && s < n; ++s)
+        if (stage_bm[s] != CHAIN_BM && stage_bm[s] != 128) return AEW_E_ARG;
+    auto bm_of = [&](int s) { return stage_bm ? (int)stage_bm[s] : CHAIN_BM; };
+    bool has_gated = false, has_dfg = false, store_win = false, any_128 = false;
     int blocks = 0, counters = 0;
     struct FullDep { int p; aew_chain_dep_t d; };
     std::vector<std::vector<FullDep>> full(n);
@@ -244,11 +270,12 @@ extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stag
         S = aew_nt_stage_t{};
         S.g = g;
         const int dwp = win_dwp(g, AEW_T());
-        S.kind = dwp == 0 ? 0 : (dwp == 1 ? 1 : 2);
+        S.kind = (dwp == 0 ? 0 : (dwp == 1 ? 1 : 2)) + (bm_of(s) == 128 ? CHAIN_KIND_128 : 0);
+        any_128 = any_128 || bm_of(s) == 128;
         has_gated = has_gated || g.epi == AEW_EPI_GATED;
         has_dfg = has_dfg || g.epi == AEW_EPI_DFG;
-        store_win = store_win || (g.epi == AEW_EPI_STORE && S.kind != 0);
-        S.n_mt = (g.M + CHAIN_BM - 1) / CHAIN_BM;
+        store_win = store_win || (g.epi == AEW_EPI_STORE && dwp != 0);
+        S.n_mt = (g.M + bm_of(s) - 1) / bm_of(s);
         S.n_nt = g.N_pad / NT_BN;
         S.first_block = blocks;
         S.n_blocks = ((S.n_mt * g.batch + 7) / 8) * 8 * S.n_nt;
@@ -301,17 +328,19 @@ extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stag
                 }
             }
             if (have) {
-                D.cnt_base = out[p].cnt_base; D.n_mt = out[p].n_mt; D.need = out[p].n_nt; D.bm = CHAIN_BM;
+                D.cnt_base = out[p].cnt_base; D.n_mt = out[p].n_mt; D.need = out[p].n_nt; D.bm = bm_of(p);
                 full[s].push_back({p, D});
             }
         }
     }
     if ((has_gated && has_dfg) || (has_gated && store_win)) return AEW_E_UNSUP;   // one body set per launch
+    if (any_128 && !(has_dfg || store_win)) return AEW_E_UNSUP;                   // 128-row bodies: the backward set's only
     if (blocks > cap_blocks) return AEW_E_ARG;
     // ---- drop dependencies that another one implies: s waits for q, every tile of q it waits for has itself waited
     // for the tiles of p that s needs (dx of a layer reads dx of the layer above through dz's rows)
-    auto need = [&](const aew_chain_dep_t& d, int M, int mt, int& lo, int& hi) {
-        const int m0 = mt * CHAIN_BM, m_last = (m0 + CHAIN_BM < M ? m0 + CHAIN_BM : M) - 1;
+    auto need = [&](const aew_chain_dep_t& d, int c, int mt, int& lo, int& hi) {      // row tile mt of consumer stage c
+        const int bm = bm_of(c), M = descs[c].M;
+        const int m0 = mt * bm, m_last = (m0 + bm < M ? m0 + bm : M) - 1;
         chain_dep_tiles(d, m0, m_last, lo, hi);
     };
     for (int s = 0; s < n; ++s) {
@@ -329,13 +358,13 @@ extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stag
                 bool all = true;
                 for (int mt = 0; mt < S.n_mt && all; ++mt) {
                     int lo, hi, qlo, qhi;
-                    need(F[i].d, S.g.M, mt, lo, hi);
-                    need(F[j].d, S.g.M, mt, qlo, qhi);
+                    need(F[i].d, s, mt, lo, hi);
+                    need(F[j].d, s, mt, qlo, qhi);
                     for (int t = lo; t <= hi && all; ++t) {
                         bool cov = false;
                         for (int u = qlo; u <= qhi && !cov; ++u) {
                             int plo, phi;
-                            need(*qp, descs[q].M, u, plo, phi);
+                            need(*qp, q, u, plo, phi);
                             cov = t >= plo && t <= phi;
                         }
                         all = cov;
@@ -354,7 +383,7 @@ extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stag
             int cnt = 0;
             for (int d = 0; d < S.n_deps; ++d) {
                 int lo, hi;
-                need(S.dep[d], S.g.M, mt, lo, hi);
+                need(S.dep[d], s, mt, lo, hi);
                 if (hi >= lo) cnt += hi - lo + 1;
             }
             if (cnt > 64) return AEW_E_UNSUP;
@@ -372,6 +401,11 @@ extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stag
     return 0;
 }
 
+extern "C" int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* out, uint16_t* block_stage,
+                                  int cap_blocks, int* n_blocks_out, int* n_counters_out, int* set_out, int force) {
+    return chain_build(descs, n, out, block_stage, cap_blocks, n_blocks_out, n_counters_out, set_out, force, nullptr);
+}
+
 // The same under a caller's tuning record (the record the launches will run under: it decides which stages take the one-window
 // body and which launches count as small) instead of the process-wide one.
 extern "C" int aew_nt_chain_build_tuned(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* out, uint16_t* block_stage,
@@ -380,6 +414,19 @@ extern "C" int aew_nt_chain_build_tuned(const aew_gemm_nt_t* descs, int n, aew_n
     const aew_tuning_t* prev = t_tune;
     if (tuning) t_tune = tuning;
     const int rc = aew_nt_chain_build(descs, n, out, block_stage, cap_blocks, n_blocks_out, n_counters_out, set_out, force);
+    t_tune = prev;
+    return rc;
+}
+
+// ... and with a row-tile height per stage: stage_bm[n], each 256 or 128 (nullptr: aew_nt_chain_build_tuned).  128 is for
+// the stages of the backward set (DFG, STORE); a run that would launch the forward set with one is refused (AEW_E_UNSUP).
+// cap_blocks counts the stages' tiles at THEIR heights.
+extern "C" int aew_nt_chain_build_bm(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* out, uint16_t* block_stage,
+                                     int cap_blocks, int* n_blocks_out, int* n_counters_out, int* set_out, int force,
+                                     const aew_tuning_t* tuning, const int32_t* stage_bm) {
+    const aew_tuning_t* prev = t_tune;
+    if (tuning) t_tune = tuning;
+    const int rc = chain_build(descs, n, out, block_stage, cap_blocks, n_blocks_out, n_counters_out, set_out, force, stage_bm);
     t_tune = prev;
     return rc;
 }

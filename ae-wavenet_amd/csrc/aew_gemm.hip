@@ -901,7 +901,8 @@ __device__ __forceinline__ void nt_tile(const aew_gemm_nt_t& g, char* smem, cons
                     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);             // MFMA
                     __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);             // VMEM (LDS-DMA)
                 }
-                __builtin_amdgcn_sched_group_barrier(0x008, 4 * MT - 4 * (Cfg::XP + Cfg::WP), 0);
+                if constexpr (MT > Cfg::XP + Cfg::WP)
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4 * MT - 4 * (Cfg::XP + Cfg::WP), 0);
             }
         }
         advance();

@@ -74,10 +74,16 @@ class TrainEngine:
                               # launch of 27 856 tiles instead of 39; 2: the pair of a layer; 0: one launch per op).  Bit-identical
                               # results; per-op timing (aew_timing_enable(1)) always runs the ops one by one.  Measured,
                               # interleaved on one box: fwd_b plan 2.089 -> 1.911 ms, step 6.865 -> 6.748 ms (profiles/r05_notes.md)
-    nt_chain_bwd = 0          # the same for the BACKWARD's d.post / dz / dx run.  Measured neutral to slightly negative (bwd plan
-                              # 4.085 -> 4.134 ms): a dz stage is 320-448 tiles - fewer than the 512 resident slots - so its
-                              # consumers (dx) are resident before it has finished and 11 000 of the launch's 20 432 tiles spin
-                              # on a counter, where the forward's stages (640-896 tiles) leave 900 of 27 856 waiting.  Option
+    nt_chain_bwd = (64, (128, 256))   # the same for the BACKWARD's d.post / dz / dx run: (stages per launch, rows per tile), rows = 256,
+                              # 128, or (rows of d.post / dz, rows of dx); a plain number means 256-row tiles; 0: one launch per op.
+                              # On 256-row tiles a dz stage is 320-448 tiles - fewer than the 512 resident slots - so its consumers
+                              # (dx) are resident before it has finished and 10 000 of the launch's 21 072 tiles spin on a counter.
+                              # dz on 128-row tiles (aew_nt_chain_build_bm; same bits) is 640-896 tiles per stage, the forward's
+                              # range: 612 tiles wait.  dx stays on 256 rows: its K loop is 4 x the dz width, and a half-height
+                              # tile stages W once more per 256 rows - 128 rows throughout leaves 7 tiles waiting and is slower.
+                              # Measured, interleaved on one box (profiles/chain_bm.txt): bwd plan 4.27 stand-alone, 3.99 chained
+                              # on 256, 4.08 on 128, 3.93 ms dz 128 / dx 256; step 6.56 / 6.37 / 6.53 / 6.35 ms.  A rank of a
+                              # data-parallel group keeps the backward unchained (_chain_args)
     nt_chain_bwd_phase = 0    # with nt_chain_bwd = 2: 0 pairs (dz.l, dx.l); 1 pairs (dx.l, dz.l-1) - the dependency whose producer stage is
                               # larger than the 512 resident tiles, so that its consumers find it finished
     nt_chain_max_stage_tiles = 2048   # runs whose stages average more tiles than this (four waves of the 512 resident slots) stay
@@ -208,16 +214,28 @@ class TrainEngine:
     def _chain_args(self) -> dict:
         """Stages per chained launch of the forward / backward as applied (nt_chain_used / nt_chain_bwd_used) and the
         keywords every insert_nt_chains call of this engine shares."""
-        # AEW_NT_CHAIN = "f" or "f,b": stages per chained launch of the forward / backward (A/B and bisecting aid)
+        # AEW_NT_CHAIN = "f", "f,b" or "f,b,bm": stages per chained launch of the forward / backward and the backward's
+        # row-tile height, 256 where it is left out (A/B and bisecting aid)
         env = os.environ.get("AEW_NT_CHAIN")
-        n_f, n_b = int(self.nt_chain), int(self.nt_chain_bwd)
+        n_b, bm_b = self.nt_chain_bwd if isinstance(self.nt_chain_bwd, (tuple, list)) else (self.nt_chain_bwd, 256)
+        n_f, n_b = int(self.nt_chain), int(n_b)
         if env is not None and env.strip():
             try:
                 v = [int(x) for x in env.split(",") if x.strip()]
             except ValueError:
-                raise ValueError(f"AEW_NT_CHAIN={env!r}: expected 'f' or 'f,b' (stages per chained launch, forward / backward)")
+                raise ValueError(f"AEW_NT_CHAIN={env!r}: expected 'f', 'f,b' or 'f,b,bm' (stages per chained launch, forward / "
+                                 "backward; rows per tile of the backward's)")
             if v:
-                n_f, n_b = v[0], (v[1] if len(v) > 1 else 0)
+                n_f, n_b, bm_b = v[0], (v[1] if len(v) > 1 else 0), (v[2] if len(v) > 2 else 256)
+        # a rank of a data-parallel group keeps the backward unchained: the cross-rank maximum of the guard word is issued
+        # before the second half of the decoder backward runs (dp.DataParallel._guard_sync), so a hand-off that gave up there
+        # would stop the update on its own rank only
+        if n_b and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            n_b = 0
+        bm_dz, bm_dx = (bm_b if isinstance(bm_b, (tuple, list)) else (bm_b, bm_b))
+        if int(bm_dz) not in (128, 256) or int(bm_dx) not in (128, 256):
+            raise ValueError(f"rows per tile of the backward chain = {bm_b!r}: 256, 128 or a pair of them")
+        self.nt_chain_bwd_bm_used = (int(bm_dz), int(bm_dx))
         self.nt_chain_used = n_f if self.impl == 0 else 0
         self.nt_chain_bwd_used = n_b if self.impl == 0 else 0
         return dict(force=bool(self.nt_chain_force), flags=int(self.nt_chain_flags), max_stage_tiles=int(self.nt_chain_max_stage_tiles),
@@ -311,7 +329,8 @@ class TrainEngine:
         if self.nt_chain_bwd_used >= 2:
             heads = ("d.post2", "d.post1")[int(self.nt_chain_bwd_phase):]    # (phase 1: pairs are (dx.l, dz.l-1), not (dz.l, dx.l))
             insert_nt_chains(bw, ws, "chain.bwd", lambda lab: lab.startswith(heads + ("dz.", "dx.")),
-                             max_len=self.nt_chain_bwd_used, **chain_kw)
+                             max_len=self.nt_chain_bwd_used, **chain_kw,
+                             bm=lambda lab: self.nt_chain_bwd_bm_used[1 if lab.startswith("dx.") else 0])
         # gradient statistics of run() (autoencoder_model.py:252-257 mel_grad_sd / bn_grad_sd; mfcc_inverter.py:100-106
         # mel_grad_sd / mel_grad_mean): by-products of this backward, reduced on a side lane as soon as their input is
         # final (d(loss)/d(code) here, under the encoder backward)

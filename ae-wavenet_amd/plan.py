@@ -391,7 +391,7 @@ def split_small_nt(plan: "Plan", ws: Workspace, name: str, target_blocks: int = 
 
 def insert_nt_chains(plan: "Plan", ws: Workspace, name: str, select, max_len: int = 0, force: bool = False,
                      spin_max: int = 0, flags: int = 0, max_stage_tiles: int = 0, sticky_ptr: int = 0,
-                     tuning: Optional["L.Tuning"] = None) -> List[Tuple[int, int]]:
+                     tuning: Optional["L.Tuning"] = None, bm=256) -> List[Tuple[int, int]]:
     """Chained NT launches (AEW_OP_NT_CHAIN, aewavenet.h): runs of consecutive main-lane bf16 NT ops of `plan` whose label
     passes `select` - no join except at the head of the run - get a chain op in front of them that launches the whole
     run as ONE kernel with tile-granular hand-off between the stages (wavenet.py:354-357: the layer loop; its backward).
@@ -404,6 +404,9 @@ def insert_nt_chains(plan: "Plan", ws: Workspace, name: str, select, max_len: in
     sticky_ptr: device word no launch clears; a wait that gives up leaves (stage + 1) there (aew_nt_chain_t.sticky).
     tuning: the record the plan will RUN under (None: the process-wide one) - the stage table is built under it and a launch
     under a record with another one-window limit falls back to the stage ops (aew_nt_chain_t.built_window).
+    bm: row-tile height of the stages, 256 or 128 - one number for every stage or a function of the stage op's label
+    (aew_nt_chain_build_bm; 128 is for the backward's DFG / STORE runs: same bits, twice the tiles per stage and half the
+    hand-off latency).  256 throughout is aew_nt_chain_build_tuned, unchanged.
     Returns [(index of the chain op, stages)]."""
     lib = L.load()
     built_window = int((tuning if tuning is not None else L.current_tuning()).nt_window)
@@ -428,11 +431,17 @@ def insert_nt_chains(plan: "Plan", ws: Workspace, name: str, select, max_len: in
         if n >= 2:
             descs = (L.GemmNT * n)(*[plan.ops[q].u.nt for q in range(i, j)])
             stages = (L.NtStage * n)()
-            cap = sum(((-(-d.M // 256) * d.batch + 7) // 8) * 8 * (d.N_pad // 128) for d in descs)
+            bms = [int(bm(plan.labels[q])) if callable(bm) else int(bm) for q in range(i, j)]
+            cap = sum(((-(-d.M // h) * d.batch + 7) // 8) * 8 * (d.N_pad // 128) for d, h in zip(descs, bms))
             bmap = (C.c_uint16 * (cap // 8))()
             nb, nc, st = C.c_int(0), C.c_int(0), C.c_int(0)
-            rc = lib.aew_nt_chain_build_tuned(C.byref(descs), n, C.byref(stages), C.byref(bmap), cap, C.byref(nb), C.byref(nc),
-                                              C.byref(st), int(force), C.byref(tuning) if tuning is not None else None)
+            tref = C.byref(tuning) if tuning is not None else None
+            if all(h == 256 for h in bms):
+                rc = lib.aew_nt_chain_build_tuned(C.byref(descs), n, C.byref(stages), C.byref(bmap), cap, C.byref(nb), C.byref(nc),
+                                                  C.byref(st), int(force), tref)
+            else:
+                rc = lib.aew_nt_chain_build_bm(C.byref(descs), n, C.byref(stages), C.byref(bmap), cap, C.byref(nb), C.byref(nc),
+                                               C.byref(st), int(force), tref, C.byref((C.c_int32 * n)(*bms)))
             if rc != L.E_UNSUP:
                 L.check(rc, f"aew_nt_chain_build ({plan.labels[i]} .. {plan.labels[j - 1]})")
                 made.append((i, n, stages, bmap, nb.value, nc.value, st.value))

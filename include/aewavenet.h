@@ -1799,6 +1799,9 @@ int aew_nt_chain_build(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* stages
 /* Producer row tiles consumer tile (first row m0 of the 256-row tile) of `stage` waits for through dependency `dep`:
  * [*t_lo, *t_hi] (empty if *t_lo > *t_hi).  The kernel uses the same arithmetic; exported for tests. */
 int aew_nt_chain_dep_tiles(const aew_nt_stage_t* stage, int dep, int m0, int* t_lo, int* t_hi);
+/* aew_nt_stage_t.kind bit of a stage on 128-row tiles (aew_nt_chain_build_bm, below): body kind = kind & 3, and m0 above
+ * is then the first row of a 128-row tile.  aew_chain_dep_t.bm is the PRODUCER's height. */
+#define AEW_CHAIN_KIND_128 4
 
 /* Split-K hint for a small bf16 launch (aew_gemm_nt_t.k_split): *k_split = the largest S in 2..8 the launcher would honour
  * for g under the calling thread's tuning record with S * blocks <= target_blocks and at least four 64-channel K tiles per
@@ -1933,6 +1936,13 @@ int aew_graph_capture_tuned(const aew_op_t* ops, int n, void** exec_out, int* fa
  * store its nt_window in aew_nt_chain_t.built_window. */
 int aew_nt_chain_build_tuned(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* stages_out, uint16_t* block_stage_out,
                              int cap_blocks, int* n_blocks, int* n_counters, int* set, int force, const aew_tuning_t* tuning);
+/* ... and with a row-tile height per stage: stage_bm[n], each 256 or 128 (NULL: 256 throughout, the call above).  A stage on
+ * 128-row tiles carries kind + AEW_CHAIN_KIND_128 and runs the same K order on half-height tiles of the same eight waves, so
+ * its results are the 256-row stage's bit for bit.  128 is for the stages of the backward set (DFG, and STORE next to them):
+ * AEW_E_UNSUP for a run that would launch the forward set with one.  cap_blocks counts every stage's tiles at its own height. */
+int aew_nt_chain_build_bm(const aew_gemm_nt_t* descs, int n, aew_nt_stage_t* stages_out, uint16_t* block_stage_out,
+                          int cap_blocks, int* n_blocks, int* n_counters, int* set, int force, const aew_tuning_t* tuning,
+                          const int32_t* stage_bm);
 
 /* Box fingerprint (measurement aid): sustained rate of THIS device on a pure bf16 MFMA loop (out[0], TFLOP/s) and on a
  * device-to-device copy of copy_bytes (out[1], TB/s read + written), HIP events on `stream`.  scratch: device memory,

@@ -3,7 +3,8 @@
 with the forward (and optionally the backward) chained - are driven in lockstep over many steps with a fresh batch each,
 and after every step the loss, the logits' checksum and the gradient buffer must be bit-identical (bias-type gradients,
 fp32-atomic sums, at round-off); no hand-off wait may give up.  A rare race in the in-launch hand-off would show here.
-    python tools/chain_soak.py [steps] [bwd: 0|1] [noise: 0|1]"""
+    python tools/chain_soak.py [steps] [bwd: 0|1|128|2] [noise: 0|1]
+bwd: 1 = the backward chained on 256-row tiles, 128 = on 128-row tiles, 2 = the engine's default setting"""
 import os
 import sys
 
@@ -17,9 +18,10 @@ from tests.test_chain_gpu import _mask
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 500
 bwd = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 noise = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+BWD_DEFAULT = M.TrainEngine.nt_chain_bwd
 M.TrainEngine.nt_chain, M.TrainEngine.nt_chain_bwd = 0, 0
 hps, ref, wts, emb, inp = seeded_full_engine(B=8, w=5000, seed=3)
-M.TrainEngine.nt_chain, M.TrainEngine.nt_chain_bwd = 64, (64 if bwd else 0)
+M.TrainEngine.nt_chain, M.TrainEngine.nt_chain_bwd = 64, {0: 0, 1: 64, 128: (64, 128)}.get(bwd, BWD_DEFAULT)
 _, eng, _, _, _ = seeded_full_engine(B=8, w=5000, seed=3)
 mask = _mask(eng)
 g = eng.geom
