@@ -19,8 +19,11 @@ states the rule bit for bit).
 sequences and over the model's own MFCC front-end; `model.search_codes()` and `model.search_wavs()` are `search` over the
 same two feature sources, `model.discover_codes()` and `model.discover_wavs()` are `discover`.  On the device dtw() and
 search() run one sweep (`align_sweep` in csrc/aew_align.hip), discover() its sibling over the same ring of local
-distances, and here the three ops share one launch path, `_SeqPlan`: it checks the two sides, fills the record fields
-the ops have in common and runs the records as a plan on torch's current stream; every host table (and
+distances, search() and discover() one pick (`seq_pick`), all three one sweep-and-second-kernel launch, and here the
+three ops share one launch path, `_SeqPlan`: it checks the two sides, fills the record
+fields the ops have in common and runs the records as a plan on torch's current stream (`_run_records`, abx_score()'s
+way too); search() and discover() share what lies on top of it - the pair table, the launch (`_HitsLaunch`), the result
+(`_Hits`) and the argument checks; the workspace of each op follows from `CELL_WORDS`.  Every host table (and
 edit_distance()'s denominator) goes up through `_upload` - pinned, behind the stream.  Nothing
 but `Alignment.path()` (and `edit_distance(collapse=True)`, which has to learn the number of units) synchronises with
 the host.  There is no CPU path: a tensor that is not on the GPU is refused.
@@ -49,6 +52,15 @@ from .plan import pinned_upload
 
 METRICS = {"euclid": L.ALIGN_EUCLID, "sqeuclid": L.ALIGN_SQEUCLID}
 STRIP = 64                                   # A frames a wave holds at a time: longer A sides carry a boundary row in the workspace
+# int32 words that travel with the fp32 value of a cell, per op (AEW_*_WORDS in csrc/aew_align.hip): a boundary row takes
+# 1 + CELL_WORDS planes of pairs * wstride 4-byte words in the workspace
+CELL_WORDS = {"align": 1, "search": 2, "discover": 3}
+
+
+def _metric_of(what: str, metric: str) -> int:
+    if metric not in METRICS:
+        raise L.AewError(f"{what}: metric must be one of {sorted(METRICS)}, got '{metric}'")
+    return METRICS[metric]
 
 
 class Ragged:
@@ -136,7 +148,7 @@ def pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, 
     consecutive pairs whose back matrices fit max_back_bytes together (one run with max_back_bytes None; a pair larger
     than the limit gets a run of its own); n_back: bytes the largest chunk needs; n_path: path entries of all pairs;
     wstride: per chunk, the longest B side among its pairs of more than STRIP A frames (the workspace is
-    8 * pairs * wstride bytes).  A pair with an empty side owns neither back bytes nor path entries."""
+    4 * (1 + CELL_WORDS["align"]) * pairs * wstride bytes).  A pair with an empty side owns neither back bytes nor path entries."""
     P = len(pairs)
     la, lb = np.asarray(lens_a, np.int64)[pairs[:, 0]], np.asarray(lens_b, np.int64)[pairs[:, 1]]
     live = (la > 0) & (lb > 0)
@@ -162,10 +174,23 @@ def _upload(table: np.ndarray, dev) -> torch.Tensor:
     return pinned_upload(dev, table)[0]
 
 
+def _run_records(dev, kind: int, field: str, recs, what: str):
+    """Records of one kind as one plan on torch's current stream of `dev`; a failure names `what` and the record."""
+    fail = C.c_int(-1)
+    ops = (L.Op * len(recs))()
+    for op, r in zip(ops, recs):
+        op.kind = kind
+        setattr(op.u, field, r)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.load().aew_run_plan(C.cast(ops, C.c_void_p), len(recs), C.c_void_p(st), C.byref(fail)), what,
+                fail.value if fail.value >= 0 else None)
+
+
 class _SeqPlan:
     """The launch path dtw() / edit_distance() (`_Launches`), search() (`_SearchLaunch`) and discover()
     (`_DiscoverLaunch`) share: the checks of the two sides, the three tables, the fields aew_seq_align_t,
-    aew_seq_search_t and aew_seq_discover_t have in common, the run as one plan."""
+    aew_seq_search_t and aew_seq_discover_t have in common, the workspace's size, the run as one plan."""
     KIND, FIELD, NOUN = None, None, None
 
     def _open(self, ra: Ragged, rb: Ragged):
@@ -185,6 +210,11 @@ class _SeqPlan:
         self.host = (self.sides[0].table(), self.sides[1].table(), tp)   # the launcher reads these at every launch
         self.tables = tuple(_upload(t, self.dev) for t in self.host)     # uploaded once per call
 
+    def _workspace(self, pairs_by_wstride: int):
+        """The boundary rows of the largest launch: pairs * wstride cells (None: no A side is longer than STRIP)."""
+        n = (1 + CELL_WORDS[self.FIELD]) * pairs_by_wstride
+        return torch.empty(n, dtype=torch.float32, device=self.dev) if n else None
+
     def _add(self, r, ws, lo: int = 0):
         """Record r, its common fields filled (the pair table from record `lo` on), joins the plan."""
         (ra, rb), (ta, tb, tp) = self.sides, self.host
@@ -198,15 +228,7 @@ class _SeqPlan:
         self.recs.append(r)
 
     def run(self, what: str):
-        fail = C.c_int(-1)
-        ops = (L.Op * len(self.recs))()
-        for op, r in zip(ops, self.recs):
-            op.kind = self.KIND
-            setattr(op.u, self.FIELD, r)
-        with torch.cuda.device(self.dev):
-            st = torch.cuda.current_stream(self.dev).cuda_stream
-            L.check(L.load().aew_run_plan(C.cast(ops, C.c_void_p), len(self.recs), C.c_void_p(st), C.byref(fail)), what,
-                    fail.value if fail.value >= 0 else None)
+        _run_records(self.dev, self.KIND, self.FIELD, self.recs, what)
         return self
 
 
@@ -225,8 +247,7 @@ class _Launches(_SeqPlan):
         self.cost = torch.empty(P, dtype=torch.float32, device=dev)
         self.steps = torch.empty(P, dtype=torch.int32, device=dev)
         self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        ws_elems = max(2 * (b - a) * w for (a, b), w in zip(self.chunks, wstride))
-        self.ws = torch.empty(ws_elems, dtype=torch.float32, device=dev) if ws_elems else None
+        self.ws = self._workspace(max((b - a) * w for (a, b), w in zip(self.chunks, wstride)))
         self.back = torch.empty(max(n_back, 1), dtype=torch.uint8, device=dev) if want_path else None
         self.path = torch.empty(max(self.n_path, 1), 2, dtype=torch.int32, device=dev) if want_path else None
         self.path_base = tp["path_base"].copy()
@@ -272,80 +293,129 @@ def dtw(a, b=None, pairs=None, metric: str = "euclid", return_path: bool = False
     pattern is the symmetric one - diagonal, up, left, each of weight 1, ties in that order - with no band.
     return_path=True keeps one back-pointer byte per cell; when those of all pairs exceed max_back_bytes the pairs run in
     several launches that share one buffer of bounded size (the tables are uploaded once).  -> `Alignment`."""
-    if metric not in METRICS:
-        raise L.AewError(f"dtw(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    metric = _metric_of("dtw()", metric)
     ra = _ragged(a, "dtw(): a", torch.float32)
     rb = ra if b is None else _ragged(b, "dtw(): b", torch.float32)
     pr = default_pairs(len(ra), None if b is None else len(rb), pairs)
-    return Alignment(_Launches(L.ALIGN_DTW, METRICS[metric], ra, rb, pr, bool(return_path), int(max_back_bytes)).run("dtw()"))
+    return Alignment(_Launches(L.ALIGN_DTW, metric, ra, rb, pr, bool(return_path), int(max_back_bytes)).run("dtw()"))
 
 
 RANKS = {"mean": L.SEARCH_MEAN, "cost": L.SEARCH_COST}
 
 
+def _hit_limits(what: str, n_hits, min_len, max_len) -> Tuple[int, int, int]:
+    """n_hits, min_len and max_len of search() / discover() as integers, checked."""
+    n_hits, min_len, max_len = int(n_hits), int(min_len), int(max_len)
+    if not 1 <= n_hits <= L.SEARCH_MAX_HITS:
+        raise L.AewError(f"{what}: n_hits must lie in [1, {L.SEARCH_MAX_HITS}], got {n_hits}")
+    if min_len < 0 or max_len < 0:
+        raise L.AewError(f"{what}: min_len and max_len must not be negative, got {min_len} and {max_len}")
+    return n_hits, min_len, max_len
+
+
+def _profile_pair_table(dtype, lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, owner: int, band=None):
+    """(records, n_prof, wstride) of search() and discover().  records: `dtype` with prof_base = the prefix sum, over
+    the pairs in order, of the lengths of the side that owns the profile (0: A, 1: B) - disjoint profile ranges - and,
+    where the record has one, the pair's band; n_prof: their total; wstride: the longest B side among the pairs whose A
+    side has more than STRIP frames."""
+    la, lb = np.asarray(lens_a, np.int64)[pairs[:, 0]], np.asarray(lens_b, np.int64)[pairs[:, 1]]
+    own = (la, lb)[owner]
+    t = np.zeros(len(pairs), dtype=dtype)
+    t["a"], t["b"] = pairs[:, 0], pairs[:, 1]
+    if band is not None:
+        t["band"] = band
+    t["prof_base"] = np.concatenate([[0], np.cumsum(own)[:-1]])
+    return t, int(own.sum()), int(np.where(la > STRIP, lb, 0).max())
+
+
 def search_pair_table(lens_q: Sequence[int], lens_d: Sequence[int], pairs: np.ndarray):
     """(records, n_prof, wstride).  records: aew_search_pair_t with prof_base = the prefix sum of the document lengths over
     the pairs in order (disjoint profile ranges); n_prof: their total; wstride: the longest document among the pairs whose
-    query has more than STRIP frames (the workspace is 12 * pairs * wstride bytes)."""
-    lq, ld = np.asarray(lens_q, np.int64)[pairs[:, 0]], np.asarray(lens_d, np.int64)[pairs[:, 1]]
-    t = np.zeros(len(pairs), dtype=L.SEARCH_PAIR_DTYPE)
-    t["a"], t["b"] = pairs[:, 0], pairs[:, 1]
-    t["prof_base"] = np.concatenate([[0], np.cumsum(ld)[:-1]])
-    return t, int(ld.sum()), int(np.where(lq > STRIP, ld, 0).max())
+    query has more than STRIP frames (the workspace is 4 * (1 + CELL_WORDS["search"]) * pairs * wstride bytes)."""
+    return _profile_pair_table(L.SEARCH_PAIR_DTYPE, lens_q, lens_d, pairs, 1)
 
 
-class _SearchLaunch(_SeqPlan):
-    """The op record of one search and everything it points to."""
-    KIND, FIELD, NOUN = L.OP_SEQ_SEARCH, "search", "search"
+def discover_pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, band: np.ndarray):
+    """(records, n_prof, wstride).  records: aew_discover_pair_t with prof_base = the prefix sum of the A lengths over the
+    pairs in order (disjoint profile ranges) and the pair's band; n_prof: their total; wstride: the longest B side among
+    the pairs whose A side has more than STRIP frames (the workspace is 4 * (1 + CELL_WORDS["discover"]) * pairs * wstride
+    bytes)."""
+    return _profile_pair_table(L.DISCOVER_PAIR_DTYPE, lens_a, lens_b, pairs, 0, band)
 
-    def __init__(self, metric: int, rank: int, rq: Ragged, rd: Ragged, pairs: np.ndarray, n_hits: int, min_len: int,
-                 max_len: int):
-        dev = self._open(rq, rd)
+
+class _HitsLaunch(_SeqPlan):
+    """The op record of one search or one discovery and everything it points to: the profile arrays `prof` (the first
+    fp32, the others int32), the hits (P, n_hits, HIT_WORDS), their `score` (search: the cost) and steps, count, bad, the
+    workspace; prof_base and own_len cut a pair's profile without a wait.  A subclass names the record (REC), its fields
+    (PROF, and SCORE for `score`), the side whose lengths the profiles have (OWNER; 0: A, 1: B) and its pair table."""
+    REC, PROF, SCORE, HIT_WORDS, OWNER = None, (), None, None, None
+
+    def __init__(self, ra: Ragged, rb: Ragged, pairs: np.ndarray, table, n_hits: int, **fields):
+        dev = self._open(ra, rb)
         P = self.P = len(pairs)
-        tp, n_prof, wstride = search_pair_table(rq.length, rd.length, pairs)
+        tp, n_prof, wstride = table
         self._tables(tp)
-        self.prof = (torch.empty(max(n_prof, 1), dtype=torch.float32, device=dev),
-                     torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev),
-                     torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev))
-        self.hits = torch.empty(P, n_hits, 2, dtype=torch.int32, device=dev)
-        self.cost = torch.empty(P, n_hits, dtype=torch.float32, device=dev)
+        self.prof = tuple(torch.empty(max(n_prof, 1), dtype=torch.int32 if k else torch.float32, device=dev)
+                          for k in range(len(self.PROF)))
+        self.hits = torch.empty(P, n_hits, self.HIT_WORDS, dtype=torch.int32, device=dev)
+        self.score = torch.empty(P, n_hits, dtype=torch.float32, device=dev)
         self.steps = torch.empty(P, n_hits, dtype=torch.int32, device=dev)
         self.count = torch.empty(P, dtype=torch.int32, device=dev)
         self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ws = torch.empty(3 * P * wstride, dtype=torch.float32, device=dev) if wstride else None
-        self.prof_base, self.doc_len = tp["prof_base"].copy(), np.asarray(rd.length, np.int64)[pairs[:, 1]]
-        r = L.SeqSearch()
-        r.metric, r.rank, r.D, r.n_pairs = metric, rank, rq.D, P
-        r.n_hits, r.min_len, r.max_len = n_hits, min_len, max_len
-        r.prof_cost, r.prof_steps, r.prof_start = (x.data_ptr() for x in self.prof)
-        r.n_prof = n_prof
-        r.hits, r.hit_cost, r.hit_steps = self.hits.data_ptr(), self.cost.data_ptr(), self.steps.data_ptr()
-        r.count, r.bad = self.count.data_ptr(), self.bad.data_ptr()
+        self.ws = self._workspace(P * wstride)
+        self.prof_base = tp["prof_base"].copy()
+        self.own_len = np.asarray((ra, rb)[self.OWNER].length, np.int64)[pairs[:, self.OWNER]]
+        r = self.REC()
+        r.D, r.n_pairs, r.n_hits, r.n_prof = ra.D, P, n_hits, n_prof
+        for name, value in fields.items():
+            setattr(r, name, value)
+        for name, x in zip(self.PROF + ("hits", self.SCORE, "hit_steps", "count", "bad"),
+                           self.prof + (self.hits, self.score, self.steps, self.count, self.bad)):
+            setattr(r, name, x.data_ptr())
         self._add(r, self.ws)
 
 
-class Matches:
-    """What search() returns.  start, end (P, n_hits) int32: the document frames [start, end] of hit r of pair p, best
-    first, (-1, -1) behind the `count[p]` hits that exist; cost (P, n_hits) fp32 (+inf there), steps (P, n_hits) int32
-    (0 there), mean = cost / steps; count (P,) int32; bad: int32 (1,), a uint32 count of the pairs that were not finite.
-    All on the device; reading them is the caller's synchronisation."""
+class _Hits:
+    """What `Matches` and `Repeats` share: steps (P, n_hits) and count (P,) int32, bad, the number of pairs, profile()."""
 
-    def __init__(self, run: _SearchLaunch):
-        self.start, self.end = run.hits[:, :, 0], run.hits[:, :, 1]
-        self.cost, self.steps, self.count, self.bad = run.cost, run.steps, run.count, run.bad
-        self.mean = run.cost / run.steps
-        self._run = run
+    def __init__(self, run: _HitsLaunch):
+        self.steps, self.count, self.bad, self._run = run.steps, run.count, run.bad, run
 
     def __len__(self) -> int:
         return self._run.P
 
     def profile(self, p: int):
-        """(end_cost, end_steps, end_start) of pair p: views of length m, entry j the best match that ENDS at document
-        frame j - its summed distance, its path length and the frame it starts at ((NaN, 0, -1) for a pair that was
-        not finite, (+inf, 0, -1) for an empty query).  The lengths come from the host tables: no wait on the device."""
+        """The profile of pair p, as the class text names it: views of the pair's range in every profile array.  The
+        lengths come from the host tables: no wait on the device."""
         p = range(len(self))[p]
-        lo, m = int(self._run.prof_base[p]), int(self._run.doc_len[p])
-        return tuple(x[lo:lo + m] for x in self._run.prof)
+        lo, n = int(self._run.prof_base[p]), int(self._run.own_len[p])
+        return tuple(x[lo:lo + n] for x in self._run.prof)
+
+
+class _SearchLaunch(_HitsLaunch):
+    KIND, FIELD, NOUN, REC = L.OP_SEQ_SEARCH, "search", "search", L.SeqSearch
+    PROF, SCORE, HIT_WORDS, OWNER = ("prof_cost", "prof_steps", "prof_start"), "hit_cost", 2, 1
+
+    def __init__(self, metric: int, rank: int, rq: Ragged, rd: Ragged, pairs: np.ndarray, n_hits: int, min_len: int,
+                 max_len: int):
+        super().__init__(rq, rd, pairs, search_pair_table(rq.length, rd.length, pairs), n_hits,
+                         metric=metric, rank=rank, min_len=min_len, max_len=max_len)
+
+
+class Matches(_Hits):
+    """What search() returns.  start, end (P, n_hits) int32: the document frames [start, end] of hit r of pair p, best
+    first, (-1, -1) behind the `count[p]` hits that exist; cost (P, n_hits) fp32 (+inf there), steps (P, n_hits) int32
+    (0 there), mean = cost / steps; count (P,) int32; bad: int32 (1,), a uint32 count of the pairs that were not finite.
+    All on the device; reading them is the caller's synchronisation.
+
+    profile(p) -> (end_cost, end_steps, end_start) of pair p: views of length m, entry j the best match that ENDS at
+    document frame j - its summed distance, its path length and the frame it starts at ((NaN, 0, -1) for a pair that was
+    not finite, (+inf, 0, -1) for an empty query)."""
+
+    def __init__(self, run: _SearchLaunch):
+        super().__init__(run)
+        self.start, self.end, self.cost = run.hits[:, :, 0], run.hits[:, :, 1], run.score
+        self.mean = run.score / run.steps
 
 
 def search(query, doc=None, pairs=None, metric: str = "euclid", n_hits: int = 1, rank: str = "mean", min_len: int = 1,
@@ -357,19 +427,14 @@ def search(query, doc=None, pairs=None, metric: str = "euclid", n_hits: int = 1,
     n_hits (1 .. 32) best stretches that do not overlap are returned best first, ranked by "mean" (cost / steps) or
     "cost".  A match may collapse onto very few document frames - min_len / max_len (document frames, max_len 0: no
     limit) bound the stretches that count.  Nothing here synchronises with the host.  -> `Matches`."""
-    if metric not in METRICS:
-        raise L.AewError(f"search(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    metric = _metric_of("search()", metric)
     if rank not in RANKS:
         raise L.AewError(f"search(): rank must be one of {sorted(RANKS)}, got '{rank}'")
-    n_hits, min_len, max_len = int(n_hits), int(min_len), int(max_len)
-    if not 1 <= n_hits <= L.SEARCH_MAX_HITS:
-        raise L.AewError(f"search(): n_hits must lie in [1, {L.SEARCH_MAX_HITS}], got {n_hits}")
-    if min_len < 0 or max_len < 0:
-        raise L.AewError(f"search(): min_len and max_len must not be negative, got {min_len} and {max_len}")
+    n_hits, min_len, max_len = _hit_limits("search()", n_hits, min_len, max_len)
     rq = _ragged(query, "search(): query", torch.float32)
     rd = rq if doc is None else _ragged(doc, "search(): doc", torch.float32)
     pr = default_pairs(len(rq), None if doc is None else len(rd), pairs)
-    return Matches(_SearchLaunch(METRICS[metric], RANKS[rank], rq, rd, pr, n_hits, min_len, max_len).run("search()"))
+    return Matches(_SearchLaunch(metric, RANKS[rank], rq, rd, pr, n_hits, min_len, max_len).run("search()"))
 
 
 def discover_pairs(n_a: int, n_b: Optional[int], pairs) -> np.ndarray:
@@ -381,72 +446,34 @@ def discover_pairs(n_a: int, n_b: Optional[int], pairs) -> np.ndarray:
     return default_pairs(n_a, n_b, pairs)
 
 
-def discover_pair_table(lens_a: Sequence[int], lens_b: Sequence[int], pairs: np.ndarray, band: np.ndarray):
-    """(records, n_prof, wstride).  records: aew_discover_pair_t with prof_base = the prefix sum of the A lengths over the
-    pairs in order (disjoint profile ranges) and the pair's band; n_prof: their total; wstride: the longest B side among
-    the pairs whose A side has more than STRIP frames (the workspace is 16 * pairs * wstride bytes)."""
-    la, lb = np.asarray(lens_a, np.int64)[pairs[:, 0]], np.asarray(lens_b, np.int64)[pairs[:, 1]]
-    t = np.zeros(len(pairs), dtype=L.DISCOVER_PAIR_DTYPE)
-    t["a"], t["b"], t["band"] = pairs[:, 0], pairs[:, 1], band
-    t["prof_base"] = np.concatenate([[0], np.cumsum(la)[:-1]])
-    return t, int(la.sum()), int(np.where(la > STRIP, lb, 0).max())
-
-
-class _DiscoverLaunch(_SeqPlan):
-    """The op record of one discovery and everything it points to."""
-    KIND, FIELD, NOUN = L.OP_SEQ_DISCOVER, "discover", "discovery"
+class _DiscoverLaunch(_HitsLaunch):
+    KIND, FIELD, NOUN, REC = L.OP_SEQ_DISCOVER, "discover", "discovery", L.SeqDiscover
+    PROF, SCORE, HIT_WORDS, OWNER = ("prof_score", "prof_end", "prof_row", "prof_col", "prof_steps"), "hit_score", 4, 0
 
     def __init__(self, metric: int, threshold: float, ra: Ragged, rb: Ragged, pairs: np.ndarray, band: np.ndarray,
                  n_hits: int, min_len: int, max_len: int):
-        dev = self._open(ra, rb)
-        P = self.P = len(pairs)
-        tp, n_prof, wstride = discover_pair_table(ra.length, rb.length, pairs, band)
-        self._tables(tp)
-        self.prof = (torch.empty(max(n_prof, 1), dtype=torch.float32, device=dev),) + tuple(
-            torch.empty(max(n_prof, 1), dtype=torch.int32, device=dev) for _ in range(4))
-        self.hits = torch.empty(P, n_hits, 4, dtype=torch.int32, device=dev)
-        self.score = torch.empty(P, n_hits, dtype=torch.float32, device=dev)
-        self.steps = torch.empty(P, n_hits, dtype=torch.int32, device=dev)
-        self.count = torch.empty(P, dtype=torch.int32, device=dev)
-        self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ws = torch.empty(4 * P * wstride, dtype=torch.float32, device=dev) if wstride else None
-        self.prof_base, self.a_len = tp["prof_base"].copy(), np.asarray(ra.length, np.int64)[pairs[:, 0]]
         self.threshold = threshold
-        r = L.SeqDiscover()
-        r.metric, r.n_hits, r.D, r.n_pairs = metric, n_hits, ra.D, P
-        r.min_len, r.max_len, r.threshold = min_len, max_len, threshold
-        r.prof_score, r.prof_end, r.prof_row, r.prof_col, r.prof_steps = (x.data_ptr() for x in self.prof)
-        r.n_prof = n_prof
-        r.hits, r.hit_score, r.hit_steps = self.hits.data_ptr(), self.score.data_ptr(), self.steps.data_ptr()
-        r.count, r.bad = self.count.data_ptr(), self.bad.data_ptr()
-        self._add(r, self.ws)
+        super().__init__(ra, rb, pairs, discover_pair_table(ra.length, rb.length, pairs, band), n_hits,
+                         metric=metric, threshold=threshold, min_len=min_len, max_len=max_len)
 
 
-class Repeats:
+class Repeats(_Hits):
     """What discover() returns.  a_start, a_end, b_start, b_end (P, n_hits) int32: hit r of pair p aligns the frames
     [a_start, a_end] of its A side with the frames [b_start, b_end] of its B side, best first, -1 behind the `count[p]`
     hits that exist; score (P, n_hits) fp32: the summed gains threshold - d along the alignment (NaN there); steps
     (P, n_hits) int32: its cells (0 there); mean = threshold - score / steps: the mean local distance along it; count
     (P,) int32; bad: int32 (1,), a uint32 count of the pairs that were not finite.  All on the device; reading them is
-    the caller's synchronisation."""
+    the caller's synchronisation.
+
+    profile(p) -> (score, end, origin_row, origin_col, steps) of pair p: views of length n, entry i the best local
+    alignment that ENDS in row i of the A side - its score E(i), the B frame it ends at, the (A, B) frames it starts at and
+    its cells; (0, -1, -1, -1, 0) where nothing ends, (NaN, -1, -1, -1, 0) for a pair that was not finite."""
 
     def __init__(self, run: _DiscoverLaunch):
+        super().__init__(run)
         self.a_start, self.a_end, self.b_start, self.b_end = (run.hits[:, :, k] for k in range(4))
-        self.score, self.steps, self.count, self.bad = run.score, run.steps, run.count, run.bad
+        self.score = run.score
         self.mean = run.threshold - run.score / run.steps
-        self._run = run
-
-    def __len__(self) -> int:
-        return self._run.P
-
-    def profile(self, p: int):
-        """(score, end, origin_row, origin_col, steps) of pair p: views of length n, entry i the best local alignment that
-        ENDS in row i of the A side - its score E(i), the B frame it ends at, the (A, B) frames it starts at and its cells;
-        (0, -1, -1, -1, 0) where nothing ends, (NaN, -1, -1, -1, 0) for a pair that was not finite.  The lengths come
-        from the host tables: no wait on the device."""
-        p = range(len(self))[p]
-        lo, n = int(self._run.prof_base[p]), int(self._run.a_len[p])
-        return tuple(x[lo:lo + n] for x in self._run.prof)
 
 
 def discover(a, b=None, pairs=None, threshold: Optional[float] = None, metric: str = "euclid", n_hits: int = 3,
@@ -461,17 +488,12 @@ def discover(a, b=None, pairs=None, threshold: Optional[float] = None, metric: s
     hit are at least min_len and, with max_len > 0, at most max_len frames.  A pair (u, u) of one list skips the cells
     with j - i < band - the trivial diagonal and the lower triangle; the default band is max(min_len, 1), an explicit
     band= replaces it, every other pair has band 0.  Nothing here synchronises with the host.  -> `Repeats`."""
-    if metric not in METRICS:
-        raise L.AewError(f"discover(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    metric = _metric_of("discover()", metric)
     with np.errstate(over="ignore"):
         finite = threshold is not None and bool(np.isfinite(np.float32(threshold)))
     if not finite:
         raise L.AewError(f"discover(): a finite threshold is needed, got {threshold}")
-    n_hits, min_len, max_len = int(n_hits), int(min_len), int(max_len)
-    if not 1 <= n_hits <= L.SEARCH_MAX_HITS:
-        raise L.AewError(f"discover(): n_hits must lie in [1, {L.SEARCH_MAX_HITS}], got {n_hits}")
-    if min_len < 0 or max_len < 0:
-        raise L.AewError(f"discover(): min_len and max_len must not be negative, got {min_len} and {max_len}")
+    n_hits, min_len, max_len = _hit_limits("discover()", n_hits, min_len, max_len)
     self_band = max(min_len, 1) if band is None else int(band)
     if not 0 <= self_band < 1 << 31:
         raise L.AewError(f"discover(): band must not be negative, got {band}")
@@ -479,7 +501,7 @@ def discover(a, b=None, pairs=None, threshold: Optional[float] = None, metric: s
     rb = ra if b is None else _ragged(b, "discover(): b", torch.float32)
     pr = discover_pairs(len(ra), None if b is None else len(rb), pairs)
     bands = np.where(pr[:, 0] == pr[:, 1], self_band, 0) if rb is ra else np.zeros(len(pr), np.int64)
-    return Repeats(_DiscoverLaunch(METRICS[metric], float(np.float32(threshold)), ra, rb, pr, bands, n_hits, min_len,
+    return Repeats(_DiscoverLaunch(metric, float(np.float32(threshold)), ra, rb, pr, bands, n_hits, min_len,
                                    max_len).run("discover()"))
 
 
@@ -565,8 +587,7 @@ def distance_matrix(items, metric: str = "euclid", value: str = "mean", max_pair
     mirrored into both triangles by one index write.  value "mean": cost / steps, "cost": the summed distance - entry
     (i, j) carries the bits dtw(items, pairs=[(i, j)]) gives, +inf for a pair with an empty side and NaN for one that
     is not finite.  The diagonal is 0.  Nothing here synchronises with the host."""
-    if metric not in METRICS:
-        raise L.AewError(f"distance_matrix(): metric must be one of {sorted(METRICS)}, got '{metric}'")
+    metric = _metric_of("distance_matrix()", metric)
     if value not in RANKS:
         raise L.AewError(f"distance_matrix(): value must be one of {sorted(RANKS)}, got '{value}'")
     max_pairs = int(max_pairs)
@@ -580,7 +601,7 @@ def distance_matrix(items, metric: str = "euclid", value: str = "mean", max_pair
     P = N * (N - 1) // 2
     for k0 in range(0, P, max_pairs):
         pr = _pair_run(N, k0, min(P, k0 + max_pairs))
-        run = _Launches(L.ALIGN_DTW, METRICS[metric], ra, ra, pr, False, None).run("distance_matrix()")
+        run = _Launches(L.ALIGN_DTW, metric, ra, ra, pr, False, None).run("distance_matrix()")
         v = run.cost / run.steps if value == "mean" else run.cost
         ij = _upload(np.concatenate([pr, pr[:, ::-1]]), dev).view(torch.int64).reshape(-1, 2)
         out[ij[:, 0], ij[:, 1]] = torch.cat([v, v])
@@ -721,11 +742,7 @@ def abx_score(dist: torch.Tensor, category, speaker=None, mode: str = "within") 
     r.groups, r.groups_host = d_groups.data_ptr(), tb.groups.ctypes.data
     r.partner, r.partner_host = d_partner.data_ptr(), partner.ctypes.data
     r.n, r.wrong2 = n.data_ptr(), wrong2.data_ptr()
-    op, fail = L.Op(), C.c_int(-1)
-    op.kind, op.u.abx = L.OP_ABX_COUNT, r
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        L.check(L.load().aew_run_plan(C.byref(op), 1, C.c_void_p(st), C.byref(fail)), "abx_score()")
+    _run_records(dev, L.OP_ABX_COUNT, "abx", [r], "abx_score()")
     res = abx_aggregate(wrong2, n, tb)
     nan = torch.isnan(dist)
     res.n_nan = nan.sum() - nan.diagonal().sum()

@@ -15,9 +15,13 @@
 // The DTW strip loop is ONE device function, align_sweep<DR, SUB>: k_align_dtw calls it with SUB = false, k_search_sweep
 // (aew_search.hip, subsequence DTW) with SUB = true; what only one of the two carries is compiled out of the other.
 // Phase (A) is a function of its own, align_fill_ring<DR>: k_discover_sweep (aew_discover.hip, local-alignment DTW) runs
-// a sibling sweep with another recurrence over the same ring.  The three ops also share the device pair loader
-// (seq_load_pair), the host checks of the fields their records have in common (align_check_record) and the ladder
-// D -> DR (align_dispatch_D).
+// a sibling sweep with another recurrence over the same ring.  The two strip loops stay apart: written once over a generic
+// carried cell, the 64-step loop of search and discover compiled to another instruction order and measured 1 - 3 %
+// slower, and as one frame around a step loop per op DTW's loop grew by a quarter (profiles/search.txt).  The three ops
+// share the sweep kernels' prologue (align_wave_of), the device pair loader (seq_load_pair), the host checks of the
+// fields their records have in common (align_check_record) with the workspace's width from each op's carried words
+// (align_ws_col), the ladder D -> DR (align_dispatch_D) and the launch of a sweep with the kernel behind it
+// (align_launch_sweep).
 //
 // Nothing here waits on another wave: no __syncthreads (the waves of a block share nothing), no flag, no atomic but the
 // count of pairs that are not finite.  The path kernel is a second launch behind the first on the same stream.
@@ -99,6 +103,22 @@ __device__ __forceinline__ int64_t align_lane(int64_t v, int l) {
 }
 
 // ---- the DTW sweep, for AEW_OP_SEQ_ALIGN and AEW_OP_SEQ_SEARCH -------------------------------------------------------------
+// A carried cell is one float and `words` int words - DTW's S; search's S, B; discover's S, R, O - and the workspace holds
+// a boundary row as 1 + words planes of n_pairs * wstride words: plane 0 the float, plane 1 + w word w.  -> the bytes a
+// pair and column take of it
+#define AEW_ALIGN_WORDS 1
+#define AEW_SEARCH_WORDS 2
+#define AEW_DISCOVER_WORDS 3
+constexpr int align_ws_col(int words) { return 4 * (1 + words); }
+// the sweep kernels' prologue: the wave's index in its workgroup (wave-uniform; it picks the wave's ring), its lane and
+// its pair.  -> 0: no pair is left for this wave
+template <class Rec>
+__device__ __forceinline__ int align_wave_of(const Rec& p, int& w, int& lane, int& pi) {
+    w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    lane = threadIdx.x & 63;
+    pi = blockIdx.x * AEW_ALIGN_WAVES + w;
+    return pi < p.n_pairs;
+}
 // what the sweep reads and writes of one pair (n, m >= 1, every record checked)
 struct align_sweep_in {
     const float *A, *B;                                 // element (0, 0) of the two sequences
@@ -267,10 +287,8 @@ __device__ __forceinline__ align_sweep_out align_sweep(const align_sweep_in& q, 
 template <int DR>
 __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_align_dtw(const aew_seq_align_t p, const int64_t wstride) {
     __shared__ float ring_all[AEW_ALIGN_WAVES][AEW_ALIGN_RING * 64];
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int pi = blockIdx.x * AEW_ALIGN_WAVES + w;
-    if (pi >= p.n_pairs) return;                                                 // wave-uniform, like every return below
+    int w, lane, pi;
+    if (!align_wave_of(p, w, lane, pi)) return;                                  // wave-uniform, like every return below
     const align_pair_view v = align_load_pair(p, pi, wstride);
     if (!v.ok) return;
     const int n = v.sa.len, m = v.sb.len;
@@ -379,8 +397,8 @@ __global__ __launch_bounds__(64 * AEW_ALIGN_EDIT_WAVES) void k_align_edit(const 
 // record with several defects gets: the fields (AEW_E_ARG) - own_ok is the verdict on the op's own ones -, the pointers'
 // alignment (AEW_E_ALIGN; own_ptrs: the op's own 4-byte pointers or-ed together), then every record of the host tables
 // (AEW_E_ARG), with room(pair, n, m) the op's own check of a pair.  frames: fp32 frames under a metric, else int64
-// symbols.  ws_col: workspace bytes per pair and column.  -> 0 and *wstride_out, the longest B side among the pairs
-// that need boundary rows.
+// symbols.  ws_col: workspace bytes per pair and column (align_ws_col).  -> 0 and *wstride_out, the longest B side among
+// the pairs that need boundary rows.
 template <class Rec, class Room>
 static int align_check_record(const Rec& p, bool frames, bool own_ok, uintptr_t own_ptrs, int ws_col, Room room, int64_t* wstride_out) {
     if (frames && p.metric != AEW_ALIGN_EUCLID && p.metric != AEW_ALIGN_SQEUCLID) return AEW_E_ARG;
@@ -424,6 +442,20 @@ static void align_dispatch_D(int D, F f) {
     else f(std::integral_constant<int, 0>());
 }
 
+// A sweep and the kernel behind it on the same stream - the path, or a pick; NULL: none -, one wave per pair each.
+// sweep_of(dr) -> the sweep kernel whose DR is decltype(dr)::value.  The second kernel is not launched behind an error.
+template <class Rec, class SweepOf>
+static int align_launch_sweep(const Rec& p, int64_t wstride, hipStream_t st, SweepOf sweep_of, void (*behind)(Rec, int64_t)) {
+    const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_WAVES - 1) / AEW_ALIGN_WAVES);
+    align_dispatch_D(p.D, [&](auto dr) {
+        hipLaunchKernelGGL(sweep_of(dr), dim3(g), dim3(64 * AEW_ALIGN_WAVES), 0, st, p, wstride);
+    });
+    const int rc = (int)hipGetLastError();
+    if (rc || !behind) return rc;
+    hipLaunchKernelGGL(behind, dim3((unsigned)p.n_pairs), dim3(64), 0, st, p, wstride);
+    return (int)hipGetLastError();
+}
+
 // ---- the launcher ------------------------------------------------------------------------------------------------------
 static int launch_seq_align(const aew_seq_align_t& p, hipStream_t st) {
     const bool edit = p.mode == AEW_ALIGN_EDIT;
@@ -431,7 +463,7 @@ static int launch_seq_align(const aew_seq_align_t& p, hipStream_t st) {
                         !(p.path && !p.back) && !(edit && (p.back || p.path)) && !(p.back && p.n_back < 0) && !(p.path && p.n_path < 0);
     const uintptr_t own_ptrs = (uintptr_t)p.cost | (uintptr_t)p.steps | (uintptr_t)p.bad | (uintptr_t)p.path;
     int64_t wstride = 0;
-    const int bad = align_check_record(p, !edit, own_ok, own_ptrs, 8, [&](const aew_align_pair_t& pr, int n, int m) {
+    const int bad = align_check_record(p, !edit, own_ok, own_ptrs, align_ws_col(AEW_ALIGN_WORDS), [&](const aew_align_pair_t& pr, int n, int m) {
         return !p.back || align_room_ok(pr, n, m, p.n_back, p.path != nullptr, p.n_path);
     }, &wstride);
     if (bad) return bad;
@@ -440,12 +472,5 @@ static int launch_seq_align(const aew_seq_align_t& p, hipStream_t st) {
         hipLaunchKernelGGL(k_align_edit, dim3(g), dim3(64 * AEW_ALIGN_EDIT_WAVES), 0, st, p, wstride);
         return (int)hipGetLastError();
     }
-    const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_WAVES - 1) / AEW_ALIGN_WAVES);
-    align_dispatch_D(p.D, [&](auto dr) {
-        hipLaunchKernelGGL(k_align_dtw<decltype(dr)::value>, dim3(g), dim3(64 * AEW_ALIGN_WAVES), 0, st, p, wstride);
-    });
-    int rc = (int)hipGetLastError();
-    if (rc || !p.path) return rc;
-    hipLaunchKernelGGL(k_align_path, dim3((unsigned)p.n_pairs), dim3(64), 0, st, p, wstride);
-    return (int)hipGetLastError();
+    return align_launch_sweep(p, wstride, st, [](auto dr) { return k_align_dtw<decltype(dr)::value>; }, p.path ? k_align_path : nullptr);
 }

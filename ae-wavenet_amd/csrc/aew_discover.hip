@@ -13,9 +13,10 @@
 // no has_up / has_left.  Each lane keeps the running maximum of its row (E, its column, origin, steps) in registers and
 // stores the five profile words when its strip ends: no cross-lane reduction.  The kernel leaves its verdict on the pair
 // in count[p] (0, or -1: a local distance inside the band was not finite) for the pick, which then owns every output of
-// the pair.  k_discover_pick, a second launch behind the first on the same stream, mirrors k_search_pick over ROWS: n_hits
-// rounds of a masked arg-max, the A ranges chosen so far in registers (lane q holds hit q).  The launcher shares its
-// record checks, its pair loader and its D ladder with launch_seq_align / launch_seq_search.
+// the pair.  k_discover_pick, a second launch behind the first on the same stream, is k_search_pick's body (seq_pick,
+// aew_search.hip) over ROWS: n_hits rounds of a masked arg-max, the A ranges chosen so far in registers (lane q holds
+// hit q).  The launcher shares its record checks, its pair loader, its D ladder and its two launches with
+// launch_seq_align / launch_seq_search.
 //
 // Nothing here waits on another wave: no __syncthreads, no flag, no atomic but the count of pairs that are not finite.
 // Part of the library's one translation unit (aewavenet.hip includes it behind aew_search.hip).
@@ -33,6 +34,15 @@ __device__ __forceinline__ discover_pair_view discover_load_pair(const aew_seq_d
     discover_pair_view v = seq_load_pair(p, pi, wstride);
     if (v.ok && !discover_room_ok(v.pr, v.sa.len, p.n_prof)) v.ok = 0;
     return v;
+}
+
+// the pair's profile as the pick reads it, n entries each
+struct discover_prof {
+    float* pe;
+    int *pj, *pr, *pc, *ps;
+};
+__device__ __forceinline__ discover_prof discover_prof_of(const aew_seq_discover_t& p, int64_t lo) {
+    return {p.prof_score + lo, p.prof_end + lo, p.prof_row + lo, p.prof_col + lo, p.prof_steps + lo};
 }
 
 // ---- the sweep ---------------------------------------------------------------------------------------------------------
@@ -119,10 +129,8 @@ __device__ __forceinline__ bool discover_sweep(const align_sweep_in& q, const di
 template <int DR>
 __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_discover_sweep(const aew_seq_discover_t p, const int64_t wstride) {
     __shared__ float ring_all[AEW_ALIGN_WAVES][AEW_ALIGN_RING * 64];
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int pi = blockIdx.x * AEW_ALIGN_WAVES + w;
-    if (pi >= p.n_pairs) return;                                                 // wave-uniform, like every return below
+    int w, lane, pi;
+    if (!align_wave_of(p, w, lane, pi)) return;                                  // wave-uniform, like every return below
     const discover_pair_view v = discover_load_pair(p, pi, wstride);
     if (!v.ok) return;
     const int n = v.sa.len, m = v.sb.len;
@@ -144,59 +152,47 @@ __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_discover_sweep(const a
 }
 
 // ---- the pick ----------------------------------------------------------------------------------------------------------
-// one wave per pair: lane l scans the rows l, l + 64, ..; hit q's A range sits in lane q's registers
+// seq_pick (aew_search.hip) over ROWS: the entries are the A rows an alignment ENDS in, the key its score, the largest
+// wins; an interval is the hit's A range
+struct discover_pick {
+    discover_prof prof;
+    int* hits;                                          // the pair's n_hits slots
+    float* hscore;
+    int* hsteps;
+    int len, min_len, max_len;
+    __device__ __forceinline__ bool candidate(int i, float& key, int& start) const {
+        const float e = prof.pe[i];
+        const int r0 = prof.pr[i];
+        const int la = i - r0 + 1, lb = prof.pj[i] - prof.pc[i] + 1;
+        key = e;
+        start = r0;
+        return e > 0.f && la >= min_len && lb >= min_len && (max_len <= 0 || (la <= max_len && lb <= max_len));
+    }
+    __device__ __forceinline__ static bool better(float a, float b) { return a > b; }
+    __device__ __forceinline__ void fill(int i, bool hurt) const {
+        prof.pe[i] = hurt ? NAN : 0.f; prof.pj[i] = -1; prof.pr[i] = -1; prof.pc[i] = -1; prof.ps[i] = 0;
+    }
+    __device__ __forceinline__ int hit(int r, int i, bool store) const {
+        const int start = prof.pr[i];
+        if (store) {
+            hits[4 * r] = start; hits[4 * r + 1] = i; hits[4 * r + 2] = prof.pc[i]; hits[4 * r + 3] = prof.pj[i];
+            hscore[r] = prof.pe[i]; hsteps[r] = prof.ps[i];
+        }
+        return start;
+    }
+    __device__ __forceinline__ void pad(int r) const {
+        hits[4 * r] = -1; hits[4 * r + 1] = -1; hits[4 * r + 2] = -1; hits[4 * r + 3] = -1;
+        hscore[r] = NAN; hsteps[r] = 0;
+    }
+};
 __global__ __launch_bounds__(64) void k_discover_pick(const aew_seq_discover_t p, const int64_t wstride) {
     const int pi = blockIdx.x, lane = threadIdx.x;
     const discover_pair_view v = discover_load_pair(p, pi, wstride);
     if (!v.ok) return;
-    const int n = v.sa.len, m = v.sb.len, H = p.n_hits;
-    float* pe = p.prof_score + v.pr.prof_base;
-    int* pj = p.prof_end + v.pr.prof_base;
-    int* pr = p.prof_row + v.pr.prof_base;
-    int* pc = p.prof_col + v.pr.prof_base;
-    int* ps = p.prof_steps + v.pr.prof_base;
-    int* hits = p.hits + 4 * (int64_t)pi * H;
-    float* hscore = p.hit_score + (int64_t)pi * H;
-    int* hsteps = p.hit_steps + (int64_t)pi * H;
-    const bool empty = n == 0 || m == 0;
-    const bool hurt = !empty && p.count[pi] != 0;
-    int found = 0;
-    if (empty || hurt) {
-        for (int i = lane; i < n; i += 64) { pe[i] = hurt ? NAN : 0.f; pj[i] = -1; pr[i] = -1; pc[i] = -1; ps[i] = 0; }
-        if (hurt && lane == 0) atomicAdd(p.bad, 1u);
-    } else {
-        int ivs = 0, ive = 0;
-        for (int r = 0; r < H; ++r) {
-            float bk = 0.f;
-            int bi = INT_MAX;                                                    // no row yet
-            for (int i = lane; i < n; i += 64) {
-                const float e = pe[i];
-                const int r0 = pr[i];
-                const int la = i - r0 + 1, lb = pj[i] - pc[i] + 1;
-                bool ok = e > 0.f && la >= p.min_len && lb >= p.min_len && (p.max_len <= 0 || (la <= p.max_len && lb <= p.max_len));
-                for (int q = 0; q < r; ++q) ok = ok && !(r0 <= align_lane(ive, q) && i >= align_lane(ivs, q));
-                if (ok && (bi == INT_MAX || e > bk)) { bk = e; bi = i; }         // (i ascends: a strict > keeps the least i)
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                const float ok_ = __shfl_xor(bk, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                if (oi != INT_MAX && (bi == INT_MAX || ok_ > bk || (ok_ == bk && oi < bi))) { bk = ok_; bi = oi; }
-            }
-            if (bi == INT_MAX) break;                                            // (wave-uniform: every lane holds the same row)
-            const int start = pr[bi];
-            if (lane == r) { ivs = start; ive = bi; }
-            if (lane == 0) {
-                hits[4 * r] = start; hits[4 * r + 1] = bi; hits[4 * r + 2] = pc[bi]; hits[4 * r + 3] = pj[bi];
-                hscore[r] = pe[bi]; hsteps[r] = ps[bi];
-            }
-            ++found;
-        }
-    }
-    for (int r = found + lane; r < H; r += 64) {
-        hits[4 * r] = -1; hits[4 * r + 1] = -1; hits[4 * r + 2] = -1; hits[4 * r + 3] = -1;
-        hscore[r] = NAN; hsteps[r] = 0;
-    }
-    if (lane == 0) p.count[pi] = found;
+    const int64_t slot = (int64_t)pi * p.n_hits;
+    const discover_pick pk = {discover_prof_of(p, v.pr.prof_base), p.hits + 4 * slot, p.hit_score + slot, p.hit_steps + slot,
+                              v.sa.len, p.min_len, p.max_len};
+    seq_pick(pk, p.n_hits, v.sa.len == 0 || v.sb.len == 0, p.count + pi, p.bad, lane);
 }
 
 // ---- the launcher ------------------------------------------------------------------------------------------------------
@@ -208,16 +204,9 @@ static int launch_seq_discover(const aew_seq_discover_t& p, hipStream_t st) {
                                (uintptr_t)p.prof_steps | (uintptr_t)p.hits | (uintptr_t)p.hit_score | (uintptr_t)p.hit_steps |
                                (uintptr_t)p.count | (uintptr_t)p.bad;
     int64_t wstride = 0;
-    const int bad = align_check_record(p, true, own_ok, own_ptrs, 16, [&](const aew_discover_pair_t& pr, int n, int) {
+    const int bad = align_check_record(p, true, own_ok, own_ptrs, align_ws_col(AEW_DISCOVER_WORDS), [&](const aew_discover_pair_t& pr, int n, int) {
         return discover_room_ok(pr, n, p.n_prof);
     }, &wstride);
     if (bad) return bad;
-    const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_WAVES - 1) / AEW_ALIGN_WAVES);
-    align_dispatch_D(p.D, [&](auto dr) {
-        hipLaunchKernelGGL(k_discover_sweep<decltype(dr)::value>, dim3(g), dim3(64 * AEW_ALIGN_WAVES), 0, st, p, wstride);
-    });
-    const int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_discover_pick, dim3((unsigned)p.n_pairs), dim3(64), 0, st, p, wstride);
-    return (int)hipGetLastError();
+    return align_launch_sweep(p, wstride, st, [](auto dr) { return k_discover_sweep<decltype(dr)::value>; }, k_discover_pick);
 }

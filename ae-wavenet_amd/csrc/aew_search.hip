@@ -8,10 +8,11 @@
 // predecessor - every column starts a match - so the start column B travels with C and S; the lane that owns row n - 1
 // stores the three profile entries of each column; there is no back matrix.  The kernel itself only loads and checks its
 // pair, fills the sweep's input and leaves its verdict on the pair in count[p] (0, or -1: a local distance was not
-// finite) for the pick, which then owns every output of the pair; the launcher shares its record checks and its D ladder
-// with launch_seq_align.  k_search_pick, a second launch behind the first on the same stream, runs n_hits rounds of a
-// masked arg-min over the pair's profile; the intervals chosen so far live in registers (lane q holds hit q), so there
-// is no mask array.
+// finite) for the pick, which then owns every output of the pair; the launcher shares its record checks, its D ladder
+// and its two launches with launch_seq_align.  k_search_pick, a second launch behind the first on the same stream, runs
+// n_hits rounds of a masked arg-min over the pair's profile; the intervals chosen so far live in registers (lane q holds
+// hit q), so there is no mask array.  That body is seq_pick, here, under the policy search_pick; k_discover_pick
+// (aew_discover.hip) runs it under its own.
 //
 // Nothing here waits on another wave: no __syncthreads, no flag, no atomic but the count of pairs that are not finite.
 // Part of the library's one translation unit (aewavenet.hip includes it behind aew_segment.hip).
@@ -36,10 +37,8 @@ __device__ __forceinline__ search_pair_view search_load_pair(const aew_seq_searc
 template <int DR>
 __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_search_sweep(const aew_seq_search_t p, const int64_t wstride) {
     __shared__ float ring_all[AEW_ALIGN_WAVES][AEW_ALIGN_RING * 64];
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int pi = blockIdx.x * AEW_ALIGN_WAVES + w;
-    if (pi >= p.n_pairs) return;                                                 // wave-uniform, like every return below
+    int w, lane, pi;
+    if (!align_wave_of(p, w, lane, pi)) return;                                  // wave-uniform, like every return below
     const search_pair_view v = search_load_pair(p, pi, wstride);
     if (!v.ok) return;
     const int n = v.sa.len, m = v.sb.len;
@@ -55,53 +54,84 @@ __global__ __launch_bounds__(64 * AEW_ALIGN_WAVES) void k_search_sweep(const aew
 }
 
 // ---- the pick ----------------------------------------------------------------------------------------------------------
-// one wave per pair: lane l scans the ends l, l + 64, ..; hit q's interval sits in lane q's registers
+// The pick of search and discover (aew_discover.hip), one wave per pair: the n_hits best entries of the pair's profile
+// whose intervals do not overlap, best first.  Lane l scans the entries l, l + 64, ..; hit q's interval sits in lane q's
+// registers, so there is no mask array.  empty: a side of the pair has no frame; *count: the sweep's verdict on the way
+// in (not 0: the pair is hurt, it was not finite), the number of hits on the way out.  A Pick gives
+//   len                                  the entries of the profile,
+//   candidate(x, key, start) -> ok       entry x: may it be a hit, its key, where its interval [start, x] begins,
+//   better(a, b)                         does key a beat key b (strict; equal keys: the least entry wins),
+//   fill(x, hurt)                        the profile entry of an empty or hurt pair,
+//   hit(r, x, store) -> start            hit r is entry x: its start and, under `store`, its slot,
+//   pad(r)                               slot r behind the hits that exist.
+template <class Pick>
+__device__ __forceinline__ void seq_pick(const Pick& pk, const int H, const bool empty, int* count, uint32_t* bad, const int lane) {
+    const bool hurt = !empty && *count != 0;
+    int found = 0;
+    if (empty || hurt) {
+        for (int x = lane; x < pk.len; x += 64) pk.fill(x, hurt);
+        if (hurt && lane == 0) atomicAdd(bad, 1u);
+    } else {
+        int ivs = 0, ive = 0;
+        for (int r = 0; r < H; ++r) {
+            float bk = 0.f;
+            int bx = INT_MAX;                                                    // no entry yet
+            for (int x = lane; x < pk.len; x += 64) {
+                float key;
+                int start;
+                bool ok = pk.candidate(x, key, start);
+                for (int q = 0; q < r; ++q) ok = ok && !(start <= align_lane(ive, q) && x >= align_lane(ivs, q));
+                if (ok && (bx == INT_MAX || pk.better(key, bk))) { bk = key; bx = x; }   // (x ascends: a strict test keeps the least x)
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ok_ = __shfl_xor(bk, off, 64);
+                const int ox = __shfl_xor(bx, off, 64);
+                if (ox != INT_MAX && (bx == INT_MAX || pk.better(ok_, bk) || (ok_ == bk && ox < bx))) { bk = ok_; bx = ox; }
+            }
+            if (bx == INT_MAX) break;                                            // (wave-uniform: every lane holds the same entry)
+            const int start = pk.hit(r, bx, lane == 0);
+            if (lane == r) { ivs = start; ive = bx; }
+            ++found;
+        }
+    }
+    for (int r = found + lane; r < H; r += 64) pk.pad(r);
+    if (lane == 0) *count = found;
+}
+
+// search: the entries are the document frames a match ENDS at, the key its cost or mean cost, the least wins
+struct search_pick {
+    float* pc;                                          // the pair's profile
+    int *ps, *pb;
+    int* hits;                                          // the pair's n_hits slots
+    float* hcost;
+    int* hsteps;
+    int len, min_len, max_len;
+    bool by_mean;
+    __device__ __forceinline__ bool candidate(int j, float& key, int& start) const {
+        const float c = pc[j];
+        const int b = pb[j];
+        key = by_mean ? c / (float)ps[j] : c;                                    // the division is IEEE-rounded here
+        const int len = j - b + 1;
+        start = b;
+        return isfinite(key) && len >= min_len && (max_len <= 0 || len <= max_len);
+    }
+    __device__ __forceinline__ static bool better(float a, float b) { return a < b; }
+    __device__ __forceinline__ void fill(int j, bool hurt) const { pc[j] = hurt ? NAN : INFINITY; ps[j] = 0; pb[j] = -1; }
+    __device__ __forceinline__ int hit(int r, int j, bool store) const {
+        const int start = pb[j];
+        if (store) { hits[2 * r] = start; hits[2 * r + 1] = j; hcost[r] = pc[j]; hsteps[r] = ps[j]; }
+        return start;
+    }
+    __device__ __forceinline__ void pad(int r) const { hits[2 * r] = -1; hits[2 * r + 1] = -1; hcost[r] = INFINITY; hsteps[r] = 0; }
+};
 __global__ __launch_bounds__(64) void k_search_pick(const aew_seq_search_t p, const int64_t wstride) {
     const int pi = blockIdx.x, lane = threadIdx.x;
     const search_pair_view v = search_load_pair(p, pi, wstride);
     if (!v.ok) return;
-    const int n = v.sa.len, m = v.sb.len, H = p.n_hits;
-    float* pc = p.prof_cost + v.pr.prof_base;
-    int* ps = p.prof_steps + v.pr.prof_base;
-    int* pb = p.prof_start + v.pr.prof_base;
-    int* hits = p.hits + 2 * (int64_t)pi * H;
-    float* hcost = p.hit_cost + (int64_t)pi * H;
-    int* hsteps = p.hit_steps + (int64_t)pi * H;
-    const bool empty = n == 0 || m == 0;
-    const bool hurt = !empty && p.count[pi] != 0;
-    int found = 0;
-    if (empty || hurt) {
-        for (int j = lane; j < m; j += 64) { pc[j] = hurt ? NAN : INFINITY; ps[j] = 0; pb[j] = -1; }
-        if (hurt && lane == 0) atomicAdd(p.bad, 1u);
-    } else {
-        const bool by_mean = p.rank == AEW_SEARCH_MEAN;
-        int ivs = 0, ive = 0;
-        for (int r = 0; r < H; ++r) {
-            float bk = 0.f;
-            int bj = INT_MAX;                                                    // no end yet
-            for (int j = lane; j < m; j += 64) {
-                const float c = pc[j];
-                const int b = pb[j];
-                const float key = by_mean ? c / (float)ps[j] : c;                // the division is IEEE-rounded here
-                const int len = j - b + 1;
-                bool ok = isfinite(key) && len >= p.min_len && (p.max_len <= 0 || len <= p.max_len);
-                for (int q = 0; q < r; ++q) ok = ok && !(b <= align_lane(ive, q) && j >= align_lane(ivs, q));
-                if (ok && (bj == INT_MAX || key < bk)) { bk = key; bj = j; }     // (j ascends: a strict < keeps the least j)
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                const float ok_ = __shfl_xor(bk, off, 64);
-                const int oj = __shfl_xor(bj, off, 64);
-                if (oj != INT_MAX && (bj == INT_MAX || ok_ < bk || (ok_ == bk && oj < bj))) { bk = ok_; bj = oj; }
-            }
-            if (bj == INT_MAX) break;                                            // (wave-uniform: every lane holds the same end)
-            const int start = pb[bj];
-            if (lane == r) { ivs = start; ive = bj; }
-            if (lane == 0) { hits[2 * r] = start; hits[2 * r + 1] = bj; hcost[r] = pc[bj]; hsteps[r] = ps[bj]; }
-            ++found;
-        }
-    }
-    for (int r = found + lane; r < H; r += 64) { hits[2 * r] = -1; hits[2 * r + 1] = -1; hcost[r] = INFINITY; hsteps[r] = 0; }
-    if (lane == 0) p.count[pi] = found;
+    const int64_t lo = v.pr.prof_base, slot = (int64_t)pi * p.n_hits;
+    const search_pick pk = {p.prof_cost + lo, p.prof_steps + lo, p.prof_start + lo, p.hits + 2 * slot, p.hit_cost + slot,
+                            p.hit_steps + slot, v.sb.len, p.min_len, p.max_len, p.rank == AEW_SEARCH_MEAN};
+    seq_pick(pk, p.n_hits, v.sa.len == 0 || v.sb.len == 0, p.count + pi, p.bad, lane);
 }
 
 // ---- the launcher ------------------------------------------------------------------------------------------------------
@@ -112,16 +142,9 @@ static int launch_seq_search(const aew_seq_search_t& p, hipStream_t st) {
     const uintptr_t own_ptrs = (uintptr_t)p.prof_cost | (uintptr_t)p.prof_steps | (uintptr_t)p.prof_start | (uintptr_t)p.hits |
                                (uintptr_t)p.hit_cost | (uintptr_t)p.hit_steps | (uintptr_t)p.count | (uintptr_t)p.bad;
     int64_t wstride = 0;
-    const int bad = align_check_record(p, true, own_ok, own_ptrs, 12, [&](const aew_search_pair_t& pr, int, int m) {
+    const int bad = align_check_record(p, true, own_ok, own_ptrs, align_ws_col(AEW_SEARCH_WORDS), [&](const aew_search_pair_t& pr, int, int m) {
         return search_room_ok(pr, m, p.n_prof);
     }, &wstride);
     if (bad) return bad;
-    const unsigned g = (unsigned)((p.n_pairs + AEW_ALIGN_WAVES - 1) / AEW_ALIGN_WAVES);
-    align_dispatch_D(p.D, [&](auto dr) {
-        hipLaunchKernelGGL(k_search_sweep<decltype(dr)::value>, dim3(g), dim3(64 * AEW_ALIGN_WAVES), 0, st, p, wstride);
-    });
-    const int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_search_pick, dim3((unsigned)p.n_pairs), dim3(64), 0, st, p, wstride);
-    return (int)hipGetLastError();
+    return align_launch_sweep(p, wstride, st, [](auto dr) { return k_search_sweep<decltype(dr)::value>; }, k_search_pick);
 }

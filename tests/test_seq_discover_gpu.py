@@ -201,6 +201,26 @@ def test_a_band_on_self_pairs_that_crosses_a_strip(kind):
     assert (got["prof_score"][lo:lo + 64] == 0).all() and (got["prof_end"][lo:lo + 64] == -1).all()
 
 
+@pytest.mark.parametrize("n_hits,min_len,max_len", [(1, 1, 0), (3, 1, 0), (32, 1, 0), (32, 2, 0), (3, 2, 6), (32, 1, 3), (3, 300, 0)])
+@pytest.mark.parametrize("kind", ["normal", "binary"])
+def test_the_pick_controls(kind, n_hits, min_len, max_len):
+    """The pick under every one of its controls, 9 pairs in one launch: one hit, the default three, all 32 slots (hits
+    held in the registers of lanes up to 31, and padding behind the hits of the pairs that have fewer), both length
+    bounds, and a min_len nothing reaches."""
+    alens, blens = (5, 70, 200), (200, 129, 3)
+    theta = THETA[kind, "euclid"]
+    A, B = _seqs(kind, 3, alens, blens)
+    want = _want(kind, 3, alens, blens, "euclid", theta, n_hits, min_len, max_len)
+    run = _Discover(SD.EUCLID, theta, _Side(A, "frame"), _Side(B, "frame"), _grid(3, 3), None, n_hits, min_len, max_len).run()
+    got = run.results()
+    run.same_as(got, want)
+    counts = got["count"].tolist()
+    if min_len == 300:
+        assert counts == [0] * 9                                              # nothing is that long: every slot is padding
+    elif (n_hits, min_len, max_len) == (32, 1, 0):
+        assert max(counts) == 32 and min(counts) < 32                         # full pairs and padded ones in one launch
+
+
 # ---- special pairs -------------------------------------------------------------------------------------------------------
 def test_a_bad_pair_and_empty_pairs_beside_ordinary_ones():
     rs = np.random.RandomState(3)
